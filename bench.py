@@ -14,10 +14,16 @@ the agreement on the step count, the gather of the per-rank rates) is RCCL ("ncc
 next to the engine's HIP runtime; `comm_backend` in the line says which.  torch touches NO device memory of the data path: frames,
 arenas and streams belong to the engine library (rtp_device_alloc).
 
-The timed region is never shorter than --min_seconds (default 2 s) and runs un-instrumented: `--steps K` is a MINIMUM, the region is
-repeated with more frames until it is long enough, and the line reports the frames actually timed as `steps` (= `steps_timed`; the flag
-as `steps_requested`) with `timed_region_s`.  Defaults per workload are measured optima (profiles/r03_in_flight.txt): COCO 1 scale 7
-frames in flight in batches of 2, several scales 3 in flight one frame per launch sequence, MPI 10 in flight in batches of 5.
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it creates the engine, runs W warm-up
+frames, times exactly K frames un-instrumented, and prints the result line (`steps` = `steps_timed` = K, `ms_per_step` = milliseconds of
+one timed frame, `timed_region_s`).  `--min_seconds S` > 0 (off by default) makes K a minimum instead: the region is repeated with more
+frames until it lasts S seconds.  `--dump-outputs DIR` writes what the timed path returned for its LAST frame (rtp_collect: the joints
+[people][parts][x, y, score] and the number of people) as DIR/joints.npy and DIR/num_people.npy; inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.  Defaults per workload are measured optima
+(profiles/r03_in_flight.txt): COCO 1 scale 7 frames in flight in batches of 2, several scales 3 in flight one frame per launch sequence,
+MPI 10 in flight in batches of 5.
+
+Everything below is measured only with `--full` (off by default):
 
 `roofline` (separate pass right after the timed region): HIP event pairs around EVERY launch of a batch, on the stream the launch runs on,
 one batch at a time — the dominant kernel shape's launches give achieved / frac (roofline_block() below), all launches grouped by kernel class
@@ -29,10 +35,10 @@ deviation field through both post-processing chains; `cpu_baseline`: the
 OpenMP oracle port and torch-CPU conv2d over the same layers; `latency_ms.p50_single_frame`: one frame alone, commit -> joints on the
 host (rtpose.cpp:1430).
 
-The printed line is COMPACT (compact_line(): <= 8 KB, one copy of the per-class rows); every leg's body — `sub_results` (resident input,
-MPI 496x368 = BASELINE configs[4] with its own roofline and parity, 3 scales = configs[2], single-pass fp16, exact-f32, post-processing alone
-on analytic heat maps), the parity explanations, the notes — goes to `bench_detail.json` next to this file (and under gpurun_out/ on the GPU
-box); the line's `summary` holds each leg's headline scalar.
+The printed line is COMPACT (compact_line(): <= 8 KB, one copy of the per-class rows); with `--full` every leg's body — `sub_results`
+(resident input, MPI 496x368 = BASELINE configs[4] with its own roofline and parity, 3 scales = configs[2], single-pass fp16, exact-f32,
+post-processing alone on analytic heat maps), the parity explanations, the notes — goes to `bench_detail.json` (write_detail()); the
+line's `summary` holds each leg's headline scalar.
 """
 import argparse
 import glob
@@ -568,8 +574,8 @@ def leg_subprocess(flags, timeout=900):
     if USER_HW_QUEUES is None:
         env.pop("GPU_MAX_HW_QUEUES", None)          # the leg picks the count of ITS batch size
     try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--no_cpu_baseline", "--no_sub_results", "--steps", "50", "--warmup", "10", "--min_seconds", "1.0",
-                            "--detail_out", path] + flags, env=env, capture_output=True, text=True, timeout=timeout)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no_cpu_baseline", "--no_sub_results", "--steps", "50", "--warmup", "10",
+                            "--min_seconds", "1.0", "--detail_out", path] + flags, env=env, capture_output=True, text=True, timeout=timeout)
         if p.returncode != 0:
             return {"error": (p.stderr or p.stdout)[-400:]}
         with open(path) as f:
@@ -647,7 +653,8 @@ def compact_line(out, detail_paths=()):
     if roof.get("classes"):
         r_["classes"] = {k: [v["steps_per_batch"], round(v["us_per_launch"], 1), round(v["tflops"])] for k, v in roof["classes"].items()}
         r_["classes_columns"] = "launches per batch, us per launch, algorithmic TFLOP/s"
-    line["roofline"] = r_
+    if roof:
+        line["roofline"] = r_
     line["conv_stack_frac"] = rnd(g(out, "conv_stack_whole_frame", "frac"))
     lat = out.get("latency_ms") or {}
     line["latency_ms"] = {k: rnd(lat[k], 3) for k in ("p50_single_frame", "p95_single_frame", "p50_pipelined", "p95_pipelined") if k in lat}
@@ -676,7 +683,7 @@ def compact_line(out, detail_paths=()):
     for drop in (("roofline", "classes_columns"), ("cpu_baseline", "sample"), ("parity", "structured"), ("config", "workload")):   # never reached at today's sizes
         if len(s) <= LINE_LIMIT:
             break
-        line[drop[0]].pop(drop[1], None)
+        line.get(drop[0], {}).pop(drop[1], None)
         s = json.dumps(line, separators=(",", ":"))
     if len(s) > LINE_LIMIT:
         line["summary"] = {k: v for k, v in line["summary"].items() if k in ("fps", "dominant_frac")}
@@ -738,7 +745,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--min_seconds", type=float, default=2.0, help="lower bound of the timed region; --steps is scaled up to reach it")
+    ap.add_argument("--min_seconds", type=float, default=0.0, help="0 (default): exactly --steps frames are timed; S > 0: lower bound of the timed region, "
+                    "--steps is scaled up to reach it")
     ap.add_argument("--num_scales", type=int, default=1)
     ap.add_argument("--scale_gap", type=float, default=0.3)
     ap.add_argument("--precision", default="mixed", choices=["mixed", "fp16", "f16x3", "fp32"],
@@ -768,6 +776,10 @@ def main():
     ap.add_argument("--no_sub_results", action="store_true")
     ap.add_argument("--no_parity", action="store_true", help="skip the people-level parity verdict against the CPU oracle chain (3 frames)")
     ap.add_argument("--dry_dispatch", action="store_true", help="self-test of the multi-rank plumbing without a GPU (no engine): tests/test_bench_spawn.py")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: roofline pass, busy / residency probes, single-frame latency, "
+                    "sub-result legs, CPU baselines, parity, exact-modes table, bench_detail.json (the --no_* flags above trim it)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned for its last frame as DIR/joints.npy and DIR/num_people.npy (rank 0)")
     args = ap.parse_args()
     if args.batch_frames is None:
         args.batch_frames = 5 if args.model == "mpi" else (2 if args.num_scales == 1 else 1)
@@ -861,9 +873,11 @@ def main():
         return [r.synth_frame(1280, 720, i, seed=2 + rank) for i in range(n)]   # the procedural "synthetic 720p video" 
 
     def measure(eng, submit, steps, warmup, in_flight, min_seconds):
-        """Pipelined submit/collect of `steps` frames (at least min_seconds; no instrumentation inside the region).  Returns a dict."""
+        """Pipelined submit/collect of exactly `steps` frames (min_seconds > 0: at least that long; no instrumentation inside the region).
+        Returns a dict; `last` = what rtp_collect returned for the last timed frame."""
         lat = []
         host = {"submit": 0.0, "collect": 0.0, "frames": 0}
+        last = {}
 
         def run(nsteps, base_tag):
             sub = col = 0
@@ -876,7 +890,7 @@ def main():
                     if base_tag:
                         host["submit"] += time.perf_counter() - t_sub[sub - 1]
                 t_c = time.perf_counter()
-                tag, _, _ = eng.collect()
+                tag, n, joints = eng.collect()
                 assert tag == base_tag + col
                 if base_tag:
                     now = time.perf_counter()
@@ -884,15 +898,19 @@ def main():
                     host["frames"] += 1
                     lat.append(now - t_sub.pop(col))
                 col += 1
+            if base_tag and nsteps:
+                last.update(num_people=n, joints=joints)
 
         run(warmup, 0)
         eng.synchronize()
-        t0 = time.perf_counter()
-        ncal = max(16, 2 * in_flight)
-        run(ncal, 0)                      # calibration pass (untimed): frames/s estimate for the step scaling
-        eng.synchronize()
-        est = ncal / (time.perf_counter() - t0)
-        nsteps = scaled_steps(steps, est * 1.1, min_seconds, dist)
+        nsteps = steps
+        if min_seconds > 0:
+            t0 = time.perf_counter()
+            ncal = max(16, 2 * in_flight)
+            run(ncal, 0)                      # calibration pass (untimed): frames/s estimate for the step scaling
+            eng.synchronize()
+            est = ncal / (time.perf_counter() - t0)
+            nsteps = scaled_steps(steps, est * 1.1, min_seconds, dist)
         for attempt in range(4):          # the short calibration pass under-estimates the steady rate: repeat until the region is long enough
             lat.clear()
             host.update(submit=0.0, collect=0.0, frames=0)
@@ -900,7 +918,7 @@ def main():
             if dt >= min_seconds or attempt == 3:
                 break
             nsteps = int(math.ceil(nsteps * min_seconds / dt * 1.15))   # dt is the MAX over ranks: every rank takes the same decision
-        return {"dt": dt, "dt_local": dt_local, "steps_timed": nsteps, "fps": aggregate_fps(nsteps, world, dt), "lat": list(lat),
+        return {"dt": dt, "dt_local": dt_local, "steps_timed": nsteps, "fps": aggregate_fps(nsteps, world, dt), "lat": list(lat), "last": dict(last),
                 "host_ms": {"submit_calls": host["submit"] / max(host["frames"], 1) * 1e3, "collect_calls_incl_wait": host["collect"] / max(host["frames"], 1) * 1e3}}
 
     def roofline_pass(eng, frames, batch_frames, precision, num_scales, model):
@@ -976,24 +994,28 @@ def main():
         del blob
     else:
         eng = make_engine(args.precision, args.num_scales, args.scale_gap, args.batch_frames, args.in_flight)
-    frames = device_frames(eng)
-    u8 = host_frames()
+    frames = device_frames(eng) if args.full or args.input == "resident" else None
+    u8 = host_frames() if args.full or args.input == "host_u8" else None
     if args.input == "host_u8":
         submit = lambda i, tag: eng.submit_frame(u8[i % len(u8)], tag=tag)       # noqa: E731
     else:
         submit = lambda i, tag: eng.submit_device(frames[i % len(frames)], tag=tag)   # noqa: E731
     m = measure(eng, submit, args.steps, args.warmup, args.in_flight, args.min_seconds)
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "joints.npy"), np.asarray(m["last"]["joints"], np.float32))
+        np.save(os.path.join(args.dump_outputs, "num_people.npy"), np.array([m["last"]["num_people"]], np.float64))
     per_rank = None
     if dist is not None:   # every rank's own rate: a straggler shows
         t = torch.zeros(world, dtype=torch.float64, device=red_dev)
         t[rank] = m["steps_timed"] / m["dt_local"]
         dist.all_reduce(t)
         per_rank = [float(v) for v in t.tolist()]
-    # Roofline pass (separate from the timed region, which runs un-instrumented)
-    roof = roofline_pass(eng, frames, args.batch_frames, args.precision, args.num_scales, args.model)
+    roof = busy = stamps = None
+    if args.full:   # Roofline pass (separate from the timed region, which runs un-instrumented)
+        roof = roofline_pass(eng, frames, args.batch_frames, args.precision, args.num_scales, args.model)
     stage = eng.last_stage_ms()
-    busy = None
-    if True:        # the same pipelined loop once more with the busy probe on (~0.5 s): when did the engine have work on the GPU — no profiler attached.
+    if args.full:   # the same pipelined loop once more with the busy probe on (~0.5 s): when did the engine have work on the GPU — no profiler attached.
         try:        # EVERY rank runs it (measure() holds the ranks' barrier and reductions); rank 0's account goes into the line
             eng.busy_probe(1)
             mb = measure(eng, submit, 200, 20, args.in_flight, 0.5)
@@ -1007,21 +1029,20 @@ def main():
         except Exception as ex:  # noqa: BLE001
             busy = {"error": str(ex)}
 
-    stamps = None
-    try:        # the same loop with the residency stamps on (~0.5 s): share of the wall with no kernel on the chip, unprofiled
-        eng.stamp_probe(1)
-        ms_ = measure(eng, submit, 200, 20, args.in_flight, 0.5)
-        eng.synchronize()
-        stamps = stamp_account(eng.stamp_probe(-1))
-        eng.stamp_probe(0)
-        if stamps:
-            stamps["frames_per_s_with_probe"] = ms_["fps"] * (1 if world == 1 else 1.0 / world)
-    except Exception as ex:  # noqa: BLE001
-        stamps = {"error": str(ex)}
-        try:
+        try:        # the same loop with the residency stamps on (~0.5 s): share of the wall with no kernel on the chip, unprofiled
+            eng.stamp_probe(1)
+            ms_ = measure(eng, submit, 200, 20, args.in_flight, 0.5)
+            eng.synchronize()
+            stamps = stamp_account(eng.stamp_probe(-1))
             eng.stamp_probe(0)
-        except Exception:  # noqa: BLE001
-            pass
+            if stamps:
+                stamps["frames_per_s_with_probe"] = ms_["fps"] * (1 if world == 1 else 1.0 / world)
+        except Exception as ex:  # noqa: BLE001
+            stamps = {"error": str(ex)}
+            try:
+                eng.stamp_probe(0)
+            except Exception:  # noqa: BLE001
+                pass
 
     if rank == 0:
         # dominant kernel: the paired 7x7 128->128 convolution (40 of the 92 layers, 50% of all FLOPs).  Average launch duration over
@@ -1049,8 +1070,10 @@ def main():
                        "parallelism": f"frame-sharded replicas x{world}"},
             "latency_ms": {"p50_pipelined": float(np.percentile(m["lat"], 50) * 1e3), "p95_pipelined": float(np.percentile(m["lat"], 95) * 1e3),
                            "batch_on_device": stage["total"]},
-            "host_ms_per_frame": m["host_ms"], "roofline": roof, "conv_stack_whole_frame": whole, "gpu_busy": busy, "kernel_residency": stamps,
+            "host_ms_per_frame": m["host_ms"], "conv_stack_whole_frame": whole,
         }
+        if args.full:
+            out.update(roofline=roof, gpu_busy=busy, kernel_residency=stamps)
         if stamps and "idle_frac" in stamps:
             roof["idle_frac_kernel_stamps"] = round(stamps["idle_frac"], 4)
         if args.precision == "mixed":
@@ -1066,7 +1089,7 @@ def main():
                 out["weight_broadcast"] = wb
         if per_rank:
             out["per_rank_frames_per_s"] = per_rank
-        if world == 1:
+        if world == 1 and args.full:
             try:   # one frame ALONE: commit -> joints on the host (the reference's per-frame latency, rtpose.cpp:1430), nothing else in flight
                 e1 = make_engine(args.precision, args.num_scales, args.scale_gap, 1, 1)
                 lat1 = []
@@ -1082,9 +1105,9 @@ def main():
                 e1.close()
             except Exception as ex:  # noqa: BLE001
                 out["latency_ms"]["single_frame_error"] = str(ex)
-        if world == 1 and not args.no_sub_results:
+        if world == 1 and args.full and not args.no_sub_results:
             out["sub_results"] = sub_results(args, r, eng, make_engine, device_frames, host_frames, measure, roofline_pass, frames, np)
-        if world == 1 and not (args.no_cpu_baseline and args.no_parity):
+        if world == 1 and args.full and not (args.no_cpu_baseline and args.no_parity):
             orc_fr = oracle_frames(eng, args.num_scales, args.model, 3 if not args.no_cpu_baseline else 1)
             if not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(eng, args.num_scales, args.model, oracle=orc_fr)
@@ -1114,7 +1137,7 @@ def main():
 
         rnd = lambda v, n=1: None if v is None else round(float(v), n)   # noqa: E731
         summ = {"fps": rnd(fps), "p50_single_frame_ms": rnd(g(out, "latency_ms", "p50_single_frame"), 3), "p50_pipelined_ms": rnd(g(out, "latency_ms", "p50_pipelined"), 2),
-                "dominant_frac": rnd(roof.get("frac"), 4), "resident_fps": rnd(g(sr, "resident_input", "value")),
+                "dominant_frac": rnd(g(out, "roofline", "frac"), 4), "resident_fps": rnd(g(sr, "resident_input", "value")),
                 "scales3_fps": rnd(g(sr, "scales3_gap0.15", "value")), "scales3_p50_ms": rnd(g(sr, "scales3_gap0.15", "p50_ms"), 2),
                 "scales3_dominant_frac": rnd(g(sr, "scales3_gap0.15", "roofline", "frac"), 4),
                 "mpi_fps": rnd(g(sr, "mpi_496x368", "value")), "mpi_dominant_frac": rnd(g(sr, "mpi_496x368", "roofline", "frac"), 4),
@@ -1124,7 +1147,7 @@ def main():
                 "parity": (g(out, "parity", "verdict") or "")[:40], "parity_replay_identical": g(out, "parity", "replay_identical"),
                 "parity_scales3": (g(sr, "scales3_gap0.15", "parity", "verdict") or "")[:40], "parity_mpi": (g(sr, "mpi_496x368", "parity", "verdict") or "")[:40]}
         out["summary"] = summ
-        detail_paths = write_detail(out)
+        detail_paths = write_detail(out) if args.full else []
         print(compact_line(out, detail_paths))
     eng.close()
     if dist is not None:

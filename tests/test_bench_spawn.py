@@ -23,7 +23,7 @@ def test_bare_gpus_2_spawns_two_ranks_and_prints_one_line():
     assert len(lines) == 1                       # rank 0 only
     out = lines[0]
     assert out["n_gpus"] == 2 and out["steps"] == 20 and out["warmup"] == 2
-    assert out["steps_timed"] >= 20              # --steps is a minimum: scaled to --min_seconds, same on every rank
+    assert out["steps_timed"] == 20              # --steps is the number of timed steps, the same on every rank
     assert out["value"] > 0
     assert len(out["per_rank_frames_per_s"]) == 2 and all(v > 0 for v in out["per_rank_frames_per_s"])   # a straggler would show here
 
@@ -60,7 +60,7 @@ def test_two_ranks_on_one_gpu_with_weight_broadcast():
     floats) broadcast to rank 1 and imported, barrier + MAX-reduce around the timed region, one line from rank 0 with both ranks' rates."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--devices", "0,0", "--comm", "gloo", "--broadcast_weights", "--steps", "60", "--warmup", "10",
-                        "--min_seconds", "0.5", "--no_cpu_baseline", "--no_sub_results", "--no_parity"], capture_output=True, text=True, timeout=900, env=env)
+                        "--min_seconds", "0.5", "--full", "--no_cpu_baseline", "--no_sub_results", "--no_parity"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

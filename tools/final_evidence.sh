@@ -17,12 +17,12 @@ T=$(mktemp -d)
   echo; echo "# ... --start_scale 0.8 --num_scales 2 --scale_gap 0.15 --resolution 640x360 (round 5: a start scale below 1, a display smaller than the net input)"
   caffe_rtpose_amd/rtpose.bin --video synthetic:1280x720:600 --model coco --start_scale 0.8 --num_scales 2 --scale_gap 0.15 --resolution 640x360 --write_json $T/j5 --no_frame_drops --no_display --frames_in_flight 4 --batch_frames 1 2>&1 | tail -4 ) 2>&1 | grep -v amdgpu.ids > $O/cli.txt
 tail -3 $O/cli.txt; rm -rf $T
-( echo "# python bench.py --gpus 2 --devices 0,0 --comm gloo --broadcast_weights --no_cpu_baseline --no_sub_results --no_parity   (two ranks on the one GPU)"
-  timeout 300 python bench.py --gpus 2 --devices 0,0 --comm gloo --broadcast_weights --no_cpu_baseline --no_sub_results --no_parity 2>&1 | grep "^{" 
+( echo "# python bench.py --gpus 2 --devices 0,0 --comm gloo --broadcast_weights --full --no_cpu_baseline --no_sub_results --no_parity   (two ranks on the one GPU)"
+  timeout 300 python bench.py --gpus 2 --devices 0,0 --comm gloo --broadcast_weights --full --no_cpu_baseline --no_sub_results --no_parity 2>&1 | grep "^{" 
   echo; echo "# the same with --comm nccl: RCCL refuses two ranks on one device; does every rank fall back to gloo?"
-  timeout 300 python bench.py --gpus 2 --devices 0,0 --comm nccl --no_cpu_baseline --no_sub_results --no_parity 2>&1 | grep "^{\|rror" | cut -c1-1500 | head -8; echo "rc $?"
-  echo; echo "# python bench.py --calibrate 2 --no_cpu_baseline --no_sub_results --no_parity   (load-time calibration on the default synthetic weights)"
-  timeout 300 python bench.py --calibrate 2 --no_cpu_baseline --no_sub_results --no_parity 2>&1 | grep "^{" ) > $O/bench_two_ranks_and_calibration.txt 2>&1
+  timeout 300 python bench.py --gpus 2 --devices 0,0 --comm nccl --full --no_cpu_baseline --no_sub_results --no_parity 2>&1 | grep "^{\|rror" | cut -c1-1500 | head -8; echo "rc $?"
+  echo; echo "# python bench.py --calibrate 2 --full --no_cpu_baseline --no_sub_results --no_parity   (load-time calibration on the default synthetic weights)"
+  timeout 300 python bench.py --calibrate 2 --full --no_cpu_baseline --no_sub_results --no_parity 2>&1 | grep "^{" ) > $O/bench_two_ranks_and_calibration.txt 2>&1
 cut -c1-300 $O/bench_two_ranks_and_calibration.txt | head -12
 bash tools/collect_profiles.sh mixed > $O/collect.log 2>&1; tail -2 $O/collect.log
 bash tools/pmc_plan.sh mixed 1 3 coco $O/dominant_conv_pmc_mixed_b1_n3.txt > /dev/null 2>&1
