@@ -42,6 +42,18 @@ class rtp_config(C.Structure):
     ]
 
 
+class rtp_frame_view(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("data", C.c_void_p),
+        ("width", C.c_int),
+        ("height", C.c_int),
+        ("row_stride", C.c_long),
+        ("pixel_stride", C.c_long),
+        ("channel_offset", C.c_long * 3),
+    ]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 vp = C.c_void_p
@@ -124,6 +136,8 @@ SIGNATURES = {
     "rtp_weight_blob_import": (C.c_int, [vp, vp, C.c_size_t]),
     "rtp_copy_weights_from": (C.c_int, [vp, vp]),
     "rtp_device_local_cpus": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t]),
+    "rtp_submit_frame_device": (C.c_int, [vp, C.POINTER(rtp_frame_view), vp, C.c_uint64, fp]),
+    "rtp_collect_rendered_device": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(rtp_frame_view), vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

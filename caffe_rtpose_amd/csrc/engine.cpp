@@ -142,6 +142,11 @@ struct Slot {
   unsigned char* render_dev = nullptr;  // cfg.render: display image with the pose overlay
   unsigned char* render_host = nullptr; // pinned copy of it
   float* render_tab = nullptr;
+  // rtp_submit_frame_device: ev_ready = the producer's stream at the submit (the staging stream waits on it), ev_read = the caller's frame
+  // has been read (the producer's stream waits on it).  rtp_collect_rendered_device: ev_export = the export of render_dev through the
+  // caller's view is done; while export_pending, the context's next batch (whose render overwrites render_dev) waits on it first.
+  hipEvent_t ev_ready = nullptr, ev_read = nullptr, ev_export = nullptr;
+  bool export_pending = false;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -1035,7 +1040,8 @@ int upload_all_weights(rtp_engine* e) {
 
 // ---- launches -------------------------------------------------------------------------------
 // Residency-stamp slots of one batch context: [0, 64) plan steps (conv stack), 64 + 8 j + {0 strip, 1 write, 2 pairs, 3 match, 4 assemble}
-// = frame j's post-processing chain, 200 + 2 j + {0 warp, 1 area/pad} = frame j's device pre-processing.
+// = frame j's post-processing chain, 64 + 8 j + 5 = the export of its rendered image (rtp_collect_rendered_device), 200 + 2 j +
+// {0 warp or import of a device frame, 1 area/pad} = frame j's device pre-processing.
 constexpr int STAMP_SLOTS = 256;
 unsigned long long* stamp_slot(const rtp_engine* e, const Ctx& cx, int idx) {
   return (e->stamp_probe && cx.stamps && idx >= 0 && idx < STAMP_SLOTS) ? cx.stamps + 2 * (size_t)idx : nullptr;
@@ -1043,6 +1049,8 @@ unsigned long long* stamp_slot(const rtp_engine* e, const Ctx& cx, int idx) {
 // the stamps of the batch that last ran on `cx` (complete: the context is idle) -> e->stamp_spans; slots zeroed for the next batch
 int stamp_harvest(rtp_engine* e, Ctx& cx) {
   if (!cx.stamps || !cx.stamps_dirty) return RTP_OK;
+  for (Slot& sl : cx.slot)   // an export on the caller's stream stamps slot 64 + 8 j + 5 (a host wait: probe runs only)
+    if (sl.export_pending) HIPCHK(e, hipEventSynchronize(sl.ev_export));
   std::vector<unsigned long long> h(2 * STAMP_SLOTS);
   HIPCHK(e, hipMemcpy(h.data(), cx.stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   HIPCHK(e, hipMemset(cx.stamps, 0, h.size() * sizeof(unsigned long long)));
@@ -1430,6 +1438,11 @@ int capture_batch(rtp_engine* e, Ctx& cx, int nframes, hipGraphExec_t* out) {
 int flush_prep(rtp_engine* e, Ctx& cx, bool force);
 int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bool materialize = false) {
   int rc;
+  for (Slot& sl : cx.slot)   // the previous batch's rendered images are still being exported on a caller's stream: this batch renders over them
+    if (sl.export_pending) {
+      HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_export, 0));
+      sl.export_pending = false;
+    }
   if (e->prep_defer && (rc = flush_prep(e, cx, true))) return rc;
   if (cx.in_pending) {   // the batch's inputs were staged on the staging stream: the conv stream starts when the last of them is complete
     if (cx.in_stream != cx.stream) {
@@ -1638,6 +1651,8 @@ void free_ctx(Ctx& cx) {
   if (cx.ev_in) (void)hipEventDestroy(cx.ev_in);
   for (Slot& sl : cx.slot) {
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);
+    if (sl.export_pending) (void)hipEventSynchronize(sl.ev_export);   // an export on the caller's stream may still read render_dev
+    for (hipEvent_t ev : {sl.ev_ready, sl.ev_read, sl.ev_export}) if (ev) (void)hipEventDestroy(ev);
     void* dptrs[] = {sl.resized, sl.peaks, sl.strip_count, sl.strip_list, sl.cand_score, sl.cand_ij, sl.cand_count, sl.cand_blk, sl.conn, sl.conn_score,
                      sl.conn_count, sl.tickets, sl.joints, sl.num_people, sl.frame_dev, sl.disp_dev, sl.render_dev, sl.render_tab};
     for (void* p : dptrs) if (p) (void)hipFree(p);
@@ -1794,6 +1809,105 @@ int flush_prep(rtp_engine* e, Ctx& cx, bool force) {
     HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * (int)sj + 1), sl.disp_cur, e->cfg.disp_w, e->cfg.disp_h, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.stream));
     sl.copy_pending = false;
   }
+  return RTP_OK;
+}
+
+// ---- frames in the caller's device memory (rtp_submit_frame_device / rtp_collect_rendered_device) ----------------------------------
+// Every view is checked here, on the host, before a kernel can see it.  Fields first (no HIP call: also for a NULL engine, whose message
+// rtp_last_error(NULL) returns); hi = the highest byte offset from data the view addresses.
+int check_view_fields(rtp_engine* e, const rtp_frame_view* v, const char* fn, FrameView* fv, long* hi) {
+  if (!v) return fail(e, RTP_EINVAL, "%s: NULL frame view", fn);
+  if (v->struct_size != sizeof(rtp_frame_view))
+    return fail(e, RTP_EINVAL, "%s: rtp_frame_view.struct_size is %u, this library's rtp_frame_view has %zu bytes", fn, v->struct_size, sizeof(rtp_frame_view));
+  if (v->width < 1 || v->height < 1) return fail(e, RTP_EINVAL, "%s: view size %d x %d", fn, v->width, v->height);
+  if ((long long)v->width * v->height >= (1LL << 31)) return fail(e, RTP_EINVAL, "%s: a view of 2^31 pixels or more", fn);
+  if (v->row_stride < 0 || v->pixel_stride < 1)
+    return fail(e, RTP_EINVAL, "%s: row_stride %ld, pixel_stride %ld (need >= 0 and >= 1)", fn, v->row_stride, v->pixel_stride);
+  long omax = 0;
+  for (int c = 0; c < 3; ++c) {
+    if (v->channel_offset[c] < 0) return fail(e, RTP_EINVAL, "%s: channel_offset[%d] = %ld is negative", fn, c, v->channel_offset[c]);
+    omax = std::max(omax, v->channel_offset[c]);
+  }
+  if (!v->data) return fail(e, RTP_EINVAL, "%s: NULL data", fn);
+  long a, b;
+  if (__builtin_mul_overflow((long)(v->height - 1), v->row_stride, &a) || __builtin_mul_overflow((long)(v->width - 1), v->pixel_stride, &b) ||
+      __builtin_add_overflow(a, b, hi) || __builtin_add_overflow(*hi, omax, hi))
+    return fail(e, RTP_EINVAL, "%s: the view's extent overflows", fn);
+  fv->data = (unsigned char*)v->data;
+  fv->w = v->width; fv->h = v->height;
+  fv->row = v->row_stride; fv->pix = v->pixel_stride;
+  for (int c = 0; c < 3; ++c) fv->off[c] = v->channel_offset[c];
+  return RTP_OK;
+}
+
+// hipStreamIsCapturing before any other HIP call of the entry point: the engine's launches cannot become part of a caller's capture
+int check_caller_stream(rtp_engine* e, void* stream, const char* fn) {
+  if (!stream) return RTP_OK;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  const hipError_t s = hipStreamIsCapturing((hipStream_t)stream, &st);
+  if (s != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(e, RTP_EINVAL, "%s: hipStreamIsCapturing on the caller's stream failed: %s", fn, hipGetErrorString(s));
+  }
+  if (st != hipStreamCaptureStatusNone) return fail(e, RTP_EINVAL, "%s: the caller's stream is capturing a graph (the engine's launches cannot join it)", fn);
+  return RTP_OK;
+}
+
+// The memory behind the view: device memory of cfg.device_id, every addressed byte inside the allocation that holds data.  A failed
+// query is cleared from HIP's last error, so that the next launch of a valid call does not report it.
+int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long hi, int* layout) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  hipError_t s = hipPointerGetAttributes(&at, fv.data);
+  if (s != hipSuccess || at.type == hipMemoryTypeUnregistered) {
+    (void)hipGetLastError();
+    return fail(e, RTP_EINVAL, "%s: data %p is not memory of this library's HIP runtime: pageable host memory, or a pointer of a second HIP "
+                "runtime in the process (PyTorch bundles its own: import torch BEFORE the engine library so that one runtime serves both)", fn, (void*)fv.data);
+  }
+  if (at.type != hipMemoryTypeDevice)
+    return fail(e, RTP_EINVAL, "%s: data %p is %s memory, not device memory", fn, (void*)fv.data, at.type == hipMemoryTypeHost ? "(pinned) host" : "managed");
+  if (at.device != e->cfg.device_id) return fail(e, RTP_EINVAL, "%s: data %p is memory of device %d, the engine runs on device %d", fn, (void*)fv.data, at.device, e->cfg.device_id);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  s = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)fv.data);
+  if (s != hipSuccess || !base) {
+    (void)hipGetLastError();
+    return fail(e, RTP_EINVAL, "%s: hipMemGetAddressRange(%p) failed: %s", fn, (void*)fv.data, hipGetErrorString(s));
+  }
+  const size_t avail = (size_t)((const char*)base + size - (const char*)fv.data);
+  if ((size_t)hi >= avail)
+    return fail(e, RTP_EINVAL, "%s: the view addresses bytes up to %ld past data, its allocation ends %zu bytes past data", fn, hi, avail);
+  *layout = frame_layout(fv, avail);
+  return RTP_OK;
+}
+
+// A caller's device frame -> frame slot sj of cx.input.  The display image is always the slot's own disp_dev (area_pad and the renderer
+// read it after this call has released the caller's memory): the import kernel when the frame has the display size, else the cubic warp
+// reading the view in place.  Ordering by events only: the staging stream waits for the producer's stream, the producer's stream waits
+// for the kernel that read the frame (not for the batch).  No copy to defer: prep_defer has nothing to do for such a frame.
+int enqueue_preprocess_view(rtp_engine* e, Ctx& cx, int sj, const FrameView& v, int layout, hipStream_t producer, float* frame_scale) {
+  Slot& sl = cx.slot[sj];
+  const int dw = e->cfg.disp_w, dh = e->cfg.disp_h;
+  if (!sl.disp_dev) { SYNC_GUARD; HIPCHK(e, hipMalloc((void**)&sl.disp_dev, (size_t)dw * dh * 3)); }
+  if (!sl.ev_ready) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_ready, hipEventDisableTiming));
+  if (!sl.ev_read) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_read, hipEventDisableTiming));
+  const double s = rtp_display_fit_scale(v.w, v.h, dw, dh);
+  if (frame_scale) *frame_scale = (float)s;
+  if (producer) {
+    HIPCHK(e, hipEventRecord(sl.ev_ready, producer));
+    HIPCHK(e, hipStreamWaitEvent(cx.in_stream, sl.ev_ready, 0));
+  }
+  unsigned long long* st = stamp_slot(e, cx, 200 + 2 * sj);
+  if (v.w == dw && v.h == dh) HIPCHK(e, launch_frame_import(st, v, layout, sl.disp_dev, cx.in_stream));
+  else HIPCHK(e, launch_warp_view(st, v, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, dw, dh, cx.in_stream));
+  sl.disp_cur = sl.disp_dev;
+  if (producer) {
+    HIPCHK(e, hipEventRecord(sl.ev_read, cx.in_stream));
+    HIPCHK(e, hipStreamWaitEvent(producer, sl.ev_read, 0));
+  }
+  float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
+  HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, dw, dh, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
+  cx.in_pending = true;
   return RTP_OK;
 }
 
@@ -2312,6 +2426,29 @@ int rtp_submit_frame(rtp_engine* e, const unsigned char* bgr, int w, int h, uint
   return commit_slot(e, ci, sj, tag);
 }
 
+// rtp_submit_frame from a view of the caller's device memory, ordered against the caller's stream by events.
+int rtp_submit_frame_device(rtp_engine* e, const rtp_frame_view* frame, void* stream, uint64_t tag, float* frame_scale) {
+  static const char* fn = "rtp_submit_frame_device";
+  FrameView fv;
+  long hi = 0;
+  int rc, layout = LAYOUT_GENERIC, ci, sj;
+  if ((rc = check_view_fields(e, frame, fn, &fv, &hi))) return rc;
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if ((rc = check_caller_stream(e, stream, fn))) return rc;
+  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
+  if ((rc = use_device(e))) return rc;
+  if ((rc = need_weights(e))) return rc;
+  if (!e->gpu_prep_ok) return fail(e, RTP_EINVAL, "device pre-processing unavailable for this configuration (a level would be enlarged)");
+  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
+  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  Ctx& cx = e->ctx[ci];
+  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
+  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier host frame of this batch whose copy is done by now
+  if ((rc = enqueue_preprocess_view(e, cx, sj, fv, layout, (hipStream_t)stream, frame_scale))) return rc;
+  cx.slot[sj].has_disp = true;
+  return commit_slot(e, ci, sj, tag);
+}
+
 // Launch a partially filled batch now (end of stream, or a latency-sensitive caller).
 int rtp_flush(rtp_engine* e) {
   if (!e) return RTP_EINVAL;
@@ -2416,6 +2553,39 @@ static int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_pe
   return RTP_OK;
 }
 
+// rtp_collect_rendered with the image exported through a view of the caller's device memory.  Every refusal happens before the frame is
+// taken off the FIFO.  The export runs on the caller's stream (NULL: on the frame's own stream, waited for here); the host has already
+// waited for the frame's last event in collect_impl, so the rendered image is complete when the export is enqueued.
+int rtp_collect_rendered_device(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, const rtp_frame_view* out, void* stream) {
+  static const char* fn = "rtp_collect_rendered_device";
+  FrameView fv;
+  long hi = 0;
+  int rc, layout = LAYOUT_GENERIC;
+  if ((rc = check_view_fields(e, out, fn, &fv, &hi))) return rc;
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if ((rc = check_caller_stream(e, stream, fn))) return rc;
+  if (!e->cfg.render) return fail(e, RTP_EINVAL, "%s needs rtp_config.render >= 1", fn);
+  if (fv.w != e->cfg.disp_w || fv.h != e->cfg.disp_h)
+    return fail(e, RTP_EINVAL, "%s: the output view is %d x %d, the display image %d x %d", fn, fv.w, fv.h, e->cfg.disp_w, e->cfg.disp_h);
+  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
+  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
+  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
+  Ctx& cx = e->ctx[ci];
+  Slot& sl = cx.slot[sj];
+  if (!sl.has_disp) return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", fn);
+  if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : sl.stream;
+  if (!sl.ev_export) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_export, hipEventDisableTiming));
+  HIPCHK(e, launch_frame_export(stamp_slot(e, cx, 64 + 8 * sj + 5), sl.render_dev, fv, layout, st));
+  HIPCHK(e, hipEventRecord(sl.ev_export, st));
+  sl.export_pending = true;
+  if (!stream) {
+    HIPCHK(e, hipEventSynchronize(sl.ev_export));
+    sl.export_pending = false;
+  }
+  return RTP_OK;
+}
+
 int rtp_last_stage_ms(const rtp_engine* e, float ms[5]) {
   if (!e || !ms) return RTP_EINVAL;
   memcpy(ms, e->last_ms, sizeof e->last_ms);
@@ -2426,7 +2596,15 @@ int rtp_last_stage_ms(const rtp_engine* e, float ms[5]) {
 static int need_idle(rtp_engine* e) {
   if (!e) return RTP_EINVAL;
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "parity taps need an idle engine (collect %zu frames first)", e->fifo.size());
-  return use_device(e);
+  int rc;
+  if ((rc = use_device(e))) return rc;
+  for (Ctx& cx : e->ctx)   // the taps reuse context 0's buffers on the host's clock: no export of a rendered image may still read them
+    for (Slot& sl : cx.slot)
+      if (sl.export_pending) {
+        HIPCHK(e, hipEventSynchronize(sl.ev_export));
+        sl.export_pending = false;
+      }
+  return RTP_OK;
 }
 
 int rtp_forward_debug(rtp_engine* e, const float* h_in, float* lowres, float* resized, float* peaks, float* joints, int* num_people) {

@@ -192,6 +192,27 @@ hipError_t launch_warp(unsigned long long* stamp, const unsigned char* src, int 
 hipError_t launch_area_pad(unsigned long long* stamp, const unsigned char* disp, int dw, int dh, const AreaScale* scales, int nscales, float* out, int net_w, int net_h,
                            hipStream_t stream);
 
+// A caller's u8 frame in device memory (rtp_frame_view, checked on the host before any launch): channel c (0 B, 1 G, 2 R) of pixel
+// (x, y) is the byte at data + y * row + x * pix + off[c].
+struct FrameView {
+  unsigned char* data;
+  int w, h;
+  long row, pix;
+  long off[3];
+};
+// How the import / export kernels address a view.  The specialised layouts move 4 pixels per thread with dword loads and stores
+// (frame_layout picks them only where data, row and every plane start are 4-byte aligned and w % 4 == 0); GENERIC gathers bytes.
+enum FrameLayout { LAYOUT_GENERIC = 0, LAYOUT_HWC3_BGR, LAYOUT_HWC3_RGB, LAYOUT_HWC4_BGR, LAYOUT_HWC4_RGB, LAYOUT_PLANAR };
+// avail = bytes from data to the end of its allocation: a 4-channel layout also reads (and rewrites unchanged) each pixel's 4th byte
+int frame_layout(const FrameView& v, size_t avail);
+// view (v.w x v.h) -> packed u8 BGR HWC of the same size
+hipError_t launch_frame_import(unsigned long long* stamp, const FrameView& v, int layout, unsigned char* dst, hipStream_t stream);
+// packed u8 BGR HWC (v.w x v.h) -> the three named channels of the view
+hipError_t launch_frame_export(unsigned long long* stamp, const unsigned char* src, const FrameView& v, int layout, hipStream_t stream);
+// launch_warp reading the caller's view in place of a packed frame (same per-pixel arithmetic)
+hipError_t launch_warp_view(unsigned long long* stamp, const FrameView& v, double inv, const short* tab2d, unsigned char* dst, int dw, int dh,
+                            hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------
 // Renderer (row 8f-3): render.hip
 // ---------------------------------------------------------------------------------------

@@ -1,9 +1,10 @@
 """ctypes mirror of include/rtpose_mi355x.h (numpy in / numpy out).  Plumbing only."""
 import ctypes as C
+import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -257,6 +258,59 @@ def plan_summary(cfg):
     return buf.raw[:n].decode()
 
 
+def frame_view(obj, order="bgr"):
+    """The rtp_frame_view fields of a u8 frame in device memory, from its __cuda_array_interface__ (nothing touches the GPU).
+
+    Shapes: (H, W, 3|4) HWC or (3, H, W) planar CHW (HWC wins where both would fit); any strides, so a crop of a larger tensor
+    keeps its parent's row pitch.  order = the frame's channel order, "bgr" or "rgb" (a 4th channel is never read or written).
+    Returns a dict: data, width, height, row_stride, pixel_stride, channel_offset = byte offsets of (B, G, R) from a pixel."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TypeError(f"{type(obj).__name__} has no __cuda_array_interface__: device frames only (host arrays go to submit_frame)")
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
+    if cai["typestr"][1:] != "u1":
+        raise ValueError(f"dtype {cai['typestr']}: frames are u8")
+    shape = tuple(int(d) for d in cai["shape"])
+    if len(shape) != 3:
+        raise ValueError(f"shape {shape}: (H, W, 3|4) or (3, H, W)")
+    strides = cai.get("strides")
+    if strides is None:   # C-contiguous
+        strides = (shape[1] * shape[2], shape[2], 1)
+    strides = tuple(int(s) for s in strides)
+    if shape[2] in (3, 4):
+        (h, w, _), (rs, ps, cs) = shape, strides
+    elif shape[0] == 3:
+        (_, h, w), (cs, rs, ps) = shape, strides
+    else:
+        raise ValueError(f"shape {shape}: 3 or 4 channels, (H, W, 3|4) or (3, H, W)")
+    offs = (0, cs, 2 * cs) if order == "bgr" else (2 * cs, cs, 0)
+    return dict(data=int(cai["data"][0]), width=w, height=h, row_stride=rs, pixel_stride=ps, channel_offset=offs)
+
+
+def _view_struct(f):
+    v = rtp_frame_view()
+    v.struct_size = C.sizeof(rtp_frame_view)
+    v.data, v.width, v.height = f["data"], f["width"], f["height"]
+    v.row_stride, v.pixel_stride = f["row_stride"], f["pixel_stride"]
+    for c in range(3):
+        v.channel_offset[c] = f["channel_offset"][c]
+    return v
+
+
+def _stream_of(obj, stream):
+    """(handle or None, torch default stream?) of the stream a device frame is ordered on.  stream: a torch.cuda.Stream, a raw
+    hipStream_t as int, or None = torch's current stream of a tensor's device, else the interface's `stream` entry, else NULL."""
+    if stream is not None:
+        return getattr(stream, "cuda_stream", stream) or None, False
+    torch = sys.modules.get("torch")   # never imported here: a torch tensor means torch is loaded already
+    if torch is not None and isinstance(obj, torch.Tensor):
+        h = torch.cuda.current_stream(obj.device).cuda_stream
+        return h or None, not h
+    s = obj.__cuda_array_interface__.get("stream")
+    return (None if s in (None, 1) else s), False   # 1 = the legacy default stream: NULL
+
+
 class Engine:
     """One engine per GPU worker, like one caffe::Net per processFrame thread (rtpose.cpp:1463-1472)."""
 
@@ -303,6 +357,18 @@ class Engine:
         self._chk(lib.rtp_submit_frame(self.h, img.ctypes.data_as(C.POINTER(C.c_ubyte)), img.shape[1], img.shape[0], tag, C.byref(fs)))
         return fs.value
 
+    def submit_frame_device(self, frame, tag=0, stream=None, order="bgr"):
+        """rtp_submit_frame_device: a u8 frame in device memory (see frame_view), read on the GPU in order with `stream` (see
+        _stream_of).  On torch's legacy default stream the frame is made complete first (the NULL-stream contract: it must then
+        stay unmodified until its collect); a side stream needs no host wait.  Returns Frame::scale."""
+        v = _view_struct(frame_view(frame, order))
+        st, legacy = _stream_of(frame, stream)
+        if legacy:
+            sys.modules["torch"].cuda.current_stream(frame.device).synchronize()
+        fs = C.c_float()
+        self._chk(lib.rtp_submit_frame_device(self.h, C.byref(v), st, tag, C.byref(fs)))
+        return fs.value
+
     def debug_preprocess(self, img_u8):
         img = np.ascontiguousarray(img_u8, np.uint8)
         x = np.empty((self.N, 3, self.net_h, self.net_w), np.float32)
@@ -347,6 +413,17 @@ class Engine:
         img = np.empty((self.cfg.c.disp_h, self.cfg.c.disp_w, 3), np.uint8)
         self._chk(lib.rtp_collect_rendered(self.h, C.byref(tag), _f(joints), C.byref(n), _u8(img)))
         return tag.value, n.value, joints[: n.value].copy(), img
+
+    def collect_rendered_device(self, out, stream=None, order="bgr"):
+        """rtp_collect_rendered_device: the rendered display image written into `out` (u8 device memory of disp_w x disp_h, see
+        frame_view); work queued on `stream` afterwards sees it.  Returns (tag, num_people, joints)."""
+        v = _view_struct(frame_view(out, order))
+        st, _ = _stream_of(out, stream)
+        tag = C.c_uint64()
+        n = C.c_int()
+        joints = np.zeros((MAX_PEOPLE, self.num_parts, 3), np.float32)
+        self._chk(lib.rtp_collect_rendered_device(self.h, C.byref(tag), _f(joints), C.byref(n), C.byref(v), st))
+        return tag.value, n.value, joints[: n.value].copy()
 
     def flush(self):
         self._chk(lib.rtp_flush(self.h))

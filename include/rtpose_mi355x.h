@@ -395,6 +395,40 @@ int rtp_caffemodel_layer(const char* path, int index, char* name, int name_len, 
  * configuration per layer, L1/L2 pairing, arena sizes).  Returns bytes written or a negative code. */
 long rtp_plan_summary(const rtp_config* cfg, char* buf, size_t buflen);
 
+/* ---- frames already in GPU memory (no reference counterpart: the producer's OpenCV frames live on the host) ---------- */
+
+/* A u8 frame in device memory: channel c of pixel (x, y) is the byte at data + y*row_stride + x*pixel_stride + channel_offset[c].
+ * HWC BGR: pixel_stride 3, offsets {0, 1, 2}; RGB: {2, 1, 0}; BGRA / RGBA: pixel_stride 4; planar CHW RGB of plane stride P:
+ * pixel_stride 1, offsets {2P, P, 0}; a crop of a larger image: its first pixel as data, the larger image's row_stride. */
+typedef struct rtp_frame_view {
+  unsigned int struct_size;   /* sizeof(rtp_frame_view); any other value -> RTP_EINVAL */
+  void* data;                 /* device memory on cfg.device_id (const for submit, written by collect) */
+  int width, height;
+  long row_stride;            /* bytes between rows, >= 0 */
+  long pixel_stride;          /* bytes between neighbouring pixels of a row, >= 1 (3 BGR, 4 BGRA, 1 planar) */
+  long channel_offset[3];     /* byte offsets of B, G, R from a pixel's address (planar RGB: 2*plane, plane, 0) */
+} rtp_frame_view;
+
+/* = rtp_submit_frame on the pixels the view describes, read on the GPU.  `stream` (a hipStream_t of the
+ * producer, may be NULL): the engine reads the frame only after the work queued on `stream` so far, and work
+ * queued on `stream` after this call returns runs only after the engine has finished reading the frame.
+ * NULL: the frame is complete now and stays unmodified until the rtp_collect* of `tag` returns.
+ * Every view is checked on the host before anything is launched (RTP_EINVAL + rtp_last_error, the engine stays
+ * usable): struct_size, sizes >= 1, strides and offsets >= 0, data = device memory of cfg.device_id
+ * (hipPointerGetAttributes: host, pinned host and another device's memory are refused), every addressed byte
+ * inside the allocation that holds data (hipMemGetAddressRange), a stream that is not capturing, and a
+ * configuration in which the device pre-processing runs (see rtp_debug_preprocess).  A process that also uses
+ * PyTorch must let ONE HIP runtime serve both: import torch before loading this library. */
+int rtp_submit_frame_device(rtp_engine* e, const rtp_frame_view* frame, void* stream, uint64_t tag, float* frame_scale);
+
+/* = rtp_collect_rendered, with the display image written through `out` (disp_w x disp_h, the three named
+ * channels only; a 4th channel is left untouched).  Work queued on `stream` after this call sees the
+ * image.  NULL stream: the image is complete when the call returns.  Refused (RTP_EINVAL, nothing collected):
+ * a view that fails the checks above or is not disp_w x disp_h, render == 0, and an oldest frame without a
+ * display image (submitted as a net input: collect it with rtp_collect). */
+int rtp_collect_rendered_device(rtp_engine* e, uint64_t* tag, float* joints, int* num_people,
+                                const rtp_frame_view* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
