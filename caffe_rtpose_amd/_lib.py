@@ -138,6 +138,10 @@ SIGNATURES = {
     "rtp_device_local_cpus": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t]),
     "rtp_submit_frame_device": (C.c_int, [vp, C.POINTER(rtp_frame_view), vp, C.c_uint64, fp]),
     "rtp_collect_rendered_device": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(rtp_frame_view), vp]),
+    "rtp_jpeg_max_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "rtp_encode_jpeg_device": (C.c_int, [vp, C.POINTER(rtp_frame_view), C.c_int, vp, C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rtp_set_render_jpeg": (C.c_int, [vp, C.c_int]),
+    "rtp_collect_rendered_jpeg": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/rtpose_mi355x.h"
+#include "jpeg_bound.h"
 
 namespace {
 
@@ -848,7 +849,83 @@ void fdct_islow(int* data) {
 
 inline int bit_category(int v) { const unsigned a = (unsigned)(v < 0 ? -v : v); return a ? 32 - __builtin_clz(a) : 0; }
 
+// jcparam.c jpeg_set_quality: the standard tables scaled by quality (clamped to 1..100), force_baseline
+void jpeg_qtables(int quality, unsigned char qt[2][64]) {
+  if (quality < 1) quality = 1;
+  if (quality > 100) quality = 100;
+  const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;  // jpeg_quality_scaling
+  for (int t = 0; t < 2; ++t)
+    for (int i = 0; i < 64; ++i) {
+      long v = ((long)(t ? kStdChrQ[i] : kStdLumQ[i]) * scale + 50L) / 100L;
+      if (v <= 0) v = 1;
+      if (v > 255) v = 255;  // force_baseline
+      qt[t][i] = (unsigned char)v;
+    }
+}
+
+// SOI, JFIF APP0, two DQT, SOF0 (4:2:0), four DHT, SOS: everything in front of the entropy-coded segment
+void jpeg_header(int W, int H, const unsigned char qt[2][64], std::vector<unsigned char>& o) {
+  auto put16 = [&](int v) { o.push_back((unsigned char)(v >> 8)); o.push_back((unsigned char)v); };
+  o.push_back(0xFF); o.push_back(0xD8);
+  const unsigned char app0[] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  o.insert(o.end(), app0, app0 + sizeof app0);
+  for (int t = 0; t < 2; ++t) {
+    o.push_back(0xFF); o.push_back(0xDB); put16(67); o.push_back((unsigned char)t);
+    for (int i = 0; i < 64; ++i) o.push_back(qt[t][kZigzag[i]]);
+  }
+  o.push_back(0xFF); o.push_back(0xC0); put16(17); o.push_back(8); put16(H); put16(W); o.push_back(3);
+  o.push_back(1); o.push_back(0x22); o.push_back(0);
+  o.push_back(2); o.push_back(0x11); o.push_back(1);
+  o.push_back(3); o.push_back(0x11); o.push_back(1);
+  auto dht = [&](int tc_th, const unsigned char* bits, const unsigned char* vals, int nv) {
+    o.push_back(0xFF); o.push_back(0xC4); put16(2 + 1 + 16 + nv); o.push_back((unsigned char)tc_th);
+    for (int i = 1; i <= 16; ++i) o.push_back(bits[i]);
+    o.insert(o.end(), vals, vals + nv);
+  };
+  dht(0x00, kDcLumBits, kDcVals, 12);
+  dht(0x10, kAcLumBits, kAcLumVals, 162);
+  dht(0x01, kDcChrBits, kDcVals, 12);
+  dht(0x11, kAcChrBits, kAcChrVals, 162);
+  const unsigned char sos[] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+  o.insert(o.end(), sos, sos + sizeof sos);
+}
+
 }  // namespace
+
+// What the GPU encoder (jpeg_enc.hip) takes from the host: the quantisers of `quality`, the header of a W x H file, the Huffman code
+// tables {DC luma, AC luma, DC chroma, AC chroma}.  Returns the header's length, or 0 if it does not fit header_cap.
+size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64], unsigned char* header, size_t header_cap,
+                               unsigned short huff_code[4][256], unsigned char huff_size[4][256]) {
+  jpeg_qtables(quality, qt);
+  std::vector<unsigned char> o;
+  jpeg_header(W, H, qt, o);
+  if (o.size() > header_cap) return 0;
+  memcpy(header, o.data(), o.size());
+  const unsigned char* bits[4] = {kDcLumBits, kAcLumBits, kDcChrBits, kAcChrBits};
+  const unsigned char* vals[4] = {kDcVals, kAcLumVals, kDcVals, kAcChrVals};
+  for (int t = 0; t < 4; ++t) {
+    EncHuff h;
+    build_enc_huff(&h, bits[t], vals[t]);
+    memcpy(huff_code[t], h.code, sizeof h.code);
+    memcpy(huff_size[t], h.size, sizeof h.size);
+  }
+  return o.size();
+}
+
+// The largest file rtp_encode_jpeg can write for w x h: the header, every block at its worst (DC: 11-bit code + 11 bits, each AC:
+// 16-bit code + 10 bits), every byte stuffed, the padded last byte, EOI.
+extern "C" size_t rtp_jpeg_max_bytes(int w, int h) {
+  if (w < 1 || h < 1) return 0;
+  static const size_t header = [] {
+    unsigned char qt[2][64];
+    jpeg_qtables(75, qt);
+    std::vector<unsigned char> o;
+    jpeg_header(1, 1, qt, o);
+    return o.size();
+  }();
+  const size_t blocks = (size_t)((w + 15) / 16) * (size_t)((h + 15) / 16) * 6;
+  return header + (blocks * kJpegMaxBlockBits + 7) / 8 * 2 + 2;
+}
 
 static long encode_jpeg_impl(const unsigned char* bgr, int W, int H, int quality, unsigned char* out, size_t capacity);
 extern "C" long rtp_encode_jpeg(const unsigned char* bgr, int W, int H, int quality, unsigned char* out, size_t capacity) {
@@ -860,17 +937,8 @@ extern "C" long rtp_encode_jpeg(const unsigned char* bgr, int W, int H, int qual
 }
 static long encode_jpeg_impl(const unsigned char* bgr, int W, int H, int quality, unsigned char* out, size_t capacity) {
   if (!bgr || W < 1 || H < 1 || W > 65535 || H > 65535) return RTP_EINVAL;
-  if (quality < 1) quality = 1;
-  if (quality > 100) quality = 100;
-  const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;  // jpeg_quality_scaling
   unsigned char qt[2][64];
-  for (int t = 0; t < 2; ++t)
-    for (int i = 0; i < 64; ++i) {
-      long v = ((long)(t ? kStdChrQ[i] : kStdLumQ[i]) * scale + 50L) / 100L;
-      if (v <= 0) v = 1;
-      if (v > 255) v = 255;  // force_baseline
-      qt[t][i] = (unsigned char)v;
-    }
+  jpeg_qtables(quality, qt);
   // ---- planes: Y at full resolution, Cb/Cr down-sampled 2x2; all padded to whole 16x16 MCUs
   const int mcux = (W + 15) / 16, mcuy = (H + 15) / 16;
   const int yw_blocks = (W + 7) / 8, yh_blocks = (H + 7) / 8;              // real blocks (width_in_blocks)
@@ -922,29 +990,7 @@ static long encode_jpeg_impl(const unsigned char* bgr, int W, int H, int quality
   }
   std::vector<unsigned char> o;
   o.reserve((size_t)W * H);
-  auto put16 = [&](int v) { o.push_back((unsigned char)(v >> 8)); o.push_back((unsigned char)v); };
-  o.push_back(0xFF); o.push_back(0xD8);
-  const unsigned char app0[] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-  o.insert(o.end(), app0, app0 + sizeof app0);
-  for (int t = 0; t < 2; ++t) {
-    o.push_back(0xFF); o.push_back(0xDB); put16(67); o.push_back((unsigned char)t);
-    for (int i = 0; i < 64; ++i) o.push_back(qt[t][kZigzag[i]]);
-  }
-  o.push_back(0xFF); o.push_back(0xC0); put16(17); o.push_back(8); put16(H); put16(W); o.push_back(3);
-  o.push_back(1); o.push_back(0x22); o.push_back(0);
-  o.push_back(2); o.push_back(0x11); o.push_back(1);
-  o.push_back(3); o.push_back(0x11); o.push_back(1);
-  auto dht = [&](int tc_th, const unsigned char* bits, const unsigned char* vals, int nv) {
-    o.push_back(0xFF); o.push_back(0xC4); put16(2 + 1 + 16 + nv); o.push_back((unsigned char)tc_th);
-    for (int i = 1; i <= 16; ++i) o.push_back(bits[i]);
-    o.insert(o.end(), vals, vals + nv);
-  };
-  dht(0x00, kDcLumBits, kDcVals, 12);
-  dht(0x10, kAcLumBits, kAcLumVals, 162);
-  dht(0x01, kDcChrBits, kDcVals, 12);
-  dht(0x11, kAcChrBits, kAcChrVals, 162);
-  const unsigned char sos[] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
-  o.insert(o.end(), sos, sos + sizeof sos);
+  jpeg_header(W, H, qt, o);
   EncHuff hdc[2], hac[2];
   build_enc_huff(&hdc[0], kDcLumBits, kDcVals); build_enc_huff(&hac[0], kAcLumBits, kAcLumVals);
   build_enc_huff(&hdc[1], kDcChrBits, kDcVals); build_enc_huff(&hac[1], kAcChrBits, kAcChrVals);

@@ -40,6 +40,8 @@ double rtp_internal_warp_inverse_scale(double s);
 bool rtp_internal_area_fast(int sw, int sh, int dw, int dh, int* ix, int* iy);
 int rtp_internal_area_table(int ssize, int dsize, std::vector<int>* start, std::vector<int>* si, std::vector<float>* alpha);
 void rtp_internal_linear_area_table(int ssize, int dsize, std::vector<int>* tab);
+size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64], unsigned char* header, size_t header_cap,
+                               unsigned short huff_code[4][256], unsigned char huff_size[4][256]);
 extern "C" double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 extern "C" int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                                     double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -147,6 +149,12 @@ struct Slot {
   // caller's view is done; while export_pending, the context's next batch (whose render overwrites render_dev) waits on it first.
   hipEvent_t ev_ready = nullptr, ev_read = nullptr, ev_export = nullptr;
   bool export_pending = false;
+  // rtp_set_render_jpeg: the GPU encoder's scratch for render_dev (allocated lazily, like render_dev) and its pinned output, which the
+  // encoder's last kernel writes: [jpeg_cap bytes] the file after the header, then its length (4 bytes)
+  JpegBufs jpeg;
+  unsigned char* jpeg_host = nullptr;
+  unsigned char* jpeg_host_dev = nullptr;   // the same memory as the device addresses it
+  size_t jpeg_cap = 0;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -232,6 +240,16 @@ struct rtp_engine {
   // end of each frame's post-processing chain incl. the D2H of the joints on the frame's stream) are read back at collect time as
   // milliseconds since `busy_base` — an UNPROFILED account of when the engine had work on the GPU (bench.py: gpu_busy)
   bool busy_probe = false;
+  // rtp_set_render_jpeg: 0 off, else the quality every rendered frame is encoded at on the GPU; the display-size header and quantisers
+  int jpeg_quality = 0;
+  std::vector<unsigned char> jpeg_hdr;
+  JpegQuant jpeg_q;
+  // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
+  JpegBufs jenc;
+  unsigned char* jenc_host = nullptr;
+  unsigned char* jenc_host_dev = nullptr;
+  size_t jenc_cap = 0;
+  hipEvent_t jenc_ev = nullptr;
   hipEvent_t busy_base = nullptr;
   std::vector<float> busy_spans;          // [n][3]: kind (0 conv stream, 1 post chain), start ms, end ms
   // rtp_stamp_probe: device-side residency stamps of every kernel of the per-frame path (no profiler, no events)
@@ -1040,8 +1058,9 @@ int upload_all_weights(rtp_engine* e) {
 
 // ---- launches -------------------------------------------------------------------------------
 // Residency-stamp slots of one batch context: [0, 64) plan steps (conv stack), 64 + 8 j + {0 strip, 1 write, 2 pairs, 3 match, 4 assemble}
-// = frame j's post-processing chain, 64 + 8 j + 5 = the export of its rendered image (rtp_collect_rendered_device), 200 + 2 j +
-// {0 warp or import of a device frame, 1 area/pad} = frame j's device pre-processing.
+// = frame j's post-processing chain, 64 + 8 j + 5 = the export of its rendered image (rtp_collect_rendered_device), 64 + 8 j + 6 = the
+// JPEG encoding of its rendered image (rtp_set_render_jpeg; all seven launches), 200 + 2 j + {0 warp or import of a device frame,
+// 1 area/pad} = frame j's device pre-processing.
 constexpr int STAMP_SLOTS = 256;
 unsigned long long* stamp_slot(const rtp_engine* e, const Ctx& cx, int idx) {
   return (e->stamp_probe && cx.stamps && idx >= 0 && idx < STAMP_SLOTS) ? cx.stamps + 2 * (size_t)idx : nullptr;
@@ -1347,6 +1366,8 @@ int run_post_fused(rtp_engine* e, Ctx& cx, int sj, hipEvent_t ev_nms) {
   return RTP_OK;
 }
 
+int jpeg_alloc(rtp_engine* e, int w, int h, JpegBufs* b, unsigned char** host, unsigned char** host_dev, size_t* cap);
+
 // one batch on one context: conv stack over nframes*num_scales images, then per frame (on the
 // frame slot's stream) resize -> nms -> connect -> D2H of the joints
 int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bool materialize, bool cap, int part = 3) {
@@ -1408,7 +1429,21 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
         vp.model = e->model; vp.part_to_show = e->cfg.render - 1;
         HIPCHK(e, launch_render_view(vp, sl.stream));
       }
-      HIPCHK(e, hipMemcpyAsync(sl.render_host, sl.render_dev, dbytes, hipMemcpyDeviceToHost, sl.stream));
+      if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
+        if (!sl.jpeg.base) {
+          SYNC_GUARD;
+          if ((rc = jpeg_alloc(e, e->cfg.disp_w, e->cfg.disp_h, &sl.jpeg, &sl.jpeg_host, &sl.jpeg_host_dev, &sl.jpeg_cap))) return rc;
+        }
+        const FrameView fv = {sl.render_dev, e->cfg.disp_w, e->cfg.disp_h, 3L * e->cfg.disp_w, 3L, {0L, 1L, 2L}};
+        HIPCHK(e, launch_jpeg_encode(stamp_slot(e, cx, 64 + 8 * j + 6), fv, e->jpeg_q, sl.jpeg, sl.jpeg_host_dev,
+                                     reinterpret_cast<unsigned*>(sl.jpeg_host_dev + sl.jpeg_cap), sl.stream));
+      } else {
+        if (!sl.render_host) {   // freed while JPEG mode was on
+          SYNC_GUARD;
+          HIPCHK(e, hipHostMalloc((void**)&sl.render_host, dbytes, hipHostMallocDefault));
+        }
+        HIPCHK(e, hipMemcpyAsync(sl.render_host, sl.render_dev, dbytes, hipMemcpyDeviceToHost, sl.stream));
+      }
     }
     HIPCHK(e, hipMemcpyAsync(sl.host_out + 4, sl.joints, jbytes, hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(e, hipMemcpyAsync(sl.host_out, sl.num_people, sizeof(int), hipMemcpyDeviceToHost, sl.stream));
@@ -1645,6 +1680,67 @@ int alloc_ctx(rtp_engine* e, Ctx& cx) {
   return RTP_OK;
 }
 
+// ---- the GPU JPEG encoder (jpeg_enc.hip) ----------------------------------------------------------------------------------------
+// A w x h encoder: one device allocation of scratch (with the Huffman code tables, filled here) and one pinned buffer that the last
+// kernel writes: the file after its header, padded to 16 bytes, then the length.  Called under SYNC_GUARD (hipMalloc, hipMemcpy).
+void jpeg_free(JpegBufs* b, unsigned char** host, size_t* cap) {
+  if (b->base) (void)hipFree(b->base);
+  if (*host) (void)hipHostFree(*host);
+  *b = JpegBufs();
+  *host = nullptr;
+  *cap = 0;
+}
+bool jpeg_size_ok(int w, int h) {  // every bit offset of the entropy-coded segment fits 31 bits
+  return w >= 1 && h >= 1 && w <= 65535 && h <= 65535 && (double)((w + 15) / 16) * ((h + 15) / 16) * 6 * kJpegMaxBlockBits < 2147483648.0;
+}
+int jpeg_alloc(rtp_engine* e, int w, int h, JpegBufs* b, unsigned char** host, unsigned char** host_dev, size_t* cap) {
+  jpeg_free(b, host, cap);
+  *host_dev = nullptr;
+  JpegBufs nb;
+  unsigned char* hb = nullptr;
+  unsigned char* hd = nullptr;
+  unsigned char qt[2][64], hdr[1024];
+  JpegHuffTab huff[4];
+  unsigned short code[4][256];
+  unsigned char size[4][256];
+  rtp_internal_jpeg_setup(w, h, 75, qt, hdr, sizeof hdr, code, size);
+  for (int t = 0; t < 4; ++t) { memcpy(huff[t].code, code[t], sizeof code[t]); memcpy(huff[t].size, size[t], sizeof size[t]); }
+  const size_t c = (rtp_jpeg_max_bytes(w, h) + 15) / 16 * 16;   // >= the stuffed data + EOI rounded up to 16 bytes
+  const char* what = "hipMalloc";
+  hipError_t st = hipMalloc(&nb.base, jpeg_bufs_bytes(w, h, nullptr));
+  if (st == hipSuccess) {
+    jpeg_bufs_bytes(w, h, &nb);
+    what = "hipMemcpy";
+    st = hipMemcpy(nb.huff, huff, sizeof huff, hipMemcpyHostToDevice);
+  }
+  if (st == hipSuccess) { what = "hipHostMalloc"; st = hipHostMalloc((void**)&hb, c + 16, hipHostMallocMapped | hipHostMallocCoherent); }
+  if (st == hipSuccess) { what = "hipHostGetDevicePointer"; st = hipHostGetDevicePointer((void**)&hd, hb, 0); }
+  if (st != hipSuccess) {   // nothing half-made stays behind
+    if (nb.base) (void)hipFree(nb.base);
+    if (hb) (void)hipHostFree(hb);
+    return fail(e, RTP_EHIP, "JPEG encoder buffers for %d x %d: %s failed: %s", w, h, what, hipGetErrorString(st));
+  }
+  *b = nb;
+  *host = hb;
+  *host_dev = hd;
+  *cap = c;
+  return RTP_OK;
+}
+// the quantisers of `quality` (jcdctmgr.c divides by 8 Q) and the header of a w x h file
+void jpeg_tables(int w, int h, int quality, JpegQuant* q, std::vector<unsigned char>* hdr) {
+  unsigned char qt[2][64], hb[1024];
+  unsigned short code[4][256];
+  unsigned char size[4][256];
+  const size_t hl = rtp_internal_jpeg_setup(w, h, quality, qt, hb, sizeof hb, code, size);
+  hdr->assign(hb, hb + hl);
+  for (int t = 0; t < 2; ++t)
+    for (int i = 0; i < 64; ++i) {
+      const uint64_t dv = (uint64_t)qt[t][i] << 3;
+      q->recip[t][i] = (unsigned)(((1ull << 32) + dv - 1) / dv);
+      q->half[t][i] = (unsigned short)(dv >> 1);
+    }
+}
+
 void free_ctx(Ctx& cx) {
   if (cx.stream) (void)hipStreamSynchronize(cx.stream);
   if (cx.in_stream && cx.in_stream != cx.stream) { (void)hipStreamSynchronize(cx.in_stream); (void)hipStreamDestroy(cx.in_stream); }
@@ -1658,6 +1754,7 @@ void free_ctx(Ctx& cx) {
     for (void* p : dptrs) if (p) (void)hipFree(p);
     if (sl.frame_host) (void)hipHostFree(sl.frame_host);
     if (sl.render_host) (void)hipHostFree(sl.render_host);
+    jpeg_free(&sl.jpeg, &sl.jpeg_host, &sl.jpeg_cap);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
     for (int i = 0; i < 5; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
     if (sl.ev_copy) (void)hipEventDestroy(sl.ev_copy);
@@ -2131,6 +2228,8 @@ void rtp_engine_destroy(rtp_engine* e) {
   if (e->prep_tables) (void)hipFree(e->prep_tables);
   if (e->copy_stream) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamDestroy(e->copy_stream); }
   for (void* p : e->user_bufs) if (p) (void)hipFree(p);
+  if (e->jenc_ev) { (void)hipEventSynchronize(e->jenc_ev); (void)hipEventDestroy(e->jenc_ev); }
+  jpeg_free(&e->jenc, &e->jenc_host, &e->jenc_cap);
   delete e;
 }
 
@@ -2502,6 +2601,9 @@ int rtp_collect(rtp_engine* e, uint64_t* tag, float* joints, int* num_people) { 
 // cv::imwrite under --write_frames --no_text, rtpose.cpp:1179-1199, 1286-1293).  Needs
 // rtp_config.render = 1 and frames submitted with rtp_submit_frame.
 int rtp_collect_rendered(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* display_bgr) {
+  if (e && e->jpeg_quality)
+    return fail(e, RTP_EINVAL, "rtp_collect_rendered: JPEG mode is on (rtp_set_render_jpeg %d), so the raw frame never reaches the host: "
+                "collect with rtp_collect_rendered_jpeg, or rtp_collect_rendered_device", e->jpeg_quality);
   return collect_impl(e, tag, joints, num_people, display_bgr, true);
 }
 static int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* rendered, bool want_render) {
@@ -2547,7 +2649,8 @@ static int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_pe
   if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->num_parts * 3 * sizeof(float));
   if (want_render) {
     if (!e->cfg.render) return fail(e, RTP_EINVAL, "rtp_collect_rendered needs rtp_config.render = 1");
-    if (!sl.has_disp || !sl.render_host) return fail(e, RTP_EINVAL, "no display image for this frame: submit it with rtp_submit_frame (device pre-processing)");
+    if (!sl.has_disp || (rendered && !sl.render_host))
+      return fail(e, RTP_EINVAL, "no display image for this frame: submit it with rtp_submit_frame (device pre-processing)");
     if (rendered) memcpy(rendered, sl.render_host, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3);
   }
   return RTP_OK;
@@ -2582,6 +2685,92 @@ int rtp_collect_rendered_device(rtp_engine* e, uint64_t* tag, float* joints, int
   if (!stream) {
     HIPCHK(e, hipEventSynchronize(sl.ev_export));
     sl.export_pending = false;
+  }
+  return RTP_OK;
+}
+
+// ---- JPEG files encoded on the GPU (jpeg_enc.hip: the bytes of rtp_encode_jpeg) ------------------------------------------------
+int rtp_set_render_jpeg(rtp_engine* e, int quality) {
+  if (!e) return fail(nullptr, RTP_EINVAL, "rtp_set_render_jpeg: NULL engine");
+  if (quality < 0 || quality > 100) return fail(e, RTP_EINVAL, "rtp_set_render_jpeg: quality %d (0 = off, 1..100)", quality);
+  if (quality && !e->cfg.render) return fail(e, RTP_EINVAL, "rtp_set_render_jpeg needs rtp_config.render >= 1");
+  if (quality && !jpeg_size_ok(e->cfg.disp_w, e->cfg.disp_h))
+    return fail(e, RTP_EINVAL, "rtp_set_render_jpeg: a %d x %d display image is too large for the GPU encoder", e->cfg.disp_w, e->cfg.disp_h);
+  if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "rtp_set_render_jpeg: %zu frames in flight (collect them first)", e->fifo.size());
+  if (quality) {
+    jpeg_tables(e->cfg.disp_w, e->cfg.disp_h, quality, &e->jpeg_q, &e->jpeg_hdr);
+    SYNC_GUARD;   // the raw frames' pinned copies are not written in JPEG mode (the engine is idle: no copy into them is pending)
+    for (Ctx& cx : e->ctx)
+      for (Slot& sl : cx.slot)
+        if (sl.render_host) { HIPCHK(e, hipHostFree(sl.render_host)); sl.render_host = nullptr; }
+  }
+  e->jpeg_quality = quality;
+  return RTP_OK;
+}
+
+// rtp_collect_rendered with the JPEG file of the rendered frame.  Every refusal happens before the frame is taken off the FIFO.
+int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* jpeg_host, size_t capacity,
+                              size_t* jpeg_bytes) {
+  static const char* fn = "rtp_collect_rendered_jpeg";
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if (!e->jpeg_quality) return fail(e, RTP_EINVAL, "%s: JPEG mode is off (rtp_set_render_jpeg)", fn);
+  const size_t need = rtp_jpeg_max_bytes(e->cfg.disp_w, e->cfg.disp_h);
+  if (!jpeg_host || capacity < need)
+    return fail(e, RTP_EINVAL, "%s: capacity %zu, need rtp_jpeg_max_bytes(%d, %d) = %zu", fn, jpeg_host ? capacity : (size_t)0, e->cfg.disp_w,
+                e->cfg.disp_h, need);
+  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
+  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
+  Slot& sl = e->ctx[ci].slot[sj];
+  if (!sl.has_disp) return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", fn);
+  int rc;
+  if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
+  unsigned n = 0;
+  memcpy(&n, sl.jpeg_host + sl.jpeg_cap, sizeof n);
+  const size_t hl = e->jpeg_hdr.size();
+  if (hl + n > capacity) return fail(e, RTP_EHIP, "%s: the encoder reported %u bytes, more than its bound", fn, n);
+  memcpy(jpeg_host, e->jpeg_hdr.data(), hl);
+  memcpy(jpeg_host + hl, sl.jpeg_host, n);
+  if (jpeg_bytes) *jpeg_bytes = hl + n;
+  return RTP_OK;
+}
+
+// rtp_encode_jpeg on the pixels of a view of device memory, ordered after the work queued on `stream`; returns with the file on the host.
+// The engine's own scratch: frames in flight are not touched.
+int rtp_encode_jpeg_device(rtp_engine* e, const rtp_frame_view* src, int quality, void* stream, unsigned char* jpeg_host, size_t capacity,
+                           size_t* jpeg_bytes) {
+  static const char* fn = "rtp_encode_jpeg_device";
+  FrameView fv;
+  long hi = 0;
+  int rc, layout = LAYOUT_GENERIC;
+  if ((rc = check_view_fields(e, src, fn, &fv, &hi))) return rc;
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if ((rc = check_caller_stream(e, stream, fn))) return rc;
+  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
+  if (!jpeg_size_ok(fv.w, fv.h)) return fail(e, RTP_EINVAL, "%s: a %d x %d frame is too large for the GPU encoder", fn, fv.w, fv.h);
+  if ((rc = use_device(e))) return rc;
+  if (quality < 1) quality = 1;
+  if (quality > 100) quality = 100;
+  if (e->jenc.w != fv.w || e->jenc.h != fv.h) {
+    SYNC_GUARD;
+    if (e->jenc_ev) HIPCHK(e, hipEventSynchronize(e->jenc_ev));
+    if ((rc = jpeg_alloc(e, fv.w, fv.h, &e->jenc, &e->jenc_host, &e->jenc_host_dev, &e->jenc_cap))) return rc;
+  }
+  if (!e->jenc_ev) HIPCHK(e, hipEventCreateWithFlags(&e->jenc_ev, hipEventDisableTiming));
+  JpegQuant q;
+  std::vector<unsigned char> hdr;
+  jpeg_tables(fv.w, fv.h, quality, &q, &hdr);
+  const hipStream_t st = (hipStream_t)stream;
+  HIPCHK(e, launch_jpeg_encode(nullptr, fv, q, e->jenc, e->jenc_host_dev, reinterpret_cast<unsigned*>(e->jenc_host_dev + e->jenc_cap), st));
+  HIPCHK(e, hipEventRecord(e->jenc_ev, st));
+  HIPCHK(e, hipEventSynchronize(e->jenc_ev));
+  unsigned n = 0;
+  memcpy(&n, e->jenc_host + e->jenc_cap, sizeof n);
+  const size_t total = hdr.size() + n;
+  if (jpeg_bytes) *jpeg_bytes = total;
+  if (jpeg_host) {
+    if (capacity < total) return fail(e, RTP_EINVAL, "%s: output buffer too small (%zu bytes, the file has %zu)", fn, capacity, total);
+    memcpy(jpeg_host, hdr.data(), hdr.size());
+    memcpy(jpeg_host + hdr.size(), e->jenc_host, n);
   }
   return RTP_OK;
 }

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "jpeg_bound.h"
+
 // Experiment knobs (tile overrides, ablation variants of the ring kernel — some of which compute WRONG results on purpose, stream
 // plans, diagnostic probes) exist only in the second build target librtpose_mi355x_exp.so (-DRTP_EXPERIMENTS, used by tools/):
 // in the production library the macro is a null pointer and the knob's name is not even a string in the binary
@@ -212,6 +214,34 @@ hipError_t launch_frame_export(unsigned long long* stamp, const unsigned char* s
 // launch_warp reading the caller's view in place of a packed frame (same per-pixel arithmetic)
 hipError_t launch_warp_view(unsigned long long* stamp, const FrameView& v, double inv, const short* tab2d, unsigned char* dst, int dw, int dh,
                             hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------
+// JPEG encoder (rtp_encode_jpeg_device, rtp_set_render_jpeg): jpeg_enc.hip, the bytes of codecs.cpp's rtp_encode_jpeg
+// ---------------------------------------------------------------------------------------
+struct JpegHuffTab { unsigned short code[256]; unsigned char size[256]; };
+// per quality: the natural-order quantiser of luma (0) and chroma (1) as jcdctmgr.c divides by it: 8 Q / 2 and ceil(2^32 / 8 Q)
+struct JpegQuant { unsigned recip[2][64]; unsigned short half[2][64]; };
+// Device scratch of one w x h encoder, carved from ONE allocation of jpeg_bufs_bytes(w, h) bytes at base
+struct JpegBufs {
+  void* base = nullptr;
+  int w = 0, h = 0;
+  JpegHuffTab* huff = nullptr;   // [4]: DC luma, AC luma, DC chroma, AC chroma (filled once by the host)
+  short* coef = nullptr;         // [blocks][64] quantised, zig-zag order
+  unsigned* bits = nullptr;      // [blocks] AC code length incl. ZRL / EOB; after jpeg_bits_kernel the block's whole code length
+  unsigned* mcubits = nullptr;   // [MCUs] bits of each MCU
+  unsigned* off = nullptr;       // [blocks] bit offset in the entropy-coded segment
+  int* dcdiff = nullptr;         // [blocks] DC difference to the component's predictor
+  unsigned* words = nullptr;     // the bit stream, MSB first, whole 4 KiB chunks
+  unsigned* counts = nullptr;    // [chunks] 0xFF bytes per chunk
+  unsigned* meta = nullptr;      // [0] bits, [1] bytes before stuffing, [2] bytes after the header (stuffed data + EOI)
+  unsigned char* data = nullptr; // stuffed data + EOI, padded to 16 bytes
+};
+// bytes of the scratch for w x h; with layout != null, its pointers are set from layout->base
+size_t jpeg_bufs_bytes(int w, int h, JpegBufs* layout);
+// the entropy-coded segment + EOI of the view -> dst (device-accessible, 16-byte aligned, room for the bytes rounded up to 16),
+// its length -> *dst_len.  Seven launches on `stream`, all stamped into `stamp`.
+hipError_t launch_jpeg_encode(unsigned long long* stamp, const FrameView& v, const JpegQuant& q, const JpegBufs& jb, unsigned char* dst,
+                              unsigned* dst_len, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------
 // Renderer (row 8f-3): render.hip

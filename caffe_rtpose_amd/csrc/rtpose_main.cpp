@@ -32,6 +32,11 @@
 #include "../../include/rtpose_mi355x.h"
 
 extern "C" {
+// Weak here: the host-side sanitizer build of this file links against link-time stand-ins of the engine (tests/helpers/engine_stub.cpp)
+// that have no GPU encoder; --dry_engine never calls these.  rtpose.bin binds them to librtpose_mi355x.so.
+int rtp_set_render_jpeg(rtp_engine* e, int quality) __attribute__((weak));
+int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* jpeg_host, size_t capacity,
+                              size_t* jpeg_bytes) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -46,6 +51,7 @@ double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::
 // ---- flags (names and defaults: rtpose.cpp:50-72) --------------------------------------------
 struct Flags {
   bool host_preprocess = false;
+  bool host_jpeg = false;        // --write_frames: encode on the host (rtp_encode_jpeg on an encoder pool) instead of on the GPU
   bool fullscreen = false, no_frame_drops = false, no_display = false, no_text = false, logtostderr = false;
   int part_to_show = 0, camera = 0, start_frame = 0, start_device = 0, num_gpu = 1, num_scales = 1;
   std::string write_frames, write_json, video, image_dir;
@@ -81,7 +87,7 @@ int parse_flags(int argc, char** argv, Flags& F) {
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
       {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}};
   std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"no_display", &F.no_display},
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"no_display", &F.no_display},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -127,7 +133,8 @@ void usage() {
          "   --calibrate K (check / widen the mixed-precision split set on the loaded weights with K sample frames)\n"
          "   --share_weights (workers 1.. copy worker 0's packed weights GPU to GPU) --nopin_workers (no CPU affinity next to each worker's GPU)]\n"
          "  --write_frames draws the pose overlay only: the FPS / people-count text of the reference (cv::putText, rtpose.cpp:1319-1333) is not\n"
-         "  drawn, i.e. --no_text is implied.\n");
+         "  drawn, i.e. --no_text is implied.  Its JPEG files (quality 98) are encoded on the GPU and only the files cross PCIe;\n"
+         "  --host_jpeg copies the raw frames to the host and encodes them there on 8 threads instead (the same bytes).\n");
 }
 
 // ---- queues (caffe::BlockingQueue, util/blocking_queue.cpp:26-61) -----------------------------
@@ -152,7 +159,8 @@ template <typename T> class BlockingQueue {
 struct Frame {
   std::vector<float> data;         // net input (only with --host_preprocess)
   std::vector<unsigned char> image;  // decoded u8 BGR frame (default: pre-processing runs on the GPU)
-  std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay
+  std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
+  bool rendered_jpeg = false;
   int img_w = 0, img_h = 0;
   double commit_time = 0, preprocessed_time = 0, gpu_fetched_time = 0, gpu_computed_time = 0, buffer_start_time = 0, buffer_end_time = 0;
   int index = 0, numPeople = 0, video_frame_number = 0;
@@ -161,7 +169,7 @@ struct Frame {
   std::vector<float> joints;
 };
 
-struct EncodeJob { std::string path; std::vector<unsigned char> bgr; };
+struct EncodeJob { std::string path; std::vector<unsigned char> bgr; bool jpeg = false; };  // jpeg: bgr already holds the file
 
 struct Global {
   BlockingQueue<Frame> input_queue, output_queue, output_queue_ordered;
@@ -374,6 +382,25 @@ void worker(int widx, int device, int* status) {
     G.quit_threads = true;
     return;
   }
+  // --write_frames: the files are encoded on the GPU (quality 98, rtpose.cpp:1367-1381) unless --host_jpeg; --dry_engine has no GPU
+  const bool gpu_jpeg = !dry && !F.write_frames.empty() && !F.host_jpeg;
+  std::vector<unsigned char> jpeg_buf(gpu_jpeg ? rtp_jpeg_max_bytes(DISP_W, DISP_H) : 0);
+  if (gpu_jpeg) {
+    const char* err = !rtp_set_render_jpeg || !rtp_collect_rendered_jpeg ? "this binary was linked without the engine's GPU JPEG encoder"
+                      : rtp_set_render_jpeg(e, 98) != RTP_OK              ? rtp_last_error(e) : nullptr;
+    if (err) {   // never a quiet fall-back to the host encoders: --host_jpeg asks for them
+      fprintf(stderr, "GPU %d: --write_frames: %s\n", device, err);
+      *status = 1;
+      G.quit_threads = true;
+      rtp_engine_destroy(e);
+      return;
+    }
+  }
+  if (!F.write_frames.empty() && widx == 0)
+    fprintf(stderr, "--write_frames: JPEG files encoded %s\n", gpu_jpeg ? "on the GPU (rtp_collect_rendered_jpeg)" : "on the host (rtp_encode_jpeg, 8 threads)");
+  // a frame whose collect failed: the host encoders write the file of the zero-filled frame they are handed, so the GPU path writes
+  // that same file (encoded once by rtp_encode_jpeg): both modes leave the same file set
+  std::vector<unsigned char> black_jpeg;
   if (!dry && F.share_weights) {
     if (widx == 0) G.engine0 = e;
     else {
@@ -431,11 +458,27 @@ void worker(int widx, int device, int* status) {
     int n = 0;
     Frame fr = std::move(inflight.front());
     inflight.pop_front();
-    if (!F.write_frames.empty()) fr.rendered.resize((size_t)DISP_W * DISP_H * 3);
+    if (!F.write_frames.empty() && !gpu_jpeg) fr.rendered.resize((size_t)DISP_W * DISP_H * 3);
+    size_t jpeg_bytes = 0;
     const int rc = dry ? dry_collect(fr, joints.data(), &n)
-                       : F.write_frames.empty() ? rtp_collect(e, &tag, joints.data(), &n)
-                                                : rtp_collect_rendered(e, &tag, joints.data(), &n, fr.rendered.data());
+                   : F.write_frames.empty() ? rtp_collect(e, &tag, joints.data(), &n)
+                   : gpu_jpeg ? rtp_collect_rendered_jpeg(e, &tag, joints.data(), &n, jpeg_buf.data(), jpeg_buf.size(), &jpeg_bytes)
+                              : rtp_collect_rendered(e, &tag, joints.data(), &n, fr.rendered.data());
     if (rc != RTP_OK) { fprintf(stderr, "GPU %d frame %d: %s\n", device, fr.index, rtp_last_error(e)); n = 0; }
+    if (gpu_jpeg) {  // only the file's bytes are kept
+      if (rc == RTP_OK) {
+        fr.rendered.assign(jpeg_buf.begin(), jpeg_buf.begin() + (long)jpeg_bytes);
+      } else {
+        if (black_jpeg.empty()) {
+          const std::vector<unsigned char> black((size_t)DISP_W * DISP_H * 3, 0);
+          black_jpeg.resize(jpeg_buf.size());
+          const long nb = rtp_encode_jpeg(black.data(), DISP_W, DISP_H, 98, black_jpeg.data(), black_jpeg.size());
+          black_jpeg.resize(nb > 0 ? (size_t)nb : 0);
+        }
+        fr.rendered = black_jpeg;
+      }
+      fr.rendered_jpeg = !fr.rendered.empty();
+    }
     fr.numPeople = n;
     fr.joints.assign(joints.begin(), joints.begin() + (size_t)n * num_parts * 3);
     fr.gpu_computed_time = wall();
@@ -527,6 +570,11 @@ void encoder() {
       std::this_thread::sleep_for(std::chrono::microseconds(500));
       continue;
     }
+    if (job.jpeg) {  // encoded on the GPU: this thread only writes the file
+      std::ofstream fs(job.path, std::ios::binary);
+      fs.write((const char*)job.bgr.data(), (std::streamsize)job.bgr.size());
+      continue;
+    }
     const long n = rtp_encode_jpeg(job.bgr.data(), DISP_W, DISP_H, 98, jpg.data(), jpg.size());
     if (n > 0) {
       std::ofstream fs(job.path, std::ios::binary);
@@ -584,7 +632,7 @@ void writer(std::atomic<bool>* reorder_done) {
       if (F.image_dir.empty()) snprintf(fname, sizeof fname, "%s/frame%06d.jpg", F.write_frames.c_str(), fr.video_frame_number);
       else snprintf(fname, sizeof fname, "%s/%s.jpg", F.write_frames.c_str(), fr.stem.c_str());
       while (G.encode_queue.size() > 32) std::this_thread::sleep_for(std::chrono::milliseconds(1));  // back-pressure on the encoders
-      G.encode_queue.push(EncodeJob{fname, std::move(fr.rendered)});
+      G.encode_queue.push(EncodeJob{fname, std::move(fr.rendered), fr.rendered_jpeg});
     }
     if (!F.write_json.empty()) {
       if (F.json_writers > 0) {

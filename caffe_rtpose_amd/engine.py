@@ -211,6 +211,11 @@ def encode_jpeg(bgr, quality=98):
     return out[:n].tobytes()
 
 
+def jpeg_max_bytes(w, h):
+    """rtp_jpeg_max_bytes: the largest JPEG file encode_jpeg / the GPU encoder can write for a w x h image."""
+    return int(lib.rtp_jpeg_max_bytes(int(w), int(h)))
+
+
 class Video:
     """cv::VideoCapture for Y4M / raw MJPEG files."""
 
@@ -424,6 +429,31 @@ class Engine:
         joints = np.zeros((MAX_PEOPLE, self.num_parts, 3), np.float32)
         self._chk(lib.rtp_collect_rendered_device(self.h, C.byref(tag), _f(joints), C.byref(n), C.byref(v), st))
         return tag.value, n.value, joints[: n.value].copy()
+
+    def set_render_jpeg(self, quality):
+        """rtp_set_render_jpeg: 0 off, 1..100 = every rendered frame is encoded on the GPU; collect it with collect_rendered_jpeg."""
+        self._chk(lib.rtp_set_render_jpeg(self.h, int(quality)))
+
+    def collect_rendered_jpeg(self):
+        """rtp_collect_rendered_jpeg: (tag, num_people, joints, JPEG file as bytes) of the oldest frame."""
+        tag = C.c_uint64()
+        n = C.c_int()
+        joints = np.zeros((MAX_PEOPLE, self.num_parts, 3), np.float32)
+        out = np.empty(jpeg_max_bytes(self.cfg.c.disp_w, self.cfg.c.disp_h), np.uint8)
+        nb = C.c_size_t()
+        self._chk(lib.rtp_collect_rendered_jpeg(self.h, C.byref(tag), _f(joints), C.byref(n), _u8(out), out.size, C.byref(nb)))
+        return tag.value, n.value, joints[: n.value].copy(), out[: nb.value].tobytes()
+
+    def encode_jpeg_device(self, obj, quality=98, stream=None, order="bgr"):
+        """rtp_encode_jpeg_device: encode_jpeg of a u8 frame in device memory (see frame_view), on the GPU after the work queued on
+        `stream` (see _stream_of) -> bytes."""
+        f = frame_view(obj, order)
+        v = _view_struct(f)
+        st, _ = _stream_of(obj, stream)
+        out = np.empty(jpeg_max_bytes(f["width"], f["height"]), np.uint8)
+        nb = C.c_size_t()
+        self._chk(lib.rtp_encode_jpeg_device(self.h, C.byref(v), int(quality), st, _u8(out), out.size, C.byref(nb)))
+        return out[: nb.value].tobytes()
 
     def flush(self):
         self._chk(lib.rtp_flush(self.h))

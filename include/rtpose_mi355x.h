@@ -429,6 +429,31 @@ int rtp_submit_frame_device(rtp_engine* e, const rtp_frame_view* frame, void* st
 int rtp_collect_rendered_device(rtp_engine* e, uint64_t* tag, float* joints, int* num_people,
                                 const rtp_frame_view* out, void* stream);
 
+/* ---- JPEG files encoded on the GPU: byte for byte what rtp_encode_jpeg writes (baseline, 4:2:0, standard tables) ---------- */
+
+/* The largest file rtp_encode_jpeg / the GPU encoder can write for a w x h image (header + every block at its worst, every byte
+ * stuffed + EOI).  Host only; 0 for w or h < 1. */
+size_t rtp_jpeg_max_bytes(int w, int h);
+
+/* = rtp_encode_jpeg on the pixels of a device view (the checks of rtp_submit_frame_device), encoded on the GPU after the work
+ * queued on `stream` so far (NULL: the null stream).  Returns with the file in jpeg_host (NULL: only *jpeg_bytes is set);
+ * capacity below the file's size -> RTP_EINVAL.  quality is clamped to 1..100 like rtp_encode_jpeg.  Uses the engine's own
+ * scratch: frames in flight are not disturbed. */
+int rtp_encode_jpeg_device(rtp_engine* e, const rtp_frame_view* src, int quality, void* stream, unsigned char* jpeg_host,
+                           size_t capacity, size_t* jpeg_bytes);
+
+/* JPEG mode of the renderer.  0: off (the default).  1..100: every rendered frame (overlay or part_to_show view) is encoded on
+ * the GPU at this quality right after the render kernel, and only the file is copied to the host; collect it with
+ * rtp_collect_rendered_jpeg (rtp_collect_rendered is refused, rtp_collect_rendered_device still works).  Refused: render == 0 or
+ * quality outside 0..100 (RTP_EINVAL), frames in flight (RTP_EAGAIN). */
+int rtp_set_render_jpeg(rtp_engine* e, int quality);
+
+/* = rtp_collect_rendered with the JPEG file of the rendered frame in place of the raw image (*jpeg_bytes = its length).
+ * Refused before the frame leaves the FIFO (RTP_EINVAL): JPEG mode off, capacity < rtp_jpeg_max_bytes(disp_w, disp_h), an
+ * oldest frame without a display image. */
+int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* jpeg_host,
+                              size_t capacity, size_t* jpeg_bytes);
+
 #ifdef __cplusplus
 }
 #endif
