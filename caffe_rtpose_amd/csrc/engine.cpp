@@ -1,8 +1,9 @@
-// engine.cpp — static execution plan + frame contexts behind the C-ABI of include/rtpose_mi355x.h.
+// engine.cpp — the static execution plan made real + frame contexts behind the C-ABI of include/rtpose_mi355x.h.
 //
 // Replaces the Caffe net runtime on the rtpose path (net.cpp:49 Net::Init, :544-556
 // ForwardFromTo, syncedmem.cpp:25-77) with a plan that is compiled ONCE per
-// (graph, resolution, num_scales, precision):
+// (graph, resolution, num_scales, precision) — by build_plan (plan.h / plan.cpp: host only, a pure function of its PlanInput); this file
+// holds the result as rtp_engine::plan, packs the weights for it, allocates the contexts and launches its steps:
 //   * every blob gets a halo'd NHWC tensor in a per-context arena (kernels.h), zeroed once;
 //   * ReLU is folded into the producing convolution, Concat is eliminated by letting producers
 //     write straight into channel slices of the consumer's tensor (multi-destination epilogue),
@@ -32,6 +33,7 @@
 #include "../../include/rtpose_mi355x.h"
 #include "kernels.h"
 #include "netdef.h"
+#include "plan.h"
 
 using namespace rtp;
 
@@ -57,57 +59,6 @@ thread_local std::string g_create_error = "";
 // (async copies, launches, event waits on the engine's own streams) never takes it.  Found by rtpose.bin --num_gpu 4 --devices 0,0,0,0.
 std::recursive_mutex g_sync_mutex;
 #define SYNC_GUARD std::lock_guard<std::recursive_mutex> sync_guard_(g_sync_mutex)
-
-struct Tensor {
-  std::string name;
-  int C = 0, Cp = 0, level = 0;
-  size_t offset = 0;        // byte offset of padded pixel 0 of image 0 inside a context arena
-  std::vector<int> chmap;   // reference channel -> internal channel
-  // split precision: [0, Cp) hi; need_lo: [Cp, 2Cp) lo = T(v - float(T(v))) (consumers running three fp16 passes);
-  // need_q: a further Cp elements = 2*Cp bytes of fp8 compensation operands (consumers running the fp8 passes, ConvDst::q_off)
-  bool need_lo = false, need_q = false;
-  bool written = true;      // false: the blob was fused away (a convolution pools in its epilogue and writes only the pooled tensor)
-  int stride() const { return Cp * (1 + (need_lo ? 1 : 0) + (need_q ? 1 : 0)); }  // channels (elements) per pixel in memory
-  int lo_off() const { return need_lo ? Cp : 0; }
-  int q_off() const { return need_q ? Cp * (need_lo ? 2 : 1) : 0; }
-};
-
-struct ConvOp {
-  std::string name;
-  int widx = 0;             // index into engine weights
-  int in_tensor = -1;
-  int k = 1, k_eff = 1;     // k_eff = 1 for the im2col-packed first layer
-  int cin = 0, cout = 0;
-  bool relu = false, first = false;
-  std::vector<std::pair<int, int>> dsts;  // (tensor, channel offset)
-  bool to_lowres = false;
-  int lowres_coff = 0;
-  int level = 0;
-  int Cin_p = 0, rowb = 128, nchunk = 1, CoutP = 0, cfg = 0;
-  int impl = 0;             // 0 = register-staged kernel (conv_igemm.hip), 1 = LDS-DMA ring (conv_ring.hip)
-  bool direct_first = false;  // conv1_1 straight from the NCHW input (conv_first.hip): no im2col tensor, no pack step
-  // split precision (RTP_PREC_MIXED / F16X3): the K loop runs the passes [a_hi x W_hi] [a_lo x W_hi] [a_hi x W_lo]
-  bool split_a = false, split_w = false;
-  bool no_h8 = false;       // rule suffix ":x": the corrections of this layer run as fp16 passes even where the fp8 chunk exists (no e4m3 range limits)
-  int ncp = 1;              // chunks of ONE pass (nchunk = ncp * passes)
-  bool h8 = false;          // the two correction passes run as ONE fp8 chunk per channel group (MX-scaled MFMA, 2x the fp16 rate)
-  int wq_exp = 0;           // h8: fp8(W * 2^wq_exp), fp8(W_lo * 2^(wq_exp + 11))
-  int passes() const { return h8 ? 2 : 1 + (split_a ? 1 : 0) + (split_w ? 1 : 0); }  // in units of one fp16 pass of MFMA time
-  int wrap_at() const { return h8 ? 0 : (split_w ? (split_a ? 2 * ncp : ncp) : 0); }
-  int last_phys() const { return h8 ? ncp - 1 : (split_w ? ncp - 1 : (split_a ? 2 * ncp - 1 : ncp - 1)); }
-  int pool = -1;            // >= 0: this convolution's only consumer is pooling layer `pool`; it pools in its epilogue (conv_ring.hip POOL)
-  int fused = 0;            // 1 / 2: first / second 1x1 of a conv_pw2 step (weights packed for that kernel)
-  int fused_chunks = 0;     // middle channels / 128
-  size_t w_off = 0, b_off = 0, w_bytes = 0;
-};
-
-struct Step {
-  int type;  // 0 pack, 1 conv, 2 pool, 3 two chained 1x1 convolutions in one launch (conv_pw2.hip), 4 input convolution from the NCHW image (conv_first.hip)
-  int a = -1, b = -1;    // conv (a) [+ the other branch's conv (b)]; pool index for type 2
-  int a2 = -1, b2 = -1;  // type 3: the second 1x1 of each branch
-};
-
-struct PoolOp { int in_tensor, out_tensor, C; };
 
 // One frame's post-processing state (a batch context carries batch_frames of them)
 struct Slot {
@@ -194,9 +145,7 @@ struct rtp_engine {
   rtp_config cfg;
   std::string proto_path, weights_path;
   NetDef net;
-  int model = 0, prec = 0, elem = 2;
-  int num_parts = 18, max_peaks = 64, heat_channels = 57, num_limbs = 19;
-  int low_w = 0, low_h = 0;
+  Plan plan;   // plan.h: everything build_plan produced for (net, cfg, N, B, mode, split_rules, split_fp8)
   float nms_threshold = 0.05f, inter_threshold = 0.05f, min_subset_score = 0.4f;
   int inter_min_above = 9, min_subset_cnt = 3;
   float start_scale = 1.f, scale_gap = 0.3f;
@@ -205,27 +154,14 @@ struct rtp_engine {
   bool broken = false;   // a re-plan failed and the previous plan could not be restored: no contexts; every entry point fails, destroy works
   int N = 1;    // images per frame (num_scales)
   int B = 1;    // frames per batch (cfg.batch_frames)
-  int NI = 1;   // images per conv launch at a full batch = N * B
   int open_ctx = -1;  // context whose batch is being filled
-  Geom geom[8];
-  int nlevels = 0;
-  std::vector<Tensor> tensors;
-  std::map<std::string, int> blob_tensor;                 // blob name -> tensor (NHWC blobs)
-  std::map<std::string, std::pair<int, int>> blob_dims;   // blob name -> (C, level)
-  std::string lowres_blob;
-  std::vector<ConvOp> convs;
-  std::vector<Step> steps;
-  std::vector<PoolOp> pools;
   std::vector<std::vector<float>> w_ref, b_ref;           // Caffe layout per conv
-  size_t arena_bytes = 0, weights_bytes = 0;
   unsigned char* dweights = nullptr;
   int* dchmap = nullptr;  // scratch for export
   std::vector<Ctx> ctx;
   std::deque<int> fifo;
-  int nstrips = 0, strip_rows = 8, max_rows = 0;
   float last_ms[5] = {0, 0, 0, 0, 0};
   std::string err;
-  int dominant_step = -1;
   bool time_dominant = false;
   double dom_ms_total = 0;
   long dom_launches = 0;
@@ -289,7 +225,7 @@ struct rtp_engine {
   int prep_defer = 0;
   hipStream_t copy_stream = nullptr;   // H2D copies only (created after every other stream)
   std::deque<int> pending_launch;      // full batches whose last frame's copy was still in flight when it was committed (launched by pump())
-  int mode = 0;  // rtp_config.precision (RTP_PREC_*); `prec` below selects the kernels' element type (0 fp16, 1 fp32)
+  int mode = 0;  // rtp_config.precision (RTP_PREC_*); plan.prec selects the kernels' element type (0 fp16, 1 fp32)
   std::string split_rules;
   int nctx_full = 1;            // batch contexts of the configured pipeline (a calibration trial runs with one)
   std::string calib_report;     // what rtp_calibrate_precision last did (rtp_calibration_report)
@@ -326,560 +262,6 @@ int fail(rtp_engine* e, int code, const char* fmt, ...) {
       return fail((e), RTP_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_s), __FILE__, __LINE__); \
   } while (0)
 
-inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
-inline size_t round_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-const int GUARD_PIX = 192;  // pixels of slack before/after each tensor (strip over-read of the last tile)
-
-// ---- split-precision policy ------------------------------------------------------------------
-// Default RTP_PREC_MIXED set, from tools/sim_precision.py (error of the final maps vs an fp32 run, per layer and per
-// rounded operand): the fp16 rounding of weights and activations contributes about equally in every layer, and the
-// final-map error is dominated by the trunk from conv2 on, the last two refinement stages and (cheaply fixed) all 1x1
-// layers; the first refinement stages are attenuated by each later stage's re-injection of conv4_4_CPM.
-// Measured (tests/test_precision.py; tools/sim_precision.py reproduces the rms to 3 digits): final maps normalised to max 1,
-//   fp16 everywhere                          rms 3.5e-4   max 2.0-2.6e-3
-//   conv2-4, stages 5-6, 1x1 (2.08x MFMA)    rms 1.36e-4  max 0.8-1.03e-3   <- no margin on the +-1e-3 tolerance
-//   + stage 4 (this default, 2.35x MFMA)     rms 1.03e-4  max <= 0.8e-3
-//   every layer (RTP_PREC_F16X3, 3x MFMA)    rms 1.6e-6   max 1e-5
-const char* kDefaultSplit = "conv2_,conv3_,conv4_,*_stage4_,*_stage5_,*_stage6_,@1x1";
-void layer_split(const rtp_engine* e, const ConvOp& c, bool* w, bool* a, bool* x = nullptr) {
-  *w = *a = false;
-  if (x) *x = false;
-  if (e->prec != 0) return;
-  if (e->mode == RTP_PREC_F16X3) { *w = *a = true; return; }
-  if (e->mode != RTP_PREC_MIXED) return;
-  const std::string& rules = e->split_rules;
-  size_t pos = 0;
-  while (pos <= rules.size()) {
-    size_t c2 = rules.find(',', pos);
-    std::string tok = rules.substr(pos, c2 == std::string::npos ? std::string::npos : c2 - pos);
-    pos = c2 == std::string::npos ? rules.size() + 1 : c2 + 1;
-    if (tok.empty()) continue;
-    bool tw = true, ta = true, tx = false;
-    if (tok.size() > 2 && tok[tok.size() - 2] == ':') {
-      const char k = tok.back();
-      tok.resize(tok.size() - 2);
-      if (k == 'w') ta = false;
-      else if (k == 'a') tw = false;
-      else if (k == 'x') tx = true;   // both operands, corrections as two more fp16 passes (what RTP_PREC_F16X3 runs everywhere)
-    }
-    bool hit;
-    if (tok == "@all") hit = true;
-    else if (tok == "@1x1") hit = c.k == 1;
-    else if (tok[0] == '*') hit = c.name.find(tok.substr(1)) != std::string::npos;
-    else hit = c.name.compare(0, tok.size(), tok) == 0;
-    if (hit) { *w = *w || tw; *a = *a || ta; if (x) *x = *x || tx; }
-  }
-}
-
-// ---- plan ---------------------------------------------------------------------------------
-int build_plan(rtp_engine* e) {
-  const NetDef& net = e->net;
-  const int CALIGN = 128 / e->elem;
-  e->blob_dims.clear();
-  if (net.inputs.empty()) return fail(e, RTP_EINVAL, "prototxt declares no input blob");
-  const std::string in_name = net.inputs[0];
-  e->blob_dims[in_name] = {3, 0};
-  struct ConcatInfo { std::vector<std::string> inputs; };
-  std::map<std::string, ConcatInfo> concats;
-  std::map<std::string, int> producer_conv;  // blob -> conv index
-  std::vector<int> level_halo(8, 0);
-  int max_level = 0;
-  bool have_resize = false, have_nms = false;
-  struct PoolTmp { std::string in, out; };
-  std::vector<std::pair<int, int>> order;  // (kind 1 conv / 2 pool, index)
-  std::vector<PoolTmp> pools;
-
-  for (size_t li = 0; li < net.layers.size(); ++li) {
-    const LayerDef& L = net.layers[li];
-    if (L.type == "Convolution") {
-      if (L.bottoms.size() != 1 || L.tops.size() != 1) return fail(e, RTP_EINVAL, "layer %s: expected 1 bottom/1 top", L.name.c_str());
-      auto it = e->blob_dims.find(L.bottoms[0]);
-      if (it == e->blob_dims.end()) return fail(e, RTP_EINVAL, "layer %s: unknown bottom %s", L.name.c_str(), L.bottoms[0].c_str());
-      if (L.stride != 1 || !(L.kernel == 1 || L.kernel == 3 || L.kernel == 7) || L.pad != (L.kernel - 1) / 2 || !L.bias_term)
-        return fail(e, RTP_EINVAL, "layer %s: only stride-1 'same' convolutions with k in {1,3,7} and a bias are on the linevec path", L.name.c_str());
-      ConvOp c;
-      c.name = L.name; c.k = L.kernel; c.k_eff = L.kernel; c.cin = it->second.first; c.cout = L.num_output;
-      c.level = it->second.second;
-      c.first = (L.bottoms[0] == in_name);
-      if (c.first && !(c.cin == 3 && c.k == 3)) return fail(e, RTP_EINVAL, "layer %s: the input convolution must be 3x3 on 3 channels", L.name.c_str());
-      if (c.first) c.k_eff = 1;
-      c.widx = (int)e->convs.size();
-      level_halo[c.level] = std::max(level_halo[c.level], c.k_eff / 2);
-      e->blob_dims[L.tops[0]] = {c.cout, c.level};
-      producer_conv[L.tops[0]] = (int)e->convs.size();
-      order.push_back({1, (int)e->convs.size()});
-      e->convs.push_back(c);
-    } else if (L.type == "ReLU") {
-      if (L.bottoms.size() != 1 || L.tops.size() != 1 || L.bottoms[0] != L.tops[0] || !producer_conv.count(L.bottoms[0]))
-        return fail(e, RTP_EINVAL, "layer %s: ReLU must be in-place on a convolution output", L.name.c_str());
-      if (L.negative_slope != 0.f) return fail(e, RTP_EINVAL, "layer %s: negative_slope != 0 unsupported", L.name.c_str());
-      e->convs[producer_conv[L.bottoms[0]]].relu = true;
-    } else if (L.type == "Pooling") {
-      auto it = e->blob_dims.find(L.bottoms.empty() ? "" : L.bottoms[0]);
-      if (it == e->blob_dims.end()) return fail(e, RTP_EINVAL, "layer %s: unknown bottom", L.name.c_str());
-      if (L.pool_method != "MAX" || L.pool_kernel != 2 || L.pool_stride != 2 || L.pool_pad != 0)
-        return fail(e, RTP_EINVAL, "layer %s: only MAX 2x2 stride 2 pooling is on the linevec path", L.name.c_str());
-      e->blob_dims[L.tops[0]] = {it->second.first, it->second.second + 1};
-      max_level = std::max(max_level, it->second.second + 1);
-      pools.push_back({L.bottoms[0], L.tops[0]});
-      order.push_back({2, (int)pools.size() - 1});
-    } else if (L.type == "Concat") {
-      if (L.axis != 1) return fail(e, RTP_EINVAL, "layer %s: only channel concat", L.name.c_str());
-      int C = 0, lvl = -1;
-      for (auto& b : L.bottoms) {
-        auto it = e->blob_dims.find(b);
-        if (it == e->blob_dims.end()) return fail(e, RTP_EINVAL, "layer %s: unknown bottom %s", L.name.c_str(), b.c_str());
-        if (!producer_conv.count(b)) return fail(e, RTP_EINVAL, "layer %s: concat inputs must be convolution outputs", L.name.c_str());
-        if (lvl >= 0 && lvl != it->second.second) return fail(e, RTP_EINVAL, "layer %s: concat inputs at different resolutions", L.name.c_str());
-        lvl = it->second.second;
-        C += it->second.first;
-      }
-      e->blob_dims[L.tops[0]] = {C, lvl};
-      concats[L.tops[0]] = ConcatInfo{L.bottoms};
-    } else if (L.type == "ImResize") {
-      if (!e->blob_dims.count(L.bottoms[0])) return fail(e, RTP_EINVAL, "resize: unknown bottom");
-      if (L.factor != 8.f) return fail(e, RTP_EINVAL, "resize: only factor 8 (the net's total stride) is supported");
-      e->lowres_blob = L.bottoms[0];
-      have_resize = true;
-    } else if (L.type == "Nms") {
-      e->num_parts = L.num_parts;
-      e->max_peaks = L.max_peaks;
-      have_nms = true;
-    } else if (L.type == "Split") {
-      // pointer share: alias tops to the bottom
-      for (auto& t : L.tops) e->blob_dims[t] = e->blob_dims[L.bottoms[0]];
-      return fail(e, RTP_EINVAL, "layer %s: explicit Split layers are not expected in a deploy prototxt", L.name.c_str());
-    } else {
-      return fail(e, RTP_EINVAL, "layer %s: type %s is not on the linevec hot path", L.name.c_str(), L.type.c_str());
-    }
-  }
-  if (!have_resize || !have_nms) return fail(e, RTP_EINVAL, "graph must end in ImResize + Nms layers");
-  if (e->num_parts == 18) e->model = RTP_MODEL_COCO_18;
-  else if (e->num_parts == 15) e->model = RTP_MODEL_MPI_15;
-  else return fail(e, RTP_EINVAL, "Unknown number of parts (%d)! Couldn't set model", e->num_parts);  // rtpose.cpp:227
-  e->num_limbs = e->model == 0 ? 19 : 14;
-  if (e->max_peaks < 1 || e->max_peaks > 127) return fail(e, RTP_EINVAL, "max_peaks %d out of range [1,127]", e->max_peaks);
-  e->heat_channels = e->blob_dims[e->lowres_blob].first;
-  if (e->blob_dims[e->lowres_blob].second != 3) return fail(e, RTP_EINVAL, "resize input must be at 1/8 resolution");
-  {
-    const int need = (e->model == 0 ? 57 : 44);
-    if (e->heat_channels != need) return fail(e, RTP_EINVAL, "resize input has %d channels, model needs %d", e->heat_channels, need);
-  }
-
-  // geometry
-  e->nlevels = max_level + 1;
-  if ((e->cfg.net_w % 16) || (e->cfg.net_h % 16) || e->cfg.net_w < 16 || e->cfg.net_h < 16)
-    return fail(e, RTP_EINVAL, "net_resolution %dx%d must be positive multiples of 16", e->cfg.net_w, e->cfg.net_h);
-  for (int l = 0; l < e->nlevels; ++l) {
-    Geom g;
-    g.N = e->NI; g.H = e->cfg.net_h >> l; g.W = e->cfg.net_w >> l; g.halo = level_halo[l];
-    // ONE zero gap of `halo` pixels between consecutive rows serves as the right halo of row y and the left halo of row y+1
-    // (flat addressing: pixel p's tap (r,s) is p + (r-pad)*Wp + (s-pad), so x+pad past the row end lands in the gap and x-pad
-    // before the row start lands in the previous row's gap).  Wp = W + halo instead of W + 2*halo: 3.4 % fewer GEMM rows at
-    // 1/8 resolution (85 instead of 88 per row) and 31 instead of 32 M-tiles of 128 per 46x82 image — a launch of the paired
-    // 7x7 layers at batch_frames = 2 is 248 workgroups, not 256: it no longer needs EVERY CU at once.
-    // The last pixel's far corner tap reads 2 pixels past Hp*Wp: the next image's top halo / the tensor's zero guard.
-    static const char* sh = RTP_EXP_ENV("RTP_HALO_SHARED");  // experiments: 0 = a halo on both sides of every row
-    const bool shared = !(sh && sh[0] == '0');
-    g.Hp = g.H + 2 * g.halo; g.Wp = g.W + (shared ? 1 : 2) * g.halo; g.img_pix = (long)g.Hp * g.Wp;
-    e->geom[l] = g;
-  }
-  e->low_w = e->cfg.net_w / 8;
-  e->low_h = e->cfg.net_h / 8;
-
-  // tensors
-  auto new_tensor = [&](const std::string& name, int C, int level) {
-    Tensor t;
-    t.name = name; t.C = C; t.level = level;
-    t.Cp = round_up(C, CALIGN);
-    t.chmap.resize(C);
-    for (int i = 0; i < C; ++i) t.chmap[i] = i;
-    e->tensors.push_back(t);
-    return (int)e->tensors.size() - 1;
-  };
-  // packed im2col input
-  int packed_tensor = -1;
-  {
-    Tensor t;
-    t.name = "__im2col_input"; t.C = 27; t.level = 0; t.Cp = 32;
-    t.chmap.resize(27);
-    for (int i = 0; i < 27; ++i) t.chmap[i] = i;
-    e->tensors.push_back(t);
-    packed_tensor = 0;
-  }
-  for (auto& c : e->convs) e->blob_tensor[c.name] = new_tensor(c.name, c.cout, c.level);
-  for (auto& p : pools) e->blob_tensor[p.out] = new_tensor(p.out, e->blob_dims[p.out].first, e->blob_dims[p.out].second);
-  // concat tensors (those read by convolutions); aligned inputs first
-  std::map<std::string, std::vector<std::pair<std::string, int>>> concat_slices;  // concat -> (input, internal offset)
-  for (auto& kv : concats) {
-    if (kv.first == e->lowres_blob) continue;
-    const auto& ins = kv.second.inputs;
-    std::vector<int> ord(ins.size());
-    for (size_t i = 0; i < ins.size(); ++i) ord[i] = (int)i;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
-      const bool ua = (e->blob_dims[ins[a]].first % 8) != 0, ub = (e->blob_dims[ins[b]].first % 8) != 0;
-      return (int)ua < (int)ub;
-    });
-    std::vector<int> internal_off(ins.size());
-    int off = 0;
-    for (int i : ord) { internal_off[i] = off; off += e->blob_dims[ins[i]].first; }
-    {  // every slice on an 8-channel boundary where the pad channels of the tensor pay for it (concat_stageK: conv4_4_CPM at 0, L1 at 128, L2 at
-       // 168 instead of 166, 192 channels either way): the producers' epilogues then write the slice with 16-byte stores instead of one 2-byte
-       // store + two fp8 byte stores per channel (conv_common.h conv_store_dst) — the branch tails' epilogue was 4.1 us of an 11 us workgroup
-       // for that reason.  The skipped channels are pad channels like the tail's: zero activations, zero weights (chmap never points at them).
-      std::vector<int> aligned(ins.size());
-      int a = 0;
-      for (int i : ord) { a = round_up(a, 8); aligned[i] = a; a += e->blob_dims[ins[i]].first; }
-      if (round_up(a, CALIGN) == round_up(off, CALIGN)) internal_off = aligned;
-    }
-    const int tid = new_tensor(kv.first, e->blob_dims[kv.first].first, e->blob_dims[kv.first].second);
-    e->blob_tensor[kv.first] = tid;
-    int refc = 0;
-    for (size_t i = 0; i < ins.size(); ++i) {
-      const int C = e->blob_dims[ins[i]].first;
-      for (int c = 0; c < C; ++c) e->tensors[tid].chmap[refc + c] = internal_off[i] + c;
-      refc += C;
-      concat_slices[kv.first].push_back({ins[i], internal_off[i]});
-    }
-  }
-  e->pools.clear();
-  for (auto& p : pools) {
-    PoolOp po;
-    po.in_tensor = e->blob_tensor.at(p.in);
-    po.out_tensor = e->blob_tensor.at(p.out);
-    po.C = e->tensors[po.out_tensor].C;
-    e->pools.push_back(po);
-  }
-  // conv inputs / destinations
-  for (auto& c : e->convs) {
-    const LayerDef* L = nullptr;
-    for (auto& l : net.layers) if (l.type == "Convolution" && l.name == c.name) L = &l;
-    if (c.first) c.in_tensor = packed_tensor;
-    else {
-      auto it = e->blob_tensor.find(L->bottoms[0]);
-      if (it == e->blob_tensor.end()) return fail(e, RTP_EINVAL, "layer %s: bottom %s has no tensor", c.name.c_str(), L->bottoms[0].c_str());
-      c.in_tensor = it->second;
-    }
-    c.dsts.push_back({e->blob_tensor[c.name], 0});
-    for (auto& cs : concat_slices)
-      for (auto& sl : cs.second)
-        if (sl.first == c.name) c.dsts.push_back({e->blob_tensor[cs.first], sl.second});
-    if ((int)c.dsts.size() > RTP_MAX_DST) return fail(e, RTP_EINVAL, "layer %s feeds %d tensors (max %d)", c.name.c_str(), (int)c.dsts.size(), RTP_MAX_DST);
-    // low-res output (the blob ImResize reads), reference channel order
-    if (c.name == e->lowres_blob) { c.to_lowres = true; c.lowres_coff = 0; }
-    else if (concats.count(e->lowres_blob)) {
-      int off = 0;
-      for (auto& in : concats[e->lowres_blob].inputs) {
-        if (in == c.name) { c.to_lowres = true; c.lowres_coff = off; }
-        off += e->blob_dims[in].first;
-      }
-    }
-    const Tensor& ti = e->tensors[c.in_tensor];
-    c.Cin_p = ti.Cp;
-    c.rowb = (c.Cin_p * e->elem >= 128) ? 128 : 64;
-    if ((c.Cin_p * e->elem) % c.rowb) return fail(e, RTP_EINVAL, "layer %s: internal channel padding error", c.name.c_str());
-    c.nchunk = c.Cin_p * e->elem / c.rowb;
-  }
-
-  // split precision: which layers, then which tensors must carry a lo block
-  for (auto& c : e->convs) {
-    layer_split(e, c, &c.split_w, &c.split_a, &c.no_h8);
-    if (c.first) c.split_a = false;  // the image (u8/256 - 0.5) is exact in fp16: its lo part is zero
-  }
-
-  // steps + pairing + tile configuration
-  e->steps.clear();
-  e->steps.push_back({0, -1, -1});
-  for (size_t oi = 0; oi < order.size(); ++oi) {
-    if (order[oi].first == 2) { e->steps.push_back({2, order[oi].second, -1}); continue; }
-    const int a = order[oi].second;
-    int b = -1;
-    if (oi + 1 < order.size() && order[oi + 1].first == 1) {
-      const int cand = order[oi + 1].second;
-      const ConvOp& A = e->convs[a];
-      const ConvOp& B = e->convs[cand];
-      bool dep = false;
-      for (auto& d : A.dsts) if (d.first == B.in_tensor) dep = true;
-      if (!dep && A.split_a == B.split_a && A.split_w == B.split_w && A.k_eff == B.k_eff && A.Cin_p == B.Cin_p && A.level == B.level && A.relu == B.relu && A.rowb == B.rowb &&
-          round_up(A.cout, 64) == round_up(B.cout, 64) && e->tensors[A.in_tensor].Cp == e->tensors[B.in_tensor].Cp)
-        b = cand;
-    }
-    e->steps.push_back({1, a, b});
-    if (b >= 0) ++oi;
-  }
-  for (size_t si_ = 0; si_ < e->steps.size(); ++si_) {
-    Step& s = e->steps[si_];
-    if (s.type != 1) continue;
-    ConvOp& A = e->convs[s.a];
-    const Geom& g = e->geom[A.level];
-    // a pooling layer follows and reads only this blob: tiles the POOL kernel exists for save its launch (fusion pass below)
-    const bool pool_next = s.b < 0 && si_ + 1 < e->steps.size() && e->steps[si_ + 1].type == 2 && A.dsts.size() == 1 &&
-                           pools[e->steps[si_ + 1].a].in == A.name && (g.H % 2) == 0 && (g.W % 2) == 0 && g.W >= 128 && !e->cfg.keep_blobs;
-    const int nprob = s.b >= 0 ? 2 : 1;
-    const int maxcout = std::max(A.cout, s.b >= 0 ? e->convs[s.b].cout : 0);
-    const long M = (long)g.H * g.Wp;
-    // Tile choice by a time model of the ring kernel (cycles; the constants are measured):
-    //   one K step (tap x chunk) of a workgroup = max(MFMA time, L2->LDS time) + barrier:
-    //     MFMA:  BM*BN*channels_per_chunk / (4 consumer waves * 32*32*16) instructions per wave at ~43 cycles on real operands
-    //     DMA:   the weight tile (BN rows) + 1/k of the (BM+k-1)-pixel strip, at ~56 B/clk/CU
-    //   a workgroup = steps * that + ~4500 cycles of prologue / epilogue; a launch = workgroups / 256 CUs rounds, where a partial
-    //   round of fill f costs 0.5 + 0.5 f of a full one (fewer busy CUs clock higher and wait less for L2: 372 workgroups of the
-    //   dominant shape take 1.70x the time of 248, not 2x), + ~6000 cycles of dispatch per launch.  (Two co-resident workgroups of
-    //   the small-LDS 64x64 kernel share one matrix pipe: no credit for them.)
-    // Replaces round 2's "fewest bytes among the tiles with >= 224 workgroups", which left plans whose M does not fill the chip
-    // (MPI 46x62 maps at batch_frames 2: 192 workgroups of 128x64) on half-size tiles in two rounds.
-    const bool ring_ok = !A.first && (A.k_eff == 3 || A.k_eff == 7);
-    const int row_bytes_all = A.Cin_p * e->elem;
-    std::vector<int> cands;
-    if (A.rowb == 64) cands = {CFG_128x64};
-    else if (maxcout <= 32 && ring_ok && row_bytes_all % 256 == 0) cands = {CFG_128x32, CFG_128x64, CFG_64x64};
-    else if (maxcout <= 64) cands = {CFG_128x64, CFG_64x64};
-    else if (ring_ok && row_bytes_all % 256 == 0) {
-      cands = {CFG_128x128, CFG_64x128, CFG_128x64, CFG_64x64, CFG_128x32};
-      // CFG_256x64 (round 5): twice the pixels per workgroup for the 7x7 layers.  Alone at batches of 4 it is 12-14 % faster per image than the
-      // 128x64 tile at batches of 2; in the PIPELINE it changes nothing (B = 4: 1012 vs 1006 frames/s against 128x128 tiles, MPI B = 5: 1209 vs
-      // 1207; profiles/r05_experiments.txt), so the production plans keep round 4's measured tiles and the candidate exists in the experiments
-      // build only (RTP_TILE_256=1: let the time model choose it; RTP_DOM_256 forces it).
-      static const char* t256 = RTP_EXP_ENV("RTP_TILE_256");
-      if (e->prec == 0 && A.k_eff == 7 && maxcout >= 64 && ((t256 && t256[0] == '1') || RTP_EXP_ENV("RTP_DOM_256"))) cands.push_back(CFG_256x64);   // (chosen by the model where 128-pixel tiles would need two rounds: batches of >= 4 images)
-    }
-    else if (ring_ok) cands = {CFG_128x128, CFG_64x128, CFG_128x64, CFG_64x64};
-    else cands = {CFG_128x128, CFG_64x128, CFG_64x64};
-    int best = cands.back();
-    double best_t = 1e300, best_bytes = 1e300;
-    static const char* tm = RTP_EXP_ENV("RTP_TILE_RULE");  // experiments: "r2" = round 2's rule
-    const bool rule_r2 = tm && !strcmp(tm, "r2");
-    long best_wg = -1;
-    bool chosen = false;
-    const int passes = (A.split_a || A.split_w) ? ((e->split_fp8 && e->mode == RTP_PREC_MIXED && A.split_a && A.split_w && !A.no_h8 && ring_ok) ? 2 : 1 + (A.split_a ? 1 : 0) + (A.split_w ? 1 : 0)) : 1;
-    for (int cf : cands) {
-      const ConvCfgInfo ci = conv_cfg_info(cf);
-      const long wg = ((M + ci.BM - 1) / ci.BM) * e->NI * (round_up(maxcout, ci.BN) / ci.BN) * nprob;
-      const double bytes = (double)wg * (ci.BN + (double)(ci.BM + A.k_eff - 1) / A.k_eff);
-      if (rule_r2) {
-        if (wg >= 224) { if (!chosen || bytes < best_bytes) { best = cf; best_bytes = bytes; chosen = true; } }
-        else if (!chosen && wg > best_wg) { best = cf; best_wg = wg; }
-        continue;
-      }
-      const int chb = (ring_ok && (cf == CFG_64x64 || cf == CFG_128x64 || cf == CFG_128x32) && row_bytes_all % 256 == 0) ? 256 : std::min(128, row_bytes_all);
-      const double chc = (double)chb / e->elem;                                     // channels per chunk
-      const double t_mfma = (double)ci.BM * ci.BN * chc / (4.0 * 32 * 32 * 16) * (e->prec ? 4 * 43.0 : 43.0);
-      const double t_dma = ((double)ci.BN * chb + (double)(ci.BM + A.k_eff - 1) * chb / A.k_eff) / 56.0;
-      const double steps = (double)A.k_eff * A.k_eff * (row_bytes_all / (double)chb) * passes;
-      const double t_wg = steps * (std::max(t_mfma, t_dma) + 60.0) + 4500.0;
-      const double full = std::floor((double)wg / 256.0), frac = (double)wg / 256.0 - full;
-      double t = (full + (frac > 0 ? 0.5 + 0.5 * frac : 0.0)) * t_wg + 6000.0;
-      if (pool_next && !(e->prec == 0 && A.k_eff == 3 && chb == 128 && (cf == CFG_128x64 || cf == CFG_128x128)))  // the stand-alone pooling launch: ~5 B per cycle and CU
-        t += 8000.0 + (double)e->NI * g.H * g.W * e->tensors[A.dsts[0].first].stride() * e->elem * 1.25 / (256.0 * 9.0);
-      if (t < best_t * 0.98 || (t < best_t * 1.02 && bytes < best_bytes)) { best = cf; best_t = std::min(t, best_t); best_bytes = bytes; }
-    }
-    // Half-chip launches.  The runtime's hardware queues run two conv stacks at a time, so two launches of <= 128
-    // workgroups share the chip: each workgroup moves half the weight bytes per MFMA and one stack's launch gaps are covered by the
-    // other's kernel.  Measured in the pipeline, same box (profiles/r03_tile_model.txt): 128x128 tiles (124 workgroups at batch_frames 2)
-    // for every k x k layer at 1/8 resolution +2.7 % frames/s, for all of them except the dominant shape +1.5..3 %.  A launch alone then
-    // fills half the chip, which is what a per-launch roofline reports (0.16 instead of 0.23 for the dominant 7x7 128->128 pair).
-    // RTP_HALF_CHIP: 1 (default) = where a 128x128 tile gives 100..128 workgroups and the model's choice 129..256, except the dominant
-    // shape (whose per-launch efficiency is the figure this path is judged on); 2 = the dominant shape too; 0 = the model alone.
-    if (!rule_r2 && ring_ok) {
-      static const char* hc = RTP_EXP_ENV("RTP_HALF_CHIP");
-      const int mode = hc ? atoi(hc) : 1;
-      const ConvCfgInfo cb = conv_cfg_info(best);
-      const long wg_best = ((M + cb.BM - 1) / cb.BM) * e->NI * (round_up(maxcout, cb.BN) / cb.BN) * nprob;
-      const long wg_128 = ((M + 127) / 128) * e->NI * (round_up(maxcout, 128) / 128) * nprob;
-      const bool has128 = std::find(cands.begin(), cands.end(), (int)CFG_128x128) != cands.end();
-      const bool dominant = A.k_eff == 7 && A.cin == 128;
-      if (mode > 0 && has128 && best != CFG_128x128 && wg_best > 128 && wg_best <= 256 && wg_128 >= 100 && wg_128 <= 128 && (mode >= 2 || !dominant))
-        best = CFG_128x128;
-    }
-    {
-      static const char* d256 = RTP_EXP_ENV("RTP_DOM_256");   // experiments: 1 = 256x64 tiles for the 7x7 layers whatever the batch (half-chip launches of double-size workgroups at batch_frames 2); 2 = the dominant shape only
-      if (d256 && ring_ok && A.k_eff == 7 && std::find(cands.begin(), cands.end(), (int)CFG_256x64) != cands.end() && (d256[0] == '1' || (d256[0] == '2' && A.cin == 128))) best = CFG_256x64;
-    }
-    if (const char* ov = RTP_EXP_ENV("RTP_TILE_OVERRIDE")) {  // experiments: "conv2_1=3,conv3_1=3" forces tile ids (kernels.h ConvCfg) per layer
-      const std::string key = A.name + "=";
-      for (const char* hit = strstr(ov, key.c_str()); hit; hit = strstr(hit + 1, key.c_str())) {  // "Mconv2_1=.." also contains "conv2_1=": take the entry that starts at a boundary
-        if (!(hit == ov || hit[-1] == ',')) continue;
-        const int v = atoi(hit + key.size());
-        if (std::find(cands.begin(), cands.end(), v) == cands.end())
-          return fail(e, RTP_EINVAL, "RTP_TILE_OVERRIDE: tile id %d is not a candidate for layer %s", v, A.name.c_str());
-        best = v;
-        break;
-      }
-    }
-    {
-      static const char* fc = RTP_EXP_ENV("RTP_FORCE_CFG");  // experiments only: force a tile for the k x k layers at 1/8 resolution
-      static const char* kd = RTP_EXP_ENV("RTP_FORCE_CFG_KEEP_DOM");  // 1: ... except the dominant shape (7x7, 128 input channels)
-      if (fc && ring_ok && A.level == 3 && maxcout > 64 && !(kd && kd[0] == '1' && A.k_eff == 7 && A.cin == 128)) {
-        const int v = atoi(fc);
-        if (std::find(cands.begin(), cands.end(), v) == cands.end())
-          return fail(e, RTP_EINVAL, "RTP_FORCE_CFG: tile id %d is not a candidate for layer %s", v, A.name.c_str());
-        best = v;
-      }
-    }
-    const ConvCfgInfo ci = conv_cfg_info(best);
-    const char* force = RTP_EXP_ENV("RTP_CONV_IMPL");
-    const bool allow_ring = !(force && !strcmp(force, "v1"));
-    for (int idx : {s.a, s.b}) {
-      if (idx < 0) continue;
-      ConvOp& c = e->convs[idx];
-      c.cfg = best;
-      c.CoutP = round_up(maxcout, ci.BN);
-      c.impl = 0;
-      if (allow_ring && !c.first && (c.k_eff == 3 || c.k_eff == 7)) {
-        const int row_bytes = c.Cin_p * e->elem;
-        static const char* f128 = RTP_EXP_ENV("RTP_RING_CHB128");
-        int chb = ((best == CFG_64x64 || best == CFG_128x64 || best == CFG_128x32) && row_bytes % 256 == 0 && !(f128 && f128[0] == '1')) ? 256 : 128;
-        if (best == CFG_128x32 && chb != 256) { best = CFG_64x64; c.cfg = best; c.CoutP = round_up(maxcout, 64); chb = 128; }
-        if (row_bytes % chb == 0) {
-          c.impl = 1;
-          c.rowb = chb;
-          c.nchunk = row_bytes / chb;
-        }
-      }
-    }
-  }
-
-  // fp8 compensation where the kernel supports it: ring kernels whose waves own >= 64 bytes of K per chunk
-  for (auto& c : e->convs) {
-    // k-split of the kernel that would run it (conv_ring.hip; q layers on the 64x64 tile with 128-byte chunks get a 2-way split)
-    const int ksplit = c.cfg == CFG_128x128 ? 1 : (c.cfg == CFG_64x64 ? (c.rowb == 128 ? 2 : 4) : 2);
-    const int gpw = (c.rowb / 32) / ksplit;
-    c.h8 = e->split_fp8 && e->mode == RTP_PREC_MIXED && e->prec == 0 && c.impl == 1 && c.split_a && c.split_w && !c.no_h8 && gpw >= 2 && gpw % 2 == 0;
-  }
-  for (auto& s : e->steps)  // both branches of a pair run the same kernel
-    if (s.type == 1 && s.b >= 0 && e->convs[s.a].h8 != e->convs[s.b].h8)
-      for (int idx : {s.a, s.b}) e->convs[idx].h8 = false;
-  for (auto& c : e->convs)  // which operand blocks the input tensors must carry, from the FINAL flags
-    if (c.split_a) { if (c.h8) e->tensors[c.in_tensor].need_q = true; else e->tensors[c.in_tensor].need_lo = true; }
-  for (size_t pi = e->pools.size(); pi-- > 0;) {  // a pool output with lo / q parts needs them in its input
-    if (e->tensors[e->pools[pi].out_tensor].need_lo) e->tensors[e->pools[pi].in_tensor].need_lo = true;
-    if (e->tensors[e->pools[pi].out_tensor].need_q) e->tensors[e->pools[pi].in_tensor].need_q = true;
-  }
-  // 2x2 max pooling inside the producing convolution's epilogue: the pooling layer's input blob has no other consumer, the layer
-  // runs on a ring kernel with 128-pixel tiles of 128-byte chunks (the trunk's conv1_2 / conv2_2 / conv3_4), even resolution.
-  // The un-pooled blob is then never written (rtp_config.keep_blobs = 1 keeps every blob tappable and pools in its own launch).
-  {
-    static const char* fp = RTP_EXP_ENV("RTP_FUSE_POOL");  // experiments: 0 = stand-alone pooling launches
-    for (size_t si = 1; si < e->steps.size() && !e->cfg.keep_blobs && !(fp && fp[0] == '0'); ++si) {
-      if (e->steps[si].type != 2 || e->steps[si - 1].type != 1 || e->steps[si - 1].b >= 0) continue;
-      const int pi = e->steps[si].a;
-      ConvOp& A = e->convs[e->steps[si - 1].a];
-      const PoolOp& po = e->pools[pi];
-      const Geom& g = e->geom[A.level];
-      bool ok = e->prec == 0 && A.impl == 1 && A.k_eff == 3 && A.rowb == 128 && (A.cfg == CFG_128x64 || A.cfg == CFG_128x128) && !A.to_lowres &&
-                A.dsts.size() == 1 && A.dsts[0].first == po.in_tensor && (g.H % 2) == 0 && (g.W % 2) == 0 && g.W >= 128 /* one wrap per tile at most */ && A.level + 1 < e->nlevels;
-      for (auto& c : e->convs) if (c.in_tensor == po.in_tensor) ok = false;  // somebody convolves the un-pooled blob
-      if (!ok) continue;
-      A.pool = pi;
-      A.dsts[0] = {po.out_tensor, 0};
-      e->tensors[po.in_tensor].written = false;
-      e->steps.erase(e->steps.begin() + (long)si);
-      --si;
-    }
-  }
-  {  // the input convolution without the im2col tensor: fp16 storage, 64 channels, one plain destination
-    static const char* fd = RTP_EXP_ENV("RTP_FIRST_DIRECT");  // experiments: 0 = the pack + 1x1 route
-    for (size_t si = 0; si + 1 < e->steps.size() && !(fd && fd[0] == '0'); ++si) {
-      const Step& s1 = e->steps[si];
-      if (s1.type != 1 || s1.b >= 0 || !e->convs[s1.a].first) continue;
-      ConvOp& c = e->convs[s1.a];
-      const Tensor& to = e->tensors[c.dsts[0].first];
-      if (e->prec != 0 || c.cout != 64 || c.split_w || c.dsts.size() != 1 || c.to_lowres || to.need_lo || to.need_q || e->steps[0].type != 0) break;
-      if (((size_t)3 * (e->geom[0].W + 2) * 3 + 8) * 2 > 64 * 1024) break;
-      c.direct_first = true;
-      e->steps[0] = Step{4, s1.a, -1};
-      e->steps.erase(e->steps.begin() + (long)si);
-      break;
-    }
-  }
-  for (auto& c : e->convs) {  // K chunks: one pass = ncp chunks of rowb bytes; split layers run 2-3 passes (h8: hi chunks + q chunks)
-    c.ncp = c.nchunk;
-    c.nchunk = c.ncp * c.passes();
-  }
-  // branch tails: 1x1 (ReLU) -> 1x1 with nobody else reading the middle blob become ONE launch (conv_pw2.hip)
-  {
-    static const char* nf = RTP_EXP_ENV("RTP_FUSE_1X1");
-    const bool allow = e->prec == 0 && !(nf && nf[0] == '0');
-    for (size_t si = 0; allow && si + 1 < e->steps.size(); ++si) {
-      Step& s1 = e->steps[si];
-      const Step& s2 = e->steps[si + 1];
-      if (s1.type != 1 || s2.type != 1 || (s1.b >= 0) != (s2.b >= 0)) continue;
-      auto chain = [&](int ia, int ic) {
-        const ConvOp& A = e->convs[ia];
-        const ConvOp& C = e->convs[ic];
-        return A.k == 1 && C.k == 1 && !A.first && A.Cin_p == 128 && A.cout % 128 == 0 && A.cout <= 512 /* conv_pw2.hip PW_MAXMID */ && C.cin == A.cout && A.dsts.size() == 1 &&
-               C.in_tensor == A.dsts[0].first && C.cout <= 64 && e->tensors[A.dsts[0].first].C == A.cout;
-      };
-      if (!chain(s1.a, s2.a) || (s1.b >= 0 && !chain(s1.b, s2.b))) continue;
-      if (s1.b >= 0 && (e->convs[s1.a].cout != e->convs[s1.b].cout)) continue;
-      s1.type = 3; s1.a2 = s2.a; s1.b2 = s2.b;
-      // the middle blob (Mconv6_stageK / conv5_4_CPM) lives in LDS between the two GEMMs; nobody reads it from memory: it is written only
-      // when every blob must stay tappable (keep_blobs) — 32-128 KB of stores per workgroup and ~0.9 us of its ~11 us otherwise
-      for (int idx : {s1.a, s1.b}) {
-        if (idx < 0 || e->cfg.keep_blobs) continue;
-        const int mid = e->convs[idx].dsts[0].first;
-        bool read_elsewhere = false;
-        for (auto& c2 : e->convs) if (c2.in_tensor == mid && &c2 != &e->convs[idx == s1.a ? s1.a2 : s1.b2]) read_elsewhere = true;
-        for (auto& po : e->pools) if (po.in_tensor == mid) read_elsewhere = true;
-        if (!read_elsewhere) e->tensors[mid].written = false;
-      }
-      for (int idx : {s1.a, s1.b}) if (idx >= 0) { ConvOp& A = e->convs[idx]; A.fused = 1; A.fused_chunks = A.cout / 128; A.CoutP = A.cout; }
-      for (int idx : {s1.a2, s1.b2}) if (idx >= 0) { ConvOp& C = e->convs[idx]; C.fused = 2; C.fused_chunks = C.cin / 128; C.CoutP = 64; }
-      e->steps.erase(e->steps.begin() + si + 1);
-    }
-  }
-  // arena layout
-  size_t off = 0;
-  for (auto& t : e->tensors) {
-    if (!t.written) { t.offset = 0; continue; }  // fused away (its convolution pools in the epilogue): never read, never written, no space
-    const Geom& g = e->geom[t.level];
-    const size_t pix_bytes = (size_t)t.stride() * e->elem;
-    off = round_up_sz(off, 256);
-    off += GUARD_PIX * pix_bytes;
-    off = round_up_sz(off, 256);
-    t.offset = off;
-    off += (size_t)e->NI * g.img_pix * pix_bytes + GUARD_PIX * pix_bytes;
-  }
-  e->arena_bytes = round_up_sz(off, 256) + (4u << 20);  // tail pad: the ring kernel's dummy prefetches read past the last strip
-  // weight arena
-  size_t woff = 0;
-  for (auto& c : e->convs) {
-    c.w_bytes = (size_t)c.k_eff * c.k_eff * c.nchunk * c.CoutP * c.rowb;
-    if (c.fused == 1) c.w_bytes = (size_t)c.fused_chunks * (c.split_w ? 2 : 1) * 128 * 256;
-    if (c.fused == 2) c.w_bytes = (size_t)c.fused_chunks * (c.split_w ? 2 : 1) * 64 * 256;
-    if (c.direct_first) c.w_bytes = 2 * 2 * 64 * 16;
-    woff = round_up_sz(woff, 256);
-    c.w_off = woff;
-    woff += c.w_bytes;
-    woff = round_up_sz(woff, 256);
-    c.b_off = woff;
-    woff += (size_t)c.CoutP * sizeof(float);
-  }
-  e->weights_bytes = round_up_sz(woff, 256) + (1u << 20);  // tail pad: dummy weight-tile prefetches of the last layer
-  // dominant conv step for the roofline probe: the first paired 7x7 step whose input is not a concat
-  e->dominant_step = -1;
-  for (size_t si = 0; si < e->steps.size(); ++si) {
-    const Step& s = e->steps[si];
-    static const char* dq = RTP_EXP_ENV("RTP_DOMINANT_Q");  // profiling: 1 = probe the first fp8-compensated launch of that shape instead (stage 4)
-    if (s.type == 1 && e->convs[s.a].k == 7 && e->convs[s.a].cin == 128 && (!(dq && dq[0] == '1') || e->convs[s.a].h8)) { e->dominant_step = (int)si; break; }
-  }
-  e->strip_rows = e->N > 1 ? 16 : 8;  // several scales: the row interpolations of a strip are the larger share, taller strips amortise them (+3 % frames/s at 3 scales)
-  if (const char* sr = RTP_EXP_ENV("RTP_NMS_STRIP_ROWS")) { const int v = atoi(sr); if (v >= 2 && v <= 16) e->strip_rows = v; }  // experiments
-  // the strip kernel keeps (strip_rows + 2 + NMSF_TROWS) rows of W floats + a W x 8-byte column table in LDS (postproc.hip, 150 KiB cap)
-  while (e->strip_rows > 2 && ((size_t)(e->strip_rows + 2 + 8 /* NMSF_TROWS */) * e->cfg.net_w * 4 + (size_t)e->cfg.net_w * 8) > 150 * 1024) e->strip_rows /= 2;
-  if (((size_t)(e->strip_rows + 2 + 8 /* NMSF_TROWS */) * e->cfg.net_w * 4 + (size_t)e->cfg.net_w * 8) > 150 * 1024)
-    return fail(e, RTP_EINVAL, "net_resolution width %d is too large for the fused ImResize+Nms strip kernel", e->cfg.net_w);
-  e->nstrips = (e->cfg.net_h + e->strip_rows - 1) / e->strip_rows;
-  e->max_rows = e->num_limbs * e->max_peaks;
-  {
-    // connect kernels: sort keys hold 7-bit peak ordinals; the subset table is int16 in LDS
-    const size_t lds2 = (size_t)e->max_rows * (sizeof(double) + sizeof(short) + sizeof(short) * e->num_parts);
-    if (e->max_peaks > 127 || lds2 > 150 * 1024) return fail(e, RTP_EINVAL, "max_peaks %d out of range [1,127]", e->max_peaks);
-  }
-  return RTP_OK;
-}
-
 // ---- weight packing -------------------------------------------------------------------------
 // float -> OCP e4m3 (round to nearest even, subnormals kept, clamped to +-448): what v_cvt_pk_fp8_f32 does after the clamp
 unsigned char f32_to_e4m3(float x) {
@@ -902,9 +284,9 @@ unsigned char f32_to_e4m3(float x) {
 }
 
 template <typename T>
-void pack_conv(const rtp_engine* e, const ConvOp& c, const std::vector<float>& w, const std::vector<float>& b,
+void pack_conv(const Plan& plan, const ConvOp& c, const std::vector<float>& w, const std::vector<float>& b,
                std::vector<unsigned char>* out_w, std::vector<float>* out_b) {
-  const Tensor& ti = e->tensors[c.in_tensor];
+  const Tensor& ti = plan.tensors[c.in_tensor];
   const int per_chunk = c.rowb / (int)sizeof(T);
   const int taps = c.k_eff * c.k_eff;
   out_w->assign(c.w_bytes, 0);
@@ -1004,24 +386,25 @@ void pack_conv(const rtp_engine* e, const ConvOp& c, const std::vector<float>& w
   for (int n = 0; n < c.cout; ++n) (*out_b)[n] = b[n];
 }
 
-// h8 layers: one power-of-two scale for the fp8 weight copies, shared by the two branches of a paired launch
+// h8 layers: one power-of-two scale for the fp8 weight copies, shared by the two branches of a paired launch (ConvOp::wq_exp: the one
+// plan field that comes from the weights, not from build_plan)
 void compute_wq_exp(rtp_engine* e) {
-  for (auto& s : e->steps) {
-    if (s.type != 1 || !e->convs[s.a].h8) continue;
+  for (auto& s : e->plan.steps) {
+    if (s.type != 1 || !e->plan.convs[s.a].h8) continue;
     float mx = 0.f;
     for (int idx : {s.a, s.b}) if (idx >= 0) for (float v : e->w_ref[idx]) mx = std::max(mx, std::fabs(v));
     int ex = mx > 0.f ? (int)std::floor(std::log2(448.0 / mx)) : 0;
     ex = std::max(-20, std::min(ex, 40));
-    for (int idx : {s.a, s.b}) if (idx >= 0) e->convs[idx].wq_exp = ex;
+    for (int idx : {s.a, s.b}) if (idx >= 0) e->plan.convs[idx].wq_exp = ex;
   }
 }
 
 int upload_conv_weights(rtp_engine* e, int i) {
-  const ConvOp& c = e->convs[i];
+  const ConvOp& c = e->plan.convs[i];
   std::vector<unsigned char> pw;
   std::vector<float> pb;
-  if (e->prec == 0) pack_conv<_Float16>(e, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
-  else pack_conv<float>(e, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
+  if (e->plan.prec == 0) pack_conv<_Float16>(e->plan, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
+  else pack_conv<float>(e->plan, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
   SYNC_GUARD;   // (the packing above, the expensive part, runs in parallel across engines)
   HIPCHK(e, hipMemcpy(e->dweights + c.w_off, pw.data(), pw.size(), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(e->dweights + c.b_off, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1032,17 +415,17 @@ int upload_conv_weights(rtp_engine* e, int i) {
 // longest part of creating or re-planning an engine when it runs on one thread), then uploaded into ONE host image of the arena with a
 // single copy.
 int upload_all_weights(rtp_engine* e) {
-  std::vector<unsigned char> image(e->weights_bytes, 0);
-  const int n = (int)e->convs.size();
+  std::vector<unsigned char> image(e->plan.weights_bytes, 0);
+  const int n = (int)e->plan.convs.size();
   const int nthr = std::max(1, std::min({(int)std::thread::hardware_concurrency(), 16, n}));
   std::atomic<int> next{0};
   auto work = [&]() {
     std::vector<unsigned char> pw;
     std::vector<float> pb;
     for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
-      const ConvOp& c = e->convs[i];
-      if (e->prec == 0) pack_conv<_Float16>(e, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
-      else pack_conv<float>(e, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
+      const ConvOp& c = e->plan.convs[i];
+      if (e->plan.prec == 0) pack_conv<_Float16>(e->plan, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
+      else pack_conv<float>(e->plan, c, e->w_ref[i], e->b_ref[i], &pw, &pb);
       memcpy(image.data() + c.w_off, pw.data(), pw.size());                      // disjoint ranges of the image
       memcpy(image.data() + c.b_off, pb.data(), pb.size() * sizeof(float));
     }
@@ -1052,7 +435,7 @@ int upload_all_weights(rtp_engine* e) {
   work();
   for (auto& t : pool) t.join();
   SYNC_GUARD;
-  HIPCHK(e, hipMemcpy(e->dweights, image.data(), e->weights_bytes, hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(e->dweights, image.data(), e->plan.weights_bytes, hipMemcpyHostToDevice));
   return RTP_OK;
 }
 
@@ -1089,12 +472,12 @@ int stamp_harvest(rtp_engine* e, Ctx& cx) {
 
 void fill_problem(const rtp_engine* e, const Ctx& cx, const ConvOp& c, ConvProblem* pr) {
   memset(pr, 0, sizeof(*pr));
-  pr->in = cx.arena + e->tensors[c.in_tensor].offset;
+  pr->in = cx.arena + e->plan.tensors[c.in_tensor].offset;
   pr->w = e->dweights + c.w_off;
   pr->bias = (const float*)(e->dweights + c.b_off);
   pr->ndst = (int)c.dsts.size();
   for (int d = 0; d < pr->ndst; ++d) {
-    const Tensor& t = e->tensors[c.dsts[d].first];
+    const Tensor& t = e->plan.tensors[c.dsts[d].first];
     pr->dst[d].base = cx.arena + t.offset;
     pr->dst[d].cstride = t.stride();
     pr->dst[d].coff = c.dsts[d].second;
@@ -1103,7 +486,7 @@ void fill_problem(const rtp_engine* e, const Ctx& cx, const ConvOp& c, ConvProbl
   }
   if (c.to_lowres) {
     pr->out_nchw = cx.lowres;
-    pr->out_C = e->heat_channels;
+    pr->out_C = e->plan.heat_channels;
     pr->out_coff = c.lowres_coff;
   }
   pr->Cout = c.cout;
@@ -1111,38 +494,36 @@ void fill_problem(const rtp_engine* e, const Ctx& cx, const ConvOp& c, ConvProbl
 
 unsigned long long* g_clkprobe = nullptr;  // diagnostics (rtp_bench_dominant_conv under RTP_CLKPROBE)
 int launch_conv_step(rtp_engine* e, Ctx& cx, const Step& s, int nimg) {
-  const ConvOp& A = e->convs[s.a];
-  const Geom& g = e->geom[A.level];
+  const ConvOp& A = e->plan.convs[s.a];
+  const Geom& g = e->plan.geom[A.level];
   ConvParams P;
   memset(&P, 0, sizeof P);
   fill_problem(e, cx, A, &P.prob[0]);
-  if (s.b >= 0) fill_problem(e, cx, e->convs[s.b], &P.prob[1]);
+  if (s.b >= 0) fill_problem(e, cx, e->plan.convs[s.b], &P.prob[1]);
   P.H = g.H; P.W = g.W; P.Wp = g.Wp; P.halo = g.halo; P.img_pix = g.img_pix;
-  P.in_cstride = e->tensors[A.in_tensor].stride();
+  P.in_cstride = e->plan.tensors[A.in_tensor].stride();
   P.nchunk = A.nchunk;
   P.wrap_at = A.wrap_at();
   P.last_phys = A.last_phys();
   {
-    const Tensor& tin = e->tensors[A.in_tensor];
-    const int qb = tin.q_off() * e->elem;  // byte offset of the input's q block inside a pixel
+    const Tensor& tin = e->plan.tensors[A.in_tensor];
+    const int qb = tin.q_off() * e->plan.elem;  // byte offset of the input's q block inside a pixel
     P.q_from = A.h8 ? A.ncp : 0;
     P.jump_delta = A.h8 ? qb - (A.ncp - 1) * A.rowb : 0;
     P.row_back = A.h8 ? qb + (A.ncp - 1) * A.rowb : A.last_phys() * A.rowb;
     P.wq_exp = A.wq_exp;
   }
   P.CoutP = A.CoutP;
-  const ConvCfgInfo ci = conv_cfg_info(A.cfg);
-  P.tiles_per_img = (int)(((long)g.H * g.Wp + ci.BM - 1) / ci.BM);
+  P.tiles_per_img = (int)conv_tiles_per_img(e->plan, A);
   if (A.pool >= 0) {  // tiles of 2 image rows x BM/2 pixels, walked with an even pitch; the epilogue writes the next level's tensor
-    const Geom& go = e->geom[A.level + 1];
+    const Geom& go = e->plan.geom[A.level + 1];
     P.pool = 1;
-    P.pool_wq = (g.W + A.k_eff / 2 + 1) & ~1;
+    P.pool_wq = pool_wq(g, A);
     P.pool_Wp = go.Wp; P.pool_halo = go.halo; P.pool_img_pix = go.img_pix;
-    P.tiles_per_img = (int)(((long)(g.H / 2) * P.pool_wq + ci.BM / 2 - 1) / (ci.BM / 2));
   }
   P.relu = A.relu ? 1 : 0;
   P.clkprobe = g_clkprobe;
-  P.stamp = stamp_slot(e, cx, (int)(&s - e->steps.data()));
+  P.stamp = stamp_slot(e, cx, (int)(&s - e->plan.steps.data()));
   P.nimg = nimg;
   {
     static const char* rot = RTP_EXP_ENV("RTP_CONV_ROTATE");
@@ -1162,32 +543,32 @@ int launch_conv_step(rtp_engine* e, Ctx& cx, const Step& s, int nimg) {
     // spills 6 registers (44.6 vs 45.3 us on the dominant shape); the plain fp16 launches are faster without.  "1" = all, "0" = none
     P.ilv = il ? (il[0] == '1' || (il[0] == 'q' && A.h8) || (il[0] == '7' && A.h8 && A.k_eff == 7)) : (A.h8 ? 1 : 0);
   }
-  if (A.impl == 1) HIPCHK(e, launch_conv_ring(e->prec, A.cfg, A.k_eff, A.rowb, P, s.b >= 0 ? 2 : 1, nimg, cx.stream));
-  else HIPCHK(e, launch_conv(e->prec, A.cfg, A.k_eff, A.rowb, P, s.b >= 0 ? 2 : 1, nimg, cx.stream));
+  if (A.impl == 1) HIPCHK(e, launch_conv_ring(e->plan.prec, A.cfg, A.k_eff, A.rowb, P, s.b >= 0 ? 2 : 1, nimg, cx.stream));
+  else HIPCHK(e, launch_conv(e->plan.prec, A.cfg, A.k_eff, A.rowb, P, s.b >= 0 ? 2 : 1, nimg, cx.stream));
   return RTP_OK;
 }
 
 int launch_pw2_step(rtp_engine* e, Ctx& cx, const Step& s, int nimg) {
-  const ConvOp& A = e->convs[s.a];
-  const ConvOp& C = e->convs[s.a2];
-  const Geom& g = e->geom[C.level];
+  const ConvOp& A = e->plan.convs[s.a];
+  const ConvOp& C = e->plan.convs[s.a2];
+  const Geom& g = e->plan.geom[C.level];
   Pw2Params Q;
   memset(&Q, 0, sizeof Q);
   ConvParams& P = Q.P2;
   fill_problem(e, cx, C, &P.prob[0]);
-  if (s.b2 >= 0) fill_problem(e, cx, e->convs[s.b2], &P.prob[1]);
+  if (s.b2 >= 0) fill_problem(e, cx, e->plan.convs[s.b2], &P.prob[1]);
   P.H = g.H; P.W = g.W; P.Wp = g.Wp; P.halo = g.halo; P.img_pix = g.img_pix;
   P.CoutP = 64;
-  P.tiles_per_img = (int)(((long)g.H * g.Wp + 63) / 64);
+  P.tiles_per_img = (int)plain_tiles_per_img(g, 64);
   P.relu = C.relu ? 1 : 0;
-  P.stamp = stamp_slot(e, cx, (int)(&s - e->steps.data()));
+  P.stamp = stamp_slot(e, cx, (int)(&s - e->plan.steps.data()));
   P.nimg = nimg;
   const int firsts[2] = {s.a, s.b};
   for (int q = 0; q < 2; ++q) {
     if (firsts[q] < 0) continue;
-    const ConvOp& F = e->convs[firsts[q]];
-    const Tensor& ti = e->tensors[F.in_tensor];
-    const Tensor& tm = e->tensors[F.dsts[0].first];
+    const ConvOp& F = e->plan.convs[firsts[q]];
+    const Tensor& ti = e->plan.tensors[F.in_tensor];
+    const Tensor& tm = e->plan.tensors[F.dsts[0].first];
     Q.x_in[q] = cx.arena + ti.offset;
     Q.x_cstride = ti.stride();
     Q.x_lo_off = F.split_a ? ti.lo_off() : 0;
@@ -1233,38 +614,38 @@ int launch_pw2_step(rtp_engine* e, Ctx& cx, const Step& s, int nimg) {
 
 namespace {
 bool is_dominant_class(const rtp_engine* e, const Step& s) {
-  if (s.type != 1 || e->dominant_step < 0) return false;
-  const ConvOp& a = e->convs[s.a];
-  const ConvOp& d = e->convs[e->steps[e->dominant_step].a];
+  if (s.type != 1 || e->plan.dominant_step < 0) return false;
+  const ConvOp& a = e->plan.convs[s.a];
+  const ConvOp& d = e->plan.convs[e->plan.steps[e->plan.dominant_step].a];
   // every launch of the dominant kernel SYMBOL (what a profiler aggregates), whatever its number of MFMA passes
-  return a.k == d.k && a.cin == d.cin && a.cout == d.cout && (s.b >= 0) == (e->steps[e->dominant_step].b >= 0);
+  return a.k == d.k && a.cin == d.cin && a.cout == d.cout && (s.b >= 0) == (e->plan.steps[e->plan.dominant_step].b >= 0);
 }
 
 int launch_first_step(rtp_engine* e, Ctx& cx, const Step& s, const float* input_dev, int nimg) {
-  const ConvOp& c = e->convs[s.a];
-  const Tensor& to = e->tensors[c.dsts[0].first];
+  const ConvOp& c = e->plan.convs[s.a];
+  const Tensor& to = e->plan.tensors[c.dsts[0].first];
   FirstParams Q;
   Q.in = input_dev;
-  Q.g = e->geom[0];
+  Q.g = e->plan.geom[0];
   Q.g.N = nimg;
   Q.wfrag = (const uint4*)(e->dweights + c.w_off);
   Q.bias = (const float*)(e->dweights + c.b_off);
   Q.out = (_Float16*)(cx.arena + to.offset);
   Q.Cp = to.stride();
   Q.relu = c.relu ? 1 : 0;
-  Q.stamp = stamp_slot(e, cx, (int)(&s - e->steps.data()));
+  Q.stamp = stamp_slot(e, cx, (int)(&s - e->plan.steps.data()));
   HIPCHK(e, launch_conv_first(Q, cx.stream));
   return RTP_OK;
 }
 
 int run_frame_stack(rtp_engine* e, Ctx& cx, const float* input_dev, int nimg, bool cap = false) {
-  const std::vector<PoolOp>& pools = e->pools;
-  auto geom_n = [&](int level) { Geom g = e->geom[level]; g.N = nimg; return g; };
-  for (size_t si = 0; si < e->steps.size(); ++si) {
-    const Step& s = e->steps[si];
+  const std::vector<PoolOp>& pools = e->plan.pools;
+  auto geom_n = [&](int level) { Geom g = e->plan.geom[level]; g.N = nimg; return g; };
+  for (size_t si = 0; si < e->plan.steps.size(); ++si) {
+    const Step& s = e->plan.steps[si];
     // timing pass: an event pair on this stream around the launch (full batches only: the FLOP count reported is the full batch's);
     // the dominant class only (rtp_kernel_timing 1 / 2) or every step of the plan (3: bench.py's roofline.classes)
-    const bool want_timed = e->time_dominant && !cap && nimg == e->NI && (e->time_all || is_dominant_class(e, s));
+    const bool want_timed = e->time_dominant && !cap && nimg == e->plan.NI && (e->time_all || is_dominant_class(e, s));
     const bool timed = want_timed && e->tev_next < (int)e->tev.size() / 2;
     if (want_timed && !timed) e->probe_dropped[0]++;
     if (timed) HIPCHK(e, hipEventRecord(e->tev[2 * (size_t)e->tev_next], cx.stream));
@@ -1274,12 +655,12 @@ int run_frame_stack(rtp_engine* e, Ctx& cx, const float* input_dev, int nimg, bo
         if (!timed) return;
         (void)hipEventRecord(e->tev[2 * (size_t)e->tev_next + 1], cx.stream);
         e->tev_step[e->tev_next] = (short)si;
-        e->tev_pass[e->tev_next++] = (unsigned char)(s.type == 1 ? e->convs[s.a].passes() : 1);
+        e->tev_pass[e->tev_next++] = (unsigned char)(s.type == 1 ? e->plan.convs[s.a].passes() : 1);
       }
     } close_{e, cx, s, si, timed};
     if (s.type == 0) {
-      const Tensor& t = e->tensors[0];
-      HIPCHK(e, launch_pack_input(e->prec, input_dev, cx.arena + t.offset, geom_n(0), t.stride(), cx.stream));
+      const Tensor& t = e->plan.tensors[0];
+      HIPCHK(e, launch_pack_input(e->plan.prec, input_dev, cx.arena + t.offset, geom_n(0), t.stride(), cx.stream));
     } else if (s.type == 1) {
       const int rc = launch_conv_step(e, cx, s, nimg);
       if (rc) return rc;
@@ -1291,10 +672,10 @@ int run_frame_stack(rtp_engine* e, Ctx& cx, const float* input_dev, int nimg, bo
       if (rc) return rc;
     } else {
       const PoolOp& p = pools[s.a];
-      const Tensor& ti = e->tensors[p.in_tensor];
-      const Tensor& to = e->tensors[p.out_tensor];
-      HIPCHK(e, launch_maxpool(e->prec, cx.arena + ti.offset, geom_n(ti.level), ti.stride(), cx.arena + to.offset, geom_n(to.level), to.stride(),
-                               round_up(p.C, 16 / e->elem), ti.lo_off(), to.lo_off(), ti.q_off(), to.q_off(), cx.stream));
+      const Tensor& ti = e->plan.tensors[p.in_tensor];
+      const Tensor& to = e->plan.tensors[p.out_tensor];
+      HIPCHK(e, launch_maxpool(e->plan.prec, cx.arena + ti.offset, geom_n(ti.level), ti.stride(), cx.arena + to.offset, geom_n(to.level), to.stride(),
+                               round_up(p.C, 16 / e->plan.elem), ti.lo_off(), to.lo_off(), ti.q_off(), to.q_off(), cx.stream));
     }
   }
   return RTP_OK;
@@ -1303,9 +684,9 @@ int run_frame_stack(rtp_engine* e, Ctx& cx, const float* input_dev, int nimg, bo
 ResizeParams resize_params(rtp_engine* e, Ctx& cx, int sj) {
   Slot& sl = cx.slot[sj];
   ResizeParams rp;
-  rp.src = cx.lowres + (size_t)sj * e->N * e->heat_channels * e->low_h * e->low_w;
-  rp.dst = sl.resized; rp.num = e->N; rp.C = e->heat_channels;
-  rp.h = e->low_h; rp.w = e->low_w; rp.tw = e->cfg.net_w; rp.th = e->cfg.net_h;
+  rp.src = cx.lowres + (size_t)sj * e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w;
+  rp.dst = sl.resized; rp.num = e->N; rp.C = e->plan.heat_channels;
+  rp.h = e->plan.low_h; rp.w = e->plan.low_w; rp.tw = e->cfg.net_w; rp.th = e->cfg.net_h;
   rp.start_scale = e->start_scale; rp.scale_gap = e->scale_gap;
   return rp;
 }
@@ -1317,8 +698,8 @@ NmsParams nms_params(rtp_engine* e, Ctx& cx, int sj) {
   Slot& sl = cx.slot[sj];
   NmsParams np;
   np.src = sl.resized; np.peaks = sl.peaks; np.strip_count = sl.strip_count; np.strip_list = sl.strip_list;
-  np.src_planes = e->heat_channels; np.H = e->cfg.net_h; np.W = e->cfg.net_w; np.num_parts = e->num_parts;
-  np.max_peaks = e->max_peaks; np.nstrips = e->nstrips; np.strip_rows = e->strip_rows; np.threshold = e->nms_threshold;
+  np.src_planes = e->plan.heat_channels; np.H = e->cfg.net_h; np.W = e->cfg.net_w; np.num_parts = e->plan.num_parts;
+  np.max_peaks = e->plan.max_peaks; np.nstrips = e->plan.nstrips; np.strip_rows = e->plan.strip_rows; np.threshold = e->nms_threshold;
   np.probe = nullptr;
   np.clear_flag = nullptr;
   np.stamp = stamp_slot(e, cx, 64 + 8 * sj);
@@ -1335,8 +716,8 @@ ConnectParams connect_params(rtp_engine* e, Ctx& cx, int sj) {
   cp.heat = sl.resized; cp.peaks = sl.peaks; cp.joints = sl.joints; cp.num_people = sl.num_people;
   cp.cand_score = sl.cand_score; cp.cand_ij = sl.cand_ij; cp.cand_count = sl.cand_count; cp.cand_blk = sl.cand_blk;
   cp.conn = sl.conn; cp.conn_score = sl.conn_score; cp.conn_count = sl.conn_count;
-  cp.max_rows = e->max_rows; cp.model = e->model; cp.num_parts = e->num_parts; cp.num_limbs = e->num_limbs;
-  cp.max_peaks = e->max_peaks; cp.net_w = e->cfg.net_w; cp.net_h = e->cfg.net_h; cp.disp_w = e->cfg.disp_w; cp.disp_h = e->cfg.disp_h;
+  cp.max_rows = e->plan.max_rows; cp.model = e->plan.model; cp.num_parts = e->plan.num_parts; cp.num_limbs = e->plan.num_limbs;
+  cp.max_peaks = e->plan.max_peaks; cp.net_w = e->cfg.net_w; cp.net_h = e->cfg.net_h; cp.disp_w = e->cfg.disp_w; cp.disp_h = e->cfg.disp_h;
   cp.inter_threshold = e->inter_threshold; cp.inter_min_above = e->inter_min_above; cp.min_subset_cnt = e->min_subset_cnt;
   cp.min_subset_score = e->min_subset_score; cp.max_people = RTP_MAX_PEOPLE;
   cp.stamp = stamp_slot(e, cx, 64 + 8 * sj + 2);
@@ -1378,7 +759,7 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
   }
   if (!(part & 2)) return RTP_OK;
   HIPCHK(e, hipEventRecord(cx.ev[1], cx.stream));
-  const size_t jbytes = (size_t)RTP_MAX_PEOPLE * e->num_parts * 3 * sizeof(float);
+  const size_t jbytes = (size_t)RTP_MAX_PEOPLE * e->plan.num_parts * 3 * sizeof(float);
   for (int j = 0; j < nframes; ++j) {
     Slot& sl = cx.slot[j];
     if (sl.stream != cx.stream) HIPCHK(e, hipStreamWaitEvent(sl.stream, cx.ev[1], 0));
@@ -1419,14 +800,14 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
         RenderParams rp;
         rp.src = sl.disp_cur; rp.dst = sl.render_dev; rp.w = e->cfg.disp_w; rp.h = e->cfg.disp_h;
         rp.poses = sl.joints; rp.num_people = sl.num_people; rp.tab = sl.render_tab;
-        rp.model = e->model; rp.googly = 0; rp.max_people = RTP_MAX_PEOPLE;
+        rp.model = e->plan.model; rp.googly = 0; rp.max_people = RTP_MAX_PEOPLE;
         HIPCHK(e, launch_render(rp, sl.stream));
       } else {  // --part_to_show view: needs the frame's net-resolution maps, which the production path never builds
         if (!(materialize || skip || (unf && unf[0] == '1')) && (rc = run_resize(e, cx, j))) return rc;
         RenderViewParams vp;
         vp.src = sl.disp_cur; vp.dst = sl.render_dev; vp.w = e->cfg.disp_w; vp.h = e->cfg.disp_h;
         vp.maps = sl.resized; vp.net_w = e->cfg.net_w; vp.net_h = e->cfg.net_h;
-        vp.model = e->model; vp.part_to_show = e->cfg.render - 1;
+        vp.model = e->plan.model; vp.part_to_show = e->cfg.render - 1;
         HIPCHK(e, launch_render_view(vp, sl.stream));
       }
       if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
@@ -1559,24 +940,24 @@ int alloc_slot(rtp_engine* e, Ctx& cx, Slot& sl, bool share_stream) {
   if (sl.preset_stream) {}  // RTP_STREAM_PLAN: alloc_ctx chose it
   else if (share_stream) sl.stream = cx.stream;
   else { HIPCHK(e, make_stream(&sl.stream, true)); sl.own_stream = true; }
-  const size_t res_floats = (size_t)e->heat_channels * e->cfg.net_h * e->cfg.net_w;
+  const size_t res_floats = (size_t)e->plan.heat_channels * e->cfg.net_h * e->cfg.net_w;
   HIPCHK(e, hipMalloc((void**)&sl.resized, res_floats * sizeof(float)));
-  const size_t peak_floats = (size_t)e->num_parts * (e->max_peaks + 1) * 3;
+  const size_t peak_floats = (size_t)e->plan.num_parts * (e->plan.max_peaks + 1) * 3;
   HIPCHK(e, hipMalloc((void**)&sl.peaks, peak_floats * sizeof(float)));
   HIPCHK(e, hipMemset(sl.peaks, 0, peak_floats * sizeof(float)));
-  HIPCHK(e, hipMalloc((void**)&sl.strip_count, (size_t)e->num_parts * e->nstrips * sizeof(int)));
-  HIPCHK(e, hipMalloc((void**)&sl.strip_list, (size_t)e->num_parts * e->nstrips * e->max_peaks * sizeof(int)));
-  const size_t pairs = (size_t)e->num_limbs * e->max_peaks * e->max_peaks;
+  HIPCHK(e, hipMalloc((void**)&sl.strip_count, (size_t)e->plan.num_parts * e->plan.nstrips * sizeof(int)));
+  HIPCHK(e, hipMalloc((void**)&sl.strip_list, (size_t)e->plan.num_parts * e->plan.nstrips * e->plan.max_peaks * sizeof(int)));
+  const size_t pairs = (size_t)e->plan.num_limbs * e->plan.max_peaks * e->plan.max_peaks;
   HIPCHK(e, hipMalloc((void**)&sl.cand_score, pairs * sizeof(float)));
   HIPCHK(e, hipMalloc((void**)&sl.cand_ij, pairs * sizeof(int)));
-  HIPCHK(e, hipMalloc((void**)&sl.cand_count, e->num_limbs * sizeof(int)));
-  HIPCHK(e, hipMalloc((void**)&sl.cand_blk, (size_t)e->num_limbs * ((e->max_peaks * e->max_peaks + 255) / 256) * sizeof(int)));
-  HIPCHK(e, hipMalloc((void**)&sl.conn, (size_t)e->num_limbs * e->max_peaks * 2 * sizeof(int)));
-  HIPCHK(e, hipMalloc((void**)&sl.conn_score, (size_t)e->num_limbs * e->max_peaks * sizeof(float)));
-  HIPCHK(e, hipMalloc((void**)&sl.conn_count, e->num_limbs * sizeof(int)));
-  HIPCHK(e, hipMalloc((void**)&sl.tickets, (e->num_limbs + 1) * sizeof(int)));
-  HIPCHK(e, hipMemset(sl.tickets, 0, (e->num_limbs + 1) * sizeof(int)));
-  const size_t jfloats = (size_t)RTP_MAX_PEOPLE * e->num_parts * 3;
+  HIPCHK(e, hipMalloc((void**)&sl.cand_count, e->plan.num_limbs * sizeof(int)));
+  HIPCHK(e, hipMalloc((void**)&sl.cand_blk, (size_t)e->plan.num_limbs * ((e->plan.max_peaks * e->plan.max_peaks + 255) / 256) * sizeof(int)));
+  HIPCHK(e, hipMalloc((void**)&sl.conn, (size_t)e->plan.num_limbs * e->plan.max_peaks * 2 * sizeof(int)));
+  HIPCHK(e, hipMalloc((void**)&sl.conn_score, (size_t)e->plan.num_limbs * e->plan.max_peaks * sizeof(float)));
+  HIPCHK(e, hipMalloc((void**)&sl.conn_count, e->plan.num_limbs * sizeof(int)));
+  HIPCHK(e, hipMalloc((void**)&sl.tickets, (e->plan.num_limbs + 1) * sizeof(int)));
+  HIPCHK(e, hipMemset(sl.tickets, 0, (e->plan.num_limbs + 1) * sizeof(int)));
+  const size_t jfloats = (size_t)RTP_MAX_PEOPLE * e->plan.num_parts * 3;
   HIPCHK(e, hipMalloc((void**)&sl.joints, jfloats * sizeof(float)));
   HIPCHK(e, hipMemset(sl.joints, 0, jfloats * sizeof(float)));
   HIPCHK(e, hipMalloc((void**)&sl.num_people, sizeof(int)));
@@ -1628,12 +1009,12 @@ int alloc_ctx(rtp_engine* e, Ctx& cx) {
   } else
 #endif
   HIPCHK(e, make_stream(&cx.stream, false));
-  HIPCHK(e, hipMalloc((void**)&cx.arena, e->arena_bytes));
-  HIPCHK(e, hipMemset(cx.arena, 0, e->arena_bytes));
-  const size_t in_floats = (size_t)e->NI * 3 * e->cfg.net_h * e->cfg.net_w;
+  HIPCHK(e, hipMalloc((void**)&cx.arena, e->plan.arena_bytes));
+  HIPCHK(e, hipMemset(cx.arena, 0, e->plan.arena_bytes));
+  const size_t in_floats = (size_t)e->plan.NI * 3 * e->cfg.net_h * e->cfg.net_w;
   HIPCHK(e, hipMalloc((void**)&cx.input, in_floats * sizeof(float)));
   HIPCHK(e, hipHostMalloc((void**)&cx.host_in, in_floats * sizeof(float), hipHostMallocDefault));
-  const size_t low_floats = (size_t)e->NI * e->heat_channels * e->low_h * e->low_w;
+  const size_t low_floats = (size_t)e->plan.NI * e->plan.heat_channels * e->plan.low_h * e->plan.low_w;
   HIPCHK(e, hipMalloc((void**)&cx.lowres, low_floats * sizeof(float)));
   HIPCHK(e, hipMemset(cx.lowres, 0, low_floats * sizeof(float)));
   for (int i = 0; i < 2; ++i) HIPCHK(e, hipEventCreateWithFlags(&cx.ev[i], event_flags(i == 1)));
@@ -2015,9 +1396,9 @@ int materialize_plan(rtp_engine* e, int nctx, bool capture) {
   if ((rc = use_device(e))) return rc;
   {
     SYNC_GUARD;
-    hipError_t s = hipMalloc((void**)&e->dweights, e->weights_bytes);
-    if (s != hipSuccess) { e->dweights = nullptr; return fail(e, RTP_ENOMEM, "hipMalloc(%zu) for weights failed: %s", e->weights_bytes, hipGetErrorString(s)); }
-    s = hipMemset(e->dweights, 0, e->weights_bytes);
+    hipError_t s = hipMalloc((void**)&e->dweights, e->plan.weights_bytes);
+    if (s != hipSuccess) { e->dweights = nullptr; return fail(e, RTP_ENOMEM, "hipMalloc(%zu) for weights failed: %s", e->plan.weights_bytes, hipGetErrorString(s)); }
+    s = hipMemset(e->dweights, 0, e->plan.weights_bytes);
     if (s != hipSuccess) return fail(e, RTP_EHIP, "hipMemset failed: %s", hipGetErrorString(s));
     if (!e->dchmap) {
       s = hipMalloc((void**)&e->dchmap, 4096 * sizeof(int));
@@ -2072,21 +1453,25 @@ void drop_plan(rtp_engine* e) {
   for (auto& c : e->ctx) free_ctx(c);
   e->ctx.clear();
   if (e->dweights) { (void)hipFree(e->dweights); e->dweights = nullptr; }
-  e->tensors.clear(); e->blob_tensor.clear(); e->blob_dims.clear(); e->convs.clear(); e->steps.clear(); e->pools.clear();
+  e->plan = Plan();
   e->open_ctx = -1;
   e->fifo.clear();
   e->pending_launch.clear();
 }
 
+// What the engine's plan depends on: the net and config it was created with, and the precision mode / split set calibration may change
+PlanInput plan_input(const rtp_engine* e) {
+  return {&e->net, e->cfg.net_w, e->cfg.net_h, e->N, e->B, e->mode, e->split_rules, e->split_fp8, e->cfg.keep_blobs};
+}
+
 // Re-plan an idle engine for another precision mode / split set (load-time calibration).  light = one context, no graph capture.
 int replan(rtp_engine* e, int mode, const std::string& rules, bool light) {
-  drop_plan(e);
+  drop_plan(e);   // first: a calibration trial relies on the memory of the previous plan being free
   e->mode = mode;
-  e->prec = mode == RTP_PREC_FP32 ? 1 : 0;
-  e->elem = e->prec ? 4 : 2;
   e->split_rules = rules;
-  int rc = build_plan(e);
-  if (rc) return rc;
+  Plan plan;   // a failed build leaves the engine with the empty plan of drop_plan, never with half of one
+  if (int rc = build_plan(plan_input(e), &plan, &e->err)) return rc;
+  e->plan = std::move(plan);
   return materialize_plan(e, light ? 1 : e->nctx_full, !light);
 }
 
@@ -2281,17 +1666,9 @@ static int engine_create_impl(const rtp_config* cfg, rtp_engine** out) {
   e->cfg = *cfg;
   if (cfg->proto_path) { e->proto_path = cfg->proto_path; e->cfg.proto_path = e->proto_path.c_str(); }
   if (cfg->weights_path) { e->weights_path = cfg->weights_path; e->cfg.weights_path = e->weights_path.c_str(); }
-  e->mode = cfg->precision;
-  e->prec = cfg->precision == RTP_PREC_FP32 ? 1 : 0;
-  e->elem = e->prec ? 4 : 2;
-  {
-    const char* sr = RTP_EXP_ENV("RTP_SPLIT_LAYERS");  // experiments: override the split set of RTP_PREC_MIXED
-    e->split_rules = sr ? sr : (cfg->split_layers ? cfg->split_layers : kDefaultSplit);
-    e->cfg.split_layers = nullptr;
-  }
-  e->N = cfg->num_scales;
-  e->B = cfg->batch_frames < 1 ? 1 : cfg->batch_frames;
-  e->NI = e->N * e->B;
+  const PlanInput in0 = plan_input_from_config(*cfg, &e->net);   // (RTP_SPLIT_LAYERS / RTP_SPLIT_FP8 of the experiments build included)
+  e->mode = in0.mode; e->split_rules = in0.split_rules; e->split_fp8 = in0.split_fp8; e->N = in0.N; e->B = in0.B;
+  e->cfg.split_layers = nullptr;
   e->start_scale = cfg->start_scale;
   e->scale_gap = cfg->scale_gap;
   {
@@ -2299,8 +1676,6 @@ static int engine_create_impl(const rtp_config* cfg, rtp_engine** out) {
     e->use_graph = cfg->exec_mode == RTP_EXEC_GRAPH;
     if (eg && !strcmp(eg, "eager")) e->use_graph = false;
     if (eg && !strcmp(eg, "graph")) e->use_graph = true;
-    const char* f8 = RTP_EXP_ENV("RTP_SPLIT_FP8");
-    e->split_fp8 = !(f8 && f8[0] == '0');
     const char* gp = RTP_EXP_ENV("RTP_GRAPH_POST");
     e->graph_post = gp && gp[0] == '1';
     const char* im = RTP_EXP_ENV("RTP_IN_STREAM");   // experiments: 0 = stage inputs on the conv stream, 1 = own stream, 2 = own high-priority stream
@@ -2313,29 +1688,19 @@ static int engine_create_impl(const rtp_config* cfg, rtp_engine** out) {
   }
   auto bail = [&](int rc) { g_create_error = e->err; rtp_engine_destroy(e); return rc; };
 
-  if (!e->proto_path.empty()) {
-    std::ifstream f(e->proto_path);
-    if (!f) return bail(fail(e, RTP_EIO, "cannot open prototxt %s", e->proto_path.c_str()));
-    std::stringstream ss;
-    ss << f.rdbuf();
-    std::string perr;
-    if (!parse_prototxt(ss.str(), &e->net, &perr)) return bail(fail(e, RTP_EIO, "prototxt %s: %s", e->proto_path.c_str(), perr.c_str()));
-  } else {
-    if (cfg->model != RTP_MODEL_COCO_18 && cfg->model != RTP_MODEL_MPI_15) return bail(fail(e, RTP_EINVAL, "unknown model %d", cfg->model));
-    e->net = build_linevec(cfg->model);
-  }
-  int rc = build_plan(e);
+  int rc = load_netdef(e->proto_path.empty() ? nullptr : e->proto_path.c_str(), cfg->model, true, &e->net, &e->err);
+  if (!rc) rc = build_plan(plan_input(e), &e->plan, &e->err);
   if (rc) return bail(rc);
   // thresholds as warmup() sets them (rtpose.cpp:212-226)
-  rtp_default_thresholds(e->model, &e->nms_threshold, &e->inter_threshold, &e->inter_min_above, &e->min_subset_cnt, &e->min_subset_score);
+  rtp_default_thresholds(e->plan.model, &e->nms_threshold, &e->inter_threshold, &e->inter_min_above, &e->min_subset_cnt, &e->min_subset_score);
 
   // weights
-  e->w_ref.resize(e->convs.size());
-  e->b_ref.resize(e->convs.size());
+  e->w_ref.resize(e->plan.convs.size());
+  e->b_ref.resize(e->plan.convs.size());
   e->weights_pending = cfg->defer_weights != 0;
   if (e->weights_pending) {   // a receiving replica: sizes only (rtp_get_conv_weights / rtp_weight_blob_bytes need them), contents arrive with the blob
-    for (size_t i = 0; i < e->convs.size(); ++i) {
-      const ConvOp& c = e->convs[i];
+    for (size_t i = 0; i < e->plan.convs.size(); ++i) {
+      const ConvOp& c = e->plan.convs[i];
       e->w_ref[i].assign((size_t)c.cout * c.cin * c.k * c.k, 0.f);
       e->b_ref[i].assign((size_t)c.cout, 0.f);
     }
@@ -2344,8 +1709,8 @@ static int engine_create_impl(const rtp_config* cfg, rtp_engine** out) {
     std::string werr;
     if (!read_caffemodel(e->weights_path, &lw, &werr)) return bail(fail(e, RTP_EIO, "%s", werr.c_str()));
     // CopyTrainedLayersFrom: match by layer name; unknown source layers ignored; shapes must match (net.cpp:750-786)
-    for (size_t i = 0; i < e->convs.size(); ++i) {
-      const ConvOp& c = e->convs[i];
+    for (size_t i = 0; i < e->plan.convs.size(); ++i) {
+      const ConvOp& c = e->plan.convs[i];
       const LayerWeights* src = nullptr;
       for (auto& L : lw) if (L.name == c.name) src = &L;
       if (!src) return bail(fail(e, RTP_EIO, "layer %s has no weights in %s", c.name.c_str(), e->weights_path.c_str()));
@@ -2355,13 +1720,13 @@ static int engine_create_impl(const rtp_config* cfg, rtp_engine** out) {
       e->b_ref[i] = src->blobs[1].data;
     }
   } else {
-    for (size_t i = 0; i < e->convs.size(); ++i) {
-      const ConvOp& c = e->convs[i];
+    for (size_t i = 0; i < e->plan.convs.size(); ++i) {
+      const ConvOp& c = e->plan.convs[i];
       synth_conv_weights(cfg->synthetic_seed, c.name, c.cout, c.cin, c.k, &e->w_ref[i], &e->b_ref[i]);
     }
   }
 
-  e->nctx_full = (cfg->frames_in_flight + e->B - 1) / e->B + (e->B > 1 ? 1 : 0);  // batches in flight (+1 being filled)
+  e->nctx_full = plan_contexts(cfg->frames_in_flight, e->B);
   if ((rc = materialize_plan(e, e->nctx_full, !e->weights_pending))) return bail(rc);   // (a receiving replica captures when its weights arrive: wq_exp is baked into the graphs)
   if ((rc = build_prep_tables(e))) return bail(rc);
   // Load-time precision calibration (net.cpp:750-803 is where real weights arrive).  The default split set was chosen on synthetic
@@ -2390,11 +1755,11 @@ static int engine_create_impl(const rtp_config* cfg, rtp_engine** out) {
 
 int rtp_engine_info(const rtp_engine* e, int* num_parts, int* max_peaks, int* heat_channels, int* low_w, int* low_h) {
   if (!e) return RTP_EINVAL;
-  if (num_parts) *num_parts = e->num_parts;
-  if (max_peaks) *max_peaks = e->max_peaks;
-  if (heat_channels) *heat_channels = e->heat_channels;
-  if (low_w) *low_w = e->low_w;
-  if (low_h) *low_h = e->low_h;
+  if (num_parts) *num_parts = e->plan.num_parts;
+  if (max_peaks) *max_peaks = e->plan.max_peaks;
+  if (heat_channels) *heat_channels = e->plan.heat_channels;
+  if (low_w) *low_w = e->plan.low_w;
+  if (low_h) *low_h = e->plan.low_h;
   return RTP_OK;
 }
 
@@ -2646,7 +2011,7 @@ static int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_pe
   }
   if (n > RTP_MAX_PEOPLE) n = RTP_MAX_PEOPLE;
   if (num_people) *num_people = n;
-  if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->num_parts * 3 * sizeof(float));
+  if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->plan.num_parts * 3 * sizeof(float));
   if (want_render) {
     if (!e->cfg.render) return fail(e, RTP_EINVAL, "rtp_collect_rendered needs rtp_config.render = 1");
     if (!sl.has_disp || (rendered && !sl.render_host))
@@ -2807,17 +2172,17 @@ int rtp_forward_debug(rtp_engine* e, const float* h_in, float* lowres, float* re
   HIPCHK(e, hipMemcpy(cx.input, h_in, bytes, hipMemcpyHostToDevice));
   if ((rc = enqueue_frame(e, cx, cx.input, true))) return rc;  // taps: materialised map
   HIPCHK(e, hipStreamSynchronize(cx.stream));
-  if (lowres) HIPCHK(e, hipMemcpy(lowres, cx.lowres, (size_t)e->N * e->heat_channels * e->low_h * e->low_w * sizeof(float), hipMemcpyDeviceToHost));
+  if (lowres) HIPCHK(e, hipMemcpy(lowres, cx.lowres, (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w * sizeof(float), hipMemcpyDeviceToHost));
   Slot& sl = cx.slot[0];
   cx.launched = false;
-  if (resized) HIPCHK(e, hipMemcpy(resized, sl.resized, (size_t)e->heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyDeviceToHost));
-  if (peaks) HIPCHK(e, hipMemcpy(peaks, sl.peaks, (size_t)e->num_parts * (e->max_peaks + 1) * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (resized) HIPCHK(e, hipMemcpy(resized, sl.resized, (size_t)e->plan.heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyDeviceToHost));
+  if (peaks) HIPCHK(e, hipMemcpy(peaks, sl.peaks, (size_t)e->plan.num_parts * (e->plan.max_peaks + 1) * 3 * sizeof(float), hipMemcpyDeviceToHost));
   int n;
   memcpy(&n, sl.host_out, sizeof(int));
   stage_ms(e, cx, sl);
   if (n < 0) { if (num_people) *num_people = 0; return fail(e, RTP_ERANGE, "connect: PAF sample coordinate out of range"); }
   if (num_people) *num_people = n;
-  if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->num_parts * 3 * sizeof(float));
+  if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->plan.num_parts * 3 * sizeof(float));
   return RTP_OK;
 }
 
@@ -2832,7 +2197,7 @@ int rtp_forward_heatmaps(rtp_engine* e, const float* h_in, float* lowres) {
   HIPCHK(e, hipMemcpy(cx.input, h_in, bytes, hipMemcpyHostToDevice));
   if ((rc = run_frame_stack(e, cx, cx.input, e->N))) return rc;
   HIPCHK(e, hipStreamSynchronize(cx.stream));
-  HIPCHK(e, hipMemcpy(lowres, cx.lowres, (size_t)e->N * e->heat_channels * e->low_h * e->low_w * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(lowres, cx.lowres, (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w * sizeof(float), hipMemcpyDeviceToHost));
   return RTP_OK;
 }
 
@@ -2842,10 +2207,10 @@ int rtp_resize(rtp_engine* e, const float* lowres, float* resized) {
   if ((rc = need_idle(e))) return rc;
   if (!lowres || !resized) return RTP_EINVAL;
   Ctx& cx = e->ctx[0];
-  HIPCHK(e, hipMemcpy(cx.lowres, lowres, (size_t)e->N * e->heat_channels * e->low_h * e->low_w * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(cx.lowres, lowres, (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w * sizeof(float), hipMemcpyHostToDevice));
   if ((rc = run_resize(e, cx))) return rc;
   HIPCHK(e, hipStreamSynchronize(cx.stream));
-  HIPCHK(e, hipMemcpy(resized, cx.slot[0].resized, (size_t)e->heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(resized, cx.slot[0].resized, (size_t)e->plan.heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyDeviceToHost));
   return RTP_OK;
 }
 
@@ -2857,8 +2222,8 @@ int rtp_post_from_lowres(rtp_engine* e, const float* lowres, float* peaks, float
   if (!lowres) return RTP_EINVAL;
   Ctx& cx = e->ctx[0];
   Slot& sl = cx.slot[0];
-  const size_t pbytes = (size_t)e->num_parts * (e->max_peaks + 1) * 3 * sizeof(float);
-  HIPCHK(e, hipMemcpy(cx.lowres, lowres, (size_t)e->N * e->heat_channels * e->low_h * e->low_w * sizeof(float), hipMemcpyHostToDevice));
+  const size_t pbytes = (size_t)e->plan.num_parts * (e->plan.max_peaks + 1) * 3 * sizeof(float);
+  HIPCHK(e, hipMemcpy(cx.lowres, lowres, (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w * sizeof(float), hipMemcpyHostToDevice));
   if (peaks) HIPCHK(e, hipMemcpy(sl.peaks, peaks, pbytes, hipMemcpyHostToDevice));  // stale slots stay, like the reference's blob
   if (RTP_EXP_ENV("RTP_NMS_PROBE")) {  // diagnostics: phase stamps of the middle strip workgroup of part 0
     unsigned long long* d = nullptr;
@@ -2890,7 +2255,7 @@ int rtp_post_from_lowres(rtp_engine* e, const float* lowres, float* peaks, float
   HIPCHK(e, hipMemcpy(&n, sl.num_people, sizeof(int), hipMemcpyDeviceToHost));
   if (n < 0) { if (num_people) *num_people = 0; return fail(e, RTP_ERANGE, "connect: PAF sample coordinate out of range"); }
   if (num_people) *num_people = n;
-  if (joints && n > 0) HIPCHK(e, hipMemcpy(joints, sl.joints, (size_t)n * e->num_parts * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (joints && n > 0) HIPCHK(e, hipMemcpy(joints, sl.joints, (size_t)n * e->plan.num_parts * 3 * sizeof(float), hipMemcpyDeviceToHost));
   return RTP_OK;
 }
 
@@ -2900,8 +2265,8 @@ int rtp_nms(rtp_engine* e, const float* resized, float* peaks) {
   if ((rc = need_idle(e))) return rc;
   if (!resized || !peaks) return RTP_EINVAL;
   Ctx& cx = e->ctx[0];
-  const size_t pbytes = (size_t)e->num_parts * (e->max_peaks + 1) * 3 * sizeof(float);
-  HIPCHK(e, hipMemcpy(cx.slot[0].resized, resized, (size_t)e->heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyHostToDevice));
+  const size_t pbytes = (size_t)e->plan.num_parts * (e->plan.max_peaks + 1) * 3 * sizeof(float);
+  HIPCHK(e, hipMemcpy(cx.slot[0].resized, resized, (size_t)e->plan.heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(cx.slot[0].peaks, peaks, pbytes, hipMemcpyHostToDevice));
   if ((rc = run_nms(e, cx))) return rc;
   HIPCHK(e, hipStreamSynchronize(cx.stream));
@@ -2915,15 +2280,15 @@ int rtp_connect(rtp_engine* e, const float* resized, const float* peaks, float* 
   if ((rc = need_idle(e))) return rc;
   if (!resized || !peaks) return RTP_EINVAL;
   Ctx& cx = e->ctx[0];
-  HIPCHK(e, hipMemcpy(cx.slot[0].resized, resized, (size_t)e->heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(cx.slot[0].peaks, peaks, (size_t)e->num_parts * (e->max_peaks + 1) * 3 * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(cx.slot[0].resized, resized, (size_t)e->plan.heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(cx.slot[0].peaks, peaks, (size_t)e->plan.num_parts * (e->plan.max_peaks + 1) * 3 * sizeof(float), hipMemcpyHostToDevice));
   if ((rc = run_connect(e, cx))) return rc;
   HIPCHK(e, hipStreamSynchronize(cx.stream));
   int n = 0;
   HIPCHK(e, hipMemcpy(&n, cx.slot[0].num_people, sizeof(int), hipMemcpyDeviceToHost));
   if (n < 0) { if (num_people) *num_people = 0; return fail(e, RTP_ERANGE, "connect: PAF sample coordinate out of range"); }
   if (num_people) *num_people = n;
-  if (joints && n > 0) HIPCHK(e, hipMemcpy(joints, cx.slot[0].joints, (size_t)n * e->num_parts * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (joints && n > 0) HIPCHK(e, hipMemcpy(joints, cx.slot[0].joints, (size_t)n * e->plan.num_parts * 3 * sizeof(float), hipMemcpyDeviceToHost));
   return RTP_OK;
 }
 
@@ -2935,9 +2300,9 @@ int rtp_render(rtp_engine* e, const unsigned char* display_bgr, const float* joi
   if ((rc = need_idle(e))) return rc;
   if (!display_bgr || !out_bgr || num_people < 0 || (num_people > 0 && !joints)) return RTP_EINVAL;
   // the last map a view reads: MPI part_to_show - 1; COCO heat maps <= 18, PAF view p reads channels up to 2*(p-20)-2+19+1
-  const int last_map = e->model != 0 ? part_to_show - 1 : (part_to_show <= 19 ? 17 : (part_to_show == 20 ? 56 : 2 * (part_to_show - 20) + 18));
-  if (part_to_show < 0 || (part_to_show > 0 && (!resized_host || last_map >= e->heat_channels)))
-    return fail(e, RTP_EINVAL, "part_to_show %d is outside the model's %d maps", part_to_show, e->heat_channels);
+  const int last_map = e->plan.model != 0 ? part_to_show - 1 : (part_to_show <= 19 ? 17 : (part_to_show == 20 ? 56 : 2 * (part_to_show - 20) + 18));
+  if (part_to_show < 0 || (part_to_show > 0 && (!resized_host || last_map >= e->plan.heat_channels)))
+    return fail(e, RTP_EINVAL, "part_to_show %d is outside the model's %d maps", part_to_show, e->plan.heat_channels);
   Ctx& cx = e->ctx[0];
   Slot& sl = cx.slot[0];
   const int w = e->cfg.disp_w, h = e->cfg.disp_h;
@@ -2951,19 +2316,19 @@ int rtp_render(rtp_engine* e, const unsigned char* display_bgr, const float* joi
   HIPCHK(e, hipMemcpy(sl.disp_dev, display_bgr, dbytes, hipMemcpyHostToDevice));
   if (part_to_show == 0) {
     const int n = std::min(num_people, (int)RTP_MAX_PEOPLE);
-    if (n > 0) HIPCHK(e, hipMemcpy(sl.joints, joints, (size_t)n * e->num_parts * 3 * sizeof(float), hipMemcpyHostToDevice));
+    if (n > 0) HIPCHK(e, hipMemcpy(sl.joints, joints, (size_t)n * e->plan.num_parts * 3 * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(sl.num_people, &n, sizeof(int), hipMemcpyHostToDevice));
     RenderParams rp;
     rp.src = sl.disp_dev; rp.dst = sl.render_dev; rp.w = w; rp.h = h;
     rp.poses = sl.joints; rp.num_people = sl.num_people; rp.tab = sl.render_tab;
-    rp.model = e->model; rp.googly = googly ? 1 : 0; rp.max_people = RTP_MAX_PEOPLE;
+    rp.model = e->plan.model; rp.googly = googly ? 1 : 0; rp.max_people = RTP_MAX_PEOPLE;
     HIPCHK(e, launch_render(rp, sl.stream));
   } else {
-    HIPCHK(e, hipMemcpy(sl.resized, resized_host, (size_t)e->heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(sl.resized, resized_host, (size_t)e->plan.heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyHostToDevice));
     RenderViewParams vp;
     vp.src = sl.disp_dev; vp.dst = sl.render_dev; vp.w = w; vp.h = h;
     vp.maps = sl.resized; vp.net_w = e->cfg.net_w; vp.net_h = e->cfg.net_h;
-    vp.model = e->model; vp.part_to_show = part_to_show;
+    vp.model = e->plan.model; vp.part_to_show = part_to_show;
     HIPCHK(e, launch_render_view(vp, sl.stream));
   }
   HIPCHK(e, hipStreamSynchronize(sl.stream));
@@ -2977,19 +2342,19 @@ int rtp_get_blob(rtp_engine* e, const char* name, float* out, size_t cap, int sh
   if ((rc = need_idle(e))) return rc;
   if (!name) return RTP_EINVAL;
   Ctx& cx = e->ctx[0];
-  if (e->lowres_blob == name) {
-    const size_t n = (size_t)e->N * e->heat_channels * e->low_h * e->low_w;
-    if (shape) { shape[0] = e->N; shape[1] = e->heat_channels; shape[2] = e->low_h; shape[3] = e->low_w; }
+  if (e->plan.lowres_blob == name) {
+    const size_t n = (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w;
+    if (shape) { shape[0] = e->N; shape[1] = e->plan.heat_channels; shape[2] = e->plan.low_h; shape[3] = e->plan.low_w; }
     if (!out) return RTP_OK;
     if (cap < n) return fail(e, RTP_EINVAL, "blob %s needs %zu floats", name, n);
     HIPCHK(e, hipMemcpy(out, cx.lowres, n * sizeof(float), hipMemcpyDeviceToHost));
     return RTP_OK;
   }
-  auto it = e->blob_tensor.find(name);
-  if (it == e->blob_tensor.end()) return fail(e, RTP_EINVAL, "Unknown blob name %s", name);  // net.cpp blob_by_name warning
-  const Tensor& t = e->tensors[it->second];
+  auto it = e->plan.blob_tensor.find(name);
+  if (it == e->plan.blob_tensor.end()) return fail(e, RTP_EINVAL, "Unknown blob name %s", name);  // net.cpp blob_by_name warning
+  const Tensor& t = e->plan.tensors[it->second];
   if (!t.written) return fail(e, RTP_EINVAL, "blob %s is not materialised: its convolution pools in the epilogue and writes only the pooled blob, or it is the middle blob of a fused branch tail that lives in LDS (create the engine with keep_blobs = 1 to tap it)", name);
-  Geom g = e->geom[t.level];
+  Geom g = e->plan.geom[t.level];
   g.N = e->N;  // the taps run one frame (slot 0 of the batch)
   const size_t n = (size_t)g.N * t.C * g.H * g.W;
   if (shape) { shape[0] = g.N; shape[1] = t.C; shape[2] = g.H; shape[3] = g.W; }
@@ -2999,7 +2364,7 @@ int rtp_get_blob(rtp_engine* e, const char* name, float* out, size_t cap, int sh
   float* dtmp = nullptr;
   HIPCHK(e, hipMalloc((void**)&dtmp, n * sizeof(float)));
   hipError_t s = hipMemcpy(e->dchmap, t.chmap.data(), t.C * sizeof(int), hipMemcpyHostToDevice);
-  if (s == hipSuccess) s = launch_export(e->prec, cx.arena + t.offset, g, t.stride(), e->dchmap, t.C, t.lo_off(), t.q_off(), dtmp, cx.stream);
+  if (s == hipSuccess) s = launch_export(e->plan.prec, cx.arena + t.offset, g, t.stride(), e->dchmap, t.C, t.lo_off(), t.q_off(), dtmp, cx.stream);
   if (s == hipSuccess) s = hipStreamSynchronize(cx.stream);
   if (s == hipSuccess) s = hipMemcpy(out, dtmp, n * sizeof(float), hipMemcpyDeviceToHost);
   (void)hipFree(dtmp);
@@ -3008,10 +2373,10 @@ int rtp_get_blob(rtp_engine* e, const char* name, float* out, size_t cap, int sh
 }
 
 // ---- weights / graph ---------------------------------------------------------------------------
-int rtp_num_conv_layers(const rtp_engine* e) { return e ? (int)e->convs.size() : RTP_EINVAL; }
+int rtp_num_conv_layers(const rtp_engine* e) { return e ? (int)e->plan.convs.size() : RTP_EINVAL; }
 int rtp_conv_layer_info(const rtp_engine* e, int i, char* name, int name_len, int* cin, int* cout, int* k) {
-  if (!e || i < 0 || i >= (int)e->convs.size()) return RTP_EINVAL;
-  const ConvOp& c = e->convs[i];
+  if (!e || i < 0 || i >= (int)e->plan.convs.size()) return RTP_EINVAL;
+  const ConvOp& c = e->plan.convs[i];
   if (name && name_len > 0) snprintf(name, name_len, "%s", c.name.c_str());
   if (cin) *cin = c.cin;
   if (cout) *cout = c.cout;
@@ -3019,28 +2384,28 @@ int rtp_conv_layer_info(const rtp_engine* e, int i, char* name, int name_len, in
   return RTP_OK;
 }
 int rtp_get_conv_weights(const rtp_engine* e, int i, float* w, float* b) {
-  if (!e || i < 0 || i >= (int)e->convs.size()) return RTP_EINVAL;
+  if (!e || i < 0 || i >= (int)e->plan.convs.size()) return RTP_EINVAL;
   if (w) memcpy(w, e->w_ref[i].data(), e->w_ref[i].size() * sizeof(float));
   if (b) memcpy(b, e->b_ref[i].data(), e->b_ref[i].size() * sizeof(float));
   return RTP_OK;
 }
 int rtp_set_conv_weights(rtp_engine* e, int i, const float* w, const float* b) {
   SYNC_GUARD;
-  if (!e || i < 0 || i >= (int)e->convs.size() || !w || !b) return RTP_EINVAL;
+  if (!e || i < 0 || i >= (int)e->plan.convs.size() || !w || !b) return RTP_EINVAL;
   int rc;
   if ((rc = need_idle(e))) return rc;
   if ((rc = need_weights(e))) return rc;   // (a defer_weights engine takes its weights as ONE blob / peer copy, not layer by layer)
   e->w_ref[i].assign(w, w + e->w_ref[i].size());
   e->b_ref[i].assign(b, b + e->b_ref[i].size());
   HIPCHK(e, hipDeviceSynchronize());
-  if (e->convs[i].h8) {  // the fp8 scale is shared with the other branch of the launch: re-pack both when it moves
-    std::vector<int> old(e->convs.size());
-    for (size_t j = 0; j < e->convs.size(); ++j) old[j] = e->convs[j].wq_exp;
+  if (e->plan.convs[i].h8) {  // the fp8 scale is shared with the other branch of the launch: re-pack both when it moves
+    std::vector<int> old(e->plan.convs.size());
+    for (size_t j = 0; j < e->plan.convs.size(); ++j) old[j] = e->plan.convs[j].wq_exp;
     compute_wq_exp(e);
     bool moved = false;
-    for (size_t j = 0; j < e->convs.size(); ++j) {
-      moved = moved || e->convs[j].wq_exp != old[j];
-      if ((int)j != i && e->convs[j].wq_exp != old[j] && (rc = upload_conv_weights(e, (int)j))) return rc;
+    for (size_t j = 0; j < e->plan.convs.size(); ++j) {
+      moved = moved || e->plan.convs[j].wq_exp != old[j];
+      if ((int)j != i && e->plan.convs[j].wq_exp != old[j] && (rc = upload_conv_weights(e, (int)j))) return rc;
     }
     if (moved && (rc = invalidate_graphs(e))) return rc;  // ConvParams::wq_exp is a by-value argument baked into the captured graphs
   }
@@ -3049,8 +2414,8 @@ int rtp_set_conv_weights(rtp_engine* e, int i, const float* w, const float* b) {
 int rtp_save_caffemodel(const rtp_engine* e, const char* path) {
   if (!e || !path) return RTP_EINVAL;
   std::vector<LayerWeights> lw;
-  for (size_t i = 0; i < e->convs.size(); ++i) {
-    const ConvOp& c = e->convs[i];
+  for (size_t i = 0; i < e->plan.convs.size(); ++i) {
+    const ConvOp& c = e->plan.convs[i];
     LayerWeights L;
     L.name = c.name; L.type = "Convolution";
     BlobData w, b;
@@ -3109,8 +2474,8 @@ int rtp_debug_connect_stats(rtp_engine* e, int* cand_count, int* conn_count) {
   int rc;
   if ((rc = need_idle(e))) return rc;
   Ctx& cx = e->ctx[0];
-  if (cand_count) HIPCHK(e, hipMemcpy(cand_count, cx.slot[0].cand_count, e->num_limbs * sizeof(int), hipMemcpyDeviceToHost));
-  if (conn_count) HIPCHK(e, hipMemcpy(conn_count, cx.slot[0].conn_count, e->num_limbs * sizeof(int), hipMemcpyDeviceToHost));
+  if (cand_count) HIPCHK(e, hipMemcpy(cand_count, cx.slot[0].cand_count, e->plan.num_limbs * sizeof(int), hipMemcpyDeviceToHost));
+  if (conn_count) HIPCHK(e, hipMemcpy(conn_count, cx.slot[0].conn_count, e->plan.num_limbs * sizeof(int), hipMemcpyDeviceToHost));
   return RTP_OK;
 }
 
@@ -3182,102 +2547,6 @@ int rtp_caffemodel_layer(const char* path, int index, char* name, int name_len, 
   return RTP_OK;
 }
 
-// Build the execution plan for cfg WITHOUT touching a device and describe it as text (tensors,
-// per-layer tile configuration, branch pairing, arena sizes).  Host logic only.
-static long plan_summary_impl(const rtp_config* cfg, char* buf, size_t buflen) {
-  if (!cfg || !buf) return RTP_EINVAL;
-  rtp_engine* e = new rtp_engine();
-  e->cfg = *cfg;
-  if (cfg->precision < RTP_PREC_FP16 || cfg->precision > RTP_PREC_F16X3) { delete e; return fail(nullptr, RTP_EINVAL, "unknown precision %d", cfg->precision); }
-  e->mode = cfg->precision;
-  e->prec = cfg->precision == RTP_PREC_FP32 ? 1 : 0;
-  e->elem = e->prec ? 4 : 2;
-  {
-    const char* sr = RTP_EXP_ENV("RTP_SPLIT_LAYERS");
-    e->split_rules = sr ? sr : (cfg->split_layers ? cfg->split_layers : kDefaultSplit);
-    const char* f8 = RTP_EXP_ENV("RTP_SPLIT_FP8");
-    e->split_fp8 = !(f8 && f8[0] == '0');
-  }
-  e->N = cfg->num_scales;
-  e->B = cfg->batch_frames < 1 ? 1 : cfg->batch_frames;
-  e->NI = e->N * e->B;
-  if (cfg->proto_path) {
-    std::ifstream f(cfg->proto_path);
-    std::stringstream ss;
-    std::string perr;
-    if (!f) { delete e; return fail(nullptr, RTP_EIO, "cannot open prototxt %s", cfg->proto_path); }
-    ss << f.rdbuf();
-    if (!parse_prototxt(ss.str(), &e->net, &perr)) { delete e; return fail(nullptr, RTP_EIO, "%s", perr.c_str()); }
-  } else {
-    if (cfg->model != RTP_MODEL_COCO_18 && cfg->model != RTP_MODEL_MPI_15) { delete e; return fail(nullptr, RTP_EINVAL, "unknown model %d", cfg->model); }
-    e->net = build_linevec(cfg->model);
-  }
-  const int rc = build_plan(e);
-  if (rc) { g_create_error = e->err; delete e; return rc; }
-  std::ostringstream o;
-  o << "model " << e->model << " parts " << e->num_parts << " max_peaks " << e->max_peaks << " heat_channels " << e->heat_channels << "\n";
-  for (int l = 0; l < e->nlevels; ++l)
-    o << "level " << l << " H " << e->geom[l].H << " W " << e->geom[l].W << " halo " << e->geom[l].halo << "\n";
-  o << "arena_bytes " << e->arena_bytes << " weights_bytes " << e->weights_bytes << " tensors " << e->tensors.size() << "\n";
-  {  // which streams a batch context gets (alloc_ctx; "hardware queues" above): one for everything when the runtime's hardware queues suffice
-    const int nctx = (e->cfg.frames_in_flight + e->B - 1) / e->B + (e->B > 1 ? 1 : 0);
-    o << "streams contexts " << nctx << " hw_queues " << hw_queue_count() << " arrangement " << ((nctx <= hw_queue_count() || e->B == 1) ? "one_per_context" : "per_frame_chains") << "\n";
-  }
-  double gflop = 0, mfma_gflop = 0;
-  for (auto& s : e->steps) {
-    if (s.type == 0) o << "step pack\n";
-    else if (s.type == 4) {
-      const ConvOp& c = e->convs[s.a];
-      const Geom& g = e->geom[c.level];
-      o << "step first " << c.name << " k 3 cin 3 cout " << c.cout << " relu " << c.relu << " passes 1 wgs " << (long)g.H * e->NI << "\n";
-      const double gf = 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->N * 1e-9;
-      gflop += gf;
-      mfma_gflop += gf;
-    } else if (s.type == 2) o << "step pool " << e->tensors[e->pools[s.a].in_tensor].name << " -> " << e->tensors[e->pools[s.a].out_tensor].name << "\n";
-    else if (s.type == 3) {
-      const ConvOp& A = e->convs[s.a];
-      const ConvOp& C = e->convs[s.a2];
-      const Geom& g = e->geom[A.level];
-      o << "step pw2 " << A.name;
-      if (s.b >= 0) o << " + " << e->convs[s.b].name;
-      o << " -> " << C.name;
-      if (s.b2 >= 0) o << " + " << e->convs[s.b2].name;
-      o << " k 1 cin_p " << A.Cin_p << " mid " << A.cout << " cout " << C.cout << " passes " << A.passes() << (A.split_a ? "a" : "") << (A.split_w ? "w" : "") << "/"
-        << C.passes() << (C.split_a ? "a" : "") << (C.split_w ? "w" : "") << " tile 64 wgs " << (((long)g.H * g.Wp + 63) / 64) * e->NI * (s.b >= 0 ? 2 : 1)
-        << " lowres " << C.to_lowres << "\n";
-      for (int idx : {s.a, s.b, s.a2, s.b2}) if (idx >= 0) {
-        const ConvOp& c = e->convs[idx];
-        const double gf = 2.0 * c.cout * c.cin * (double)g.H * g.W * e->N * 1e-9;
-        gflop += gf;
-        mfma_gflop += gf * c.passes();
-      }
-    } else {
-      const ConvOp& A = e->convs[s.a];
-      const ConvCfgInfo ci = conv_cfg_info(A.cfg);
-      const Geom& g = e->geom[A.level];
-      const long tiles = A.pool >= 0 ? ((long)(g.H / 2) * ((g.W + A.k_eff / 2 + 1) & ~1) + ci.BM / 2 - 1) / (ci.BM / 2) : ((long)g.H * g.Wp + ci.BM - 1) / ci.BM;
-      o << "step conv " << A.name;
-      if (A.pool >= 0) o << " +pool";
-      if (s.b >= 0) o << " + " << e->convs[s.b].name;
-      o << " k " << A.k << " cin_p " << A.Cin_p << " cout " << A.cout << " coutp " << A.CoutP << " relu " << A.relu << " tile " << ci.BM << "x" << ci.BN
-        << " rowb " << A.rowb << " passes " << A.passes() << (A.h8 ? "q" : "") << (!A.h8 && A.split_a ? "a" : "") << (!A.h8 && A.split_w ? "w" : "") << " impl " << (A.impl ? "ring" : "reg") << " wgs " << tiles * e->NI * (A.CoutP / ci.BN) * (s.b >= 0 ? 2 : 1) << " dsts " << A.dsts.size() << " lowres " << A.to_lowres << "\n";
-      for (int idx : {s.a, s.b}) if (idx >= 0) {
-        const ConvOp& c = e->convs[idx];
-        const double gf = 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->N * 1e-9;
-        gflop += gf;
-        mfma_gflop += gf * c.passes();
-      }
-    }
-  }
-  o << "conv_gflop " << gflop << "\n";
-  o << "mfma_gflop " << mfma_gflop << "\n";
-  delete e;
-  const std::string str = o.str();
-  if (str.size() + 1 > buflen) return RTP_ERANGE;
-  memcpy(buf, str.c_str(), str.size() + 1);
-  return (long)str.size();
-}
-
 int rtp_kernel_timing(rtp_engine* e, int enable, double* total_ms, long* launches, double* flops_per_launch) {
   SYNC_GUARD;
   if (!e) return RTP_EINVAL;
@@ -3290,11 +2559,11 @@ int rtp_kernel_timing(rtp_engine* e, int enable, double* total_ms, long* launche
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, e->tev[2 * (size_t)i], e->tev[2 * (size_t)i + 1]) == hipSuccess && ms > 0.f) {
         const int si = e->tev_step[i];
-        if (si >= 0 && si < (int)e->steps.size()) {
-          if (e->step_ms.size() != e->steps.size()) { e->step_ms.assign(e->steps.size(), 0.0); e->step_n.assign(e->steps.size(), 0); }
+        if (si >= 0 && si < (int)e->plan.steps.size()) {
+          if (e->step_ms.size() != e->plan.steps.size()) { e->step_ms.assign(e->plan.steps.size(), 0.0); e->step_n.assign(e->plan.steps.size(), 0); }
           e->step_ms[si] += ms; e->step_n[si]++;
         }
-        if (si < 0 || si >= (int)e->steps.size() || is_dominant_class(e, e->steps[si])) {
+        if (si < 0 || si >= (int)e->plan.steps.size() || is_dominant_class(e, e->plan.steps[si])) {
           e->dom_ms_total += ms; e->dom_launches++;
           e->dom_ms_pass[e->tev_pass[i] & 3] += ms; e->dom_n_pass[e->tev_pass[i] & 3]++;
         }
@@ -3306,10 +2575,10 @@ int rtp_kernel_timing(rtp_engine* e, int enable, double* total_ms, long* launche
   if (launches) *launches = e->dom_launches;
   if (flops_per_launch) {
     double fl = 0;
-    if (e->dominant_step >= 0) {
-      const Step& s = e->steps[e->dominant_step];
-      const Geom& g = e->geom[e->convs[s.a].level];
-      for (int idx : {s.a, s.b}) if (idx >= 0) { const ConvOp& c = e->convs[idx]; fl += 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->NI; }
+    if (e->plan.dominant_step >= 0) {
+      const Step& s = e->plan.steps[e->plan.dominant_step];
+      const Geom& g = e->plan.geom[e->plan.convs[s.a].level];
+      for (int idx : {s.a, s.b}) if (idx >= 0) { const ConvOp& c = e->plan.convs[idx]; fl += 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->plan.NI; }
     }
     *flops_per_launch = fl;
   }
@@ -3318,7 +2587,7 @@ int rtp_kernel_timing(rtp_engine* e, int enable, double* total_ms, long* launche
     if ((enable != 0) != e->time_dominant || enable >= 2) {  // 2 = on + reset; 3 = on + reset, every step of the plan
       e->dom_ms_total = 0; e->dom_launches = 0;
       for (int i = 0; i < 4; ++i) { e->dom_ms_pass[i] = 0; e->dom_n_pass[i] = 0; }
-      e->step_ms.assign(e->steps.size(), 0.0); e->step_n.assign(e->steps.size(), 0);
+      e->step_ms.assign(e->plan.steps.size(), 0.0); e->step_n.assign(e->plan.steps.size(), 0);
     }
     e->time_dominant = enable != 0;
     e->time_all = enable == 3;
@@ -3413,7 +2682,7 @@ int rtp_probe_dropped(const rtp_engine* e, long out[3]) {
 // rtp_plan_summary's "step" lines); returns the number of steps.  Harvest first with rtp_kernel_timing(e, -1, ..) on an idle engine.
 int rtp_kernel_timing_steps(const rtp_engine* e, double* ms, long* launches, int cap) {
   if (!e || !ms || !launches || cap < 0) return RTP_EINVAL;
-  const int n = (int)e->steps.size();
+  const int n = (int)e->plan.steps.size();
   for (int i = 0; i < n && i < cap; ++i) {
     ms[i] = i < (int)e->step_ms.size() ? e->step_ms[i] : 0.0;
     launches[i] = i < (int)e->step_n.size() ? e->step_n[i] : 0;
@@ -3436,26 +2705,26 @@ int rtp_profile_steps(rtp_engine* e, int iters, float* ms, double* gflop, int ca
   if ((rc = need_idle(e))) return rc;
   if (iters < 1) return RTP_EINVAL;
   Ctx& cx = e->ctx[0];
-  auto geom_n = [&](int level) { Geom g = e->geom[level]; g.N = e->NI; return g; };
+  auto geom_n = [&](int level) { Geom g = e->plan.geom[level]; g.N = e->plan.NI; return g; };
   int n = 0;
-  for (auto& s : e->steps) {
+  for (auto& s : e->plan.steps) {
     if (n >= cap) break;
     auto once = [&]() -> int {
       if (s.type == 0) {
-        const Tensor& t = e->tensors[0];
-        HIPCHK(e, launch_pack_input(e->prec, cx.input, cx.arena + t.offset, geom_n(0), t.stride(), cx.stream));
+        const Tensor& t = e->plan.tensors[0];
+        HIPCHK(e, launch_pack_input(e->plan.prec, cx.input, cx.arena + t.offset, geom_n(0), t.stride(), cx.stream));
       } else if (s.type == 1) {
-        return launch_conv_step(e, cx, s, e->NI);
+        return launch_conv_step(e, cx, s, e->plan.NI);
       } else if (s.type == 3) {
-        return launch_pw2_step(e, cx, s, e->NI);
+        return launch_pw2_step(e, cx, s, e->plan.NI);
       } else if (s.type == 4) {
-        return launch_first_step(e, cx, s, cx.input, e->NI);
+        return launch_first_step(e, cx, s, cx.input, e->plan.NI);
       } else {
-        const PoolOp& p = e->pools[s.a];
-        const Tensor& ti = e->tensors[p.in_tensor];
-        const Tensor& to = e->tensors[p.out_tensor];
-        HIPCHK(e, launch_maxpool(e->prec, cx.arena + ti.offset, geom_n(ti.level), ti.stride(), cx.arena + to.offset, geom_n(to.level), to.stride(),
-                                 round_up(p.C, 16 / e->elem), ti.lo_off(), to.lo_off(), ti.q_off(), to.q_off(), cx.stream));
+        const PoolOp& p = e->plan.pools[s.a];
+        const Tensor& ti = e->plan.tensors[p.in_tensor];
+        const Tensor& to = e->plan.tensors[p.out_tensor];
+        HIPCHK(e, launch_maxpool(e->plan.prec, cx.arena + ti.offset, geom_n(ti.level), ti.stride(), cx.arena + to.offset, geom_n(to.level), to.stride(),
+                                 round_up(p.C, 16 / e->plan.elem), ti.lo_off(), to.lo_off(), ti.q_off(), to.q_off(), cx.stream));
       }
       return RTP_OK;
     };
@@ -3469,8 +2738,8 @@ int rtp_profile_steps(rtp_engine* e, int iters, float* ms, double* gflop, int ca
     if (ms) ms[n] = t / iters;
     double fl = 0;
     if (s.type == 1 || s.type == 3 || s.type == 4) {
-      const Geom& g = e->geom[e->convs[s.a].level];
-      for (int idx : {s.a, s.b, s.a2, s.b2}) if (idx >= 0) { const ConvOp& c = e->convs[idx]; fl += 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->NI; }
+      const Geom& g = e->plan.geom[e->plan.convs[s.a].level];
+      for (int idx : {s.a, s.b, s.a2, s.b2}) if (idx >= 0) { const ConvOp& c = e->plan.convs[idx]; fl += 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->plan.NI; }
     }
     if (gflop) gflop[n] = fl * 1e-9;
     ++n;
@@ -3482,14 +2751,14 @@ int rtp_bench_dominant_conv(rtp_engine* e, int iters, float* avg_ms, double* flo
   SYNC_GUARD;
   int rc;
   if ((rc = need_idle(e))) return rc;
-  if (e->dominant_step < 0 || iters < 1) return fail(e, RTP_EINVAL, "no 7x7 128->128 convolution step in this graph");
+  if (e->plan.dominant_step < 0 || iters < 1) return fail(e, RTP_EINVAL, "no 7x7 128->128 convolution step in this graph");
   Ctx& cx = e->ctx[0];
-  const Step& s = e->steps[e->dominant_step];
-  const ConvOp& A = e->convs[s.a];
-  const Geom& g = e->geom[A.level];
-  for (int i = 0; i < 3; ++i) if ((rc = launch_conv_step(e, cx, s, e->NI))) return rc;
+  const Step& s = e->plan.steps[e->plan.dominant_step];
+  const ConvOp& A = e->plan.convs[s.a];
+  const Geom& g = e->plan.geom[A.level];
+  for (int i = 0; i < 3; ++i) if ((rc = launch_conv_step(e, cx, s, e->plan.NI))) return rc;
   HIPCHK(e, hipEventRecord(cx.ev[0], cx.stream));
-  for (int i = 0; i < iters; ++i) if ((rc = launch_conv_step(e, cx, s, e->NI))) return rc;
+  for (int i = 0; i < iters; ++i) if ((rc = launch_conv_step(e, cx, s, e->plan.NI))) return rc;
   HIPCHK(e, hipEventRecord(cx.ev[1], cx.stream));
   HIPCHK(e, hipEventSynchronize(cx.ev[1]));
   if (RTP_EXP_ENV("RTP_CLKPROBE")) {  // diagnostics: effective shader clock while this kernel runs back to back
@@ -3497,7 +2766,7 @@ int rtp_bench_dominant_conv(rtp_engine* e, int iters, float* avg_ms, double* flo
     HIPCHK(e, hipMalloc((void**)&d, 32));
     HIPCHK(e, hipMemset(d, 0, 32));
     g_clkprobe = d;
-    for (int i = 0; i < 20; ++i) if ((rc = launch_conv_step(e, cx, s, e->NI))) return rc;
+    for (int i = 0; i < 20; ++i) if ((rc = launch_conv_step(e, cx, s, e->plan.NI))) return rc;
     g_clkprobe = nullptr;
     HIPCHK(e, hipStreamSynchronize(cx.stream));
     unsigned long long h[4] = {0, 0, 0, 0};
@@ -3515,7 +2784,7 @@ int rtp_bench_dominant_conv(rtp_engine* e, int iters, float* avg_ms, double* flo
   if (avg_ms) *avg_ms = ms / iters;
   const int nprob = s.b >= 0 ? 2 : 1;
   double fl = 0;
-  for (int idx : {s.a, s.b}) if (idx >= 0) { const ConvOp& c = e->convs[idx]; fl += 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->NI; }
+  for (int idx : {s.a, s.b}) if (idx >= 0) { const ConvOp& c = e->plan.convs[idx]; fl += 2.0 * c.cout * c.cin * c.k * c.k * (double)g.H * g.W * e->plan.NI; }
   (void)nprob;
   if (flops_per_launch) *flops_per_launch = fl;
   return RTP_OK;
@@ -3611,7 +2880,7 @@ int rtp_calibrate_precision(rtp_engine* e, const float* frames_host, int nframes
   if (nframes < 1 || nframes > 64) return fail(e, RTP_EINVAL, "calibration frames %d out of range [1, 64]", nframes);
   if (!(target > 0.f)) target = 0.7e-3f;
   const size_t in_floats = (size_t)e->N * 3 * e->cfg.net_h * e->cfg.net_w;
-  const size_t low_floats = (size_t)e->N * e->heat_channels * e->low_h * e->low_w;
+  const size_t low_floats = (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w;
   std::vector<float> synth;
   if (!frames_host) {  // what process_and_pad_image makes of a u8 frame: v / 256 - 0.5 (rtpose.cpp:259), seeded
     synth.resize(in_floats * nframes);
@@ -3672,7 +2941,7 @@ int rtp_calibrate_precision(rtp_engine* e, const float* frames_host, int nframes
   std::vector<std::string> all_groups;
   {
     auto add = [&](const std::string& g) { if (std::find(all_groups.begin(), all_groups.end(), g) == all_groups.end()) all_groups.push_back(g); };
-    for (auto& c : e->convs) {
+    for (auto& c : e->plan.convs) {
       const size_t st = c.name.find("_stage");
       if (st != std::string::npos) { size_t en = st + 6; while (en < c.name.size() && isdigit((unsigned char)c.name[en])) ++en; add("*" + c.name.substr(st, en - st) + "_"); }
       else { const size_t us = c.name.find('_'); add(us == std::string::npos ? c.name : c.name.substr(0, us + 1)); }
@@ -3683,7 +2952,7 @@ int rtp_calibrate_precision(rtp_engine* e, const float* frames_host, int nframes
     std::vector<std::string> gs;
     for (auto& g : all_groups) {
       bool open = false;
-      for (auto& c : e->convs) if (in_group(g, c) && (want_h8 ? c.h8 : !(c.split_w && (c.split_a || c.first)))) open = true;
+      for (auto& c : e->plan.convs) if (in_group(g, c) && (want_h8 ? c.h8 : !(c.split_w && (c.split_a || c.first)))) open = true;
       if (open) gs.push_back(g);
     }
     return gs;
@@ -3769,9 +3038,9 @@ namespace {
 uint64_t plan_hash(const rtp_engine* e) {
   uint64_t h = 1469598103934665603ull;
   auto mix = [&](uint64_t v) { for (int i = 0; i < 8; ++i) { h ^= (v >> (8 * i)) & 0xff; h *= 1099511628211ull; } };
-  mix(e->weights_bytes); mix(e->convs.size()); mix((uint64_t)e->mode);
-  mix((uint64_t)e->prec); mix((uint64_t)e->split_fp8);
-  for (auto& c : e->convs) {
+  mix(e->plan.weights_bytes); mix(e->plan.convs.size()); mix((uint64_t)e->mode);
+  mix((uint64_t)e->plan.prec); mix((uint64_t)e->split_fp8);
+  for (auto& c : e->plan.convs) {
     mix(c.w_off); mix(c.b_off); mix(c.w_bytes); mix((uint64_t)c.cfg); mix((uint64_t)c.nchunk); mix((uint64_t)c.h8);
     // what decides the CONTENTS of the packed arena at equal sizes: which operand the second pass carries (":w" = W_lo, ":a" = W_hi
     // again), fp16 instead of fp8 corrections (":x"), the chunking, the kernel the weights are packed for
@@ -3784,13 +3053,13 @@ uint64_t plan_hash(const rtp_engine* e) {
 }
 size_t ref_floats(const rtp_engine* e) {
   size_t n = 0;
-  for (size_t i = 0; i < e->convs.size(); ++i) n += e->w_ref[i].size() + e->b_ref[i].size();
+  for (size_t i = 0; i < e->plan.convs.size(); ++i) n += e->w_ref[i].size() + e->b_ref[i].size();
   return n;
 }
 }  // namespace
 long rtp_weight_blob_bytes(const rtp_engine* e) {
   if (!e) return RTP_EINVAL;
-  return (long)(4 * sizeof(uint64_t) + e->convs.size() * sizeof(int) + e->weights_bytes + ref_floats(e) * sizeof(float));
+  return (long)(4 * sizeof(uint64_t) + e->plan.convs.size() * sizeof(int) + e->plan.weights_bytes + ref_floats(e) * sizeof(float));
 }
 int rtp_weight_blob_export(rtp_engine* e, void* host, size_t capacity) {
   SYNC_GUARD;
@@ -3799,11 +3068,11 @@ int rtp_weight_blob_export(rtp_engine* e, void* host, size_t capacity) {
   if ((rc = need_weights(e))) return rc;
   if (!host || (long)capacity < rtp_weight_blob_bytes(e)) return fail(e, RTP_EINVAL, "weight blob needs %ld bytes", rtp_weight_blob_bytes(e));
   unsigned char* p = (unsigned char*)host;
-  const uint64_t head[4] = {0x5254505742303031ull /* "RTPWB001" */, plan_hash(e), (uint64_t)e->convs.size(), (uint64_t)e->weights_bytes};
+  const uint64_t head[4] = {0x5254505742303031ull /* "RTPWB001" */, plan_hash(e), (uint64_t)e->plan.convs.size(), (uint64_t)e->plan.weights_bytes};
   memcpy(p, head, sizeof head); p += sizeof head;
-  for (auto& c : e->convs) { memcpy(p, &c.wq_exp, sizeof(int)); p += sizeof(int); }
-  HIPCHK(e, hipMemcpy(p, e->dweights, e->weights_bytes, hipMemcpyDeviceToHost)); p += e->weights_bytes;
-  for (size_t i = 0; i < e->convs.size(); ++i) {
+  for (auto& c : e->plan.convs) { memcpy(p, &c.wq_exp, sizeof(int)); p += sizeof(int); }
+  HIPCHK(e, hipMemcpy(p, e->dweights, e->plan.weights_bytes, hipMemcpyDeviceToHost)); p += e->plan.weights_bytes;
+  for (size_t i = 0; i < e->plan.convs.size(); ++i) {
     memcpy(p, e->w_ref[i].data(), e->w_ref[i].size() * sizeof(float)); p += e->w_ref[i].size() * sizeof(float);
     memcpy(p, e->b_ref[i].data(), e->b_ref[i].size() * sizeof(float)); p += e->b_ref[i].size() * sizeof(float);
   }
@@ -3818,13 +3087,13 @@ int rtp_weight_blob_import(rtp_engine* e, const void* host, size_t bytes) {
   uint64_t head[4];
   memcpy(head, p, sizeof head); p += sizeof head;
   if (head[0] != 0x5254505742303031ull) return fail(e, RTP_EINVAL, "not a weight blob");
-  if (head[1] != plan_hash(e) || head[2] != e->convs.size() || head[3] != e->weights_bytes)
+  if (head[1] != plan_hash(e) || head[2] != e->plan.convs.size() || head[3] != e->plan.weights_bytes)
     return fail(e, RTP_EINVAL, "weight blob was exported by an engine with another plan (model / resolution / precision / split set must match)");
   bool moved = false;
-  for (auto& c : e->convs) { int ex; memcpy(&ex, p, sizeof(int)); p += sizeof(int); moved = moved || ex != c.wq_exp; c.wq_exp = ex; }
+  for (auto& c : e->plan.convs) { int ex; memcpy(&ex, p, sizeof(int)); p += sizeof(int); moved = moved || ex != c.wq_exp; c.wq_exp = ex; }
   HIPCHK(e, hipDeviceSynchronize());
-  HIPCHK(e, hipMemcpy(e->dweights, p, e->weights_bytes, hipMemcpyHostToDevice)); p += e->weights_bytes;
-  for (size_t i = 0; i < e->convs.size(); ++i) {
+  HIPCHK(e, hipMemcpy(e->dweights, p, e->plan.weights_bytes, hipMemcpyHostToDevice)); p += e->plan.weights_bytes;
+  for (size_t i = 0; i < e->plan.convs.size(); ++i) {
     memcpy(e->w_ref[i].data(), p, e->w_ref[i].size() * sizeof(float)); p += e->w_ref[i].size() * sizeof(float);
     memcpy(e->b_ref[i].data(), p, e->b_ref[i].size() * sizeof(float)); p += e->b_ref[i].size() * sizeof(float);
   }
@@ -3841,11 +3110,11 @@ int rtp_copy_weights_from(rtp_engine* dst, rtp_engine* src) {
   if (src->weights_pending) return fail(dst, RTP_EINVAL, "rtp_copy_weights_from: the source engine has no weights itself (defer_weights)");
   if (plan_hash(dst) != plan_hash(src)) return fail(dst, RTP_EINVAL, "rtp_copy_weights_from: the engines have different plans");
   HIPCHK(dst, hipDeviceSynchronize());
-  HIPCHK(dst, hipMemcpyPeer(dst->dweights, dst->cfg.device_id, src->dweights, src->cfg.device_id, dst->weights_bytes));
+  HIPCHK(dst, hipMemcpyPeer(dst->dweights, dst->cfg.device_id, src->dweights, src->cfg.device_id, dst->plan.weights_bytes));
   bool moved = false;
-  for (size_t i = 0; i < dst->convs.size(); ++i) {
-    moved = moved || dst->convs[i].wq_exp != src->convs[i].wq_exp;
-    dst->convs[i].wq_exp = src->convs[i].wq_exp;
+  for (size_t i = 0; i < dst->plan.convs.size(); ++i) {
+    moved = moved || dst->plan.convs[i].wq_exp != src->plan.convs[i].wq_exp;
+    dst->plan.convs[i].wq_exp = src->plan.convs[i].wq_exp;
     dst->w_ref[i] = src->w_ref[i];
     dst->b_ref[i] = src->b_ref[i];
   }
@@ -3873,10 +3142,24 @@ int rtp_engine_create(const rtp_config* cfg, rtp_engine** out) {
     return fail(nullptr, RTP_EINVAL, "engine creation failed: %s", ex.what());
   }
 }
+// Build the execution plan for cfg WITHOUT touching a device and describe it as text (tensors, per-layer tile configuration, branch
+// pairing, arena sizes).  Host logic only: no engine is involved.
 long rtp_plan_summary(const rtp_config* cfg, char* buf, size_t buflen) {
   if (int rc = config_layout_ok(cfg)) return rc;
+  if (!cfg || !buf) return RTP_EINVAL;
+  if (cfg->precision < RTP_PREC_FP16 || cfg->precision > RTP_PREC_F16X3) return fail(nullptr, RTP_EINVAL, "unknown precision %d", cfg->precision);
   try {
-    return plan_summary_impl(cfg, buf, buflen);
+    NetDef net;
+    Plan plan;
+    std::string err;
+    int rc = load_netdef(cfg->proto_path, cfg->model, false, &net, &err);
+    const PlanInput in = plan_input_from_config(*cfg, &net);
+    if (!rc) rc = build_plan(in, &plan, &err);
+    if (rc) return fail(nullptr, rc, "%s", err.c_str());
+    const std::string str = describe_plan(plan, in.N, in.B, cfg->frames_in_flight, hw_queue_count());
+    if (str.size() + 1 > buflen) return RTP_ERANGE;
+    memcpy(buf, str.c_str(), str.size() + 1);
+    return (long)str.size();
   } catch (const std::exception& ex) {
     return fail(nullptr, RTP_ENOMEM, "plan summary failed: %s", ex.what());
   }

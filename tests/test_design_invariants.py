@@ -16,7 +16,7 @@ def _pooled_walk(H, W, halo, seed=0):
     Wp, Hp = W + halo, H + 2 * halo
     BM, HALF, KS, PAD = 128, 64, 3, 1
     PHALF = HALF + KS - 1
-    Wq = (W + PAD + 1) & ~1                              # engine.cpp: pool_wq
+    Wq = (W + PAD + 1) & ~1                              # plan.h: pool_wq
     rs = np.random.RandomState(seed)
     flat = np.zeros(Hp * Wp + 8 * Wp)                    # halo'd tensor, flat (kernels.h), + slack the last tile reads
     img = rs.rand(H, W)
@@ -27,7 +27,7 @@ def _pooled_walk(H, W, halo, seed=0):
     conv = sum(wts[r, s] * pad[r:r + H, s:s + W] for r in range(3) for s in range(3))
     ref = conv.reshape(H // 2, 2, W // 2, 2).max(axis=(1, 3))
     out = np.full((H // 2, W // 2), np.nan)
-    ntiles = ((H // 2) * Wq + HALF - 1) // HALF          # engine.cpp: tiles_per_img
+    ntiles = ((H // 2) * Wq + HALF - 1) // HALF          # plan.cpp: conv_tiles_per_img
     for t in range(ntiles):
         q0 = t * HALF
         pair, x0 = divmod(q0, Wq)

@@ -48,7 +48,7 @@ def test_production_library_has_no_experiment_knobs():
     removed = {b"RTP_RING_VAR", b"RTP_FORCE_CFG", b"RTP_TILE_OVERRIDE", b"RTP_DIAG_SKIP_POST", b"RTP_RING_SB", b"RTP_RING_SPEC", b"RTP_POST_CUS", b"RTP_NMS_PROBE",
                b"RTP_SPLIT_LAYERS", b"RTP_HALO_SHARED", b"RTP_HALF_CHIP", b"RTP_GRAPH_POST", b"RTP_STREAM_PLAN", b"RTP_MATCH_WGS"}
     assert os.path.exists(exp) and removed <= names(exp)            # the experiments build still has them (tools/, tests of the variants)
-    src = open(os.path.join(ROOT, "caffe_rtpose_amd", "csrc", "engine.cpp")).read() + open(os.path.join(ROOT, "caffe_rtpose_amd", "csrc", "conv_ring.hip")).read()
+    src = "".join(open(os.path.join(ROOT, "caffe_rtpose_amd", "csrc", f)).read() for f in ("engine.cpp", "plan.cpp", "conv_ring.hip"))
     assert re.findall(r"[^_A-Z]getenv\(\"(RTP_[A-Z_]+)\"\)", src.replace("#ifdef RTP_EXPERIMENTS", "")) .count("RTP_EXEC") == 1
 
 
@@ -196,6 +196,34 @@ def test_plan_mpi_and_errors():
         _plan_lines(net_w=650)  # not a multiple of 16
     with pytest.raises(r.RtpError):
         _plan_lines(model=5)
+
+
+def test_plan_summary_needs_no_engine_and_is_reentrant():
+    """rtp_plan_summary builds a Plan from its PlanInput and describes it: no engine is constructed or mutated, so concurrent callers
+    (an invalid config among them: the error path interleaved) get exactly the single-threaded texts."""
+    import threading
+    import caffe_rtpose_amd as r
+    configs = [dict(), dict(model=1, net_w=496, net_h=368, batch_frames=5), dict(precision=r.PREC_F16X3, num_scales=3, scale_gap=0.15, keep_blobs=1),
+               dict(net_w=650)]
+    expect = [r.plan_summary(r.Config(**kw)) for kw in configs[:3]]
+    assert len(set(expect)) == 3
+    results = [[] for _ in range(8)]
+
+    def work(out):
+        for _ in range(20):
+            for kw in configs:
+                try:
+                    out.append(r.plan_summary(r.Config(**kw)))
+                except r.RtpError as ex:
+                    out.append(ex.code)
+
+    threads = [threading.Thread(target=work, args=(results[i],)) for i in range(8)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for out in results:
+        assert out == (expect + [r.RTP_EINVAL]) * 20
 
 
 def _golden_table(model):
