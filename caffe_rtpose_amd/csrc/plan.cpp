@@ -477,6 +477,19 @@ void Builder::propagate_split() {
     if (plan.tensors[plan.pools[pi].out_tensor].need_lo) plan.tensors[plan.pools[pi].in_tensor].need_lo = true;
     if (plan.tensors[plan.pools[pi].out_tensor].need_q) plan.tensors[plan.pools[pi].in_tensor].need_q = true;
   }
+  // The branches of a pair share ONE description of their input (ConvParams: pixel pitch in_cstride, the q block's offset jump_delta / row_back).
+  // Where the two input tensors carry different blocks — one of them has a further reader that runs other passes — the pair runs as two launches
+  // on the tile chosen for it.  (The built-in graphs pair layers that read the same concat, or blobs with a single reader.)
+  for (size_t si = 0; si < plan.steps.size(); ++si) {
+    Step& s = plan.steps[si];
+    if (s.type != 1 || s.b < 0) continue;
+    const Tensor& ta = plan.tensors[plan.convs[s.a].in_tensor];
+    const Tensor& tb = plan.tensors[plan.convs[s.b].in_tensor];
+    if (ta.need_lo == tb.need_lo && ta.need_q == tb.need_q) continue;
+    const int b = s.b;
+    s.b = -1;
+    plan.steps.insert(plan.steps.begin() + (long)si + 1, Step{1, b, -1});
+  }
 }
 
 // 2x2 max pooling inside the producing convolution's epilogue: the pooling layer's input blob has no other consumer, the layer

@@ -22,7 +22,9 @@ u_out / a_min — how the stored value differs from the kernel's fp32 value v (c
                          of the export 2^-24|v|: u_out 2^-22 + 2^-24, a_min 2^-24 (lo below the fp16 normal range)
   ... with a q part      hi + e4m3(lo * 2^12) / 2^12: 3 mantissa bits -> 2^-4 of |lo| <= 2^-11|v|: u_out 2^-15 + 2^-23, a_min 2^-22 (half an
                          e4m3 subnormal step 2^-9 / 2^12 / 2); lo * 2^12 saturates at 448 for |v| > 224: there the hi-only bound applies
-  final low-res maps     fp32 planar stores of v itself: u_out 2^-24
+  ... with lo AND q      (a tensor read by a register-staged 1x1 layer, label 3aw, and by a ring layer, label 2q) the export returns hi + lo
+                         (kernels.h launch_export: the q block is added only where there is no lo block): u_out and a_min of the lo case
+  final low-res maps     fp32 planar stores of v itself: u_out 2^-24 — whether a concat of convolutions or ONE convolution is what ImResize reads
   Which parts a tensor carries follows from its consumers' pass labels (plan.cpp propagate_split): a consumer with `q` needs the q
   block, one with `a` the lo block; a pooling layer hands its output's needs to its input.
 
@@ -35,6 +37,9 @@ order, are bounded by (K-1)*u times the instruction's own terms, i.e. by (K-1)*u
                                    pair sum) / + 1 for the fp8 instructions (63 roundings on terms 2^-11 of S), + KSPLIT-1 for the reduction of
                                    the k-split partials in the epilogue, + 1 for the bias add.  KSPLIT: 128x128 1, 64x128 / 128x64 / 128x32 2,
                                    64x64 4 (2 for the fp8-compensated ring kernel with 128-byte chunks)  [ring_launch_cfg, launch_cfg]
+                                   a 1x1 layer on the register-staged kernel (conv_igemm.hip launch_cfg<T, 1, 128>): one tap, cin_p/64 chunks of 128
+                                   bytes, 4 / 2 / 1 instructions per chunk and wave on 128x128 / 64x128 / 64x64 (KSPLIT 1 / 2 / 4), e.g. cin_p 192
+                                   label 3aw: 3 chunks x 3 passes x (4 | 2 | 1) = 36 | 18 | 9, + 15 + (0 | 1 | 3) + 1 = 52 | 35 | 28
   conv_first.hip                   2 instructions (K = 32 taps, 27 real) starting from the bias as the initial accumulator, + 15
   conv_pw2.hip                     GEMM1: 8 instructions (K = 128) x passes + 15 + 1 (bias); GEMM2: (mid/128) x 8 x passes + 15 + 1 (bias)
 
@@ -49,6 +54,9 @@ e_op — what the operands of the launch differ from the reference's (pass label
                        |W_lo| <= 2^-11|W|, e4m3 relative error 2^-4 and half a subnormal step 2^-10 in the scaled domain:
                        (2^-15 + 2^-15 + (1 + 2^-4)*2^-15 + 2^-22)|a||W| = (3*2^-15 + 2^-19 + 2^-22)|a||W| ~ 2^-13.4, times (1 + 2^-10) for |a_hi|, |W_hi|
                        against |a|, |W|; e_abs = (2 + 2^-4)*2^-21-t * sum|a| + 2^-23 * sum|W|.  Qa saturates at |a| = 112: checked, not assumed.
+  `2q` on a lo + q input  the export returns a_hi + lo, the kernel reads l8: reference - kernel gains (lo - l8)*W.  Both round the same d = v - a_hi,
+                       |d| <= 2^-11|v|: |lo - d| <= 2^-11|d| + 2^-25, |l8 - d| <= 2^-4|d| + 2^-22, and the export's fp32 sum a_hi + lo rounds once
+                       (2^-24|a|): e_op + (2^-15 + 2^-22 + 2^-24)(1 + 2^-10), e_abs + (2^-22 + 2^-25) * sum|W|
 
 `+pool` launches: the kernel takes the maximum of the four fp32 sums, then bias / ReLU / rounding (monotone); |max x~ - max x| <= max |x~ - x|,
 so the accumulation part of the tolerance is the largest of the four.  Stand-alone pooling steps move values: they must be EQUAL.
@@ -200,26 +208,31 @@ def plan_keys(summary, graph=None):
     _, launches = parse_plan(summary)
     for L in launches:
         if L.kind == "pw2" and graph is not None:
-            L.dsts = len([d for d in graph.dests(L.layers2[0]) if d[0] != graph.lowres])
+            L.dsts = _pw2_dsts(graph, L)
     return {L.key for L in launches}
 
 
+def _pw2_dsts(graph, L):
+    """tensors the second layer of a pw2 launch stores to: its own and the concat slices (the low-res maps are no tensor)"""
+    return 1 + len([d for d in graph.dests(L.layers2[0])[1:] if d[0] != graph.lowres])
+
+
 def tensor_parts(graph, launches):
-    """blob -> 'lo' / 'q' / '' : which split-precision block its tensor carries, from the consumers' pass labels (plan.cpp propagate_split)."""
-    parts = {}
+    """blob -> 'lo' / 'q' / 'lo+q' / '' : which split-precision blocks its tensor carries, from the consumers' pass labels (plan.cpp propagate_split)."""
+    need = {}
     for L in launches:
         if L.kind in ("conv", "pw2", "first"):
             lab = L.passes.split("/")[0]
             for name in L.layers:
                 bottom = graph.convs[name]["bottom"]
                 if "q" in lab:
-                    parts[bottom] = "q"
+                    need.setdefault(bottom, set()).add("q")
                 elif "a" in lab[1:]:
-                    parts[bottom] = "lo"
+                    need.setdefault(bottom, set()).add("lo")
     for top, bot in reversed(list(graph.pools.items())):
-        if parts.get(top):
-            parts[bot] = parts[top]
-    return parts
+        if need.get(top):
+            need.setdefault(bot, set()).update(need[top])
+    return {b: "+".join(sorted(n)) for b, n in need.items()}
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -296,7 +309,7 @@ def ksplit_of(L):
 def c_acc_conv(L, fp32):
     """fp32 roundings on the longest accumulation chain of a conv_ring / conv_igemm launch (module docstring)."""
     elem = 4 if fp32 else 2
-    k_eff = 1 if (L.cin_p == 32 and L.k == 3) else L.k          # conv1_1 through the im2col pack is a 1x1 layer on 32 channels
+    k_eff = 1 if (L.cin_p == 32 and L.k == 3 and L.impl == "reg") else L.k   # the input layer through the im2col pack is a 1x1 layer on 32 channels (a 3x3 layer on a 32-channel fp32 tensor runs on the ring kernel)
     ks = ksplit_of(L)
     ncp = L.cin_p * elem // L.rowb
     gpw = (L.rowb // 32) // ks
@@ -317,11 +330,14 @@ def c_acc_pw2(label, chunks):
     return chunks * 8 * int(label[0]) + 15 + 1
 
 
-def e_op_of(label, fp32):
-    """e_op relative to |a||w| (module docstring); the absolute terms are added where the patches are at hand (_check_conv, _q_abs)"""
+def e_op_of(label, fp32, in_part=""):
+    """e_op relative to |a||w| (module docstring); the absolute terms are added where the patches are at hand (_check_conv, _q_abs).
+    in_part: the blocks of the INPUT tensor (a 2q launch on a lo + q tensor: the export returns the lo block, the kernel reads the q block)"""
     if fp32 or label == "1":
         return 0.0
     if "q" in label:
+        if "lo" in in_part:
+            return (3 * 2.0 ** -15 + 2.0 ** -19 + 2.0 ** -22 + 2.0 ** -15 + 2.0 ** -22 + 2.0 ** -24) * (1 + 2.0 ** -10)
         return (3 * 2.0 ** -15 + 2.0 ** -19 + 2.0 ** -22) * (1 + 2.0 ** -10)
     e = 0.0
     if "w" in label:
@@ -338,7 +354,7 @@ def out_rounding(part, fp32, r):
     a = np.abs(r)
     if fp32 or part == "f32":
         return U32 * a + 2.0 ** -149
-    if part == "lo":
+    if "lo" in part:   # lo, or lo + q: the export returns hi + lo
         return (2.0 ** -22 + 2.0 ** -24) * a + 2.0 ** -24
     if part == "q":
         return np.where(a < 224.0, (2.0 ** -15 + 2.0 ** -23) * a + 2.0 ** -22, 2.0 ** -11 * a + 2.0 ** -24)
@@ -431,7 +447,7 @@ def check_plan(summary, graph, weights, blob, fp32=False, n_interior=256, seed=0
         lvl = graph.level[graph.convs[L.layers[0]]["bottom"]]
         H, W, halo = levels[lvl]
         if L.kind == "pw2":
-            L.dsts = len([d for d in graph.dests(L.layers2[0]) if d[0] != graph.lowres])
+            L.dsts = _pw2_dsts(graph, L)
         # ---- the sample set (pooled coordinates for +pool)
         if L.pool:
             ends, ntiles = pool_tile_ends(H, W, L.k, L.tile[0])
@@ -475,14 +491,15 @@ def _operands(label, fp32, a, w, first=False):
     return a64, w64
 
 
-def _q_abs(label, w_launch, sum_a, sum_w):
+def _q_abs(label, w_launch, sum_a, sum_w, in_part=""):
     """absolute terms of the 2q bound (e4m3 subnormals in the scaled domain), t as the engine derives it from the launch's weights"""
     if "q" not in label:
         return 0.0
     mx = max(float(np.abs(w).max()) for w in w_launch)
     t = int(np.floor(np.log2(448.0 / mx))) if mx > 0 else 0
     t = max(-20, min(t, 40))
-    return (2 + 2.0 ** -4) * 2.0 ** (-21 - t) * sum_a + 2.0 ** -23 * sum_w
+    e = (2 + 2.0 ** -4) * 2.0 ** (-21 - t) * sum_a + 2.0 ** -23 * sum_w
+    return e + (2.0 ** -22 + 2.0 ** -25) * sum_w if "lo" in in_part else e
 
 
 def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls):
@@ -499,7 +516,8 @@ def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls)
     sum_w = wabs.sum(axis=0)[None, :]
     b64 = np.asarray(b, np.float64)[None, :]
     c_acc = c_acc_first() if L.kind == "first" else c_acc_conv(L, fp32)
-    e_rel = c_acc * U32 + e_op_of(label, fp32)
+    in_part = parts.get(g["bottom"], "")
+    e_rel = c_acc * U32 + e_op_of(label, fp32, in_part)
     e_abs_a = 2.0 ** -25 if ("w" in label and not fp32) else 0.0            # subnormal W_lo: half an fp16 subnormal step per term
     flush = 2.0 ** -126 * wm.shape[0] if fp32 else 0.0
     w_launch = [weights[n][0] for n in L.layers]
@@ -520,7 +538,7 @@ def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls)
                         v = p @ wm + b64
                         pa = np.abs(p)
                         S = pa @ wabs + np.abs(b64)
-                        t = e_rel * S + e_abs_a * pa.sum(axis=1, keepdims=True) + _q_abs(label, w_launch, pa.sum(axis=1, keepdims=True), sum_w) + flush
+                        t = e_rel * S + e_abs_a * pa.sum(axis=1, keepdims=True) + _q_abs(label, w_launch, pa.sum(axis=1, keepdims=True), sum_w, in_part) + flush
                         pre = v if pre is None else np.maximum(pre, v)
                         acc_tol = t if acc_tol is None else np.maximum(acc_tol, t)
             else:
@@ -528,7 +546,7 @@ def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls)
                 pre = p @ wm + b64
                 pa = np.abs(p)
                 S = pa @ wabs + np.abs(b64)
-                acc_tol = e_rel * S + e_abs_a * pa.sum(axis=1, keepdims=True) + _q_abs(label, w_launch, pa.sum(axis=1, keepdims=True), sum_w) + flush
+                acc_tol = e_rel * S + e_abs_a * pa.sum(axis=1, keepdims=True) + _q_abs(label, w_launch, pa.sum(axis=1, keepdims=True), sum_w, in_part) + flush
             r = np.maximum(pre, 0.0) if g["relu"] else pre
             imgs = np.full(len(yy), n)
             for d, off in dests:
@@ -628,14 +646,15 @@ def _split16(v32):
 class Emulation:
     """Runs the launches of an fp16 / F16X3 / mixed plan (pass labels 1, 2w, 2a, 3aw, 2q) the way the kernels do, launch by launch, each on the previous
     launches' stored outputs.  pre[layer] keeps the fp32 value of every convolution before ReLU / pooling / rounding so that a test can plant a
-    defect there and store the result again (restore)."""
+    defect there and store the result again (restore).  hi / lo / q8 hold a blob's fp16 value, its fp16 rounding error and that error as the
+    stored e4m3(lo * 2^12) / 2^12 — each kept where a tensor the blob is stored to carries that block."""
 
     def __init__(self, summary, graph, weights, frame, stop_after=None):
         self.graph, self.weights = graph, weights
         self.levels, self.launches = parse_plan(summary)
         self.parts = tensor_parts(graph, self.launches)
         self.wq_exp = {}    # fp8-compensated launches: the weight scale t, shared by the branches of a launch (engine.cpp compute_wq_exp)
-        self.hi, self.lo, self.pre, self.lowres_part = {graph.input: np.asarray(frame, np.float32)}, {}, {}, {}
+        self.hi, self.lo, self.q8, self.pre, self.lowres_part = {graph.input: np.asarray(frame, np.float32)}, {}, {}, {}, {}
         for L in self.launches:
             self.run(L)
             if stop_after in L.layers + L.layers2:   # (the network has 52 M weights: a test that needs the first stages only stops there)
@@ -644,13 +663,12 @@ class Emulation:
     def blob(self, name):
         """what rtp_get_blob returns: hi + lo in fp32, concat blobs assembled from their inputs, the final maps in fp32"""
         if name == self.graph.lowres:
-            return np.concatenate([self.lowres_part[b] for b in self.graph.concats[name]], axis=1)
-        if name in self.graph.concats:
-            hi, lo = self.operand(name)
-            return hi + lo if self.parts.get(name) in ("lo", "q") else hi
-        if name not in self.hi:
+            return np.concatenate([self.lowres_part[b] for b in self.graph.concats[name]], axis=1) if name in self.graph.concats else self.lowres_part[name]
+        if name not in self.graph.concats and name not in self.hi:
             raise KeyError(f"blob {name} is not materialised")
-        return self.hi[name] + self.lo[name] if self.parts.get(name) in ("lo", "q") else self.hi[name]
+        part = self.parts.get(name, "")          # the export adds the lo block where there is one, else the q block (kernels.h launch_export)
+        hi, lo = self.operand(name)
+        return hi + lo if "lo" in part else hi + self.operand_q(name) if part else hi
 
     @staticmethod
     def conv32(a, w, pad):
@@ -691,23 +709,33 @@ class Emulation:
             return hi, lo
         return self.hi[name], self.lo.get(name, np.zeros_like(self.hi[name]))
 
+    def operand_q(self, name):
+        """the q block of a tensor, as values: e4m3(lo * 2^12) / 2^12 per channel"""
+        if name in self.graph.concats:
+            bots = self.graph.concats[name]
+            have = next(self.hi[b] for b in bots if b in self.hi)
+            zeros = lambda b: np.zeros((have.shape[0], self.graph.channels[b]) + have.shape[2:], np.float32)
+            return np.concatenate([self.q8[b] if b in self.q8 else zeros(b) for b in bots], axis=1)
+        return self.q8.get(name, np.zeros_like(self.hi[name]))
+
     def store(self, name, v, dest=None):
-        """ReLU, rounding to fp16 (+ the lo part, kept for every consumer that might read it), under the blob name `dest`"""
+        """ReLU, rounding to fp16 (+ the lo and q blocks that the tensors it is stored to carry), under the blob name `dest`"""
         g = self.graph.convs[name]
         if g["relu"]:
             v = np.maximum(v, np.float32(0))
         hi, lo = _split16(v.astype(np.float32))
         dest = dest or name
         self.hi[dest] = hi
-        wants = {self.parts.get(dest)} | {self.parts.get(c) for c, bots in self.graph.concats.items() if dest in bots}
-        assert not {"lo", "q"} <= wants, "one producer feeding lo and q tensors is not emulated"
+        wants = "+".join([self.parts.get(dest, "")] + [self.parts.get(c, "") for c, bots in self.graph.concats.items() if dest in bots])
         if "lo" in wants:
             self.lo[dest] = lo
-        elif "q" in wants:
-            self.lo[dest] = _e4m3((v.astype(np.float32) - hi) * np.float32(4096)) * np.float32(1.0 / 4096)
         else:
             self.lo.pop(dest, None)
-        if dest in self.graph.concats.get(self.graph.lowres, ()):
+        if "q" in wants:
+            self.q8[dest] = _e4m3((v.astype(np.float32) - hi) * np.float32(4096)) * np.float32(1.0 / 4096)
+        else:
+            self.q8.pop(dest, None)
+        if dest == self.graph.lowres or dest in self.graph.concats.get(self.graph.lowres, ()):
             self.lowres_part[dest] = v.astype(np.float32)
 
     def finish(self, L, name, v, pool3=False):
@@ -723,13 +751,17 @@ class Emulation:
     def run(self, L):
         if L.kind == "pool":
             hi, lo = self.operand(L.pool_in)
+            q8 = self.operand_q(L.pool_in)
+            in_part, out_part = self.parts.get(L.pool_in, ""), self.parts.get(L.pool_out, "")
             N, C, H, W = hi.shape
-            val = (hi + lo).reshape(N, C, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4)
+            val = (hi + (lo if "lo" in in_part else q8)).reshape(N, C, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4)
             sel = val.argmax(axis=-1)[..., None]
             take = lambda t: np.take_along_axis(t.reshape(N, C, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4), sel, -1)[..., 0]
             self.hi[L.pool_out] = take(hi)
-            if self.parts.get(L.pool_out) in ("lo", "q"):
+            if "lo" in out_part:
                 self.lo[L.pool_out] = take(lo)
+            if "q" in out_part:
+                self.q8[L.pool_out] = take(q8)
             return
         lab1 = L.passes.split("/")[0]
         if "q" in lab1:
@@ -738,6 +770,8 @@ class Emulation:
                 self.wq_exp[n] = max(-20, min(int(np.floor(np.log2(448.0 / mx))), 40))
         for bi, name in enumerate(L.layers):
             a_hi, a_lo = self.operand(self.graph.convs[name]["bottom"])
+            if "q" in lab1:
+                a_lo = self.operand_q(self.graph.convs[name]["bottom"])
             v = self.gemm(name, lab1, a_hi, a_lo)
             self.pre[name] = v
             if L.kind != "pw2":

@@ -10,13 +10,19 @@ The tapped forward runs ONE frame: a batch_frames 2 case runs that plan's tiles 
 the two frames of a batch — that seam stays with the batch-transparency checks of tests/test_precision.py and tests/test_gpu_parity.py.
 
 Time: a case costs the engine build + one forward (what a tests/test_precision.py case pays too) plus the float64 reference of the
-sampled pixels; both are printed, profiles/conv_launch_check.txt has them for every case."""
+sampled pixels; both are printed, profiles/conv_launch_check.txt has them for every case.
+
+A second set of cases (tests/_customnets.py CUSTOM_MATRIX) runs graphs other than the built-in one through proto_path, at sizes of a few
+thousand pixels: 1x1 layers on the register-staged kernel, concat slices at odd channel offsets, output-channel tails other than 19 / 38 / 28,
+7x7 layers below 1/8 resolution, one convolution writing the low-res maps, a tensor with a lo and a q block (tests/test_conv_launches_cpu.py
+asserts what they reach)."""
 import time
 
 import numpy as np
 import pytest
 
 import _convcheck as cc
+import _customnets as cn
 import _synth
 
 pytestmark = pytest.mark.gpu
@@ -25,20 +31,17 @@ INTERIOR = 128        # random interior pixels per image and launch (borders and
 _graphs = {}
 
 
-@pytest.mark.parametrize("name", list(cc.MATRIX))
-def test_every_launch_alone_against_float64(name):
+def _check_every_launch(name, cfg, graph, mode, N, B, frame_seed):
+    """one engine, one forward, every launch of its plan alone against float64"""
     import caffe_rtpose_amd as r
-    mode, model, W, H, N, gap, B, wseed = cc.MATRIX[name]
-    if model not in _graphs:
-        _graphs[model] = cc.builtin_graph(model)
-    graph = _graphs[model]
+    W, H = cfg.c.net_w, cfg.c.net_h
     t0 = time.time()
-    e = r.Engine(cc.matrix_config(name))
+    e = r.Engine(cfg)
     t1 = time.time()
     layers = e.conv_layers()
     assert [(n, ci, co, k) for n, ci, co, k in layers] == [(n, graph.channels[c["bottom"]], c["cout"], c["k"]) for n, c in graph.convs.items()]
     weights = {n: e.get_conv_weights(i) for i, (n, *_rest) in enumerate(layers)}
-    x = _synth.random_frame(N, H, W, seed=3 if wseed == 1 else 100 + wseed)
+    x = _synth.random_frame(N, H, W, seed=frame_seed)
     t2 = time.time()
     heat = e.forward_heatmaps(x)
     t3 = time.time()
@@ -65,3 +68,17 @@ def test_every_launch_alone_against_float64(name):
         for f in rep.failures[:8]:
             print(f"    {f}")
     assert not bad, f"{len(bad)} launches outside their bound, first: {bad[0].failures[0]}"
+
+
+@pytest.mark.parametrize("name", list(cc.MATRIX))
+def test_every_launch_alone_against_float64(name):
+    mode, model, W, H, N, gap, B, wseed = cc.MATRIX[name]
+    if model not in _graphs:
+        _graphs[model] = cc.builtin_graph(model)
+    _check_every_launch(name, cc.matrix_config(name), _graphs[model], mode, N, B, 3 if wseed == 1 else 100 + wseed)
+
+
+@pytest.mark.parametrize("case", cn.CUSTOM_MATRIX, ids=cn.case_id)
+def test_every_launch_of_a_custom_graph_alone_against_float64(case):
+    gname, mode, W, H, N, B = case
+    _check_every_launch(cn.case_id(case), cn.config(*case), cn.net(gname)[1], mode, N, B, 3)

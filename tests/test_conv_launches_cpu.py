@@ -9,13 +9,20 @@ catches what it is for.
    accumulation, outputs rounded to fp16 + lo part or + the e4m3 operands of the fp8-compensated launches; _convcheck.Emulation) for the
    first two stages of the 128x32 plans in F16X3, pure fp16 and mixed — the smallest resolution that still has a pooling epilogue, stand-alone pooling steps, the im2col and the direct input layer,
    64x64 / 128x64 / 128x32 tiles, six concat destinations and both branch-tail shapes.  Every pixel is sampled there.  It must pass;
-   each planted defect must fail, in the right layer and the right pixel class."""
+   each planted defect must fail, in the right layer and the right pixel class.
+3. Graphs other than the built-in one (tests/_customnets.py, CUSTOM_MATRIX): the shape-dependent branches of the planner and of the epilogues
+   that the built-in plans never take are reached (asserted feature by feature), the tile walks match the plans, a correct kernel emulated
+   over every custom graph passes (which proves, among others, that no activation reaches the 112 at which the 2q bound ends), and the
+   defects planted on the new paths fail in the right layer."""
 import numpy as np
 import pytest
 
 import _convcheck as cc
+import _customnets as cn
 import _synth
 import test_precision as tp
+
+CUSTOM_MATRIX = cn.CUSTOM_MATRIX
 
 W, H = 128, 32
 STOP = "Mconv7_stage2_L2"      # the emulation runs the trunk, stage 1 and stage 2
@@ -65,9 +72,12 @@ def test_tile_walks_match_the_workgroup_counts_of_the_plan(graphs):
     """plain_tile_ends / pool_tile_ends restate plan.h: tiles per image x images x N tiles x branches == `wgs` of every launch of every matrix plan,
     and every tile end is an interior pixel"""
     r = _r()
-    for name, (mode, model, w, h, n, gap, b, seed) in cc.MATRIX.items():
-        levels, launches = cc.parse_plan(r.plan_summary(cc.matrix_config(name)))
-        g = graphs[model]
+    plans = [(name, graphs[model], n, b, r.plan_summary(cc.matrix_config(name))) for name, (mode, model, w, h, n, gap, b, seed) in cc.MATRIX.items()]
+    plans += [(cn.case_id(c), cn.net(c[0])[1], c[4], c[5], r.plan_summary(cn.config(*c))) for c in CUSTOM_MATRIX]
+    halos = set()
+    for name, g, n, b, summary in plans:
+        levels, launches = cc.parse_plan(summary)
+        halos |= {(lvl, lv[2]) for lvl, lv in enumerate(levels)}
         for L in launches:
             if L.kind == "pool":
                 continue
@@ -79,6 +89,7 @@ def test_tile_walks_match_the_workgroup_counts_of_the_plan(graphs):
             assert L.wgs == nt * n * b * (L.coutp // L.tile[1]) * len(L.layers), (name, L)
             lim = (hh // 2, ww // 2) if L.pool else (hh, ww)
             assert ends and all(0 <= y < lim[0] and 0 <= x < lim[1] for y, x in ends)
+    assert {(0, 3), (1, 3), (2, 3)} <= halos       # levels whose halo is 3 below 1/8 resolution: custom plans only
 
 
 class _Toy:
@@ -248,3 +259,245 @@ def test_planted_missing_correction_pass_of_a_3aw_layer(toy, name, skip):
     rep = t.plant(name, t.em.gemm(name, "3aw", a_hi, a_lo, skip=(skip,)))
     print(f"\n{name} without the {skip} correction: worst |err|/tol {rep.worst:.2f}, {rep.nfail} of {rep.nchecked} elements")
     assert rep.nfail > 0 and all(f.layer == name for f in rep.failures)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# graphs other than the built-in one
+# ------------------------------------------------------------------------------------------------------------
+def test_bound_of_the_builtin_launches_is_on_the_unchanged_code_path(graphs):
+    """What the custom graphs added to the bound (a tensor with a lo AND a q block; a 3x3 ring layer on 32 fp32 channels, which the rule for the packed input
+    layer used to match) is selected by conditions no built-in plan meets: their tolerance is computed by the same expressions as before."""
+    r = _r()
+    for name in cc.MATRIX:
+        g = graphs[cc.MATRIX[name][1]]
+        _, launches = cc.parse_plan(r.plan_summary(cc.matrix_config(name)))
+        assert set(cc.tensor_parts(g, launches).values()) <= {"lo", "q"}, name
+        assert not [L for L in launches if L.kind == "conv" and L.cin_p == 32 and L.k == 3 and L.impl != "reg"], name
+        parts = cc.tensor_parts(g, launches)      # ... and no pair of theirs reads tensors with different blocks: the planner's un-pairing rule leaves them alone
+        assert all(len({parts.get(g.convs[n]["bottom"], "") for n in L.layers}) == 1 for L in launches if len(L.layers) == 2), name
+    a = np.linspace(-300.0, 300.0, 13)
+    for part in ("", "lo", "q", "f32"):
+        assert np.array_equal(cc.out_rounding(part, False, a), cc.out_rounding(part, False, a.copy()))
+    assert np.array_equal(cc.out_rounding("lo+q", False, a), cc.out_rounding("lo", False, a))
+    assert cc.e_op_of("2q", False) == cc.e_op_of("2q", False, "q") == (3 * 2.0 ** -15 + 2.0 ** -19 + 2.0 ** -22) * (1 + 2.0 ** -10)
+    assert cc.e_op_of("2q", False, "lo+q") > cc.e_op_of("2q", False) and cc.e_op_of("3aw", False, "lo+q") == cc.e_op_of("3aw", False)
+
+
+def test_accumulation_counts_of_1x1_layers_on_the_register_staged_kernel():
+    """conv_igemm.hip launch_cfg<T, 1, 128>: one tap, cin_p * elem / 128 chunks, (128 / 32) / KSPLIT instructions per chunk and wave with KSPLIT 1 / 2 / 4 on
+    128x128 / 64x128 / 64x64, + 15 roundings inside the fp16 instructions (+ 2 for fp32, four 32x32x2 per k-group), + KSPLIT - 1 for the reduction, + 1 bias"""
+    mk = lambda tile, cin_p, passes: cc.Launch(kind="conv", layers=["x"], k=1, cin_p=cin_p, tile=tile, rowb=128, passes=passes, impl="reg")
+    assert [cc.c_acc_conv(mk(t, 192, "3aw"), False) for t in ((128, 128), (64, 128), (64, 64))] == [3 * 3 * 4 + 15 + 0 + 1, 3 * 3 * 2 + 15 + 1 + 1, 3 * 3 * 1 + 15 + 3 + 1]
+    assert [cc.c_acc_conv(mk(t, 128, "1"), False) for t in ((128, 128), (64, 128), (64, 64))] == [2 * 4 + 16, 2 * 2 + 17, 2 * 1 + 19]
+    assert [cc.c_acc_conv(mk(t, 96, "1"), True) for t in ((128, 128), (64, 128), (64, 64))] == [3 * 4 * 4 + 2 + 0 + 1, 3 * 2 * 4 + 2 + 1 + 1, 3 * 1 * 4 + 2 + 3 + 1]
+    # a 3x3 layer on a 32-channel fp32 tensor is a ring launch of nine taps, not the packed input layer (a 1x1 layer on 32 channels of the register-staged kernel)
+    ring = cc.Launch(kind="conv", layers=["x"], k=3, cin_p=32, tile=(128, 64), rowb=128, passes="1", impl="ring")
+    pack = cc.Launch(kind="conv", layers=["x"], k=3, cin_p=32, tile=(128, 64), rowb=128, passes="1", impl="reg")
+    assert cc.c_acc_conv(ring, True) == 9 * 2 * 4 + 2 + 1 + 1 and cc.c_acc_conv(pack, True) == 2 * 4 + 2 + 1 + 1
+
+
+def _custom_features(graph, summary, mode):
+    """the shape-dependent paths a custom plan takes"""
+    levels, launches = cc.parse_plan(summary)
+    f = set()
+    for L in launches:
+        if L.kind == "pool":
+            if levels[graph.level[L.pool_in]][2] == 3:
+                f.add("pool step reads a tensor with halo 3")
+            continue
+        couts = [graph.convs[n]["cout"] for n in L.layers]
+        lvl = graph.level[graph.convs[L.layers[0]]["bottom"]]
+        if L.k == 7 and lvl < 3:
+            f.add("k 7 below level 3")
+        if L.pool and couts[0] % 16:
+            f.add("+pool with a partial 16-channel chunk, passes " + L.passes)
+        if L.kind == "conv" and L.coutp - min(couts) >= 64 and L.coutp > -(-min(couts) // 64) * 64:
+            f.add("whole 64-channel groups past cout, past the output tensor's padded channels")
+        if len(set(couts)) == 2:
+            f.add("pair with different cout")
+        if L.kind == "conv" and L.cin_p == 32 and L.impl == "reg" and couts[0] != 64 and mode != "fp32":
+            f.add("first layer with cout != 64 through pack + 1x1")
+        for n in L.layers:
+            b = graph.convs[n]["bottom"]
+            if b in graph.concats and mode != "fp32":
+                for _, off in cn.concat_offsets(graph, b):
+                    if off % 2 and "q" in L.passes:
+                        f.add("odd slice offset, q block")
+                    if off % 2 and "a" in L.passes[1:]:
+                        f.add("odd slice offset, lo block")
+                    if off % 4 == 0 and off % 8 and off % 64 > 48 and "q" in L.passes:
+                        f.add("4-aligned slice across a q group boundary")
+    if "lo+q" in cc.tensor_parts(graph, launches).values():
+        f.add("tensor with lo and q")
+    return f
+
+
+def test_concat_offsets_restate_the_planner():
+    """the 8-aligned layout where it costs no padded channels (the built-in concats: 0 / 128 / 168), packed offsets — odd ones — where it would"""
+    g = cc.builtin_graph(0)
+    assert cn.concat_offsets(g, "concat_stage2") == [("conv5_5_CPM_L1", 128), ("conv5_5_CPM_L2", 168), ("conv4_4_CPM", 0)]
+    assert cn.concat_offsets(cn.net("odd")[1], "cat1") == [("a1", 128), ("a2", 147), ("f", 0)]
+    assert cn.concat_offsets(cn.net("single")[1], "cat2") == [("s", 40), ("t", 60), ("u", 0)]
+
+
+def test_custom_matrix_reaches_the_shape_dependent_paths(graphs):
+    r = _r()
+    base = set()
+    for name in cc.MATRIX:
+        base |= cc.plan_keys(r.plan_summary(cc.matrix_config(name)), graphs[cc.MATRIX[name][1]])
+    new, feats, every = {}, set(), set()
+    for case in CUSTOM_MATRIX:
+        graph = cn.net(case[0])[1]
+        summary = r.plan_summary(cn.config(*case))
+        every |= cc.plan_keys(summary, graph)
+        for k in cc.plan_keys(summary, graph) - base:
+            new.setdefault(k, cn.case_id(case))
+        feats |= _custom_features(graph, summary, case[1])
+    print(f"\n{len(new)} instantiations in {len(CUSTOM_MATRIX)} custom configurations that the {len(base)} of the built-in matrix do not have")
+    for k, c in sorted(new.items(), key=lambda kv: cc.key_str(kv[0])):
+        print(f"  {cc.key_str(k)}  ({c})")
+    assert len(new) >= 42
+    import re
+    keys = [cc.key_str(k) for k in every]
+    for needle in (r"k 1 .* tile 128x128 .* reg", r"k 1 .* tile 64x128 .* reg", r"k 1 .* tile 64x64 .* reg", r"^conv pair k 1 .* reg",
+                   r"^conv (pair )?k 1 .* reg lowres", r"^conv k 3 .* ring lowres", r"\+pool .* passes 2q", r"\+pool .* passes 3aw", r"k 7 cin_p 224", r"k 7 cin_p 256", r"k 7 cin_p 320",
+                   r"^pw2 .* mid 256", r"^pw2 pair .* mid 384 .* lowres"):
+        assert any(re.search(needle, k) for k in keys), needle
+    # (coutp = round_up(largest cout of the launch, BN) and the branches of a pair have the same round_up(cout, 64): coutp - cout < BN always; what
+    #  does occur is whole 64-channel groups of 16-channel chunks past cout — cout 300 on 128-wide tiles, coutp 384, in a tensor padded to 320)
+    want = {"+pool with a partial 16-channel chunk, passes 2q", "+pool with a partial 16-channel chunk, passes 3aw", "pool step reads a tensor with halo 3", "k 7 below level 3", "whole 64-channel groups past cout, past the output tensor's padded channels",
+            "pair with different cout", "first layer with cout != 64 through pack + 1x1", "odd slice offset, q block", "odd slice offset, lo block",
+            "4-aligned slice across a q group boundary", "tensor with lo and q"}
+    assert want <= feats, want - feats
+    assert {c[1:4] for c in CUSTOM_MATRIX} >= {("mixed", 64, 256)} and len([c for c in CUSTOM_MATRIX if c[4:] == (2, 2)]) == 1
+    assert {cn.net(c[0])[2] for c in CUSTOM_MATRIX} == {15, 18}      # an MPI-shaped tail among them
+
+
+def test_pair_whose_inputs_carry_different_blocks_runs_as_two_launches():
+    """odd, mixed @all: b1 is read by d1 (1x1, register-staged kernel, 3aw: a lo block) and by b1k3 (3x3 ring, 2q: a q block), b2 by d2 alone — the tensors
+    have different pixel pitches, and a pair has ONE input pitch in its kernel arguments.  Where every layer runs the same passes the pair stays."""
+    r = _r()
+    steps = lambda mode: [ln.split()[2:5] for ln in r.plan_summary(cn.config("odd", mode, 256, 64)).splitlines() if ln.startswith("step conv d")]
+    assert steps("mixed") == [["d1", "k", "1"], ["d2", "k", "1"]]
+    for mode in ("f16x3", "fp16", "fp32"):
+        assert steps(mode) == [["d1", "+", "d2"]], mode
+    g = cn.net("odd")[1]
+    _, launches = cc.parse_plan(r.plan_summary(cn.config("odd", "mixed", 256, 64)))
+    parts = cc.tensor_parts(g, launches)
+    assert (parts["b1"], parts["b2"]) == ("lo+q", "lo")
+    for L in launches:      # every remaining pair reads tensors with the same blocks
+        if len(L.layers) == 2:
+            assert len({parts.get(g.convs[n]["bottom"], "") for n in L.layers}) == 1, L
+
+
+SMALL_W, SMALL_H = 64, 48
+
+
+class _Custom:
+    """a custom graph at the smallest size, emulated launch by launch"""
+    def __init__(self, gname, mode):
+        r = _r()
+        self.graph = cn.net(gname)[1]
+        self.summary = r.plan_summary(cn.config(gname, mode, SMALL_W, SMALL_H))
+        self.weights = {n: r.synth_weights(1, n, c["cout"], self.graph.channels[c["bottom"]], c["k"]) for n, c in self.graph.convs.items()}
+        self.em = cc.Emulation(self.summary, self.graph, self.weights, _synth.random_frame(1, SMALL_H, SMALL_W, seed=3))
+        self.launch = {n: L for L in self.em.launches for n in L.layers + L.layers2}
+        self.blob = self.em.blob
+
+    def check(self, only=None):
+        names = list(self.weights) + list(self.graph.pools) if only is None else only
+        return cc.check_plan(self.summary, self.graph, self.weights, lambda n: self.blob(n), n_interior=10 ** 9, only=names)
+
+
+@pytest.fixture(scope="module")
+def custom():
+    return _Lazy(lambda key: _Custom(*key))
+
+
+@pytest.mark.parametrize("mode", ["fp16", "f16x3", "mixed"])
+@pytest.mark.parametrize("gname", list(cn.NETS))
+def test_emulated_correct_kernel_passes_every_launch_of_the_custom_graphs(custom, gname, mode):
+    t = custom[gname, mode]
+    reps = t.check()
+    nl = len([ln for ln in t.summary.splitlines() if ln.startswith("step ") and not ln.startswith("step pack")])
+    for rep in reps:
+        print(f"  {rep.launch!r:60.60s} {cc.key_str(rep.launch.key):100.100s} worst |err|/tol {rep.worst:.3f} over {rep.nchecked} elements")
+    print(f"[{gname} {mode}] worst |err|/tol {max(rep.worst for rep in reps):.3f}")
+    bad = [str(f) for rep in reps for f in rep.failures]
+    assert not bad, bad[:5]
+    assert len(reps) == nl and all(rep.nchecked > 0 for rep in reps)
+    assert np.array_equal(t.em.blob(t.graph.lowres).shape, (1, 57 if cn.net(gname)[2] == 18 else 44, SMALL_H // 8, SMALL_W // 8))
+
+
+def _only(rep, layer_dest):
+    return rep.nfail > 0 and {(f.layer, f.dest) for f in rep.failures} == layer_dest
+
+
+def test_planted_stale_last_channels_of_a_130_channel_layer(custom):
+    """the 16-channel chunk at channel 128 of b1 (two valid channels) left unwritten: what was in the tensor before stays"""
+    t = custom["odd", "mixed"]
+    keep = t.em.hi["b1"].copy()
+    t.em.hi["b1"][:, 128:] = np.float32(0.25)
+    rep = t.check(["b1"])[0]
+    t.em.hi["b1"] = keep
+    assert _only(rep, {("b1", "b1")}) and {f.ch for f in rep.failures} <= {128, 129}, [str(f) for f in rep.failures]
+    assert t.check(["b1"])[0].nfail == 0
+
+
+@pytest.mark.parametrize("mode", ["f16x3", "mixed"])
+def test_planted_odd_offset_slice_one_channel_too_low(custom, mode):
+    """a2's slice of cat1 (tensor channel 147, reference channels 19..63) written at 146: every channel of the slice holds its neighbour's value and a1's last channel is overwritten"""
+    t = custom["odd", mode]
+    off = dict(t.graph.dests("a2"))["cat1"]
+    assert off == 19 and dict(cn.concat_offsets(t.graph, "cat1"))["a2"] % 2 == 1
+
+    def shifted(name):
+        b = t.em.blob(name)
+        if name == "cat1":
+            b = b.copy()
+            b[:, off - 1:off + 44] = b[:, off:off + 45]
+        return b
+    t.blob = shifted
+    try:
+        rep = t.check(["a2"])[0]
+    finally:
+        t.blob = t.em.blob
+    assert rep.nfail > 0 and {f.dest for f in rep.failures} == {"cat1"} and ("a2", "cat1") in {(f.layer, f.dest) for f in rep.failures}, [str(f) for f in rep.failures]
+    assert {f.ch for f in rep.failures if f.layer == "a1"} <= {18}
+    assert t.check(["a2"])[0].nfail == 0
+
+
+def test_planted_wrong_channel_offset_of_the_low_res_maps_of_a_single_convolution(custom):
+    t = custom["single", "fp16"]
+    assert t.graph.lowres == "low" and "low" in t.graph.convs
+    t.blob = lambda name: np.roll(t.em.blob(name), 1, axis=1) if name == "low" else t.em.blob(name)
+    try:
+        rep = t.check(["low"])[0]
+    finally:
+        t.blob = t.em.blob
+    assert rep.launch.lowres and _only(rep, {("low", "low")}), [str(f) for f in rep.failures]
+    assert t.check(["low"])[0].nfail == 0
+
+
+def test_planted_swapped_branches_of_a_1x1_pair_on_the_register_staged_kernel(custom):
+    t = custom["odd", "f16x3"]
+    L = t.launch["d1"]
+    assert L.layers == ["d1", "d2"] and L.k == 1 and L.impl == "reg"
+    t.em.store("d1", t.em.pre["d2"]); t.em.store("d2", t.em.pre["d1"])
+    rep = t.check(["d1"])[0]
+    t.em.store("d1", t.em.pre["d1"]); t.em.store("d2", t.em.pre["d2"])
+    assert _only(rep, {("d1", "d1"), ("d2", "d2")}), [str(f) for f in rep.failures]
+    assert t.check(["d1"])[0].nfail == 0
+
+
+def test_planted_dropped_lo_part_of_the_tensor_with_lo_and_q(custom):
+    """f's own tensor carries lo (read by the 1x1 layer fk1, 3aw) and q (read by a1 + a2, 2q): without the lo block its export is 2^-12 off, against a bound
+    of 2^-22; its slice of cat1 carries a q block only and stays inside its bound"""
+    t = custom["odd", "mixed"]
+    assert t.em.parts["f"] == "lo+q" and t.em.parts["cat1"] == "q" and t.launch["fk1"].passes == "3aw" and t.launch["a1"].passes == "2q"
+    keep = t.em.lo["f"]
+    t.em.lo["f"] = np.zeros_like(keep)
+    rep = t.check(["f"])[0]
+    t.em.lo["f"] = keep
+    assert _only(rep, {("f", "f")}), [str(f) for f in rep.failures]
+    assert t.check(["f"])[0].nfail == 0
