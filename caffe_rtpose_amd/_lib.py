@@ -54,6 +54,23 @@ class rtp_frame_view(C.Structure):
     ]
 
 
+class rtp_yuv_view(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("matrix", C.c_int),
+        ("y", C.c_void_p),
+        ("u", C.c_void_p),
+        ("v", C.c_void_p),
+        ("width", C.c_int),
+        ("height", C.c_int),
+        ("chroma_shift_x", C.c_int),
+        ("chroma_shift_y", C.c_int),
+        ("y_stride", C.c_long),
+        ("uv_stride", C.c_long),
+        ("uv_pixel_stride", C.c_long),
+    ]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 vp = C.c_void_p
@@ -142,6 +159,12 @@ SIGNATURES = {
     "rtp_encode_jpeg_device": (C.c_int, [vp, C.POINTER(rtp_frame_view), C.c_int, vp, C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(C.c_size_t)]),
     "rtp_set_render_jpeg": (C.c_int, [vp, C.c_int]),
     "rtp_collect_rendered_jpeg": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rtp_convert_yuv": (C.c_int, [C.POINTER(rtp_yuv_view), C.POINTER(C.c_ubyte), C.c_size_t]),
+    "rtp_video_chroma": (C.c_int, [vp]),
+    "rtp_video_read_yuv": (C.c_int, [vp, C.POINTER(rtp_yuv_view)]),
+    "rtp_submit_frame_yuv": (C.c_int, [vp, C.POINTER(rtp_yuv_view), C.c_uint64, fp]),
+    "rtp_submit_frame_yuv_device": (C.c_int, [vp, C.POINTER(rtp_yuv_view), vp, C.c_uint64, fp]),
+    "rtp_convert_yuv_device": (C.c_int, [vp, C.POINTER(rtp_yuv_view), C.POINTER(rtp_frame_view), vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1101,6 +1101,84 @@ int rtp_internal_load_png_jpeg(const char* path, unsigned char* out_bgr, size_t 
 // cv::VideoCapture(path) for the two container-less formats decodable here.
 static int video_open_impl(const char* path, rtp_video** out, int* w, int* h, int* nframes);
 static int video_read_impl(rtp_video* v, unsigned char* out_bgr, size_t capacity);
+static int video_read_yuv_impl(rtp_video* v, rtp_yuv_view* out);
+
+// Field checks of an rtp_yuv_view, shared by rtp_convert_yuv and the engine's YUV entries (no HIP call, no engine): struct_size,
+// matrix, sizes, shifts, strides, the NULL rules, and the extents with overflow checks.  hi[0..2] = the highest byte offset the view
+// addresses from y, u and v.  On failure the message (without the entry's name) is written to msg.
+int rtp_internal_yuv_fields(const rtp_yuv_view* v, char* msg, size_t msg_len, long hi[3]) {
+  const auto bad = [&](const char* fmt, auto... a) {
+    if constexpr (sizeof...(a) == 0) snprintf(msg, msg_len, "%s", fmt);
+    else snprintf(msg, msg_len, fmt, a...);
+    return RTP_EINVAL;
+  };
+  if (!v) return bad("NULL yuv view");
+  if (v->struct_size != sizeof(rtp_yuv_view))
+    return bad("rtp_yuv_view.struct_size is %u, this library's rtp_yuv_view has %zu bytes", v->struct_size, sizeof(rtp_yuv_view));
+  if (v->matrix != RTP_YUV_BT601_LIMITED) return bad("matrix %d: only RTP_YUV_BT601_LIMITED (0) is implemented", v->matrix);
+  if (v->width < 1 || v->height < 1) return bad("view size %d x %d", v->width, v->height);
+  if ((long long)v->width * v->height >= (1LL << 31)) return bad("a view of 2^31 pixels or more");
+  const int sx = v->chroma_shift_x, sy = v->chroma_shift_y;
+  if (sx < 0 || sx > 1 || sy < 0 || sy > 1 || (sx == 0 && sy == 1))
+    return bad("chroma shifts (%d, %d): 4:2:0 = (1, 1), 4:2:2 = (1, 0), 4:4:4 = (0, 0)", sx, sy);
+  if (v->y_stride < 0 || v->uv_stride < 0) return bad("y_stride %ld, uv_stride %ld (need >= 0)", v->y_stride, v->uv_stride);
+  if (v->uv_pixel_stride != 1 && v->uv_pixel_stride != 2) return bad("uv_pixel_stride %ld: 1 (planar) or 2 (interleaved)", v->uv_pixel_stride);
+  if (!v->y) return bad("NULL y plane");
+  if (!v->u != !v->v) return bad("exactly one of u and v is NULL (both NULL: luma only)");
+  long a;
+  if (__builtin_mul_overflow((long)(v->height - 1), v->y_stride, &a) || __builtin_add_overflow(a, (long)(v->width - 1), &hi[0]))
+    return bad("the luma plane's extent overflows");
+  hi[1] = hi[2] = 0;
+  if (v->u) {
+    const long cw = ((long)v->width + sx) >> sx, ch = ((long)v->height + sy) >> sy;
+    if (__builtin_mul_overflow(ch - 1, v->uv_stride, &a) || __builtin_add_overflow(a, (cw - 1) * v->uv_pixel_stride, &hi[1]))
+      return bad("the chroma planes' extent overflows");
+    hi[2] = hi[1];
+  }
+  return RTP_OK;
+}
+
+// The per-pixel arithmetic of every YUV path (the GPU kernels of yuv_import.hip restate it): BT.601 limited range, integers only
+int rtp_convert_yuv(const rtp_yuv_view* v, unsigned char* out_bgr, size_t capacity) {
+  char msg[256];
+  long hi[3];
+  if (rtp_internal_yuv_fields(v, msg, sizeof msg, hi)) return cfail(RTP_EINVAL, std::string("rtp_convert_yuv: ") + msg);
+  if (!out_bgr) return cfail(RTP_EINVAL, "rtp_convert_yuv: NULL output");
+  const int W = v->width, H = v->height, sx = v->chroma_shift_x, sy = v->chroma_shift_y;
+  if (capacity < (size_t)W * H * 3) return cfail(RTP_EINVAL, "output buffer too small");
+  const unsigned char* Y = (const unsigned char*)v->y;
+  const unsigned char* U = (const unsigned char*)v->u;
+  const unsigned char* V = (const unsigned char*)v->v;
+  const long ps = v->uv_pixel_stride;
+  for (int y = 0; y < H; ++y) {
+    const unsigned char* yr = Y + (size_t)y * v->y_stride;
+    const unsigned char* ur = U ? U + (size_t)(y >> sy) * v->uv_stride : nullptr;
+    const unsigned char* vr = U ? V + (size_t)(y >> sy) * v->uv_stride : nullptr;
+    unsigned char* o = out_bgr + (size_t)y * W * 3;
+    for (int x = 0; x < W; ++x, o += 3) {
+      const int c = 298 * (yr[x] - 16);
+      int d = 0, e = 0;
+      if (ur) {
+        const long cx = (long)(x >> sx) * ps;
+        d = ur[cx] - 128;
+        e = vr[cx] - 128;
+      }
+      o[2] = clamp255((c + 409 * e + 128) >> 8);
+      o[1] = clamp255((c - 100 * d - 208 * e + 128) >> 8);
+      o[0] = clamp255((c + 516 * d + 128) >> 8);
+    }
+  }
+  return RTP_OK;
+}
+
+int rtp_video_chroma(const rtp_video* v) { return v && v->kind == 1 ? v->chroma : 0; }
+int rtp_video_read_yuv(rtp_video* v, rtp_yuv_view* out) {
+  try {
+    return video_read_yuv_impl(v, out);
+  } catch (const std::exception& ex) {
+    return cfail(RTP_ENOMEM, std::string("video read: ") + ex.what());
+  }
+}
 int rtp_video_open(const char* path, rtp_video** out, int* w, int* h, int* nframes) {
   try {
     return video_open_impl(path, out, w, h, nframes);
@@ -1178,37 +1256,43 @@ static int video_open_impl(const char* path, rtp_video** out, int* w, int* h, in
   return RTP_OK;
 }
 
+// next Y4M frame -> v->yuv, described by *out (planar, pitches = plane widths); RTP_EAGAIN at the end of the stream
+static int video_read_yuv_impl(rtp_video* v, rtp_yuv_view* out) {
+  if (!v || !out) return RTP_EINVAL;
+  if (v->kind != 1) return cfail(RTP_EINVAL, "rtp_video_read_yuv: not a Y4M stream (MJPEG frames decode to BGR: rtp_video_read)");
+  std::string line;
+  if (!std::getline(v->f, line)) return RTP_EAGAIN;
+  if (line.rfind("FRAME", 0) != 0) return cfail(RTP_EIO, "Y4M: FRAME marker expected");
+  v->f.read((char*)v->yuv.data(), (std::streamsize)v->yuv.size());
+  if (!v->f) return RTP_EAGAIN;
+  const int W = v->w, H = v->h;
+  const int cw = v->chroma == 444 ? W : (W + 1) / 2;
+  const int chh = v->chroma == 420 ? (H + 1) / 2 : H;
+  memset(out, 0, sizeof *out);
+  out->struct_size = sizeof *out;
+  out->matrix = RTP_YUV_BT601_LIMITED;
+  out->width = W; out->height = H;
+  out->y = v->yuv.data();
+  out->y_stride = W;
+  out->uv_pixel_stride = 1;
+  if (v->chroma != 400) {
+    out->u = v->yuv.data() + (size_t)W * H;
+    out->v = v->yuv.data() + (size_t)W * H + (size_t)cw * chh;
+    out->uv_stride = cw;
+    out->chroma_shift_x = v->chroma == 444 ? 0 : 1;
+    out->chroma_shift_y = v->chroma == 420 ? 1 : 0;
+  }
+  return RTP_OK;
+}
+
 // next frame -> BGR HWC; RTP_EAGAIN at the end of the stream
 static int video_read_impl(rtp_video* v, unsigned char* out_bgr, size_t capacity) {
   if (!v || !out_bgr) return RTP_EINVAL;
   if (capacity < (size_t)v->w * v->h * 3) return cfail(RTP_EINVAL, "output buffer too small");
   if (v->kind == 1) {
-    std::string line;
-    if (!std::getline(v->f, line)) return RTP_EAGAIN;
-    if (line.rfind("FRAME", 0) != 0) return cfail(RTP_EIO, "Y4M: FRAME marker expected");
-    v->f.read((char*)v->yuv.data(), (std::streamsize)v->yuv.size());
-    if (!v->f) return RTP_EAGAIN;
-    const int W = v->w, H = v->h;
-    const int cw = v->chroma == 444 ? W : (W + 1) / 2;
-    const int chh = v->chroma == 420 ? (H + 1) / 2 : H;
-    const unsigned char* Y = v->yuv.data();
-    const unsigned char* U = Y + (size_t)W * H;
-    const unsigned char* V = U + (size_t)cw * chh;
-    for (int y = 0; y < H; ++y)
-      for (int x = 0; x < W; ++x) {
-        const int c = 298 * (Y[(size_t)y * W + x] - 16);
-        int d = 0, e = 0;
-        if (v->chroma != 400) {
-          const int cx = v->chroma == 444 ? x : x >> 1, cy = v->chroma == 420 ? y >> 1 : y;
-          d = U[(size_t)cy * cw + cx] - 128;
-          e = V[(size_t)cy * cw + cx] - 128;
-        }
-        unsigned char* o = out_bgr + ((size_t)y * W + x) * 3;
-        o[2] = clamp255((c + 409 * e + 128) >> 8);
-        o[1] = clamp255((c - 100 * d - 208 * e + 128) >> 8);
-        o[0] = clamp255((c + 516 * d + 128) >> 8);
-      }
-    return RTP_OK;
+    rtp_yuv_view yv;
+    const int rc = video_read_yuv_impl(v, &yv);
+    return rc ? rc : rtp_convert_yuv(&yv, out_bgr, capacity);
   }
   // MJPEG: next SOI..EOI
   const std::vector<unsigned char>& d = v->data;

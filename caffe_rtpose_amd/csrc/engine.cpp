@@ -85,6 +85,8 @@ struct Slot {
   hipEvent_t ev_copy = nullptr;
   bool copy_pending = false;
   int pend_w = 0, pend_h = 0;
+  bool pend_yuv = false;                // the staged frame is YUV (rtp_submit_frame_yuv): yuv_dev describes its planes behind the BGR image in frame_dev,
+  YuvView yuv_dev = {};                 // and the conversion kernel runs in front of the warp
   unsigned char* frame_dev = nullptr;   // raw u8 frame (device) for rtp_submit_frame
   unsigned char* frame_host = nullptr;  // pinned staging of the raw frame
   size_t frame_cap = 0;
@@ -936,6 +938,14 @@ hipError_t make_stream(hipStream_t* s, bool post) {
   return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
 
+// Bytes of a w x h YUV frame staged behind its BGR image in frame_dev: the image rounded up to 256 (*planes_off, may be null), then
+// Y and two chroma planes of ((w + sx) >> sx) x ((h + sy) >> sy) samples, pitches dropped
+size_t staged_yuv_bytes(int w, int h, int sx, int sy, size_t* planes_off) {
+  const size_t off = round_up_sz((size_t)w * h * 3, 256);
+  if (planes_off) *planes_off = off;
+  return off + (size_t)w * h + 2 * (size_t)((w + sx) >> sx) * (size_t)((h + sy) >> sy);
+}
+
 int alloc_slot(rtp_engine* e, Ctx& cx, Slot& sl, bool share_stream) {
   if (sl.preset_stream) {}  // RTP_STREAM_PLAN: alloc_ctx chose it
   else if (share_stream) sl.stream = cx.stream;
@@ -968,9 +978,11 @@ int alloc_slot(rtp_engine* e, Ctx& cx, Slot& sl, bool share_stream) {
   // frame is larger than the display image.
   {
     const size_t fbytes = (size_t)e->cfg.disp_w * e->cfg.disp_h * 3;
-    HIPCHK(e, hipMalloc((void**)&sl.frame_dev, fbytes));
-    HIPCHK(e, hipHostMalloc((void**)&sl.frame_host, fbytes, hipHostMallocDefault));
-    sl.frame_cap = fbytes;
+    // (room for a 4:2:0 frame of the display size behind its BGR image: rtp_submit_frame_yuv)
+    const size_t cbytes = staged_yuv_bytes(e->cfg.disp_w, e->cfg.disp_h, 1, 1, nullptr);
+    HIPCHK(e, hipMalloc((void**)&sl.frame_dev, cbytes));
+    HIPCHK(e, hipHostMalloc((void**)&sl.frame_host, cbytes, hipHostMallocDefault));
+    sl.frame_cap = cbytes;
     HIPCHK(e, hipMalloc((void**)&sl.disp_dev, fbytes));
     if (e->cfg.render) {
       HIPCHK(e, hipMalloc((void**)&sl.render_dev, fbytes));
@@ -1230,40 +1242,102 @@ int build_prep_tables(rtp_engine* e) {
   return RTP_OK;
 }
 
-// raw u8 BGR frame (host) -> frame slot sj of cx.input on the device
-int enqueue_preprocess(rtp_engine* e, Ctx& cx, int sj, const unsigned char* bgr, int w, int h, float* frame_scale) {
+// Room for `bytes` in the slot's raw-frame buffers
+int ensure_frame_cap(rtp_engine* e, Ctx& cx, Slot& sl, size_t bytes) {
+  if (bytes <= sl.frame_cap) return RTP_OK;
+  // first frame of this slot (or a larger one): rare, and hipFree synchronises the device
+  SYNC_GUARD;
+  HIPCHK(e, hipStreamSynchronize(cx.in_stream));
+  if (sl.frame_dev) (void)hipFree(sl.frame_dev);
+  if (sl.frame_host) (void)hipHostFree(sl.frame_host);
+  sl.frame_dev = nullptr; sl.frame_host = nullptr; sl.frame_cap = 0;
+  HIPCHK(e, hipMalloc((void**)&sl.frame_dev, bytes));
+  HIPCHK(e, hipHostMalloc((void**)&sl.frame_host, bytes, hipHostMallocDefault));
+  sl.frame_cap = bytes;
+  return RTP_OK;
+}
+
+// The planes of a host YUV view, row by row without their pitches, into the slot's pinned staging: Y, then U and V (planar) or the
+// interleaved pairs as they arrived.  *dv = the same planes where the H2D copy puts them: behind the BGR image in frame_dev.
+size_t stage_yuv_planes(const YuvView& h, Slot& sl, size_t dev_off, YuvView* dv) {
+  const int cw = (h.w + h.sx) >> h.sx, ch = (h.h + h.sy) >> h.sy;
+  unsigned char* p = sl.frame_host;
+  for (int y = 0; y < h.h; ++y) memcpy(p + (size_t)y * h.w, h.y + (size_t)y * h.ys, (size_t)h.w);
+  size_t n = (size_t)h.w * h.h;
+  *dv = h;
+  dv->y = sl.frame_dev + dev_off;
+  dv->ys = h.w;
+  if (!h.u) return n;
+  const bool inter = h.uvp == 2 && (h.v == h.u + 1 || h.u == h.v + 1);
+  if (inter) {   // one plane of pairs, in the caller's order
+    const unsigned char* first = h.v == h.u + 1 ? h.u : h.v;
+    for (int y = 0; y < ch; ++y) memcpy(p + n + (size_t)y * cw * 2, first + (size_t)y * h.uvs, (size_t)cw * 2);
+    dv->u = sl.frame_dev + dev_off + n + (first == h.u ? 0 : 1);
+    dv->v = sl.frame_dev + dev_off + n + (first == h.u ? 1 : 0);
+    dv->uvs = 2L * cw; dv->uvp = 2;
+  } else {       // two planes (a pixel stride of 2 without a neighbouring partner is dropped like a pitch)
+    unsigned char* pu = p + n;
+    unsigned char* pv = pu + (size_t)cw * ch;
+    for (int y = 0; y < ch; ++y) {
+      const unsigned char* su = h.u + (size_t)y * h.uvs;
+      const unsigned char* sv = h.v + (size_t)y * h.uvs;
+      if (h.uvp == 1) { memcpy(pu + (size_t)y * cw, su, (size_t)cw); memcpy(pv + (size_t)y * cw, sv, (size_t)cw); }
+      else for (int x = 0; x < cw; ++x) { pu[(size_t)y * cw + x] = su[2 * x]; pv[(size_t)y * cw + x] = sv[2 * x]; }
+    }
+    dv->u = sl.frame_dev + dev_off + n;
+    dv->v = sl.frame_dev + dev_off + n + (size_t)cw * ch;
+    dv->uvs = cw; dv->uvp = 1;
+  }
+  return n + 2 * (size_t)cw * ch;
+}
+
+// The pre-processing kernels of a staged host frame on `stream`: YUV planes -> BGR image in frame_dev (rtp_submit_frame_yuv), the
+// cubic warp unless the frame has the display size, the area pyramid
+int launch_prep_kernels(rtp_engine* e, Ctx& cx, int sj, int w, int h, hipStream_t stream) {
+  Slot& sl = cx.slot[sj];
+  const double s = rtp_display_fit_scale(w, h, e->cfg.disp_w, e->cfg.disp_h);
+  float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
+  if (sl.pend_yuv) {
+    const FrameView bgr = packed_bgr_view(sl.frame_dev, w, h);
+    HIPCHK(e, launch_yuv_import(stamp_slot(e, cx, 200 + 2 * sj), sl.yuv_dev, bgr, yuv_layout(sl.yuv_dev, bgr), stream));
+  }
+  if (w == e->cfg.disp_w && h == e->cfg.disp_h) sl.disp_cur = sl.frame_dev;   // identity warp (20 us per 720p frame saved)
+  else {
+    sl.disp_cur = sl.disp_dev;
+    HIPCHK(e, launch_warp(stamp_slot(e, cx, 200 + 2 * sj), sl.frame_dev, w, h, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, e->cfg.disp_w, e->cfg.disp_h, stream));
+  }
+  HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, e->cfg.disp_w, e->cfg.disp_h, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, stream));
+  return RTP_OK;
+}
+
+// raw u8 BGR frame (host), or — yuv != null — the planes of a host YUV frame -> frame slot sj of cx.input on the device
+int enqueue_preprocess(rtp_engine* e, Ctx& cx, int sj, const unsigned char* bgr, int w, int h, float* frame_scale, const YuvView* yuv = nullptr) {
   Slot& sl = cx.slot[sj];
   const size_t fbytes = (size_t)w * h * 3;
-  if (fbytes > sl.frame_cap) {   // first frame of this slot (or a larger one): rare, and hipFree synchronises the device
-    SYNC_GUARD;
-    HIPCHK(e, hipStreamSynchronize(cx.in_stream));
-    if (sl.frame_dev) (void)hipFree(sl.frame_dev);
-    if (sl.frame_host) (void)hipHostFree(sl.frame_host);
-    sl.frame_dev = nullptr; sl.frame_host = nullptr; sl.frame_cap = 0;
-    HIPCHK(e, hipMalloc((void**)&sl.frame_dev, fbytes));
-    HIPCHK(e, hipHostMalloc((void**)&sl.frame_host, fbytes, hipHostMallocDefault));
-    sl.frame_cap = fbytes;
-  }
+  size_t yuv_off = 0;
+  const size_t need = yuv ? staged_yuv_bytes(w, h, yuv->sx, yuv->sy, &yuv_off) : fbytes;
+  int rc;
+  if ((rc = ensure_frame_cap(e, cx, sl, need))) return rc;
   if (!sl.disp_dev) { SYNC_GUARD; HIPCHK(e, hipMalloc((void**)&sl.disp_dev, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3)); }
   const double s = rtp_display_fit_scale(w, h, e->cfg.disp_w, e->cfg.disp_h);
   if (frame_scale) *frame_scale = (float)s;
-  memcpy(sl.frame_host, bgr, fbytes);
+  sl.pend_yuv = yuv != nullptr;
+  size_t cbytes = fbytes;
+  unsigned char* cdst = sl.frame_dev;
+  if (yuv) {
+    cbytes = stage_yuv_planes(*yuv, sl, yuv_off, &sl.yuv_dev);
+    cdst = sl.frame_dev + yuv_off;
+  } else memcpy(sl.frame_host, bgr, fbytes);
   if (e->prep_defer) {   // copy now, kernels when the copy is done (flush_prep)
     if (!sl.ev_copy) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_copy, hipEventDisableTiming));
-    HIPCHK(e, hipMemcpyAsync(sl.frame_dev, sl.frame_host, fbytes, hipMemcpyHostToDevice, e->copy_stream));
+    HIPCHK(e, hipMemcpyAsync(cdst, sl.frame_host, cbytes, hipMemcpyHostToDevice, e->copy_stream));
     HIPCHK(e, hipEventRecord(sl.ev_copy, e->copy_stream));
     sl.copy_pending = true;
     sl.pend_w = w; sl.pend_h = h;
     return RTP_OK;
   }
-  float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
-  HIPCHK(e, hipMemcpyAsync(sl.frame_dev, sl.frame_host, fbytes, hipMemcpyHostToDevice, cx.in_stream));
-  if (w == e->cfg.disp_w && h == e->cfg.disp_h) sl.disp_cur = sl.frame_dev;   // identity warp (20 us per 720p frame saved)
-  else {
-    sl.disp_cur = sl.disp_dev;
-    HIPCHK(e, launch_warp(stamp_slot(e, cx, 200 + 2 * sj), sl.frame_dev, w, h, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, e->cfg.disp_w, e->cfg.disp_h, cx.in_stream));
-  }
-  HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, e->cfg.disp_w, e->cfg.disp_h, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
+  HIPCHK(e, hipMemcpyAsync(cdst, sl.frame_host, cbytes, hipMemcpyHostToDevice, cx.in_stream));
+  if ((rc = launch_prep_kernels(e, cx, sj, w, h, cx.in_stream))) return rc;
   cx.in_pending = true;
   return RTP_OK;
 }
@@ -1277,14 +1351,8 @@ int flush_prep(rtp_engine* e, Ctx& cx, bool force) {
     if (force) HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_copy, 0));
     else if (hipEventQuery(sl.ev_copy) != hipSuccess) continue;
     if (sl.pend_w == 0) { sl.copy_pending = false; continue; }   // rtp_submit: the copy WAS the staging (net input already pre-processed)
-    const double s = rtp_display_fit_scale(sl.pend_w, sl.pend_h, e->cfg.disp_w, e->cfg.disp_h);
-    float* dst = cx.input + sj * (size_t)e->N * 3 * e->cfg.net_h * e->cfg.net_w;
-    if (sl.pend_w == e->cfg.disp_w && sl.pend_h == e->cfg.disp_h) sl.disp_cur = sl.frame_dev;
-    else {
-      sl.disp_cur = sl.disp_dev;
-      HIPCHK(e, launch_warp(stamp_slot(e, cx, 200 + 2 * (int)sj), sl.frame_dev, sl.pend_w, sl.pend_h, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, e->cfg.disp_w, e->cfg.disp_h, cx.stream));
-    }
-    HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * (int)sj + 1), sl.disp_cur, e->cfg.disp_w, e->cfg.disp_h, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.stream));
+    int rc;
+    if ((rc = launch_prep_kernels(e, cx, (int)sj, sl.pend_w, sl.pend_h, cx.stream))) return rc;   // (sl.pend_yuv: the slot holds YUV planes)
     sl.copy_pending = false;
   }
   return RTP_OK;
@@ -1333,29 +1401,58 @@ int check_caller_stream(rtp_engine* e, void* stream, const char* fn) {
 
 // The memory behind the view: device memory of cfg.device_id, every addressed byte inside the allocation that holds data.  A failed
 // query is cleared from HIP's last error, so that the next launch of a valid call does not report it.
-int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long hi, int* layout) {
+// `what` names the pointer in the messages ("data", "y", "u", "v"); *avail = bytes from p to the end of its allocation.
+int check_device_range(rtp_engine* e, const char* fn, const char* what, const void* p, long hi, size_t* avail) {
   hipPointerAttribute_t at;
   memset(&at, 0, sizeof at);
-  hipError_t s = hipPointerGetAttributes(&at, fv.data);
+  hipError_t s = hipPointerGetAttributes(&at, p);
   if (s != hipSuccess || at.type == hipMemoryTypeUnregistered) {
     (void)hipGetLastError();
-    return fail(e, RTP_EINVAL, "%s: data %p is not memory of this library's HIP runtime: pageable host memory, or a pointer of a second HIP "
-                "runtime in the process (PyTorch bundles its own: import torch BEFORE the engine library so that one runtime serves both)", fn, (void*)fv.data);
+    return fail(e, RTP_EINVAL, "%s: %s %p is not memory of this library's HIP runtime: pageable host memory, or a pointer of a second HIP "
+                "runtime in the process (PyTorch bundles its own: import torch BEFORE the engine library so that one runtime serves both)", fn, what, p);
   }
   if (at.type != hipMemoryTypeDevice)
-    return fail(e, RTP_EINVAL, "%s: data %p is %s memory, not device memory", fn, (void*)fv.data, at.type == hipMemoryTypeHost ? "(pinned) host" : "managed");
-  if (at.device != e->cfg.device_id) return fail(e, RTP_EINVAL, "%s: data %p is memory of device %d, the engine runs on device %d", fn, (void*)fv.data, at.device, e->cfg.device_id);
+    return fail(e, RTP_EINVAL, "%s: %s %p is %s memory, not device memory", fn, what, p, at.type == hipMemoryTypeHost ? "(pinned) host" : "managed");
+  if (at.device != e->cfg.device_id) return fail(e, RTP_EINVAL, "%s: %s %p is memory of device %d, the engine runs on device %d", fn, what, p, at.device, e->cfg.device_id);
   hipDeviceptr_t base = nullptr;
   size_t size = 0;
-  s = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)fv.data);
+  s = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
   if (s != hipSuccess || !base) {
     (void)hipGetLastError();
-    return fail(e, RTP_EINVAL, "%s: hipMemGetAddressRange(%p) failed: %s", fn, (void*)fv.data, hipGetErrorString(s));
+    return fail(e, RTP_EINVAL, "%s: hipMemGetAddressRange(%p) failed: %s", fn, p, hipGetErrorString(s));
   }
-  const size_t avail = (size_t)((const char*)base + size - (const char*)fv.data);
-  if ((size_t)hi >= avail)
-    return fail(e, RTP_EINVAL, "%s: the view addresses bytes up to %ld past data, its allocation ends %zu bytes past data", fn, hi, avail);
+  *avail = (size_t)((const char*)base + size - (const char*)p);
+  if ((size_t)hi >= *avail)
+    return fail(e, RTP_EINVAL, "%s: the view addresses bytes up to %ld past %s, its allocation ends %zu bytes past %s", fn, hi, what, *avail, what);
+  return RTP_OK;
+}
+
+int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long hi, int* layout) {
+  size_t avail = 0;
+  const int rc = check_device_range(e, fn, "data", fv.data, hi, &avail);
+  if (rc) return rc;
   *layout = frame_layout(fv, avail);
+  return RTP_OK;
+}
+
+// rtp_yuv_view: the field checks of codecs.cpp (no HIP call: also for a NULL engine), then — check_yuv_memory — each plane on its own
+// (y, u and v may be three allocations): device memory of cfg.device_id, the last byte it addresses inside its allocation.
+extern "C" int rtp_internal_yuv_fields(const rtp_yuv_view* v, char* msg, size_t msg_len, long hi[3]);
+int check_yuv_fields(rtp_engine* e, const rtp_yuv_view* v, const char* fn, YuvView* yv, long hi[3]) {
+  char msg[256];
+  if (rtp_internal_yuv_fields(v, msg, sizeof msg, hi)) return fail(e, RTP_EINVAL, "%s: %s", fn, msg);
+  yv->y = (const unsigned char*)v->y; yv->u = (const unsigned char*)v->u; yv->v = (const unsigned char*)v->v;
+  yv->w = v->width; yv->h = v->height;
+  yv->sx = v->chroma_shift_x; yv->sy = v->chroma_shift_y;
+  yv->ys = v->y_stride; yv->uvs = v->uv_stride; yv->uvp = v->uv_pixel_stride;
+  return RTP_OK;
+}
+int check_yuv_memory(rtp_engine* e, const char* fn, const YuvView& yv, const long hi[3]) {
+  size_t avail;
+  int rc;
+  if ((rc = check_device_range(e, fn, "y", yv.y, hi[0], &avail))) return rc;
+  if (yv.u && (rc = check_device_range(e, fn, "u", yv.u, hi[1], &avail))) return rc;
+  if (yv.v && (rc = check_device_range(e, fn, "v", yv.v, hi[2], &avail))) return rc;
   return RTP_OK;
 }
 
@@ -1383,6 +1480,40 @@ int enqueue_preprocess_view(rtp_engine* e, Ctx& cx, int sj, const FrameView& v, 
     HIPCHK(e, hipEventRecord(sl.ev_read, cx.in_stream));
     HIPCHK(e, hipStreamWaitEvent(producer, sl.ev_read, 0));
   }
+  float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
+  HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, dw, dh, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
+  cx.in_pending = true;
+  return RTP_OK;
+}
+
+// A caller's YUV frame in device memory -> frame slot sj of cx.input: enqueue_preprocess_view with the conversion kernel as the reader
+// of the caller's memory.  At the display size it writes disp_dev; otherwise the BGR image goes to the slot's frame_dev and the cubic
+// warp reads that — the producer's stream is released after the conversion alone.
+int enqueue_preprocess_yuv_view(rtp_engine* e, Ctx& cx, int sj, const YuvView& v, hipStream_t producer, float* frame_scale) {
+  Slot& sl = cx.slot[sj];
+  const int dw = e->cfg.disp_w, dh = e->cfg.disp_h;
+  const bool same = v.w == dw && v.h == dh;
+  int rc;
+  if (!same && (rc = ensure_frame_cap(e, cx, sl, (size_t)v.w * v.h * 3))) return rc;
+  if (!sl.disp_dev) { SYNC_GUARD; HIPCHK(e, hipMalloc((void**)&sl.disp_dev, (size_t)dw * dh * 3)); }
+  if (!sl.ev_ready) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_ready, hipEventDisableTiming));
+  if (!sl.ev_read) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_read, hipEventDisableTiming));
+  const double s = rtp_display_fit_scale(v.w, v.h, dw, dh);
+  if (frame_scale) *frame_scale = (float)s;
+  sl.pend_yuv = false;
+  if (producer) {
+    HIPCHK(e, hipEventRecord(sl.ev_ready, producer));
+    HIPCHK(e, hipStreamWaitEvent(cx.in_stream, sl.ev_ready, 0));
+  }
+  unsigned long long* st = stamp_slot(e, cx, 200 + 2 * sj);
+  const FrameView bgr = packed_bgr_view(same ? sl.disp_dev : sl.frame_dev, v.w, v.h);
+  HIPCHK(e, launch_yuv_import(st, v, bgr, yuv_layout(v, bgr), cx.in_stream));
+  if (producer) {
+    HIPCHK(e, hipEventRecord(sl.ev_read, cx.in_stream));
+    HIPCHK(e, hipStreamWaitEvent(producer, sl.ev_read, 0));
+  }
+  if (!same) HIPCHK(e, launch_warp(st, sl.frame_dev, v.w, v.h, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, dw, dh, cx.in_stream));
+  sl.disp_cur = sl.disp_dev;
   float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
   HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, dw, dh, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
   cx.in_pending = true;
@@ -1911,6 +2042,92 @@ int rtp_submit_frame_device(rtp_engine* e, const rtp_frame_view* frame, void* st
   if ((rc = enqueue_preprocess_view(e, cx, sj, fv, layout, (hipStream_t)stream, frame_scale))) return rc;
   cx.slot[sj].has_disp = true;
   return commit_slot(e, ci, sj, tag);
+}
+
+// Which kernel rtp_convert_yuv_device would launch for (src, dst): a YuvLayout value, or RTP_EINVAL.  Host only (field checks and
+// yuv_layout, no HIP call, pointers are never dereferenced); not part of the public header — the tests use it to see that aligned
+// 4:2:0 frames really take the 4 x 2 kernel and everything else the generic one.
+extern "C" int rtp_internal_yuv_layout(const rtp_yuv_view* src, const rtp_frame_view* dst) {
+  static const char* fn = "rtp_internal_yuv_layout";
+  YuvView yv;
+  FrameView fv;
+  long hi[3], dhi = 0;
+  int rc;
+  if ((rc = check_yuv_fields(nullptr, src, fn, &yv, hi))) return rc;
+  if ((rc = check_view_fields(nullptr, dst, fn, &fv, &dhi))) return rc;
+  return yuv_layout(yv, fv);
+}
+
+// rtp_submit_frame on the pixels rtp_convert_yuv makes of a host YUV view: the planes cross PCIe, a kernel converts them.
+int rtp_submit_frame_yuv(rtp_engine* e, const rtp_yuv_view* frame, uint64_t tag, float* frame_scale) {
+  static const char* fn = "rtp_submit_frame_yuv";
+  YuvView yv;
+  long hi[3];
+  int rc, ci, sj;
+  if ((rc = check_yuv_fields(e, frame, fn, &yv, hi))) return rc;
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if (!e->gpu_prep_ok) {   // the host fallback of rtp_submit_frame, on the converted pixels
+    try {   // (nothing may unwind through the C boundary)
+      std::vector<unsigned char> bgr((size_t)yv.w * yv.h * 3);
+      if ((rc = rtp_convert_yuv(frame, bgr.data(), bgr.size()))) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
+      return rtp_submit_frame(e, bgr.data(), yv.w, yv.h, tag, frame_scale);
+    } catch (const std::exception& ex) {
+      return fail(e, RTP_ENOMEM, "%s: host conversion: %s", fn, ex.what());
+    }
+  }
+  if ((rc = use_device(e))) return rc;
+  if ((rc = need_weights(e))) return rc;
+  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
+  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  Ctx& cx = e->ctx[ci];
+  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
+  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier frame of this batch whose copy is done by now
+  cx.slot[sj].has_disp = true;
+  if ((rc = enqueue_preprocess(e, cx, sj, nullptr, yv.w, yv.h, frame_scale, &yv))) return rc;
+  return commit_slot(e, ci, sj, tag);
+}
+
+// rtp_submit_frame_device for a YUV frame in the caller's device memory
+int rtp_submit_frame_yuv_device(rtp_engine* e, const rtp_yuv_view* frame, void* stream, uint64_t tag, float* frame_scale) {
+  static const char* fn = "rtp_submit_frame_yuv_device";
+  YuvView yv;
+  long hi[3];
+  int rc, ci, sj;
+  if ((rc = check_yuv_fields(e, frame, fn, &yv, hi))) return rc;
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if ((rc = check_caller_stream(e, stream, fn))) return rc;
+  if ((rc = check_yuv_memory(e, fn, yv, hi))) return rc;
+  if ((rc = use_device(e))) return rc;
+  if ((rc = need_weights(e))) return rc;
+  if (!e->gpu_prep_ok) return fail(e, RTP_EINVAL, "device pre-processing unavailable for this configuration (a level would be enlarged)");
+  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
+  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  Ctx& cx = e->ctx[ci];
+  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
+  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier host frame of this batch whose copy is done by now
+  if ((rc = enqueue_preprocess_yuv_view(e, cx, sj, yv, (hipStream_t)stream, frame_scale))) return rc;
+  cx.slot[sj].has_disp = true;
+  return commit_slot(e, ci, sj, tag);
+}
+
+// The conversion kernel alone, on the caller's stream: no frame slot, no engine buffer.
+int rtp_convert_yuv_device(rtp_engine* e, const rtp_yuv_view* src, const rtp_frame_view* dst, void* stream) {
+  static const char* fn = "rtp_convert_yuv_device";
+  YuvView yv;
+  FrameView fv;
+  long hi[3], dhi = 0;
+  int rc, layout = LAYOUT_GENERIC;
+  if ((rc = check_yuv_fields(e, src, fn, &yv, hi))) return rc;
+  if ((rc = check_view_fields(e, dst, fn, &fv, &dhi))) return rc;
+  if (fv.w != yv.w || fv.h != yv.h) return fail(e, RTP_EINVAL, "%s: the destination is %d x %d, the frame %d x %d", fn, fv.w, fv.h, yv.w, yv.h);
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if ((rc = check_caller_stream(e, stream, fn))) return rc;
+  if ((rc = check_yuv_memory(e, fn, yv, hi))) return rc;
+  if ((rc = check_view_memory(e, fn, fv, dhi, &layout))) return rc;
+  if ((rc = use_device(e))) return rc;
+  HIPCHK(e, launch_yuv_import(nullptr, yv, fv, yuv_layout(yv, fv), (hipStream_t)stream));
+  if (!stream) HIPCHK(e, hipStreamSynchronize(nullptr));
+  return RTP_OK;
 }
 
 // Launch a partially filled batch now (end of stream, or a latency-sensitive caller).

@@ -215,6 +215,26 @@ hipError_t launch_frame_export(unsigned long long* stamp, const unsigned char* s
 hipError_t launch_warp_view(unsigned long long* stamp, const FrameView& v, double inv, const short* tab2d, unsigned char* dst, int dw, int dh,
                             hipStream_t stream);
 
+// A caller's (or the staged) 8-bit YUV frame in device memory (rtp_yuv_view, checked on the host before any launch): luma of pixel
+// (x, y) is y[y * ys + x], its chroma samples u / v[(y >> sy) * uvs + (x >> sx) * uvp].  u == v == nullptr: luma only.
+struct YuvView {
+  const unsigned char* y;
+  const unsigned char* u;
+  const unsigned char* v;
+  int w, h, sx, sy;
+  long ys, uvs, uvp;
+};
+// How the conversion kernels (yuv_import.hip) address a frame.  The 4:2:0 layouts give each thread a 4 x 2 luma block: two dword Y
+// loads, the block's two U and two V samples as one 16-bit load per plane (PLANAR) or one dword (NV12: u, v, u, v; NV21: v, u, v, u),
+// two rows of three dword stores.  yuv_layout picks them only for 4:2:0 with w % 4 == 0, h % 2 == 0, a packed-BGR destination
+// (pix 3, offsets 0 1 2) and every dword / 16-bit access aligned: y, ys, dst.data and dst.row to 4 bytes, the chroma pointers and uvs
+// to 2 bytes (PLANAR) or to 4 (interleaved, v == u + 1 or u == v + 1).  GENERIC: one thread per pixel, byte loads and stores.
+enum YuvLayout { YUV_GENERIC = 0, YUV_420_PLANAR, YUV_420_NV12, YUV_420_NV21 };
+int yuv_layout(const YuvView& s, const FrameView& d);
+inline FrameView packed_bgr_view(unsigned char* p, int w, int h) { return FrameView{p, w, h, 3L * w, 3, {0, 1, 2}}; }
+// YUV (BT.601 limited range, the integer arithmetic of codecs.cpp rtp_convert_yuv) -> the three named channels of the view (s.w x s.h)
+hipError_t launch_yuv_import(unsigned long long* stamp, const YuvView& s, const FrameView& d, int layout, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------
 // JPEG encoder (rtp_encode_jpeg_device, rtp_set_render_jpeg): jpeg_enc.hip, the bytes of codecs.cpp's rtp_encode_jpeg
 // ---------------------------------------------------------------------------------------

@@ -37,6 +37,8 @@ extern "C" {
 int rtp_set_render_jpeg(rtp_engine* e, int quality) __attribute__((weak));
 int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* jpeg_host, size_t capacity,
                               size_t* jpeg_bytes) __attribute__((weak));
+// (the stand-ins have no YUV entry either: without it every frame takes the BGR path, as with --host_yuv)
+int rtp_submit_frame_yuv(rtp_engine* e, const rtp_yuv_view* frame_host, uint64_t tag, float* frame_scale) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -52,6 +54,7 @@ double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::
 struct Flags {
   bool host_preprocess = false;
   bool host_jpeg = false;        // --write_frames: encode on the host (rtp_encode_jpeg on an encoder pool) instead of on the GPU
+  bool host_yuv = false;         // --video x.y4m: convert every frame to BGR on the producer thread (rtp_video_read) instead of on the GPU
   bool fullscreen = false, no_frame_drops = false, no_display = false, no_text = false, logtostderr = false;
   int part_to_show = 0, camera = 0, start_frame = 0, start_device = 0, num_gpu = 1, num_scales = 1;
   std::string write_frames, write_json, video, image_dir;
@@ -87,7 +90,7 @@ int parse_flags(int argc, char** argv, Flags& F) {
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
       {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}};
   std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"no_display", &F.no_display},
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_yuv", &F.host_yuv}, {"no_display", &F.no_display},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -134,7 +137,9 @@ void usage() {
          "   --share_weights (workers 1.. copy worker 0's packed weights GPU to GPU) --nopin_workers (no CPU affinity next to each worker's GPU)]\n"
          "  --write_frames draws the pose overlay only: the FPS / people-count text of the reference (cv::putText, rtpose.cpp:1319-1333) is not\n"
          "  drawn, i.e. --no_text is implied.  Its JPEG files (quality 98) are encoded on the GPU and only the files cross PCIe;\n"
-         "  --host_jpeg copies the raw frames to the host and encodes them there on 8 threads instead (the same bytes).\n");
+         "  --host_jpeg copies the raw frames to the host and encodes them there on 8 threads instead (the same bytes).\n"
+         "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
+         "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n");
 }
 
 // ---- queues (caffe::BlockingQueue, util/blocking_queue.cpp:26-61) -----------------------------
@@ -158,7 +163,10 @@ template <typename T> class BlockingQueue {
 // include/caffe/cpm/frame.h:6-34
 struct Frame {
   std::vector<float> data;         // net input (only with --host_preprocess)
-  std::vector<unsigned char> image;  // decoded u8 BGR frame (default: pre-processing runs on the GPU)
+  std::vector<unsigned char> image;  // decoded u8 BGR frame (default: pre-processing runs on the GPU), or — yuv — the planes of a Y4M frame
+  bool yuv = false;                // image = Y (img_w x img_h), then U and V ((img_w + sx) >> sx by (img_h + sy) >> sy each; none for mono)
+  int chroma_sx = 0, chroma_sy = 0;
+  bool mono = false;
   std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
   bool rendered_jpeg = false;
   int img_w = 0, img_h = 0;
@@ -215,6 +223,9 @@ void producer() {
     std::vector<unsigned char> skip((size_t)sw * sh * 3);
     for (int i = 0; i < F.start_frame; ++i) if (rtp_video_read(vid, skip.data(), skip.size()) != RTP_OK) break;  // CAP_PROP_POS_FRAMES, :411
   } else nframes = (int)G.image_list.size();
+  // Y4M: the planes go to the engine as they are in the file, unless the frames do not reach rtp_submit_frame at all (--host_preprocess,
+  // --dry_engine), --host_yuv asks for the host conversion, or this binary was linked without the entry
+  const bool yuv_planes = vid && rtp_video_chroma(vid) != 0 && !F.host_yuv && !F.host_preprocess && !(F.dry_engine > 0) && rtp_submit_frame_yuv != nullptr;
   std::vector<unsigned char> img;
   // --image_dir files and synthetic frames are produced a few ahead by a small pool (a 720p JPEG takes ~13 ms on one core, a
   // synthetic frame ~1 ms; 8 GPUs at 1 scale want ~8000 frames/s); the producer still hands the frames over in index order,
@@ -265,8 +276,22 @@ void producer() {
     Frame fr;
     int w = sw, h = sh;
     if (vid) {
-      img.resize((size_t)w * h * 3);
-      const int rc = rtp_video_read(vid, img.data(), img.size());
+      int rc;
+      if (yuv_planes) {   // the view points into the reader's buffer (valid until the next read): Y, U, V back to back
+        rtp_yuv_view yv;
+        rc = rtp_video_read_yuv(vid, &yv);
+        if (rc == RTP_OK) {
+          const size_t cw = (size_t)(w + yv.chroma_shift_x) >> yv.chroma_shift_x, ch = (size_t)(h + yv.chroma_shift_y) >> yv.chroma_shift_y;
+          fr.yuv = true;
+          fr.mono = yv.u == nullptr;
+          fr.chroma_sx = yv.chroma_shift_x; fr.chroma_sy = yv.chroma_shift_y;
+          const unsigned char* p = (const unsigned char*)yv.y;
+          img.assign(p, p + (size_t)w * h + (fr.mono ? 0 : 2 * cw * ch));
+        }
+      } else {
+        img.resize((size_t)w * h * 3);
+        rc = rtp_video_read(vid, img.data(), img.size());
+      }
       if (rc == RTP_EAGAIN) break;  // end of the stream
       if (rc != RTP_OK) { fprintf(stderr, "video frame %d: %s\n", fi, rtp_codec_last_error()); break; }
       char nm[64]; snprintf(nm, sizeof nm, "frame%06d", fi); fr.stem = nm;
@@ -498,8 +523,26 @@ void worker(int widx, int device, int* status) {
         continue;
       }
       if (dry && !F.host_preprocess) fr.scale = (float)rtp_display_fit_scale(fr.img_w, fr.img_h, DISP_W, DISP_H);
+      rtp_yuv_view yv;
+      if (fr.yuv) {   // the producer's copy of the file's planes
+        const size_t cw = (size_t)(fr.img_w + fr.chroma_sx) >> fr.chroma_sx, ch = (size_t)(fr.img_h + fr.chroma_sy) >> fr.chroma_sy;
+        memset(&yv, 0, sizeof yv);
+        yv.struct_size = sizeof yv;
+        yv.matrix = RTP_YUV_BT601_LIMITED;
+        yv.width = fr.img_w; yv.height = fr.img_h;
+        yv.y = fr.image.data();
+        yv.y_stride = fr.img_w;
+        yv.uv_pixel_stride = 1;
+        if (!fr.mono) {
+          yv.u = fr.image.data() + (size_t)fr.img_w * fr.img_h;
+          yv.v = fr.image.data() + (size_t)fr.img_w * fr.img_h + cw * ch;
+          yv.uv_stride = (long)cw;
+          yv.chroma_shift_x = fr.chroma_sx; yv.chroma_shift_y = fr.chroma_sy;
+        }
+      }
       const int src = dry ? dry_submit(fr)
                           : F.host_preprocess ? rtp_submit(e, fr.data.data(), (uint64_t)fr.index)
+                          : fr.yuv            ? rtp_submit_frame_yuv(e, &yv, (uint64_t)fr.index, &fr.scale)
                                               : rtp_submit_frame(e, fr.image.data(), fr.img_w, fr.img_h, (uint64_t)fr.index, &fr.scale);
       fr.image.clear();
       fr.image.shrink_to_fit();

@@ -4,7 +4,7 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -237,6 +237,12 @@ class Video:
             raise RtpError(rc, lib.rtp_codec_last_error().decode())
         return out
 
+    def chroma(self):
+        return video_chroma(self)
+
+    def read_yuv(self):
+        return video_read_yuv(self)
+
     def close(self):
         if self.h:
             lib.rtp_video_close(self.h)
@@ -301,6 +307,124 @@ def _view_struct(f):
     for c in range(3):
         v.channel_offset[c] = f["channel_offset"][c]
     return v
+
+
+def _plane(obj, name, ndim):
+    """(pointer, shape, strides, on the device?) of one u8 plane: a host numpy array or a __cuda_array_interface__ object."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is not None:
+        typestr, shape, strides, ptr = cai["typestr"], cai["shape"], cai.get("strides"), int(cai["data"][0])
+    elif isinstance(obj, np.ndarray):
+        typestr, shape, strides, ptr = obj.dtype.str, obj.shape, obj.strides, obj.ctypes.data
+    else:
+        raise TypeError(f"{name}: {type(obj).__name__} is neither a numpy array nor a __cuda_array_interface__ object")
+    if typestr[1:] != "u1":
+        raise ValueError(f"{name}: dtype {typestr}: planes are u8")
+    shape = tuple(int(d) for d in shape)
+    if len(shape) != ndim or min(shape) < 1:
+        raise ValueError(f"{name}: shape {shape}: " + ("(H, W)" if ndim == 2 else "(H/2, W/2, 2)"))
+    if strides is None:   # C-contiguous
+        strides = tuple(int(np.prod(shape[i + 1:])) for i in range(ndim))
+    return ptr, shape, tuple(int(s) for s in strides), cai is not None
+
+
+def yuv_view(y, u, v=None, *, interleaved_order="uv"):
+    """The rtp_yuv_view fields of an 8-bit YUV frame: host numpy arrays or __cuda_array_interface__ objects (nothing touches the GPU).
+
+    (y, u, v): planar; y is (H, W), u and v have one shape, from which the sampling is inferred — ((H+1)//2, (W+1)//2) 4:2:0,
+    (H, (W+1)//2) 4:2:2, (H, W) 4:4:4.  (y, uv) with uv of shape (ch, cw, 2): interleaved pairs, NV12 (interleaved_order "uv") or
+    NV21 ("vu").  (y, None): luma only.  Any row pitch (a crop keeps its parent's); luma columns must be contiguous.
+    Returns a dict: y, u, v (addresses or None), width, height, chroma_shift_x, chroma_shift_y, y_stride, uv_stride, uv_pixel_stride,
+    device (whether the planes are device memory)."""
+    if interleaved_order not in ("uv", "vu"):
+        raise ValueError(f"interleaved_order {interleaved_order!r}: 'uv' (NV12) or 'vu' (NV21)")
+    yp, (h, w), (yrs, yps), dev = _plane(y, "y", 2)
+    if yps != 1 and w > 1:
+        raise ValueError(f"y: column stride {yps}: luma columns must be contiguous (shape (H, W))")
+    f = dict(y=yp, u=None, v=None, width=w, height=h, chroma_shift_x=0, chroma_shift_y=0, y_stride=yrs, uv_stride=0, uv_pixel_stride=1,
+             device=dev)
+    if u is None:
+        if v is not None:
+            raise ValueError("v without u: pass (y, u, v), (y, uv) or (y, None)")
+        return f
+    if v is None:   # interleaved
+        up, ushape, (urs, ups, ucs), udev = _plane(u, "uv", 3)
+        if ushape[2] != 2 or (ucs, ups) != (1, 2):
+            raise ValueError(f"uv: shape {ushape}, strides {(urs, ups, ucs)}: interleaved chroma is (ch, cw, 2) with pairs of neighbouring bytes")
+        (ch, cw), ps, planes = ushape[:2], 2, ((up, up + 1) if interleaved_order == "uv" else (up + 1, up))
+        devs = (udev,)
+    else:
+        up, ushape, (urs, ups), udev = _plane(u, "u", 2)
+        vp_, vshape, (vrs, vps), vdev = _plane(v, "v", 2)
+        if ushape != vshape:
+            raise ValueError(f"u and v: shapes {ushape} and {vshape} differ")
+        if ushape[0] > 1 and urs != vrs or ushape[1] > 1 and ups != vps:
+            raise ValueError(f"u and v: strides {(urs, ups)} and {(vrs, vps)} differ (rtp_yuv_view has one chroma pitch)")
+        if ushape[1] == 1:
+            ups = 1
+        if ups not in (1, 2):
+            raise ValueError(f"u, v: column stride {ups}: 1 (planar) or 2")
+        (ch, cw), ps, planes = ushape, ups, (up, vp_)
+        devs = (udev, vdev)
+    if any(d != dev for d in devs):
+        raise ValueError("planes in host and in device memory mixed in one frame")
+    for sx, sy in ((1, 1), (1, 0), (0, 0)):
+        if cw == (w + sx) >> sx and ch == (h + sy) >> sy:
+            break
+    else:
+        raise ValueError(f"chroma shape {(ch, cw)} for a {h} x {w} luma plane matches no supported sampling (4:2:0, 4:2:2, 4:4:4)")
+    f.update(u=planes[0], v=planes[1], chroma_shift_x=sx, chroma_shift_y=sy, uv_stride=urs, uv_pixel_stride=ps)
+    return f
+
+
+def _yuv_struct(f):
+    s = rtp_yuv_view()
+    s.struct_size = C.sizeof(rtp_yuv_view)
+    s.matrix = 0   # RTP_YUV_BT601_LIMITED
+    s.y, s.u, s.v = f["y"], f["u"], f["v"]
+    s.width, s.height = f["width"], f["height"]
+    s.chroma_shift_x, s.chroma_shift_y = f["chroma_shift_x"], f["chroma_shift_y"]
+    s.y_stride, s.uv_stride, s.uv_pixel_stride = f["y_stride"], f["uv_stride"], f["uv_pixel_stride"]
+    return s
+
+
+def convert_yuv(y, u, v=None, *, interleaved_order="uv"):
+    """rtp_convert_yuv: host planes (see yuv_view) -> BGR HWC u8, BT.601 limited range — the pixels every YUV entry works on."""
+    f = yuv_view(y, u, v, interleaved_order=interleaved_order)
+    if f["device"]:
+        raise TypeError("convert_yuv takes host arrays (device planes: Engine.convert_yuv_device)")
+    out = np.empty((f["height"], f["width"], 3), np.uint8)
+    s = _yuv_struct(f)
+    rc = lib.rtp_convert_yuv(C.byref(s), _u8(out), out.size)
+    if rc:
+        raise RtpError(rc, lib.rtp_codec_last_error().decode())
+    return out
+
+
+def video_chroma(video):
+    """rtp_video_chroma: 420, 422, 444 or 400 for a Y4M Video, 0 for anything else."""
+    return int(lib.rtp_video_chroma(video.h))
+
+
+def video_read_yuv(video):
+    """rtp_video_read_yuv: the next Y4M frame as (y, u, v) numpy planes (u = v = None for a luma-only stream), copied out of the
+    reader's buffer; None at the end of the stream."""
+    s = rtp_yuv_view()
+    rc = lib.rtp_video_read_yuv(video.h, C.byref(s))
+    if rc == RTP_EAGAIN:
+        return None
+    if rc:
+        raise RtpError(rc, lib.rtp_codec_last_error().decode())
+
+    def plane(ptr, rows, cols, pitch):
+        a = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_ubyte)), shape=(rows * pitch,))
+        return a.reshape(rows, pitch)[:, :cols].copy()
+
+    y = plane(s.y, s.height, s.width, s.y_stride)
+    if not s.u:
+        return y, None, None
+    cw, ch = (s.width + s.chroma_shift_x) >> s.chroma_shift_x, (s.height + s.chroma_shift_y) >> s.chroma_shift_y
+    return y, plane(s.u, ch, cw, s.uv_stride), plane(s.v, ch, cw, s.uv_stride)
 
 
 def _stream_of(obj, stream):
@@ -373,6 +497,42 @@ class Engine:
         fs = C.c_float()
         self._chk(lib.rtp_submit_frame_device(self.h, C.byref(v), st, tag, C.byref(fs)))
         return fs.value
+
+    def submit_frame_yuv(self, y, u, v=None, tag=0, *, interleaved_order="uv"):
+        """rtp_submit_frame_yuv: submit_frame of convert_yuv's pixels from HOST planes (see yuv_view); the planes cross PCIe and are
+        converted on the GPU.  Returns Frame::scale."""
+        f = yuv_view(y, u, v, interleaved_order=interleaved_order)
+        if f["device"]:
+            raise TypeError("submit_frame_yuv takes host arrays (device planes go to submit_frame_yuv_device)")
+        s = _yuv_struct(f)
+        fs = C.c_float()
+        self._chk(lib.rtp_submit_frame_yuv(self.h, C.byref(s), tag, C.byref(fs)))
+        return fs.value
+
+    def submit_frame_yuv_device(self, y, u, v=None, tag=0, stream=None, *, interleaved_order="uv"):
+        """rtp_submit_frame_yuv_device: a YUV frame in device memory (see yuv_view), read on the GPU in order with `stream` (as
+        submit_frame_device).  Returns Frame::scale."""
+        f = yuv_view(y, u, v, interleaved_order=interleaved_order)
+        if not f["device"]:
+            raise TypeError("submit_frame_yuv_device takes device planes (__cuda_array_interface__); host arrays go to submit_frame_yuv")
+        s = _yuv_struct(f)
+        st, legacy = _stream_of(y, stream)
+        if legacy:
+            sys.modules["torch"].cuda.current_stream(y.device).synchronize()
+        fs = C.c_float()
+        self._chk(lib.rtp_submit_frame_yuv_device(self.h, C.byref(s), st, tag, C.byref(fs)))
+        return fs.value
+
+    def convert_yuv_device(self, y, u, v, out, stream=None, order="bgr", *, interleaved_order="uv"):
+        """rtp_convert_yuv_device: device planes (see yuv_view; v = None: interleaved or luma only) -> the u8 device frame `out`
+        (see frame_view) of the same size, on the GPU in order with `stream`."""
+        f = yuv_view(y, u, v, interleaved_order=interleaved_order)
+        if not f["device"]:
+            raise TypeError("convert_yuv_device takes device planes (host arrays: convert_yuv)")
+        s = _yuv_struct(f)
+        d = _view_struct(frame_view(out, order))
+        st, _ = _stream_of(out, stream)
+        self._chk(lib.rtp_convert_yuv_device(self.h, C.byref(s), C.byref(d), st))
 
     def debug_preprocess(self, img_u8):
         img = np.ascontiguousarray(img_u8, np.uint8)

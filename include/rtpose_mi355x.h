@@ -311,6 +311,28 @@ const char* rtp_codec_last_error(void);
  * baseline 4:2:0 encoder restated, byte-identical files.  Returns the size in bytes (out may be NULL
  * to query it) or a negative RTP_E* code. */
 long rtp_encode_jpeg(const unsigned char* bgr, int w, int h, int quality, unsigned char* out, size_t capacity);
+/* An 8-bit YUV frame (no reference counterpart: cv::VideoCapture hands the producer BGR): luma of pixel (x, y) is the byte
+ * y[y*y_stride + x], its chroma samples u / v[(y >> chroma_shift_y)*uv_stride + (x >> chroma_shift_x)*uv_pixel_stride].  A chroma
+ * plane has (width + sx) >> sx by (height + sy) >> sy samples, so odd sizes are in contract.  I420: three planes, shifts 1 1,
+ * uv_pixel_stride 1 (YV12: u and v exchanged); NV12: v = u + 1, uv_pixel_stride 2 (NV21: u = v + 1); 4:2:2: shifts 1 0; 4:4:4: 0 0.
+ * The pointers are host memory for rtp_convert_yuv / rtp_submit_frame_yuv and device memory for the _device entries. */
+#define RTP_YUV_BT601_LIMITED 0 /* ITU-R BT.601, Y 16..235, C 16..240, in the integer arithmetic of rtp_convert_yuv */
+typedef struct rtp_yuv_view {
+  unsigned int struct_size;     /* sizeof(rtp_yuv_view); any other value -> RTP_EINVAL */
+  int matrix;                   /* RTP_YUV_BT601_LIMITED; anything else -> RTP_EINVAL */
+  void* y; void* u; void* v;    /* u == v == NULL: luma only (Y4M "mono"); exactly one NULL -> RTP_EINVAL */
+  int width, height;            /* luma size, >= 1 */
+  int chroma_shift_x, chroma_shift_y;  /* 0 or 1 each: 4:2:0 = 1,1; 4:2:2 = 1,0; 4:4:4 = 0,0; (0,1) is refused */
+  long y_stride;                /* bytes between luma rows, >= 0 */
+  long uv_stride;               /* bytes between chroma rows (same for u and v), >= 0 */
+  long uv_pixel_stride;         /* 1 = planar (I420/YV12), 2 = interleaved (NV12: v = u + 1, NV21: u = v + 1) */
+} rtp_yuv_view;
+/* The view as packed u8 BGR HWC (width x height x 3 bytes; capacity in bytes), BT.601 limited range, integers only:
+ *   c = 298 (Y - 16), d = U - 128, e = V - 128 (d = e = 0 without chroma)
+ *   R = clamp255((c + 409 e + 128) >> 8), G = clamp255((c - 100 d - 208 e + 128) >> 8), B = clamp255((c + 516 d + 128) >> 8)
+ * (arithmetic shift).  This is what rtp_video_read makes of a Y4M frame, and what the GPU entries below compute bit for bit.
+ * RTP_EINVAL + rtp_codec_last_error for a view that fails the field checks or a capacity below the image. */
+int rtp_convert_yuv(const rtp_yuv_view* host, unsigned char* bgr_out, size_t capacity);
 /* cv::VideoCapture(path) (rtpose.cpp:402-411, 431) for the container-less formats decodable here:
  * Y4M (YUV4MPEG2, 8 bit) and raw MJPEG streams.  nframes may be NULL; rtp_video_read returns
  * RTP_EAGAIN at the end of the stream. */
@@ -318,6 +340,12 @@ typedef struct rtp_video rtp_video;
 int rtp_video_open(const char* path, rtp_video** v, int* w, int* h, int* nframes);
 int rtp_video_read(rtp_video* v, unsigned char* out_bgr, size_t capacity);
 void rtp_video_close(rtp_video* v);
+/* 420, 422, 444 or 400 (luma only) for a Y4M stream, 0 for anything else (MJPEG, NULL). */
+int rtp_video_chroma(const rtp_video* v);
+/* rtp_video_read without the colour conversion: the next Y4M frame as a view into the reader's own buffer (planar, pitches =
+ * plane widths), valid until the next read or close.  rtp_convert_yuv of it = what rtp_video_read would have returned.
+ * RTP_EAGAIN at the end of the stream; RTP_EINVAL for an MJPEG stream (nothing is consumed). */
+int rtp_video_read_yuv(rtp_video* v, rtp_yuv_view* out);
 int rtp_synth_frame(unsigned char* out_bgr, int w, int h, int index, uint64_t seed);
 
 /* Parse a deploy prototxt and report the graph it describes (for tests / tools). */
@@ -453,6 +481,26 @@ int rtp_set_render_jpeg(rtp_engine* e, int quality);
  * oldest frame without a display image. */
 int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* jpeg_host,
                               size_t capacity, size_t* jpeg_bytes);
+
+/* ---- YUV frames, converted on the GPU (the planes a video decoder or a Y4M file delivers; see rtp_yuv_view) ---------- */
+
+/* = rtp_submit_frame on the pixels rtp_convert_yuv makes of the HOST view: same joints, frame_scale and rendered frames.  The planes
+ * are staged without their pitches (1.5 bytes per pixel cross PCIe for 4:2:0 instead of 3) and converted by a kernel in front of
+ * the warp.  Where the device pre-processing cannot run (see rtp_debug_preprocess) the frame is converted on the host. */
+int rtp_submit_frame_yuv(rtp_engine* e, const rtp_yuv_view* frame_host, uint64_t tag, float* frame_scale);
+
+/* = rtp_submit_frame_device for a YUV frame in device memory (a hardware decoder's NV12 surface): the contract and the `stream`
+ * ordering of that entry; the caller's planes are released after the conversion kernel alone.  Checked on the host before any
+ * launch (RTP_EINVAL + rtp_last_error, the engine stays usable): the fields as documented at rtp_yuv_view (also for a NULL
+ * engine), extents without overflow, and for EACH of y, u, v on its own (they may be three allocations) device memory of
+ * cfg.device_id whose last addressed byte lies inside its allocation; a stream that is not capturing. */
+int rtp_submit_frame_yuv_device(rtp_engine* e, const rtp_yuv_view* frame_dev, void* stream, uint64_t tag, float* frame_scale);
+
+/* The conversion alone: src_dev -> the three named channels of dst_dev (same width and height; a 4th channel is left untouched),
+ * both in device memory and checked as above.  Runs after the work queued on `stream`; work queued on `stream` afterwards sees the
+ * image (NULL: the null stream, and the image is complete when the call returns).  Uses no frame slot: frames in flight are not
+ * disturbed. */
+int rtp_convert_yuv_device(rtp_engine* e, const rtp_yuv_view* src_dev, const rtp_frame_view* dst_dev, void* stream);
 
 #ifdef __cplusplus
 }
