@@ -165,6 +165,9 @@ SIGNATURES = {
     "rtp_submit_frame_yuv": (C.c_int, [vp, C.POINTER(rtp_yuv_view), C.c_uint64, fp]),
     "rtp_submit_frame_yuv_device": (C.c_int, [vp, C.POINTER(rtp_yuv_view), vp, C.c_uint64, fp]),
     "rtp_convert_yuv_device": (C.c_int, [vp, C.POINTER(rtp_yuv_view), C.POINTER(rtp_frame_view), vp]),
+    "rtp_video_read_jpeg": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(C.c_size_t)]),
+    "rtp_decode_jpeg_device": (C.c_int, [vp, C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(rtp_frame_view), vp, ip]),
+    "rtp_submit_frame_jpeg": (C.c_int, [vp, C.POINTER(C.c_ubyte), C.c_size_t, C.c_uint64, fp, ip, ip]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -31,6 +31,7 @@
 
 #include "../../include/rtpose_mi355x.h"
 #include "jpeg_bound.h"
+#include "jpeg_plan.h"
 
 namespace {
 
@@ -269,8 +270,10 @@ int upsample(const JComp& c, int hmax, int vmax, int W, int H, std::vector<unsig
   return RTP_OK;
 }
 
-int decode_jpeg(const unsigned char* d, size_t n, unsigned char* out, size_t cap, int* ow_, int* oh_) {
-  if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return cfail(RTP_EIO, "JPEG: no SOI");
+// Everything the markers and scans of a file say: "headers and scans -> coefficients" (jpeg_coefficients) fills it, jpeg_reconstruct
+// turns it into pixels.  The GPU decoder (jpeg_plan) takes the same parse and either the coefficients or, for a single-scan
+// sequential file, the scan itself.
+struct JpegFile {
   uint16_t qt[4][64];
   bool qset[4] = {false, false, false, false};
   Huff hdc[4], hac[4];
@@ -279,6 +282,29 @@ int decode_jpeg(const unsigned char* d, size_t n, unsigned char* out, size_t cap
   int adobe_transform = -1;
   bool have_sof = false, progressive = false, geometry_done = false;
   int hmax = 1, vmax = 1, mcux = 0, mcuy = 0, scans_done = 0;
+};
+
+// A request to leave the entropy decoding of the (one) scan to the device: set by jpeg_coefficients when the file qualifies
+struct ScanRequest {
+  int sub_bits = 0;
+  uint32_t* stage = nullptr;
+  size_t stage_words = 0;
+  bool taken = false;      // out: the scan was staged instead of decoded
+  rtp::JpegPlan* plan = nullptr;
+};
+bool plan_scan(const unsigned char* d, size_t n, size_t pos, JpegFile& J, JComp* const* sc, int ns, ScanRequest* rq);
+
+// size_only: return at the frame header with W and H.  rq: see ScanRequest.
+int jpeg_coefficients(const unsigned char* d, size_t n, JpegFile* J, bool size_only, ScanRequest* rq) {
+  if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return cfail(RTP_EIO, "JPEG: no SOI");
+  auto& qt = J->qt;
+  auto& qset = J->qset;
+  auto& hdc = J->hdc;
+  auto& hac = J->hac;
+  std::vector<JComp>& comps = J->comps;
+  int &W = J->W, &H = J->H, &restart = J->restart, &adobe_transform = J->adobe_transform;
+  bool &have_sof = J->have_sof, &progressive = J->progressive, &geometry_done = J->geometry_done;
+  int &hmax = J->hmax, &vmax = J->vmax, &mcux = J->mcux, &mcuy = J->mcuy, &scans_done = J->scans_done;
   size_t pos = 2;
   auto u16 = [&](size_t o) { return (d[o] << 8) | d[o + 1]; };
   while (pos + 4 <= n) {
@@ -337,7 +363,7 @@ int decode_jpeg(const unsigned char* d, size_t n, unsigned char* out, size_t cap
         if (comps[i].h < 1 || comps[i].h > 4 || comps[i].v < 1 || comps[i].v > 4 || comps[i].tq > 3) return cfail(RTP_EIO, "JPEG: bad SOF");
       }
       have_sof = true;
-      if (!out) { *ow_ = W; *oh_ = H; return RTP_OK; }  // size query: the frame header is enough
+      if (size_only) return RTP_OK;  // size query: the frame header is enough
     } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
       return cfail(RTP_EINVAL, "JPEG: this coding process is not supported (Huffman sequential and progressive only)");
     } else if (m == 0xDD) {
@@ -379,6 +405,7 @@ int decode_jpeg(const unsigned char* d, size_t n, unsigned char* out, size_t cap
         }
         geometry_done = true;
       }
+      if (rq && scans_done == 0 && plan_scan(d, n, pos, *J, sc, ns, rq)) { rq->taken = true; return RTP_OK; }
       for (int i = 0; i < ns; ++i) sc[i]->pred = 0;
       BitReader br;
       br.p = d + pos; br.end = d + n;
@@ -517,70 +544,198 @@ int decode_jpeg(const unsigned char* d, size_t n, unsigned char* out, size_t cap
     pos += len;
   }
   if (!scans_done) return cfail(RTP_EIO, "JPEG: no scan found");
-  {
-    {
-      // ---- coefficients -> samples: dequantise + IDCT of every block ----
-      for (auto& c : comps) {
-        if (!qset[c.tq]) return cfail(RTP_EIO, "JPEG: missing quantisation table");
-        c.plane.assign((size_t)c.bw * 8 * c.bh * 8, 0);
-        int coef[64];
-        for (int by = 0; by < c.bh; ++by)
-          for (int bx = 0; bx < c.bw; ++bx) {
-            const short* blk = c.coef.data() + ((size_t)by * c.bw + bx) * 64;
-            for (int k = 0; k < 64; ++k) coef[kZigzag[k]] = blk[kZigzag[k]] * qt[c.tq][k];
-            idct_islow(coef, c.plane.data() + ((size_t)by * 8) * (c.bw * 8) + (size_t)bx * 8, c.bw * 8);
-          }
+  return RTP_OK;
+}
+
+// coefficients -> pixels (BGR HWC).  out may be NULL: everything but the up-sampling and colour stage runs (the size query of a
+// file whose SOF came after its scans never got here before either).
+int jpeg_reconstruct(JpegFile* J, unsigned char* out, size_t cap, int* ow_, int* oh_) {
+  auto& qt = J->qt;
+  auto& qset = J->qset;
+  std::vector<JComp>& comps = J->comps;
+  const int W = J->W, H = J->H, adobe_transform = J->adobe_transform, hmax = J->hmax, vmax = J->vmax;
+  // ---- coefficients -> samples: dequantise + IDCT of every block ----
+  for (auto& c : comps) {
+    if (!qset[c.tq]) return cfail(RTP_EIO, "JPEG: missing quantisation table");
+    c.plane.assign((size_t)c.bw * 8 * c.bh * 8, 0);
+    int coef[64];
+    for (int by = 0; by < c.bh; ++by)
+      for (int bx = 0; bx < c.bw; ++bx) {
+        const short* blk = c.coef.data() + ((size_t)by * c.bw + bx) * 64;
+        for (int k = 0; k < 64; ++k) coef[kZigzag[k]] = blk[kZigzag[k]] * qt[c.tq][k];
+        idct_islow(coef, c.plane.data() + ((size_t)by * 8) * (c.bw * 8) + (size_t)bx * 8, c.bw * 8);
       }
-      // ---- up-sample + colour ----
-      *ow_ = W; *oh_ = H;
-      if (!out) return RTP_OK;
-      if (cap < (size_t)W * H * 3) return cfail(RTP_EINVAL, "output buffer too small");
-      if (comps.size() == 1) {
-        const int stride = comps[0].bw * 8;
-        for (int y = 0; y < H; ++y)
-          for (int x = 0; x < W; ++x) {
-            const unsigned char v = comps[0].plane[(size_t)y * stride + x];
-            unsigned char* o = out + ((size_t)y * W + x) * 3;
-            o[0] = o[1] = o[2] = v;
-          }
-        return RTP_OK;
-      }
-      std::vector<unsigned char> f[3];
-      for (int i = 0; i < 3; ++i) {
-        const int rc = upsample(comps[i], hmax, vmax, W, H, &f[i]);
-        if (rc) return rc;
-      }
-      const bool rgb = adobe_transform == 0 || (adobe_transform < 0 && comps[0].id == 'R' && comps[1].id == 'G' && comps[2].id == 'B');
-      if (rgb) {
-        for (size_t i = 0; i < (size_t)W * H; ++i) { out[i * 3] = f[2][i]; out[i * 3 + 1] = f[1][i]; out[i * 3 + 2] = f[0][i]; }
-        return RTP_OK;
-      }
-      // jdcolor.c build_ycc_rgb_table / ycc_rgb_convert
-      struct YccTab {  // built once, thread-safely (C++11 static initialisation): decoders run on several threads
-        int cr_r[256], cb_b[256];
-        long cr_g[256], cb_g[256];
-        YccTab() {
-          for (int i = 0; i < 256; ++i) {
-            const long x = i - 128;
-            cr_r[i] = (int)((91881L * x + 32768L) >> 16);
-            cb_b[i] = (int)((116130L * x + 32768L) >> 16);
-            cr_g[i] = -46802L * x;
-            cb_g[i] = -22554L * x + 32768L;
-          }
-        }
-      };
-      static const YccTab T;
-      const int* cr_r = T.cr_r; const int* cb_b = T.cb_b;
-      const long* cr_g = T.cr_g; const long* cb_g = T.cb_g;
-      for (size_t i = 0; i < (size_t)W * H; ++i) {
-        const int y = f[0][i], cb = f[1][i], cr = f[2][i];
-        out[i * 3 + 2] = clamp255(y + cr_r[cr]);
-        out[i * 3 + 1] = clamp255(y + (int)((cb_g[cb] + cr_g[cr]) >> 16));
-        out[i * 3] = clamp255(y + cb_b[cb]);
-      }
-      return RTP_OK;
-    }
   }
+  // ---- up-sample + colour ----
+  *ow_ = W; *oh_ = H;
+  if (!out) return RTP_OK;
+  if (cap < (size_t)W * H * 3) return cfail(RTP_EINVAL, "output buffer too small");
+  if (comps.size() == 1) {
+    const int stride = comps[0].bw * 8;
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const unsigned char v = comps[0].plane[(size_t)y * stride + x];
+        unsigned char* o = out + ((size_t)y * W + x) * 3;
+        o[0] = o[1] = o[2] = v;
+      }
+    return RTP_OK;
+  }
+  std::vector<unsigned char> f[3];
+  for (int i = 0; i < 3; ++i) {
+    const int rc = upsample(comps[i], hmax, vmax, W, H, &f[i]);
+    if (rc) return rc;
+  }
+  const bool rgb = adobe_transform == 0 || (adobe_transform < 0 && comps[0].id == 'R' && comps[1].id == 'G' && comps[2].id == 'B');
+  if (rgb) {
+    for (size_t i = 0; i < (size_t)W * H; ++i) { out[i * 3] = f[2][i]; out[i * 3 + 1] = f[1][i]; out[i * 3 + 2] = f[0][i]; }
+    return RTP_OK;
+  }
+  // jdcolor.c build_ycc_rgb_table / ycc_rgb_convert
+  struct YccTab {  // built once, thread-safely (C++11 static initialisation): decoders run on several threads
+    int cr_r[256], cb_b[256];
+    long cr_g[256], cb_g[256];
+    YccTab() {
+      for (int i = 0; i < 256; ++i) {
+        const long x = i - 128;
+        cr_r[i] = (int)((91881L * x + 32768L) >> 16);
+        cb_b[i] = (int)((116130L * x + 32768L) >> 16);
+        cr_g[i] = -46802L * x;
+        cb_g[i] = -22554L * x + 32768L;
+      }
+    }
+  };
+  static const YccTab T;
+  const int* cr_r = T.cr_r; const int* cb_b = T.cb_b;
+  const long* cr_g = T.cr_g; const long* cb_g = T.cb_g;
+  for (size_t i = 0; i < (size_t)W * H; ++i) {
+    const int y = f[0][i], cb = f[1][i], cr = f[2][i];
+    out[i * 3 + 2] = clamp255(y + cr_r[cr]);
+    out[i * 3 + 1] = clamp255(y + (int)((cb_g[cb] + cr_g[cr]) >> 16));
+    out[i * 3] = clamp255(y + cb_b[cb]);
+  }
+  return RTP_OK;
+}
+
+// ---- the GPU decoder's planner -----------------------------------------------------------------------------------------------
+void fill_geom(const JpegFile& J, rtp::JpegGeom* g) {
+  g->W = J.W; g->H = J.H; g->ncomp = (int)J.comps.size();
+  g->hmax = J.hmax; g->vmax = J.vmax; g->mcux = J.mcux; g->mcuy = J.mcuy;
+  for (int c = 0; c < g->ncomp; ++c) {
+    const JComp& jc = J.comps[c];
+    g->h[c] = jc.h; g->v[c] = jc.v; g->bw[c] = jc.bw; g->bh[c] = jc.bh; g->dw[c] = jc.dw; g->dh[c] = jc.dh;
+    for (int k = 0; k < 64; ++k) g->qn[c][kZigzag[k]] = J.qt[jc.tq][k];
+  }
+  g->rgb = g->ncomp == 3 && (J.adobe_transform == 0 ||
+                             (J.adobe_transform < 0 && J.comps[0].id == 'R' && J.comps[1].id == 'G' && J.comps[2].id == 'B'));
+}
+
+void copy_huff(const Huff& h, JdHuff* o) {
+  memcpy(o->fast, h.fast, sizeof o->fast);
+  memcpy(o->maxcode, h.maxcode, sizeof o->maxcode);
+  o->mincode[0] = o->valptr[0] = 0; o->maxcode[0] = -1;
+  for (int l = 1; l <= 16; ++l) { o->mincode[l] = h.mincode[l]; o->valptr[l] = h.valptr[l]; }
+  memcpy(o->vals, h.vals, sizeof o->vals);
+}
+
+// The one scan of a sequential file, at d[pos...]: staged for the device when the file is regular.  false = decode it on the host
+// (which accepts or rejects the file as it always did).  Regular: every component in the scan, at most 10 blocks per MCU, integral
+// sampling ratios, all quantisers present, the RSTn markers in order and as many as the MCU count asks for, nothing but EOI (or
+// the end of the data) behind the scan, and the scan fits the staging buffer.
+bool plan_scan(const unsigned char* d, size_t n, size_t pos, JpegFile& J, JComp* const* sc, int ns, ScanRequest* rq) {
+  if (J.progressive || ns != (int)J.comps.size() || !rq->stage || rq->sub_bits < 32 || rq->sub_bits % 32) return false;
+  for (int i = 0; i < ns; ++i)
+    for (int j = 0; j < i; ++j) if (sc[i] == sc[j]) return false;
+  int nblk = 0;
+  for (int i = 0; i < ns; ++i) {
+    nblk += sc[i]->h * sc[i]->v;
+    if (!J.qset[sc[i]->tq] || J.hmax % sc[i]->h || J.vmax % sc[i]->v) return false;
+  }
+  if (nblk > JD_MAX_MCU_BLOCKS) return false;
+  const long mcus = (long)J.mcux * J.mcuy;
+  const long nseg = J.restart ? (mcus + J.restart - 1) / J.restart : 1;
+  if (mcus * nblk >= (1L << 28) || nseg >= (1L << 24)) return false;
+  rtp::JpegPlan& P = *rq->plan;
+  unsigned char* sb = (unsigned char*)rq->stage;
+  const size_t cap = rq->stage_words * 4;
+  if (cap >= (1u << 27)) return false;   // bit positions are ints
+  P.segs.clear(); P.subs.clear();
+  size_t o = 0, seg_o = 0, p = pos;
+  long seg = 0;
+  const auto close_segment = [&]() -> bool {
+    size_t padded = (o + 3) / 4 * 4;
+    if (padded == seg_o) padded += 4;   // an empty segment still owns a word: its blocks are decoded from zero bits
+    if (padded > cap) return false;
+    JdSeg s;
+    s.first_sub = (int)P.subs.size();
+    s.blk0 = (int)(seg * J.restart * nblk);
+    s.nblocks = (int)((J.restart ? std::min<long>(J.restart, mcus - seg * J.restart) : mcus) * nblk);
+    s.start = (int)(seg_o * 8);
+    s.limit = (int)(o * 8);
+    const int pend = (int)(padded * 8);
+    for (int b = s.start; b < pend; b += rq->sub_bits) {
+      JdSub u;
+      u.start = b; u.end = std::min(b + rq->sub_bits, pend); u.seg = (int)seg;
+      u.flags = (b == s.start ? JD_SUB_ANCHORED : 0) | (u.end == pend ? JD_SUB_LAST : 0);
+      P.subs.push_back(u);
+    }
+    P.segs.push_back(s);
+    memset(sb + o, 0, padded - o);
+    o = seg_o = padded;
+    return true;
+  };
+  for (;;) {
+    if (p >= n) break;
+    const int b = d[p];
+    if (b != 0xFF) {
+      if (o >= cap) return false;
+      sb[o++] = (unsigned char)b; ++p;
+      continue;
+    }
+    if (p + 1 >= n) break;   // a lone 0xFF ends the data (the reader feeds zeros from here)
+    const int b1 = d[p + 1];
+    if (b1 == 0x00) {
+      if (o >= cap) return false;
+      sb[o++] = 0xFF; p += 2;
+      continue;
+    }
+    if (b1 >= 0xD0 && b1 <= 0xD7) {
+      if (!J.restart || (b1 & 7) != (int)(seg & 7) || seg + 1 >= nseg) return false;
+      if (!close_segment()) return false;
+      ++seg; p += 2;
+      continue;
+    }
+    if (b1 == 0xFF) return false;   // fill bytes inside a scan
+    break;                          // another marker: the scan is over
+  }
+  if (seg != nseg - 1 || !close_segment()) return false;
+  if (!(p + 1 >= n || d[p + 1] == 0xD9)) return false;   // more segments behind the scan (tables, a second scan, ...)
+  for (size_t i = 0; i < o / 4; ++i) rq->stage[i] = __builtin_bswap32(rq->stage[i]);
+  P.nwords = o / 4;
+  JdScan& S = P.scan;
+  memset(&S, 0, sizeof S);
+  S.nblk = nblk; S.ncomp = ns; S.mcux = J.mcux; S.restart_blocks = J.restart * nblk;
+  int b = 0, off = 0;
+  for (int c = 0; c < ns; ++c) {
+    const JComp& jc = J.comps[c];
+    S.h[c] = jc.h; S.v[c] = jc.v; S.bw[c] = jc.bw; S.coef_off[c] = off;
+    off += jc.bw * jc.bh;
+    copy_huff(J.hdc[jc.td], &P.dc[c]);
+    copy_huff(J.hac[jc.ta], &P.ac[c]);
+  }
+  for (int i = 0; i < ns; ++i) {
+    const int c = (int)(sc[i] - J.comps.data());
+    for (int by = 0; by < sc[i]->v; ++by)
+      for (int bx = 0; bx < sc[i]->h; ++bx, ++b) { S.comp[b] = c; S.bx[b] = bx; S.by[b] = by; }
+  }
+  return true;
+}
+
+int decode_jpeg(const unsigned char* d, size_t n, unsigned char* out, size_t cap, int* ow_, int* oh_) {
+  JpegFile J;
+  const int rc = jpeg_coefficients(d, n, &J, out == nullptr, nullptr);
+  if (rc) return rc;
+  if (!out && J.have_sof && !J.scans_done) { *ow_ = J.W; *oh_ = J.H; return RTP_OK; }
+  return jpeg_reconstruct(&J, out, cap, ow_, oh_);
 }
 
 // =================================================================================================
@@ -1179,6 +1334,29 @@ int rtp_video_read_yuv(rtp_video* v, rtp_yuv_view* out) {
     return cfail(RTP_ENOMEM, std::string("video read: ") + ex.what());
   }
 }
+// The next frame of a raw MJPEG stream behind v->pos: bytes [*p, *q) = SOI .. EOI (v->pos is not moved); false at the end of the stream.
+// The one definition of a frame's byte range: rtp_video_read decodes it, rtp_video_read_jpeg returns it.
+static bool mjpeg_next_range(const rtp_video* v, size_t* p_, size_t* q_) {
+  const std::vector<unsigned char>& d = v->data;
+  size_t p = v->pos;
+  while (p + 1 < d.size() && !(d[p] == 0xFF && d[p + 1] == 0xD8)) ++p;
+  if (p + 1 >= d.size()) return false;
+  size_t q = p + 2;
+  while (q + 1 < d.size() && !(d[q] == 0xFF && d[q + 1] == 0xD9)) ++q;
+  if (q + 1 >= d.size()) return false;
+  *p_ = p; *q_ = q + 2;
+  return true;
+}
+int rtp_video_read_jpeg(rtp_video* v, const unsigned char** bytes, size_t* n) {
+  if (!v || !bytes || !n) return RTP_EINVAL;
+  if (v->kind != 2) return cfail(RTP_EINVAL, "rtp_video_read_jpeg: not an MJPEG stream (Y4M frames are planes: rtp_video_read_yuv)");
+  size_t p, q;
+  if (!mjpeg_next_range(v, &p, &q)) return RTP_EAGAIN;
+  v->pos = q;
+  *bytes = v->data.data() + p;
+  *n = q - p;
+  return RTP_OK;
+}
 int rtp_video_open(const char* path, rtp_video** out, int* w, int* h, int* nframes) {
   try {
     return video_open_impl(path, out, w, h, nframes);
@@ -1296,13 +1474,8 @@ static int video_read_impl(rtp_video* v, unsigned char* out_bgr, size_t capacity
   }
   // MJPEG: next SOI..EOI
   const std::vector<unsigned char>& d = v->data;
-  size_t p = v->pos;
-  while (p + 1 < d.size() && !(d[p] == 0xFF && d[p + 1] == 0xD8)) ++p;
-  if (p + 1 >= d.size()) return RTP_EAGAIN;
-  size_t q = p + 2;
-  while (q + 1 < d.size() && !(d[q] == 0xFF && d[q + 1] == 0xD9)) ++q;
-  if (q + 1 >= d.size()) return RTP_EAGAIN;
-  q += 2;
+  size_t p, q;
+  if (!mjpeg_next_range(v, &p, &q)) return RTP_EAGAIN;
   int w = 0, h = 0;
   const int rc = rtp_decode_image(d.data() + p, q - p, nullptr, 0, &w, &h);
   if (rc) return rc;
@@ -1312,5 +1485,207 @@ static int video_read_impl(rtp_video* v, unsigned char* out_bgr, size_t capacity
 }
 
 void rtp_video_close(rtp_video* v) { delete v; }
+
+}  // extern "C"
+
+// =================================================================================================
+// GPU JPEG decoder: planner, host counterparts and the serial emulation of the device's entropy decoder (jpeg_dec.h, jpeg_dec.hip)
+// =================================================================================================
+namespace rtp {
+
+const char* jpeg_entropy_message(int jd_err) {
+  return jd_err == JD_ERR_DC ? "JPEG: corrupt DC code" : (jd_err == JD_ERR_AC ? "JPEG: corrupt AC code" : "JPEG: corrupt AC run");
+}
+
+int jpeg_plan(const unsigned char* bytes, size_t n, int sub_bits, uint32_t* stage, size_t stage_words, bool force_host, JpegPlan* out) {
+  if (!(n >= 3 && bytes[0] == 0xFF && bytes[1] == 0xD8)) return cfail(RTP_EIO, "not a PNG or JPEG byte string");
+  JpegFile J;
+  ScanRequest rq;
+  rq.sub_bits = sub_bits; rq.stage = stage; rq.stage_words = stage_words; rq.plan = out;
+  int rc = jpeg_coefficients(bytes, n, &J, false, force_host ? nullptr : &rq);
+  if (rc) return rc;
+  out->path = rq.taken ? RTP_JPEG_ENTROPY_DEVICE : RTP_JPEG_ENTROPY_HOST;
+  for (auto& c : J.comps) {
+    if (!J.qset[c.tq]) return cfail(RTP_EIO, "JPEG: missing quantisation table");
+  }
+  if (J.comps.size() == 3)
+    for (auto& c : J.comps)
+      if (J.hmax % c.h || J.vmax % c.v) return cfail(RTP_EINVAL, "JPEG: fractional sampling ratios are not supported");
+  fill_geom(J, &out->g);
+  out->coef.clear();
+  if (!rq.taken) {
+    out->coef.reserve((size_t)out->g.blocks() * 64);
+    for (auto& c : J.comps) out->coef.insert(out->coef.end(), c.coef.begin(), c.coef.end());
+  }
+  return RTP_OK;
+}
+
+int jpeg_reconstruct_host(const JpegGeom& g, const short* coef, unsigned char* out_bgr, size_t capacity) {
+  JpegFile J;
+  J.W = g.W; J.H = g.H; J.hmax = g.hmax; J.vmax = g.vmax; J.mcux = g.mcux; J.mcuy = g.mcuy;
+  J.adobe_transform = g.rgb ? 0 : 1;
+  J.comps.resize(g.ncomp);
+  size_t off = 0;
+  for (int c = 0; c < g.ncomp; ++c) {
+    JComp& jc = J.comps[c];
+    jc.id = c + 1; jc.h = g.h[c]; jc.v = g.v[c]; jc.tq = c; jc.bw = g.bw[c]; jc.bh = g.bh[c]; jc.dw = g.dw[c]; jc.dh = g.dh[c];
+    const size_t nc = (size_t)jc.bw * jc.bh * 64;
+    jc.coef.assign(coef + off, coef + off + nc);
+    off += nc;
+    for (int k = 0; k < 64; ++k) J.qt[c][k] = g.qn[c][kZigzag[k]];
+    J.qset[c] = true;
+  }
+  int w = 0, h = 0;
+  return jpeg_reconstruct(&J, out_bgr, capacity, &w, &h);
+}
+
+// The device's algorithm, serially: speculative decode of every subsequence, rounds of exit_i = f_i(exit_{i-1}) in groups of
+// `group` subsequences (inner rounds inside a group, outer rounds = launches carry states between groups), the block counts, the
+// final pass, the DC scan.  rounds[0] = launches that changed something + the one that found nothing to do, rounds[1] = the largest
+// number of inner rounds a group needed.  Returns JD_OK or (block << 2 | JD_ERR_*) of the first failure in scan order.
+unsigned jpeg_entropy_emulate(const JpegPlan& P, const uint32_t* words, int group, short* coef, int rounds[2]) {
+  const int ns = (int)P.subs.size();
+  const JdBits br = {words, (int)P.nwords};
+  std::vector<JdState> entry(ns), exit_(ns);
+  std::vector<int> count(ns);
+  const auto guess = [&](int i) { return JdState{P.subs[i].start, 0, 0}; };
+  const auto run = [&](int i) { exit_[i] = jd_run_sub(br, P.subs[i], P.segs[P.subs[i].seg].limit, P.dc, P.ac, P.scan, entry[i], &count[i]); };
+  const int ngroups = (ns + group - 1) / group;
+  std::vector<JdState> gexit[2] = {std::vector<JdState>(ngroups), std::vector<JdState>(ngroups)};
+  rounds[0] = rounds[1] = 0;
+  for (int launch = 0; launch < ngroups; ++launch) {   // what the device enqueues
+    bool any = false;
+    for (int gi = 0; gi < ngroups; ++gi) {
+      const int i0 = gi * group, i1 = std::min(ns, i0 + group);
+      if (launch == 0) for (int i = i0; i < i1; ++i) { entry[i] = guess(i); run(i); }
+      for (int it = 0; it < group; ++it) {
+        std::vector<JdState> snap(exit_.begin() + i0, exit_.begin() + i1);   // every thread reads its neighbour's state of the round before
+        bool changed = false;
+        for (int i = i0; i < i1; ++i) {
+          JdState want;
+          if (P.subs[i].flags & JD_SUB_ANCHORED) want = guess(i);
+          else if (i > i0) want = snap[i - 1 - i0];
+          else if (launch == 0) want = entry[i];
+          else want = gexit[(launch - 1) & 1][gi - 1];
+          if (!jd_same(want, entry[i])) { entry[i] = want; run(i); changed = true; }
+        }
+        if (!changed) break;
+        any = true;
+        rounds[1] = std::max(rounds[1], it + 1);
+      }
+      gexit[launch & 1][gi] = exit_[i1 - 1];
+    }
+    rounds[0] = launch + 1;
+    if (launch > 0 && !any) break;
+  }
+  // block counts -> the blocks in front of every subsequence inside its segment
+  unsigned status = 0xffffffffu;
+  std::vector<long> excl(ns + 1, 0);
+  for (int i = 0; i < ns; ++i) excl[i + 1] = excl[i] + count[i];
+  for (int i = 0; i < ns; ++i) {
+    const JdSeg& sg = P.segs[P.subs[i].seg];
+    const int base = (int)(excl[i] - excl[sg.first_sub]);
+    jd_write_sub(br, P.subs[i], sg, P.dc, P.ac, P.scan, entry[i], base, coef, [&](unsigned v) { status = std::min(status, v); });
+  }
+  // DC differences -> DC values, component by component in scan order, reset at segment starts
+  for (int c = 0; c < P.scan.ncomp; ++c) {
+    int per_mcu = P.scan.h[c] * P.scan.v[c];
+    const long per_seg = P.scan.restart_blocks ? (long)(P.scan.restart_blocks / P.scan.nblk) * per_mcu : 0;
+    const long total = (long)P.g.mcux * P.g.mcuy * per_mcu;
+    int32_t pred = 0;
+    for (long j = 0; j < total; ++j) {
+      if (per_seg && j % per_seg == 0) pred = 0;
+      const long mcu = j / per_mcu, b = j % per_mcu;
+      const long my = mcu / P.g.mcux, mx = mcu % P.g.mcux;
+      const long blk = P.scan.coef_off[c] + (my * P.scan.v[c] + b / P.scan.h[c]) * P.scan.bw[c] + mx * P.scan.h[c] + b % P.scan.h[c];
+      pred += coef[blk * 64];
+      coef[blk * 64] = (short)pred;
+    }
+  }
+  return status == 0xffffffffu ? 0u : status;
+}
+
+}  // namespace rtp
+
+extern "C" {
+
+// Internal (not in the public header; tests and tools reach them through ctypes) ---------------------------------------------------
+// info[0..7]: path, W, H, components, restart segments, subsequences, staged words, blocks.  force_host = 1: the host's entropy decoder.
+// coef (may be NULL): blocks() * 64 shorts, component after component.  Same return code and message as rtp_decode_image.
+int rtp_internal_jpeg_coefficients(const unsigned char* bytes, size_t n, int force_host, short* coef, size_t coef_cap, int* info) {
+  if (!bytes || !info) return RTP_EINVAL;
+  try {
+    rtp::JpegPlan P;
+    std::vector<uint32_t> stage(n / 4 + 16);
+    const int rc = rtp::jpeg_plan(bytes, n, 1024, stage.data(), stage.size(), force_host != 0, &P);
+    if (rc) return rc;
+    info[0] = P.path; info[1] = P.g.W; info[2] = P.g.H; info[3] = P.g.ncomp; info[4] = (int)P.segs.size(); info[5] = (int)P.subs.size();
+    info[6] = (int)P.nwords; info[7] = (int)P.g.blocks();
+    if (coef && P.path == RTP_JPEG_ENTROPY_HOST) {
+      if (coef_cap < P.coef.size()) return cfail(RTP_EINVAL, "coefficient buffer too small");
+      memcpy(coef, P.coef.data(), P.coef.size() * sizeof(short));
+    }
+    return RTP_OK;
+  } catch (const std::exception& ex) {
+    return cfail(RTP_ENOMEM, std::string("jpeg plan: ") + ex.what());
+  }
+}
+
+// The serial emulation of the device's entropy decoder on the file's scan: S = sub_bits, `group` subsequences per workgroup.
+// info as above (a HOST-path file returns its coefficients from the host decoder and rounds 0), rounds[2] see jpeg_entropy_emulate.
+int rtp_internal_jpeg_entropy_emulate(const unsigned char* bytes, size_t n, int sub_bits, int group, short* coef, size_t coef_cap, int* info,
+                                      int* rounds) {
+  if (!bytes || !info || !rounds || !coef || group < 1 || sub_bits < 32 || sub_bits % 32) return RTP_EINVAL;
+  try {
+    rtp::JpegPlan P;
+    std::vector<uint32_t> stage(n / 4 + 16);
+    const int rc = rtp::jpeg_plan(bytes, n, sub_bits, stage.data(), stage.size(), false, &P);
+    if (rc) return rc;
+    info[0] = P.path; info[1] = P.g.W; info[2] = P.g.H; info[3] = P.g.ncomp; info[4] = (int)P.segs.size(); info[5] = (int)P.subs.size();
+    info[6] = (int)P.nwords; info[7] = (int)P.g.blocks();
+    rounds[0] = rounds[1] = 0;
+    const size_t nc = (size_t)P.g.blocks() * 64;
+    if (coef_cap < nc) return cfail(RTP_EINVAL, "coefficient buffer too small");
+    if (P.path == RTP_JPEG_ENTROPY_HOST) { memcpy(coef, P.coef.data(), nc * sizeof(short)); return RTP_OK; }
+    memset(coef, 0, nc * sizeof(short));
+    const unsigned st = rtp::jpeg_entropy_emulate(P, stage.data(), group, coef, rounds);
+    if (st) return cfail(RTP_EIO, rtp::jpeg_entropy_message((int)(st & 3u)));
+    return RTP_OK;
+  } catch (const std::exception& ex) {
+    return cfail(RTP_ENOMEM, std::string("jpeg emulate: ") + ex.what());
+  }
+}
+
+// Host counterpart of rtp_internal_jpeg_reconstruct_device: a W x H image of `ncomp` components with sampling factors hv[2 c], hv[2 c + 1],
+// natural-order 16-bit quantisers qn[c][64], coefficients component after component -> BGR HWC
+int rtp_internal_jpeg_geom(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, rtp::JpegGeom* g) {
+  if (W < 1 || H < 1 || (ncomp != 1 && ncomp != 3) || !hv || !qn) return cfail(RTP_EINVAL, "jpeg geometry: bad arguments");
+  g->W = W; g->H = H; g->ncomp = ncomp; g->rgb = ncomp == 3 && rgb;
+  g->hmax = g->vmax = 1;
+  for (int c = 0; c < ncomp; ++c) {
+    g->h[c] = ncomp == 1 ? 1 : hv[2 * c]; g->v[c] = ncomp == 1 ? 1 : hv[2 * c + 1];
+    if (g->h[c] < 1 || g->h[c] > 4 || g->v[c] < 1 || g->v[c] > 4) return cfail(RTP_EINVAL, "jpeg geometry: bad sampling factors");
+    g->hmax = std::max(g->hmax, g->h[c]); g->vmax = std::max(g->vmax, g->v[c]);
+  }
+  g->mcux = (W + 8 * g->hmax - 1) / (8 * g->hmax); g->mcuy = (H + 8 * g->vmax - 1) / (8 * g->vmax);
+  for (int c = 0; c < ncomp; ++c) {
+    if (g->hmax % g->h[c] || g->vmax % g->v[c]) return cfail(RTP_EINVAL, "JPEG: fractional sampling ratios are not supported");
+    g->bw[c] = g->mcux * g->h[c]; g->bh[c] = g->mcuy * g->v[c];
+    g->dw[c] = (W * g->h[c] + g->hmax - 1) / g->hmax; g->dh[c] = (H * g->v[c] + g->vmax - 1) / g->vmax;
+    memcpy(g->qn[c], qn + 64 * c, 64 * sizeof(unsigned short));
+  }
+  return RTP_OK;
+}
+int rtp_internal_jpeg_reconstruct_host(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, const short* coef,
+                                       unsigned char* out_bgr, size_t capacity) {
+  if (!coef || !out_bgr) return RTP_EINVAL;
+  try {
+    rtp::JpegGeom g;
+    const int rc = rtp_internal_jpeg_geom(W, H, ncomp, hv, qn, rgb, &g);
+    return rc ? rc : rtp::jpeg_reconstruct_host(g, coef, out_bgr, capacity);
+  } catch (const std::exception& ex) {
+    return cfail(RTP_ENOMEM, std::string("jpeg reconstruct: ") + ex.what());
+  }
+}
 
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/rtpose_mi355x.h"
+#include "jpeg_plan.h"
 #include "kernels.h"
 #include "netdef.h"
 #include "plan.h"
@@ -60,6 +61,32 @@ thread_local std::string g_create_error = "";
 std::recursive_mutex g_sync_mutex;
 #define SYNC_GUARD std::lock_guard<std::recursive_mutex> sync_guard_(g_sync_mutex)
 
+// The GPU JPEG decoder's buffers (jpeg_dec.hip): one device allocation carved by JdLayout, the pinned staging of what the host sends
+// (the de-stuffed scan with its tables, or the host decoder's coefficients), and a pinned status word the last entropy kernel writes
+struct JdBufs {
+  unsigned char* dev = nullptr;
+  size_t dev_cap = 0;
+  unsigned char* host = nullptr;
+  size_t host_cap = 0;
+  unsigned* status_host = nullptr;
+  unsigned* status_host_dev = nullptr;
+};
+// One planned decode: what to copy, what to launch
+struct JdJob {
+  int path = RTP_JPEG_ENTROPY_HOST;
+  JdLayout L;
+  JdDev d = {};
+  JdRecon g = {};
+  int group = 0, mcus = 0;
+  size_t copy_bytes = 0, copy_dst = 0;   // pinned [0, copy_bytes) -> dev + copy_dst
+  short* coef = nullptr;
+  unsigned char* planes = nullptr;
+};
+constexpr int kJdSubBits = 512;      // S: bits per subsequence (profiles/r09_jpeg_decode.txt)
+constexpr int kJdGroup = 256;        // subsequences per workgroup
+constexpr int kJdMaxGroups = 512;    // most synchronisation launches one decode may enqueue (16 MB of scan at the defaults)
+constexpr size_t kJdStageCap = (size_t)64 << 20;   // staged scans above this take the host entropy path
+
 // One frame's post-processing state (a batch context carries batch_frames of them)
 struct Slot {
   hipStream_t stream = nullptr;  // resize -> nms -> connect -> D2H of this frame (slot 0 shares the context's stream)
@@ -87,6 +114,11 @@ struct Slot {
   int pend_w = 0, pend_h = 0;
   bool pend_yuv = false;                // the staged frame is YUV (rtp_submit_frame_yuv): yuv_dev describes its planes behind the BGR image in frame_dev,
   YuvView yuv_dev = {};                 // and the conversion kernel runs in front of the warp
+  // rtp_submit_frame_jpeg: the staged frame is a JPEG file's scan (or its coefficients) in jd's pinned buffer; the decode kernels run in
+  // front of the warp and write the BGR image to frame_dev.  jpeg_status: the collect of this frame reads jd's status word.
+  bool pend_jpeg = false, jpeg_status = false;
+  JdBufs jd;
+  JdJob jd_job;
   unsigned char* frame_dev = nullptr;   // raw u8 frame (device) for rtp_submit_frame
   unsigned char* frame_host = nullptr;  // pinned staging of the raw frame
   size_t frame_cap = 0;
@@ -188,6 +220,11 @@ struct rtp_engine {
   unsigned char* jenc_host_dev = nullptr;
   size_t jenc_cap = 0;
   hipEvent_t jenc_ev = nullptr;
+  // rtp_decode_jpeg_device: the engine's own decoder buffers; jd_sub_bits / jd_group = S and subsequences per workgroup of every decode
+  // (rtp_internal_jpeg_knobs; tests and the sweep of tools/bench_jpeg_decode.py change them)
+  JdBufs jdec;
+  hipEvent_t jdec_ev = nullptr;
+  int jd_sub_bits = kJdSubBits, jd_group = kJdGroup;
   hipEvent_t busy_base = nullptr;
   std::vector<float> busy_spans;          // [n][3]: kind (0 conv stream, 1 post chain), start ms, end ms
   // rtp_stamp_probe: device-side residency stamps of every kernel of the per-frame path (no profiler, no events)
@@ -750,6 +787,8 @@ int run_post_fused(rtp_engine* e, Ctx& cx, int sj, hipEvent_t ev_nms) {
 }
 
 int jpeg_alloc(rtp_engine* e, int w, int h, JpegBufs* b, unsigned char** host, unsigned char** host_dev, size_t* cap);
+void jd_free(JdBufs* b);
+int jd_launch(rtp_engine* e, unsigned long long* stamp, const JdJob& job, const FrameView& dst, hipStream_t stream);
 
 // one batch on one context: conv stack over nframes*num_scales images, then per frame (on the
 // frame slot's stream) resize -> nms -> connect -> D2H of the joints
@@ -1148,6 +1187,7 @@ void free_ctx(Ctx& cx) {
     if (sl.frame_host) (void)hipHostFree(sl.frame_host);
     if (sl.render_host) (void)hipHostFree(sl.render_host);
     jpeg_free(&sl.jpeg, &sl.jpeg_host, &sl.jpeg_cap);
+    jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
     for (int i = 0; i < 5; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
     if (sl.ev_copy) (void)hipEventDestroy(sl.ev_copy);
@@ -1301,6 +1341,10 @@ int launch_prep_kernels(rtp_engine* e, Ctx& cx, int sj, int w, int h, hipStream_
     const FrameView bgr = packed_bgr_view(sl.frame_dev, w, h);
     HIPCHK(e, launch_yuv_import(stamp_slot(e, cx, 200 + 2 * sj), sl.yuv_dev, bgr, yuv_layout(sl.yuv_dev, bgr), stream));
   }
+  if (sl.pend_jpeg) {
+    int rc;
+    if ((rc = jd_launch(e, stamp_slot(e, cx, 232 + sj), sl.jd_job, packed_bgr_view(sl.frame_dev, w, h), stream))) return rc;
+  }
   if (w == e->cfg.disp_w && h == e->cfg.disp_h) sl.disp_cur = sl.frame_dev;   // identity warp (20 us per 720p frame saved)
   else {
     sl.disp_cur = sl.disp_dev;
@@ -1311,34 +1355,171 @@ int launch_prep_kernels(rtp_engine* e, Ctx& cx, int sj, int w, int h, hipStream_
 }
 
 // raw u8 BGR frame (host), or — yuv != null — the planes of a host YUV frame -> frame slot sj of cx.input on the device
-int enqueue_preprocess(rtp_engine* e, Ctx& cx, int sj, const unsigned char* bgr, int w, int h, float* frame_scale, const YuvView* yuv = nullptr) {
+// jpeg: the frame is the file planned into sl.jd_job (staged in sl.jd's pinned buffer); frame_dev receives the decoded image
+int enqueue_preprocess(rtp_engine* e, Ctx& cx, int sj, const unsigned char* bgr, int w, int h, float* frame_scale, const YuvView* yuv = nullptr,
+                       bool jpeg = false) {
   Slot& sl = cx.slot[sj];
   const size_t fbytes = (size_t)w * h * 3;
   size_t yuv_off = 0;
   const size_t need = yuv ? staged_yuv_bytes(w, h, yuv->sx, yuv->sy, &yuv_off) : fbytes;
   int rc;
   if ((rc = ensure_frame_cap(e, cx, sl, need))) return rc;
+  sl.pend_jpeg = jpeg;
+  sl.jpeg_status = false;
   if (!sl.disp_dev) { SYNC_GUARD; HIPCHK(e, hipMalloc((void**)&sl.disp_dev, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3)); }
   const double s = rtp_display_fit_scale(w, h, e->cfg.disp_w, e->cfg.disp_h);
   if (frame_scale) *frame_scale = (float)s;
   sl.pend_yuv = yuv != nullptr;
   size_t cbytes = fbytes;
   unsigned char* cdst = sl.frame_dev;
-  if (yuv) {
+  const unsigned char* csrc = sl.frame_host;
+  if (jpeg) {
+    cbytes = sl.jd_job.copy_bytes;
+    cdst = sl.jd.dev + sl.jd_job.copy_dst;
+    csrc = sl.jd.host;
+  } else if (yuv) {
     cbytes = stage_yuv_planes(*yuv, sl, yuv_off, &sl.yuv_dev);
     cdst = sl.frame_dev + yuv_off;
   } else memcpy(sl.frame_host, bgr, fbytes);
   if (e->prep_defer) {   // copy now, kernels when the copy is done (flush_prep)
     if (!sl.ev_copy) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_copy, hipEventDisableTiming));
-    HIPCHK(e, hipMemcpyAsync(cdst, sl.frame_host, cbytes, hipMemcpyHostToDevice, e->copy_stream));
+    HIPCHK(e, hipMemcpyAsync(cdst, csrc, cbytes, hipMemcpyHostToDevice, e->copy_stream));
     HIPCHK(e, hipEventRecord(sl.ev_copy, e->copy_stream));
     sl.copy_pending = true;
     sl.pend_w = w; sl.pend_h = h;
     return RTP_OK;
   }
-  HIPCHK(e, hipMemcpyAsync(cdst, sl.frame_host, cbytes, hipMemcpyHostToDevice, cx.in_stream));
+  HIPCHK(e, hipMemcpyAsync(cdst, csrc, cbytes, hipMemcpyHostToDevice, cx.in_stream));
   if ((rc = launch_prep_kernels(e, cx, sj, w, h, cx.in_stream))) return rc;
   cx.in_pending = true;
+  return RTP_OK;
+}
+
+// ---- the GPU JPEG decoder (jpeg_dec.hip) -------------------------------------------------------------------------------------------
+void jd_free(JdBufs* b) {
+  if (b->dev) (void)hipFree(b->dev);
+  if (b->host) (void)hipHostFree(b->host);
+  if (b->status_host) (void)hipHostFree(b->status_host);
+  *b = JdBufs();
+}
+
+// Room in the decoder's buffers; the first `keep` bytes of the pinned buffer survive its growth.  Rare (the first file of a slot, or a
+// larger one): under the creation lock, and hipFree synchronises the device.
+int jd_ensure(rtp_engine* e, JdBufs* b, size_t host_bytes, size_t dev_bytes, size_t keep) {
+  if (host_bytes <= b->host_cap && dev_bytes <= b->dev_cap && b->status_host) return RTP_OK;
+  SYNC_GUARD;
+  if (!b->status_host) {
+    HIPCHK(e, hipHostMalloc((void**)&b->status_host, 64, hipHostMallocDefault));
+    HIPCHK(e, hipHostGetDevicePointer((void**)&b->status_host_dev, b->status_host, 0));
+    *b->status_host = 0xffffffffu;
+  }
+  if (host_bytes > b->host_cap) {
+    const size_t cap = round_up_sz(host_bytes + host_bytes / 4, 4096);
+    unsigned char* nh = nullptr;
+    HIPCHK(e, hipHostMalloc((void**)&nh, cap, hipHostMallocDefault));
+    if (keep && b->host) memcpy(nh, b->host, std::min(keep, b->host_cap));
+    if (b->host) (void)hipHostFree(b->host);
+    b->host = nh; b->host_cap = cap;
+  }
+  if (dev_bytes > b->dev_cap) {
+    const size_t cap = round_up_sz(dev_bytes + dev_bytes / 4, 4096);
+    if (b->dev) (void)hipFree(b->dev);
+    b->dev = nullptr; b->dev_cap = 0;
+    HIPCHK(e, hipMalloc((void**)&b->dev, cap));
+    b->dev_cap = cap;
+  }
+  return RTP_OK;
+}
+
+void jd_fill_recon(const JpegGeom& g, JdRecon* r, long* plane_bytes) {
+  memset(r, 0, sizeof *r);
+  r->W = g.W; r->H = g.H; r->ncomp = g.ncomp; r->rgb = g.rgb; r->hmax = g.hmax; r->vmax = g.vmax;
+  long off = 0;
+  int blocks = 0;
+  for (int c = 0; c < g.ncomp; ++c) {
+    r->h[c] = g.h[c]; r->v[c] = g.v[c]; r->bw[c] = g.bw[c]; r->bh[c] = g.bh[c]; r->dw[c] = g.dw[c]; r->dh[c] = g.dh[c];
+    r->coef_off[c] = blocks;
+    blocks += g.bw[c] * g.bh[c];
+    r->plane_off[c] = off;
+    off += (long)round_up_sz((size_t)g.bw[c] * 8 * g.bh[c] * 8, 256);
+    memcpy(r->qn[c], g.qn[c], sizeof r->qn[c]);
+  }
+  r->blocks = blocks;
+  *plane_bytes = off;
+}
+
+// Parse the file, stage what the device needs in b's pinned buffer and describe the launches in *job.  No HIP work is enqueued.
+// Failures carry the code and the message of rtp_decode_image.
+int jd_plan(rtp_engine* e, const char* fn, const unsigned char* bytes, size_t n, int sub_bits, int group, bool force_host, JdBufs* b, JdJob* job) {
+  int rc;
+  const size_t wcap = std::min(kJdStageCap, round_up_sz(n + n / 2 + 64, 4));
+  if ((rc = jd_ensure(e, b, wcap, 0, 0))) return rc;
+  JpegPlan P;
+  try {
+    rc = jpeg_plan(bytes, n, sub_bits, reinterpret_cast<uint32_t*>(b->host), wcap / 4, force_host, &P);
+  } catch (const std::exception& ex) {
+    return fail(e, RTP_ENOMEM, "%s: %s", fn, ex.what());
+  }
+  if (rc) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
+  // one synchronisation launch is enqueued per workgroup of subsequences: a scan that would need more than kJdMaxGroups of them (a
+  // huge file, or tiny S / group from a test or a sweep) takes the host's entropy decoder instead of flooding the stream
+  if (P.path == RTP_JPEG_ENTROPY_DEVICE && (P.subs.size() + group - 1) / group > (size_t)kJdMaxGroups) {
+    try {
+      rc = jpeg_plan(bytes, n, sub_bits, nullptr, 0, true, &P);
+    } catch (const std::exception& ex) {
+      return fail(e, RTP_ENOMEM, "%s: %s", fn, ex.what());
+    }
+    if (rc) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
+  }
+  long plane_bytes = 0;
+  jd_fill_recon(P.g, &job->g, &plane_bytes);
+  const bool dev = P.path == RTP_JPEG_ENTROPY_DEVICE;
+  job->path = P.path;
+  job->group = group;
+  job->mcus = P.g.mcux * P.g.mcuy;
+  job->L = jd_layout(job->g.blocks, plane_bytes, dev ? P.nwords : 0, dev ? P.segs.size() : 0, dev ? P.subs.size() : 0, group);
+  const JdLayout& L = job->L;
+  const size_t coef_bytes = (size_t)job->g.blocks * 64 * sizeof(short);
+  if ((rc = jd_ensure(e, b, dev ? L.staged : coef_bytes, L.total, dev ? P.nwords * 4 : 0))) return rc;
+  job->coef = reinterpret_cast<short*>(b->dev + L.coef);
+  job->planes = b->dev + L.planes;
+  if (!dev) {
+    memcpy(b->host, P.coef.data(), coef_bytes);
+    job->copy_bytes = coef_bytes; job->copy_dst = L.coef;
+    return RTP_OK;
+  }
+  JdTables* tab = reinterpret_cast<JdTables*>(b->host + L.tab);
+  tab->scan = P.scan;
+  memcpy(tab->dc, P.dc, sizeof tab->dc);
+  memcpy(tab->ac, P.ac, sizeof tab->ac);
+  memcpy(b->host + L.segs, P.segs.data(), P.segs.size() * sizeof(JdSeg));
+  memcpy(b->host + L.subs, P.subs.data(), P.subs.size() * sizeof(JdSub));
+  job->copy_bytes = L.staged; job->copy_dst = 0;
+  JdDev& d = job->d;
+  d.tab = reinterpret_cast<const JdTables*>(b->dev + L.tab);
+  d.segs = reinterpret_cast<const JdSeg*>(b->dev + L.segs);
+  d.subs = reinterpret_cast<const JdSub*>(b->dev + L.subs);
+  d.words = reinterpret_cast<const uint32_t*>(b->dev + L.words);
+  d.nsub = (int)P.subs.size(); d.nwords = (int)P.nwords; d.ngroups = L.ngroups;
+  d.entry = reinterpret_cast<JdState*>(b->dev + L.entry);
+  d.exit_ = reinterpret_cast<JdState*>(b->dev + L.exit_);
+  d.count = reinterpret_cast<int*>(b->dev + L.count);
+  d.excl = reinterpret_cast<int*>(b->dev + L.excl);
+  d.gexit = reinterpret_cast<JdState*>(b->dev + L.gexit);
+  d.flags = reinterpret_cast<int*>(b->dev + L.flags);
+  d.status = reinterpret_cast<unsigned*>(b->dev + L.status);
+  d.status_out = b->status_host_dev;
+  d.coef = job->coef;
+  d.dcsum = reinterpret_cast<int*>(b->dev + L.dcsum);
+  return RTP_OK;
+}
+
+// The kernels of a planned decode on `stream` (behind the copy of its staged bytes): entropy decoding where the device does it,
+// then the reconstruction into the three named channels of dst
+int jd_launch(rtp_engine* e, unsigned long long* stamp, const JdJob& job, const FrameView& dst, hipStream_t stream) {
+  if (job.path == RTP_JPEG_ENTROPY_DEVICE)
+    HIPCHK(e, launch_jpeg_entropy(stamp, job.d, job.group, job.mcus, job.g.ncomp, job.g.blocks, stream));
+  HIPCHK(e, launch_jpeg_reconstruct(stamp, job.g, job.coef, job.planes, dst, stream));
   return RTP_OK;
 }
 
@@ -1501,6 +1682,7 @@ int enqueue_preprocess_yuv_view(rtp_engine* e, Ctx& cx, int sj, const YuvView& v
   const double s = rtp_display_fit_scale(v.w, v.h, dw, dh);
   if (frame_scale) *frame_scale = (float)s;
   sl.pend_yuv = false;
+  sl.pend_jpeg = false;
   if (producer) {
     HIPCHK(e, hipEventRecord(sl.ev_ready, producer));
     HIPCHK(e, hipStreamWaitEvent(cx.in_stream, sl.ev_ready, 0));
@@ -1746,6 +1928,8 @@ void rtp_engine_destroy(rtp_engine* e) {
   for (void* p : e->user_bufs) if (p) (void)hipFree(p);
   if (e->jenc_ev) { (void)hipEventSynchronize(e->jenc_ev); (void)hipEventDestroy(e->jenc_ev); }
   jpeg_free(&e->jenc, &e->jenc_host, &e->jenc_cap);
+  if (e->jdec_ev) { (void)hipEventSynchronize(e->jdec_ev); (void)hipEventDestroy(e->jdec_ev); }
+  jd_free(&e->jdec);
   delete e;
 }
 
@@ -2130,6 +2314,141 @@ int rtp_convert_yuv_device(rtp_engine* e, const rtp_yuv_view* src, const rtp_fra
   return RTP_OK;
 }
 
+// ---- JPEG files decoded on the GPU ---------------------------------------------------------------------------------------------------
+// rtp_decode_jpeg_device with the test knobs: sub_bits = S (0: the engine's), group = subsequences per workgroup (0: the engine's),
+// force_host = 1: the host's entropy decoder whatever the file.  rounds (may be NULL): [0] launches of the synchronisation kernel that
+// did work, [1] launches enqueued.  Not part of the public header.
+extern "C" int rtp_internal_jpeg_decode_device(rtp_engine* e, const unsigned char* jpeg_host, size_t n, const rtp_frame_view* dst, void* stream,
+                                               int sub_bits, int group, int force_host, int* entropy_path, int* rounds) {
+  static const char* fn = "rtp_decode_jpeg_device";
+  FrameView fv;
+  long hi = 0;
+  int rc, layout = LAYOUT_GENERIC;
+  if ((rc = check_view_fields(e, dst, fn, &fv, &hi))) return rc;
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if (!jpeg_host) return fail(e, RTP_EINVAL, "%s: NULL file", fn);
+  if (n >= 8 && jpeg_host[0] == 0x89 && jpeg_host[1] == 'P') return fail(e, RTP_EINVAL, "%s: a PNG file (only JPEG is decoded on the GPU: rtp_decode_image)", fn);
+  if (sub_bits <= 0) sub_bits = e->jd_sub_bits;
+  if (group <= 0) group = e->jd_group;
+  if (sub_bits < 32 || sub_bits % 32 || group < 1 || group > 1024) return fail(e, RTP_EINVAL, "%s: S = %d bits (a multiple of 32), %d subsequences per workgroup (1..1024)", fn, sub_bits, group);
+  if ((rc = check_caller_stream(e, stream, fn))) return rc;
+  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
+  if ((rc = use_device(e))) return rc;
+  if (e->jdec_ev) HIPCHK(e, hipEventSynchronize(e->jdec_ev));
+  else HIPCHK(e, hipEventCreateWithFlags(&e->jdec_ev, hipEventDisableTiming));
+  JdJob job;
+  if ((rc = jd_plan(e, fn, jpeg_host, n, sub_bits, group, force_host != 0, &e->jdec, &job))) return rc;
+  if (job.g.W != fv.w || job.g.H != fv.h) return fail(e, RTP_EINVAL, "%s: the destination is %d x %d, the file %d x %d", fn, fv.w, fv.h, job.g.W, job.g.H);
+  if (entropy_path) *entropy_path = job.path;
+  const hipStream_t st = (hipStream_t)stream;
+  *e->jdec.status_host = 0xffffffffu;
+  HIPCHK(e, hipMemcpyAsync(e->jdec.dev + job.copy_dst, e->jdec.host, job.copy_bytes, hipMemcpyHostToDevice, st));
+  if ((rc = jd_launch(e, nullptr, job, fv, st))) return rc;
+  HIPCHK(e, hipEventRecord(e->jdec_ev, st));
+  HIPCHK(e, hipEventSynchronize(e->jdec_ev));
+  if (rounds) {
+    rounds[0] = rounds[1] = 0;
+    if (job.path == RTP_JPEG_ENTROPY_DEVICE) {
+      std::vector<int> flags((size_t)job.d.ngroups);
+      HIPCHK(e, hipMemcpy(flags.data(), job.d.flags, flags.size() * sizeof(int), hipMemcpyDeviceToHost));
+      rounds[1] = job.d.ngroups;
+      for (int r = 0; r < job.d.ngroups; ++r) if (r == 0 || flags[r - 1]) rounds[0] = r + 1;
+    }
+  }
+  const unsigned s = *e->jdec.status_host;
+  if (s != 0xffffffffu) return fail(e, RTP_EIO, "%s: %s", fn, jpeg_entropy_message((int)(s & 3u)));
+  return RTP_OK;
+}
+
+int rtp_decode_jpeg_device(rtp_engine* e, const unsigned char* jpeg_host, size_t n, const rtp_frame_view* dst, void* stream, int* entropy_path) {
+  return rtp_internal_jpeg_decode_device(e, jpeg_host, n, dst, stream, 0, 0, 0, entropy_path, nullptr);
+}
+
+// S and subsequences per workgroup of every later decode of this engine (0: back to the defaults)
+extern "C" int rtp_internal_jpeg_knobs(rtp_engine* e, int sub_bits, int group) {
+  if (!e) return RTP_EINVAL;
+  if (sub_bits < 0 || sub_bits % 32 || group < 0 || group > 1024) return fail(e, RTP_EINVAL, "rtp_internal_jpeg_knobs: S = %d, group = %d", sub_bits, group);
+  e->jd_sub_bits = sub_bits ? sub_bits : kJdSubBits;
+  e->jd_group = group ? group : kJdGroup;
+  return RTP_OK;
+}
+
+// The reconstruction kernels alone: coefficient blocks (host, component after component, natural order) and natural-order 16-bit
+// quantisers -> the view.  The device counterpart of codecs.cpp's rtp_internal_jpeg_reconstruct_host.
+extern "C" int rtp_internal_jpeg_geom(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, rtp::JpegGeom* g);
+extern "C" int rtp_internal_jpeg_reconstruct_device(rtp_engine* e, int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb,
+                                                    const short* coef_host, const rtp_frame_view* dst, void* stream) {
+  static const char* fn = "rtp_internal_jpeg_reconstruct_device";
+  FrameView fv;
+  long hi = 0;
+  int rc, layout = LAYOUT_GENERIC;
+  if ((rc = check_view_fields(e, dst, fn, &fv, &hi))) return rc;
+  if (!e || !coef_host) return fail(e, RTP_EINVAL, "%s: NULL argument", fn);
+  JpegGeom g;
+  if ((rc = rtp_internal_jpeg_geom(W, H, ncomp, hv, qn, rgb, &g))) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
+  if (fv.w != W || fv.h != H) return fail(e, RTP_EINVAL, "%s: the destination is %d x %d, the image %d x %d", fn, fv.w, fv.h, W, H);
+  if ((rc = check_caller_stream(e, stream, fn))) return rc;
+  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
+  if ((rc = use_device(e))) return rc;
+  if (e->jdec_ev) HIPCHK(e, hipEventSynchronize(e->jdec_ev));
+  else HIPCHK(e, hipEventCreateWithFlags(&e->jdec_ev, hipEventDisableTiming));
+  JdJob job;
+  long plane_bytes = 0;
+  jd_fill_recon(g, &job.g, &plane_bytes);
+  job.L = jd_layout(job.g.blocks, plane_bytes, 0, 0, 0, 1);
+  const size_t coef_bytes = (size_t)job.g.blocks * 64 * sizeof(short);
+  if ((rc = jd_ensure(e, &e->jdec, coef_bytes, job.L.total, 0))) return rc;
+  memcpy(e->jdec.host, coef_host, coef_bytes);
+  job.coef = reinterpret_cast<short*>(e->jdec.dev + job.L.coef);
+  job.planes = e->jdec.dev + job.L.planes;
+  const hipStream_t st = (hipStream_t)stream;
+  HIPCHK(e, hipMemcpyAsync(job.coef, e->jdec.host, coef_bytes, hipMemcpyHostToDevice, st));
+  if ((rc = jd_launch(e, nullptr, job, fv, st))) return rc;
+  HIPCHK(e, hipEventRecord(e->jdec_ev, st));
+  HIPCHK(e, hipEventSynchronize(e->jdec_ev));
+  return RTP_OK;
+}
+
+// rtp_submit_frame on the pixels rtp_decode_image makes of the file: the scan (or the host decoder's coefficients) crosses PCIe, the
+// decode kernels run in front of the warp.
+int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t n, uint64_t tag, float* frame_scale, int* w, int* h) {
+  static const char* fn = "rtp_submit_frame_jpeg";
+  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
+  if (!jpeg_host) return fail(e, RTP_EINVAL, "%s: NULL file", fn);
+  int rc, ci, sj;
+  const bool png = n >= 8 && jpeg_host[0] == 0x89 && jpeg_host[1] == 'P';
+  if (!e->gpu_prep_ok || png) {   // the host fallback of rtp_submit_frame, on the decoded pixels (a PNG file always is decoded there)
+    try {   // (nothing may unwind through the C boundary)
+      int iw = 0, ih = 0;
+      if ((rc = rtp_decode_image(jpeg_host, n, nullptr, 0, &iw, &ih))) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
+      std::vector<unsigned char> bgr((size_t)iw * ih * 3);
+      if ((rc = rtp_decode_image(jpeg_host, n, bgr.data(), bgr.size(), &iw, &ih))) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
+      if (w) *w = iw;
+      if (h) *h = ih;
+      return rtp_submit_frame(e, bgr.data(), iw, ih, tag, frame_scale);
+    } catch (const std::exception& ex) {
+      return fail(e, RTP_ENOMEM, "%s: host decoding: %s", fn, ex.what());
+    }
+  }
+  if ((rc = use_device(e))) return rc;
+  if ((rc = need_weights(e))) return rc;
+  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
+  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  Ctx& cx = e->ctx[ci];
+  Slot& sl = cx.slot[sj];
+  // everything that can refuse the file happens before the slot is committed: a failed call leaves the open batch as it was
+  if ((rc = jd_plan(e, fn, jpeg_host, n, e->jd_sub_bits, e->jd_group, false, &sl.jd, &sl.jd_job))) return rc;
+  if (w) *w = sl.jd_job.g.W;
+  if (h) *h = sl.jd_job.g.H;
+  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
+  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier frame of this batch whose copy is done by now
+  sl.has_disp = true;
+  *sl.jd.status_host = 0xffffffffu;
+  if ((rc = enqueue_preprocess(e, cx, sj, nullptr, sl.jd_job.g.W, sl.jd_job.g.H, frame_scale, nullptr, true))) return rc;
+  sl.jpeg_status = sl.jd_job.path == RTP_JPEG_ENTROPY_DEVICE;
+  return commit_slot(e, ci, sj, tag);
+}
+
 // Launch a partially filled batch now (end of stream, or a latency-sensitive caller).
 int rtp_flush(rtp_engine* e) {
   if (!e) return RTP_EINVAL;
@@ -2220,6 +2539,15 @@ static int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_pe
         hipEventElapsedTime(&t1, e->busy_base, cx.ev[1]) == hipSuccess) { e->busy_spans.push_back(0.f); e->busy_spans.push_back(t0); e->busy_spans.push_back(t1); }
     if (hipEventElapsedTime(&t0, e->busy_base, sl.ev[0]) == hipSuccess && hipEventElapsedTime(&t1, e->busy_base, sl.ev[4]) == hipSuccess) {
       e->busy_spans.push_back(1.f); e->busy_spans.push_back(t0); e->busy_spans.push_back(t1);
+    }
+  }
+  if (sl.jpeg_status) {   // rtp_submit_frame_jpeg: what the entropy kernels found in the scan
+    sl.jpeg_status = false;
+    const unsigned st = *sl.jd.status_host;
+    if (st != 0xffffffffu) {
+      if (num_people) *num_people = 0;
+      return fail(e, RTP_EIO, "rtp_submit_frame_jpeg (tag %llu): %s (block %u of the scan); the frame is dropped", (unsigned long long)sl.tag,
+                  jpeg_entropy_message((int)(st & 3u)), st >> 2);
     }
   }
   if (n < 0) {

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "jpeg_bound.h"
+#include "jpeg_dec.h"
 
 // Experiment knobs (tile overrides, ablation variants of the ring kernel — some of which compute WRONG results on purpose, stream
 // plans, diagnostic probes) exist only in the second build target librtpose_mi355x_exp.so (-DRTP_EXPERIMENTS, used by tools/):
@@ -262,6 +263,47 @@ size_t jpeg_bufs_bytes(int w, int h, JpegBufs* layout);
 // its length -> *dst_len.  Seven launches on `stream`, all stamped into `stamp`.
 hipError_t launch_jpeg_encode(unsigned long long* stamp, const FrameView& v, const JpegQuant& q, const JpegBufs& jb, unsigned char* dst,
                               unsigned* dst_len, hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------
+// JPEG decoder (rtp_decode_jpeg_device, rtp_submit_frame_jpeg): jpeg_dec.hip, the pixels of codecs.cpp's decode_jpeg
+// ---------------------------------------------------------------------------------------
+struct JdTables { JdScan scan; JdHuff dc[3], ac[3]; };
+// Byte offsets of one decode's buffers inside ONE device allocation of `total` bytes; [0, staged) is what the host stages (the same
+// offsets inside its pinned buffer) and one copy brings over
+struct JdLayout {
+  size_t words = 0, tab = 0, segs = 0, subs = 0, staged = 0;
+  size_t entry = 0, exit_ = 0, count = 0, excl = 0, gexit = 0, flags = 0, status = 0, coef = 0, dcsum = 0, planes = 0, total = 0;
+  int ngroups = 0;
+};
+JdLayout jd_layout(long blocks, long plane_bytes, size_t nwords, size_t nsegs, size_t nsubs, int group);
+// The entropy kernels' view of those buffers
+struct JdDev {
+  const JdTables* tab;
+  const JdSeg* segs;
+  const JdSub* subs;
+  const uint32_t* words;
+  int nsub, nwords, ngroups;
+  JdState* entry;
+  JdState* exit_;
+  int* count;
+  int* excl;
+  JdState* gexit;     // [2][ngroups]: the exit state of every workgroup's last subsequence, by launch parity
+  int* flags;         // [ngroups]: launch r changed something
+  unsigned* status;   // 0xffffffff, or (scan-order block << 2 | JD_ERR_*) of the first failure
+  unsigned* status_out;   // where the last kernel copies *status (pinned host memory as the device addresses it), or null
+  short* coef;
+  int* dcsum;
+};
+// Geometry, quantisers and colour model of a file for the reconstruction kernels
+struct JdRecon {
+  int W, H, ncomp, rgb, hmax, vmax, blocks;
+  int h[3], v[3], bw[3], bh[3], dw[3], dh[3], coef_off[3];
+  long plane_off[3];
+  unsigned short qn[3][64];
+};
+hipError_t launch_jpeg_entropy(unsigned long long* stamp, const JdDev& d, int group, int mcus, int ncomp, long blocks, hipStream_t stream);
+// coefficient blocks (component after component, natural order) -> planes (scratch) -> the three named channels of dv (W x H)
+hipError_t launch_jpeg_reconstruct(unsigned long long* stamp, const JdRecon& g, const short* coef, unsigned char* planes, const FrameView& dv, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------
 // Renderer (row 8f-3): render.hip

@@ -10,6 +10,7 @@
 // process exits at end of input also without --write_frames (the reference loops the video forever).
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -39,6 +40,8 @@ int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* 
                               size_t* jpeg_bytes) __attribute__((weak));
 // (the stand-ins have no YUV entry either: without it every frame takes the BGR path, as with --host_yuv)
 int rtp_submit_frame_yuv(rtp_engine* e, const rtp_yuv_view* frame_host, uint64_t tag, float* frame_scale) __attribute__((weak));
+// (nor a JPEG entry: without it every file is decoded on the producer side, as with --host_decode)
+int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t n, uint64_t tag, float* frame_scale, int* w, int* h) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -55,6 +58,10 @@ struct Flags {
   bool host_preprocess = false;
   bool host_jpeg = false;        // --write_frames: encode on the host (rtp_encode_jpeg on an encoder pool) instead of on the GPU
   bool host_yuv = false;         // --video x.y4m: convert every frame to BGR on the producer thread (rtp_video_read) instead of on the GPU
+  // JPEG files are decoded on the GPU (rtp_submit_frame_jpeg: only the file crosses PCIe) or on the producer side (rtp_decode_image).
+  // Default by source (profiles/r09_jpeg_decode.txt): --video x.mjpeg on the GPU (one producer thread decodes a video), --image_dir on
+  // the producer pool (many host cores outrun the GPU decoder).  --host_decode / --gpu_decode choose for both sources.
+  bool host_decode = false, gpu_decode = false;
   bool fullscreen = false, no_frame_drops = false, no_display = false, no_text = false, logtostderr = false;
   int part_to_show = 0, camera = 0, start_frame = 0, start_device = 0, num_gpu = 1, num_scales = 1;
   std::string write_frames, write_json, video, image_dir;
@@ -90,7 +97,7 @@ int parse_flags(int argc, char** argv, Flags& F) {
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
       {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}};
   std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_yuv", &F.host_yuv}, {"no_display", &F.no_display},
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -139,7 +146,11 @@ void usage() {
          "  drawn, i.e. --no_text is implied.  Its JPEG files (quality 98) are encoded on the GPU and only the files cross PCIe;\n"
          "  --host_jpeg copies the raw frames to the host and encodes them there on 8 threads instead (the same bytes).\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
-         "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n");
+         "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
+         "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
+         "  header; Huffman decoding, IDCT, up-sampling and colour conversion run on the GPU); --host_decode decodes on the producer thread\n"
+         "  instead.  --image_dir *.jpg|*.jpeg decodes on the producer pool (faster than the GPU decoder where host cores are free);\n"
+         "  --gpu_decode hands those files' bytes to the engine as well.  Same output either way; a file whose scan is corrupt is skipped.\n");
 }
 
 // ---- queues (caffe::BlockingQueue, util/blocking_queue.cpp:26-61) -----------------------------
@@ -164,6 +175,7 @@ template <typename T> class BlockingQueue {
 struct Frame {
   std::vector<float> data;         // net input (only with --host_preprocess)
   std::vector<unsigned char> image;  // decoded u8 BGR frame (default: pre-processing runs on the GPU), or — yuv — the planes of a Y4M frame
+  bool jpeg = false;               // image = the bytes of a JPEG file (img_w x img_h from its header): decoded on the GPU (rtp_submit_frame_jpeg)
   bool yuv = false;                // image = Y (img_w x img_h), then U and V ((img_w + sx) >> sx by (img_h + sy) >> sy each; none for mono)
   int chroma_sx = 0, chroma_sy = 0;
   bool mono = false;
@@ -226,11 +238,15 @@ void producer() {
   // Y4M: the planes go to the engine as they are in the file, unless the frames do not reach rtp_submit_frame at all (--host_preprocess,
   // --dry_engine), --host_yuv asks for the host conversion, or this binary was linked without the entry
   const bool yuv_planes = vid && rtp_video_chroma(vid) != 0 && !F.host_yuv && !F.host_preprocess && !(F.dry_engine > 0) && rtp_submit_frame_yuv != nullptr;
+  // JPEG files go to the engine as they are on disk (the same exceptions; --host_decode asks for the host decoder)
+  const bool jpeg_can = !F.host_decode && !F.host_preprocess && !(F.dry_engine > 0) && rtp_submit_frame_jpeg != nullptr;
+  const bool jpeg_files = jpeg_can && F.gpu_decode;                           // --image_dir: the producer pool unless asked
+  const bool mjpeg_bytes = vid && rtp_video_chroma(vid) == 0 && jpeg_can;     // --video x.mjpeg: the GPU unless asked
   std::vector<unsigned char> img;
   // --image_dir files and synthetic frames are produced a few ahead by a small pool (a 720p JPEG takes ~13 ms on one core, a
   // synthetic frame ~1 ms; 8 GPUs at 1 scale want ~8000 frames/s); the producer still hands the frames over in index order,
   // like the reference's single loop.  Video files are read sequentially (one decoder state).
-  struct Decoded { std::vector<unsigned char> bgr; int w = 0, h = 0; std::string err; };
+  struct Decoded { std::vector<unsigned char> bgr; int w = 0, h = 0; std::string err; bool jpeg = false; };   // jpeg: bgr holds the file
   const int hw = (int)std::thread::hardware_concurrency();
   const int pool_n = (synthetic || vid == nullptr) ? (F.producer_threads > 0 ? std::min(F.producer_threads, 64) : std::max(2, std::min(16, hw / 4))) : 0;
   const int window = 4 * std::max(pool_n, 1);
@@ -247,6 +263,20 @@ void producer() {
       rtp_synth_frame(d.bgr.data(), sw, sh, fi, seed);
     } else {
       const std::string& path = G.image_list[fi];
+      const size_t dot = path.find_last_of('.');
+      std::string ext = dot == std::string::npos ? "" : path.substr(dot);
+      for (char& ch : ext) ch = (char)tolower((unsigned char)ch);
+      if (jpeg_files && (ext == ".jpg" || ext == ".jpeg")) {   // the file and its header only
+        FILE* f = fopen(path.c_str(), "rb");
+        if (!f) { d.err = "cannot read the file"; return d; }
+        unsigned char chunk[65536];
+        size_t got;
+        while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) d.bgr.insert(d.bgr.end(), chunk, chunk + got);
+        fclose(f);
+        if (rtp_decode_image(d.bgr.data(), d.bgr.size(), nullptr, 0, &d.w, &d.h) != RTP_OK) { d.err = rtp_codec_last_error(); d.w = 0; return d; }
+        d.jpeg = true;
+        return d;
+      }
       if (rtp_load_image(path.c_str(), nullptr, 0, &d.w, &d.h) != RTP_OK) { d.err = rtp_codec_last_error(); d.w = 0; return d; }
       d.bgr.resize((size_t)d.w * d.h * 3);
       if (rtp_load_image(path.c_str(), d.bgr.data(), d.bgr.size(), &d.w, &d.h) != RTP_OK) { d.err = rtp_codec_last_error(); d.w = 0; }
@@ -288,6 +318,13 @@ void producer() {
           const unsigned char* p = (const unsigned char*)yv.y;
           img.assign(p, p + (size_t)w * h + (fr.mono ? 0 : 2 * cw * ch));
         }
+      } else if (mjpeg_bytes) {   // the frame's byte range inside the reader's copy of the file
+        const unsigned char* jb = nullptr;
+        size_t jn = 0;
+        rc = rtp_video_read_jpeg(vid, &jb, &jn);
+        if (rc == RTP_OK) rc = rtp_decode_image(jb, jn, nullptr, 0, &w, &h);
+        if (rc == RTP_OK && (w != sw || h != sh)) { fprintf(stderr, "video frame %d: MJPEG: frame size changes inside the stream\n", fi); break; }   // (as rtp_video_read)
+        if (rc == RTP_OK) { img.assign(jb, jb + jn); fr.jpeg = true; }
       } else {
         img.resize((size_t)w * h * 3);
         rc = rtp_video_read(vid, img.data(), img.size());
@@ -308,6 +345,7 @@ void producer() {
       if (d.w == 0) { fprintf(stderr, "cannot decode %s: %s\n", G.image_list[fi].c_str(), d.err.c_str()); continue; }
       img.swap(d.bgr);
       w = d.w; h = d.h;
+      fr.jpeg = d.jpeg;
       if (synthetic) { char nm[64]; snprintf(nm, sizeof nm, "frame%06d", fi); fr.stem = nm; }
       else {
         const std::string& path = G.image_list[fi];
@@ -490,6 +528,12 @@ void worker(int widx, int device, int* status) {
                    : gpu_jpeg ? rtp_collect_rendered_jpeg(e, &tag, joints.data(), &n, jpeg_buf.data(), jpeg_buf.size(), &jpeg_bytes)
                               : rtp_collect_rendered(e, &tag, joints.data(), &n, fr.rendered.data());
     if (rc != RTP_OK) { fprintf(stderr, "GPU %d frame %d: %s\n", device, fr.index, rtp_last_error(e)); n = 0; }
+    if (rc == RTP_EIO && fr.jpeg) {   // the scan of this file was corrupt: skipped, like a file the producer cannot decode
+      std::lock_guard<std::mutex> l(G.mutex);
+      G.dropped_index.push(fr.index);
+      G.dropped++;
+      return;
+    }
     if (gpu_jpeg) {  // only the file's bytes are kept
       if (rc == RTP_OK) {
         fr.rendered.assign(jpeg_buf.begin(), jpeg_buf.begin() + (long)jpeg_bytes);
@@ -543,9 +587,17 @@ void worker(int widx, int device, int* status) {
       const int src = dry ? dry_submit(fr)
                           : F.host_preprocess ? rtp_submit(e, fr.data.data(), (uint64_t)fr.index)
                           : fr.yuv            ? rtp_submit_frame_yuv(e, &yv, (uint64_t)fr.index, &fr.scale)
+                          : fr.jpeg           ? rtp_submit_frame_jpeg(e, fr.image.data(), fr.image.size(), (uint64_t)fr.index, &fr.scale, nullptr, nullptr)
                                               : rtp_submit_frame(e, fr.image.data(), fr.img_w, fr.img_h, (uint64_t)fr.index, &fr.scale);
       fr.image.clear();
       fr.image.shrink_to_fit();
+      if (src != RTP_OK && fr.jpeg && (src == RTP_EIO || src == RTP_EINVAL)) {   // a file the decoder refuses: skipped like one the producer cannot decode
+        fprintf(stderr, "cannot decode frame %d: %s\n", fr.video_frame_number, rtp_last_error(e));
+        std::lock_guard<std::mutex> l(G.mutex);
+        G.dropped_index.push(fr.index);
+        G.dropped++;
+        continue;
+      }
       if (src != RTP_OK) {  // nobody else may be left to drain the queue: stop the producer too
         fprintf(stderr, "GPU %d: %s\n", device, rtp_last_error(e));
         *status = 1;

@@ -216,6 +216,9 @@ def jpeg_max_bytes(w, h):
     return int(lib.rtp_jpeg_max_bytes(int(w), int(h)))
 
 
+JPEG_ENTROPY_DEVICE, JPEG_ENTROPY_HOST = 0, 1   # RTP_JPEG_ENTROPY_*: where a file's Huffman decoding ran (Engine.decode_jpeg_device)
+
+
 class Video:
     """cv::VideoCapture for Y4M / raw MJPEG files."""
 
@@ -242,6 +245,16 @@ class Video:
 
     def read_yuv(self):
         return video_read_yuv(self)
+
+    def read_jpeg(self):
+        """rtp_video_read_jpeg: the next frame of a raw MJPEG stream as the bytes of its file (None at the end), not decoded."""
+        p, n = C.POINTER(C.c_ubyte)(), C.c_size_t()
+        rc = lib.rtp_video_read_jpeg(self.h, C.byref(p), C.byref(n))
+        if rc == -11:
+            return None
+        if rc:
+            raise RtpError(rc, lib.rtp_codec_last_error().decode())
+        return C.string_at(p, n.value)
 
     def close(self):
         if self.h:
@@ -533,6 +546,35 @@ class Engine:
         d = _view_struct(frame_view(out, order))
         st, _ = _stream_of(out, stream)
         self._chk(lib.rtp_convert_yuv_device(self.h, C.byref(s), C.byref(d), st))
+
+    def decode_jpeg_device(self, data, out=None, stream=None, order="bgr"):
+        """rtp_decode_jpeg_device: the pixels decode_image makes of the JPEG file `data`, decoded on the GPU into the u8 device
+        frame `out` (see frame_view; None: a new (H, W, 3) torch tensor on the engine's device, torch must be imported), after the
+        work queued on `stream`.  Returns (out, path) with path = JPEG_ENTROPY_DEVICE or JPEG_ENTROPY_HOST: where the Huffman
+        decoding ran."""
+        buf = (C.c_ubyte * len(data)).from_buffer_copy(data)
+        if out is None:
+            torch = sys.modules.get("torch")
+            if torch is None:
+                raise TypeError("decode_jpeg_device(out=None) allocates a torch tensor: import torch first, or pass a device frame")
+            w, h = C.c_int(), C.c_int()
+            rc = lib.rtp_decode_image(buf, len(data), None, 0, C.byref(w), C.byref(h))
+            if rc:
+                raise RtpError(rc, lib.rtp_codec_last_error().decode())
+            out = torch.empty((h.value, w.value, 3), dtype=torch.uint8, device=f"cuda:{self.cfg.c.device_id}")
+        v = _view_struct(frame_view(out, order))
+        st, _ = _stream_of(out, stream)
+        path = C.c_int(-1)
+        self._chk(lib.rtp_decode_jpeg_device(self.h, buf, len(data), C.byref(v), st, C.byref(path)))
+        return out, path.value
+
+    def submit_frame_jpeg(self, data, tag=0):
+        """rtp_submit_frame_jpeg: submit_frame of decode_image's pixels of the JPEG file `data`; the file's scan crosses PCIe and is
+        decoded on the GPU.  Returns Frame::scale."""
+        buf = (C.c_ubyte * len(data)).from_buffer_copy(data)
+        fs = C.c_float()
+        self._chk(lib.rtp_submit_frame_jpeg(self.h, buf, len(data), tag, C.byref(fs), None, None))
+        return fs.value
 
     def debug_preprocess(self, img_u8):
         img = np.ascontiguousarray(img_u8, np.uint8)

@@ -346,6 +346,10 @@ int rtp_video_chroma(const rtp_video* v);
  * plane widths), valid until the next read or close.  rtp_convert_yuv of it = what rtp_video_read would have returned.
  * RTP_EAGAIN at the end of the stream; RTP_EINVAL for an MJPEG stream (nothing is consumed). */
 int rtp_video_read_yuv(rtp_video* v, rtp_yuv_view* out);
+/* rtp_video_read without the decoding: the byte range (SOI .. EOI) of the next frame of a raw MJPEG stream, inside the reader's own
+ * copy of the file, valid until close.  rtp_decode_image of it = what rtp_video_read would have returned.  RTP_EAGAIN at the end
+ * of the stream; RTP_EINVAL for a Y4M stream (nothing is consumed). */
+int rtp_video_read_jpeg(rtp_video* v, const unsigned char** bytes, size_t* n);
 int rtp_synth_frame(unsigned char* out_bgr, int w, int h, int index, uint64_t seed);
 
 /* Parse a deploy prototxt and report the graph it describes (for tests / tools). */
@@ -501,6 +505,30 @@ int rtp_submit_frame_yuv_device(rtp_engine* e, const rtp_yuv_view* frame_dev, vo
  * image (NULL: the null stream, and the image is complete when the call returns).  Uses no frame slot: frames in flight are not
  * disturbed. */
 int rtp_convert_yuv_device(rtp_engine* e, const rtp_yuv_view* src_dev, const rtp_frame_view* dst_dev, void* stream);
+
+/* ---- JPEG files, decoded on the GPU (jpeg_dec.hip): byte for byte the pixels of rtp_decode_image ---------------------- */
+
+/* Where the Huffman decoding of a file ran.  DEVICE: baseline / extended sequential files (SOF0 / SOF1, 8 bit) whose one scan holds
+ * all components (at most 10 blocks per MCU) with regular restart markers: only the scan crosses PCIe.  HOST: everything else the
+ * host decoder accepts (progressive, several scans, irregular markers, tables behind the scan): codecs.cpp's own entropy decoder
+ * fills the coefficient blocks and those are staged.  Dequantisation, IDCT, up-sampling and colour run on the GPU either way. */
+#define RTP_JPEG_ENTROPY_DEVICE 0
+#define RTP_JPEG_ENTROPY_HOST 1
+
+/* Decodes the file into the three named channels of dst_dev (device memory, checked as in rtp_convert_yuv_device; width and
+ * height must be the file's; a 4th channel is left untouched).  Runs after the work queued on `stream` and returns when the
+ * decode status is known (the image is then complete).  Every file rtp_decode_image rejects is rejected here with the same code
+ * and message (rtp_last_error), corrupt Huffman codes and AC runs past 63 found on the device included.  Uses engine scratch
+ * only: frames in flight are not disturbed.  *entropy_path (may be NULL) = RTP_JPEG_ENTROPY_*. */
+int rtp_decode_jpeg_device(rtp_engine* e, const unsigned char* jpeg_host, size_t n, const rtp_frame_view* dst_dev, void* stream,
+                           int* entropy_path);
+
+/* = rtp_submit_frame on the pixels rtp_decode_image makes of the file: same joints, frame_scale and rendered frames.  Only the
+ * scan (or, on the HOST entropy path, the coefficients) crosses PCIe; the decode kernels run in front of the warp and the call does
+ * not wait for the GPU.  Header errors are reported by the call (the code of rtp_decode_image); corrupt entropy-coded data found on
+ * the device makes the rtp_collect* of this tag release the frame and return RTP_EIO with a message, and the engine stays usable.
+ * *w, *h (may be NULL) = the file's size.  Where the device pre-processing cannot run the file is decoded on the host. */
+int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t n, uint64_t tag, float* frame_scale, int* w, int* h);
 
 #ifdef __cplusplus
 }
