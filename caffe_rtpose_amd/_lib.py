@@ -113,6 +113,7 @@ SIGNATURES = {
     "rtp_connect": (C.c_int, [vp, fp, fp, fp, ip]),
     "rtp_forward_debug": (C.c_int, [vp, fp, fp, fp, fp, fp, ip]),
     "rtp_get_blob": (C.c_int, [vp, C.c_char_p, fp, C.c_size_t, ip]),
+    "rtp_get_batch_blob": (C.c_int, [vp, C.c_int, C.c_char_p, fp, C.c_size_t, ip, C.POINTER(C.c_uint64), ip]),
     "rtp_num_conv_layers": (C.c_int, [vp]),
     "rtp_conv_layer_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, ip, ip, ip]),
     "rtp_get_conv_weights": (C.c_int, [vp, C.c_int, fp, fp]),

@@ -169,6 +169,10 @@ struct Ctx {
   bool stage0_set = false;
   bool graph_run = false;                 // the batch in flight was ONE graph replay incl. post-processing (collect waits on gev[1])
   bool graph_conv = false;                // the conv stack was a replay, the post-processing chains were launched eagerly
+  // rtp_get_batch_blob: the batch launch_batch ran last on this context (the one-frame taps record one frame); nothing on the frame path reads it
+  int last_nframes = 0;
+  bool last_own_input = false;            // its conv stack read cx.input (not the caller's tensor of an eager batch_frames 1 rtp_submit_device)
+  std::vector<uint64_t> last_tags;        // in slot order
   unsigned long long* stamps = nullptr;   // rtp_stamp_probe: STAMP_SLOTS x {~first workgroup start, last workgroup end} of this context's launches (kernels.h KStamp)
   bool stamps_dirty = false;
 };
@@ -895,6 +899,10 @@ int capture_batch(rtp_engine* e, Ctx& cx, int nframes, hipGraphExec_t* out) {
 int flush_prep(rtp_engine* e, Ctx& cx, bool force);
 int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bool materialize = false) {
   int rc;
+  cx.last_nframes = nframes;
+  cx.last_own_input = input_dev == cx.input;
+  cx.last_tags.resize(nframes);
+  for (int j = 0; j < nframes; ++j) cx.last_tags[j] = cx.slot[j].tag;
   for (Slot& sl : cx.slot)   // the previous batch's rendered images are still being exported on a caller's stream: this batch renders over them
     if (sl.export_pending) {
       HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_export, 0));
@@ -2740,6 +2748,9 @@ int rtp_forward_heatmaps(rtp_engine* e, const float* h_in, float* lowres) {
   Ctx& cx = e->ctx[0];
   const size_t bytes = (size_t)e->N * 3 * e->cfg.net_h * e->cfg.net_w * sizeof(float);
   HIPCHK(e, hipMemcpy(cx.input, h_in, bytes, hipMemcpyHostToDevice));
+  cx.last_nframes = 1;
+  cx.last_own_input = true;
+  cx.last_tags.assign(1, cx.slot[0].tag);
   if ((rc = run_frame_stack(e, cx, cx.input, e->N))) return rc;
   HIPCHK(e, hipStreamSynchronize(cx.stream));
   HIPCHK(e, hipMemcpy(lowres, cx.lowres, (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w * sizeof(float), hipMemcpyDeviceToHost));
@@ -2901,6 +2912,55 @@ int rtp_get_blob(rtp_engine* e, const char* name, float* out, size_t cap, int sh
   if (!t.written) return fail(e, RTP_EINVAL, "blob %s is not materialised: its convolution pools in the epilogue and writes only the pooled blob, or it is the middle blob of a fused branch tail that lives in LDS (create the engine with keep_blobs = 1 to tap it)", name);
   Geom g = e->plan.geom[t.level];
   g.N = e->N;  // the taps run one frame (slot 0 of the batch)
+  const size_t n = (size_t)g.N * t.C * g.H * g.W;
+  if (shape) { shape[0] = g.N; shape[1] = t.C; shape[2] = g.H; shape[3] = g.W; }
+  if (!out) return RTP_OK;
+  if (cap < n) return fail(e, RTP_EINVAL, "blob %s needs %zu floats", name, n);
+  if (t.C > 4096) return fail(e, RTP_EINVAL, "blob too wide");
+  float* dtmp = nullptr;
+  HIPCHK(e, hipMalloc((void**)&dtmp, n * sizeof(float)));
+  hipError_t s = hipMemcpy(e->dchmap, t.chmap.data(), t.C * sizeof(int), hipMemcpyHostToDevice);
+  if (s == hipSuccess) s = launch_export(e->plan.prec, cx.arena + t.offset, g, t.stride(), e->dchmap, t.C, t.lo_off(), t.q_off(), dtmp, cx.stream);
+  if (s == hipSuccess) s = hipStreamSynchronize(cx.stream);
+  if (s == hipSuccess) s = hipMemcpy(out, dtmp, n * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(dtmp);
+  if (s != hipSuccess) return fail(e, RTP_EHIP, "export failed: %s", hipGetErrorString(s));
+  return RTP_OK;
+}
+
+// rtp_get_blob for a whole batch: what the last batch that ran on context `ctx` left in that context's buffers
+int rtp_get_batch_blob(rtp_engine* e, int ctx, const char* name, float* out, size_t cap, int shape[4], uint64_t* tags_out, int* nframes_out) {
+  SYNC_GUARD;
+  int rc;
+  if ((rc = need_idle(e))) return rc;
+  if (!name) return RTP_EINVAL;
+  if (ctx < 0 || ctx >= (int)e->ctx.size()) return fail(e, RTP_EINVAL, "rtp_get_batch_blob: context %d of %zu", ctx, e->ctx.size());
+  Ctx& cx = e->ctx[ctx];
+  if (cx.last_nframes < 1) return fail(e, RTP_EINVAL, "rtp_get_batch_blob: context %d has not run a batch", ctx);
+  const int nimg = cx.last_nframes * e->N;
+  if (nframes_out) *nframes_out = cx.last_nframes;
+  if (tags_out) memcpy(tags_out, cx.last_tags.data(), cx.last_nframes * sizeof(uint64_t));
+  const float* plain = nullptr;   // a planar fp32 buffer of the context: the low-res maps or the staged input
+  int C = 0, H = 0, W = 0;
+  if (e->plan.lowres_blob == name) { plain = cx.lowres; C = e->plan.heat_channels; H = e->plan.low_h; W = e->plan.low_w; }
+  else if (!e->net.inputs.empty() && e->net.inputs[0] == name) {
+    if (!cx.last_own_input) return fail(e, RTP_EINVAL, "rtp_get_batch_blob: the last batch of context %d read the caller's tensor, not the staged input", ctx);
+    plain = cx.input; C = 3; H = e->cfg.net_h; W = e->cfg.net_w;
+  }
+  if (plain) {
+    const size_t n = (size_t)nimg * C * H * W;
+    if (shape) { shape[0] = nimg; shape[1] = C; shape[2] = H; shape[3] = W; }
+    if (!out) return RTP_OK;
+    if (cap < n) return fail(e, RTP_EINVAL, "blob %s needs %zu floats", name, n);
+    HIPCHK(e, hipMemcpy(out, plain, n * sizeof(float), hipMemcpyDeviceToHost));
+    return RTP_OK;
+  }
+  auto it = e->plan.blob_tensor.find(name);
+  if (it == e->plan.blob_tensor.end()) return fail(e, RTP_EINVAL, "Unknown blob name %s", name);
+  const Tensor& t = e->plan.tensors[it->second];
+  if (!t.written) return fail(e, RTP_EINVAL, "blob %s is not materialised (see rtp_get_blob)", name);
+  Geom g = e->plan.geom[t.level];
+  g.N = nimg;
   const size_t n = (size_t)g.N * t.C * g.H * g.W;
   if (shape) { shape[0] = g.N; shape[1] = t.C; shape[2] = g.H; shape[3] = g.W; }
   if (!out) return RTP_OK;

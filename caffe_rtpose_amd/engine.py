@@ -729,6 +729,16 @@ class Engine:
         self._chk(lib.rtp_get_blob(self.h, name.encode(), _f(out), out.size, shape))
         return out
 
+    def get_batch_blob(self, ctx, name):
+        """rtp_get_batch_blob: (blob [nframes * N][C][H][W], tags of the frames in slot order) of the last batch that ran on batch context `ctx`."""
+        shape = (C.c_int * 4)()
+        tags = (C.c_uint64 * max(int(self.cfg.c.batch_frames), 1))()
+        nf = C.c_int()
+        self._chk(lib.rtp_get_batch_blob(self.h, int(ctx), name.encode(), None, 0, shape, tags, C.byref(nf)))
+        out = np.empty(tuple(shape), np.float32)
+        self._chk(lib.rtp_get_batch_blob(self.h, int(ctx), name.encode(), _f(out), out.size, shape, None, None))
+        return out, list(tags)[: nf.value]
+
     def connect_stats(self):
         nl = 19 if self.num_parts == 18 else 14
         a = (C.c_int * nl)()

@@ -226,6 +226,20 @@ int rtp_forward_debug(rtp_engine* e, const float* nchw_input_host, float* lowres
  * (rtp_forward_heatmaps / rtp_forward_debug), as N x C x H x W fp32.  shape[4] out. */
 int rtp_get_blob(rtp_engine* e, const char* name, float* out_host, size_t out_capacity_floats,
                  int shape[4]);
+/* rtp_get_blob for a WHOLE batch: the named blob as the last batch that ran on batch context `ctx` (0 .. frames_in_flight /
+ * batch_frames - 1) left it in that context's buffers — nframes x num_scales images, frame j's at [j * num_scales, (j + 1) *
+ * num_scales); shape[0] = nframes * num_scales.  rtp_submit* fills context after context, a batch is launched when its last slot is
+ * filled (or by rtp_flush / a blocking rtp_collect), through the captured graph in RTP_EXEC_GRAPH.  name: every name rtp_get_blob
+ * accepts; the low-res blob (what the post-processing chains of all frames of the batch read); the graph's input blob (the
+ * batch's slice of the staged input tensor, i.e. what the conv stack consumed).  tags_out (batch_frames entries, may be NULL) /
+ * nframes_out (may be NULL) receive the tags of that batch's frames in slot order and their count; a one-frame tap
+ * (rtp_forward_heatmaps / rtp_forward_debug, context 0) counts as a batch of one frame.  out_host == NULL: shape, tags and count
+ * only.  Idle engines only.  RTP_EINVAL for a context outside the engine's, for one that has not run a batch since the engine
+ * was created or re-planned, and for the input blob of a batch that read the caller's tensor in place (rtp_submit_device, eager,
+ * batch_frames 1).  The buffers are returned as they stand: whatever ran on the context since (a tap on context 0,
+ * rtp_profile_steps) shows. */
+int rtp_get_batch_blob(rtp_engine* e, int ctx, const char* name, float* out_host, size_t out_capacity_floats, int shape[4],
+                       uint64_t* tags_out, int* nframes_out);
 
 /* ---- weights / graph (net.cpp:750-803, caffe.proto:6-22,64-95,310-330) ------------------ */
 int rtp_num_conv_layers(const rtp_engine* e);

@@ -813,3 +813,40 @@ def matrix_config(name):
     mode, model, W, H, N, gap, B, wseed = MATRIX[name]
     prec = {"fp16": r.PREC_FP16, "fp32": r.PREC_FP32, "mixed": r.PREC_MIXED, "f16x3": r.PREC_F16X3}[mode]
     return r.Config(model=model, net_w=W, net_h=H, num_scales=N, scale_gap=gap, precision=prec, frames_in_flight=B, batch_frames=B, synthetic_seed=wseed)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the configurations of tests/test_batch_launches.py: FULL batches of different frames through rtp_submit / rtp_collect, read back with
+# rtp_get_batch_blob.  What is under test is decided by the image count and the grid (the XCD remap of the block index and its q / r split
+# where the grid is no multiple of 8, img = tile / tiles_per_img for the images of the frames behind the first, the seam between two frames'
+# images in the arena, the partial-batch graphs), not by the image size: the shapes are the smallest that reach the tile classes of the
+# benched batch plans (tests/test_batch_launches_cpu.py asserts which).  The last entry is there for ONE class, `conv ring 128x128 rowb 128
+# passes 1` without a pooling epilogue (conv4_3_CPM / conv4_4_CPM of the benched batch plans): the planner gives a 3x3 layer at 1/8 resolution
+# 128x128 tiles only where the launch still has enough workgroups, and the first nine cases are too small for that.  Searched with
+# rtp_plan_summary over every multiple-of-16 shape up to 656x368, 1-3 scales, batch_frames 2-6: with batch_frames 2 the fewest pixels per launch
+# that reach it are 192x304 at three scales (350208; 512x368 at one scale: 376832).  Only more frames per batch go lower (32x304, three scales,
+# batch_frames 6: 175104 pixels, 1/8 maps four pixels wide, 17 frames to tap).  It runs the bitwise test like every case; that test needs no
+# float64 reference.
+# ------------------------------------------------------------------------------------------------------------
+BATCH_MATRIX = OrderedDict([   # name -> (mode, model, W, H, num_scales, scale_gap, batch_frames, synthetic_seed)
+    ("mixed_coco_64x48_b2", ("mixed", 0, 64, 48, 1, 0.3, 2, 1)),               # a 1/8 image smaller than one tile
+    ("mixed_coco_144x80_b3", ("mixed", 0, 144, 80, 1, 0.3, 3, 1)),             # odd image count
+    ("mixed_coco_176x320_2s_b2", ("mixed", 0, 176, 320, 2, 0.3, 2, 1)),        # portrait, 4 images, 128x128 tiles
+    ("mixed_coco_160x96_3s_b2", ("mixed", 0, 160, 96, 3, 0.15, 2, 1)),         # 6 images, like coco_3s_b2
+    ("mixed_coco_320x176_b2", ("mixed", 0, 320, 176, 1, 0.3, 2, 1)),           # tile set of the default plan
+    ("mixed_mpi_96x64_b5", ("mixed", 1, 96, 64, 1, 0.3, 5, 1)),                # 5 images like bench.py --model mpi; cout 28 tails; stand-alone pool; pw2 grid no multiple of 8
+    ("f16x3_coco_144x80_b2", ("f16x3", 0, 144, 80, 1, 0.3, 2, 1)),             # 3aw / 2w, register-staged kernel with a grid that is no multiple of 8
+    ("fp16_coco_144x80_b3", ("fp16", 0, 144, 80, 1, 0.3, 3, 1)),
+    ("fp32_coco_160x96_2s_b2", ("fp32", 0, 160, 96, 2, 0.3, 2, 1)),            # 64x128 / 64x64 / 128x64 reg tiles
+    ("mixed_coco_192x304_3s_b2", ("mixed", 0, 192, 304, 3, 0.15, 2, 1)),       # conv ring 128x128 rowb 128 passes 1 without a pooling epilogue
+])
+BATCH_FLOAT64 = ("mixed_coco_160x96_3s_b2", "mixed_mpi_96x64_b5", "fp32_coco_160x96_2s_b2")   # cases that also run every launch of the full batch against float64
+
+
+def batch_config(name, exec_mode=None, contexts=2):
+    """the engine configuration of a BATCH_MATRIX entry: `contexts` full batches in flight"""
+    import caffe_rtpose_amd as r
+    mode, model, W, H, N, gap, B, wseed = BATCH_MATRIX[name]
+    prec = {"fp16": r.PREC_FP16, "fp32": r.PREC_FP32, "mixed": r.PREC_MIXED, "f16x3": r.PREC_F16X3}[mode]
+    kw = {} if exec_mode is None else dict(exec_mode=exec_mode)
+    return r.Config(model=model, net_w=W, net_h=H, num_scales=N, scale_gap=gap, precision=prec, frames_in_flight=contexts * B, batch_frames=B, synthetic_seed=wseed, **kw)

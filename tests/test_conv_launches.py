@@ -6,8 +6,9 @@ tolerance of a launch holds no upstream error:  tol = u_out*|r| + (c_acc*2^-24 +
 image and launch: the first and last 4 rows and columns in full, the first and last pixel of every workgroup's tile, a seeded interior set.
 tests/test_conv_launches_cpu.py keeps the matrix a superset of the kernel instantiations bench.py's plans run.
 
-The tapped forward runs ONE frame: a batch_frames 2 case runs that plan's tiles (chosen for 2 x N images per launch), not the seam between
-the two frames of a batch — that seam stays with the batch-transparency checks of tests/test_precision.py and tests/test_gpu_parity.py.
+The tapped forward runs ONE frame: a batch_frames 2 case runs that plan's tiles (chosen for 2 x N images per launch) on half the grid.
+Full batches — every image of every frame, through rtp_submit / rtp_collect and the captured graphs — are checked blob by blob in
+tests/test_batch_launches.py.
 
 Time: a case costs the engine build + one forward (what a tests/test_precision.py case pays too) plus the float64 reference of the
 sampled pixels; both are printed, profiles/conv_launch_check.txt has them for every case.

@@ -69,11 +69,12 @@ def test_matrix_reaches_every_instantiation_of_the_benchmarked_plans(graphs):
 
 
 def test_tile_walks_match_the_workgroup_counts_of_the_plan(graphs):
-    """plain_tile_ends / pool_tile_ends restate plan.h: tiles per image x images x N tiles x branches == `wgs` of every launch of every matrix plan,
+    """plain_tile_ends / pool_tile_ends restate plan.h: tiles per image x images x N tiles x branches == `wgs` of every launch of every matrix plan (the batch matrix of tests/test_batch_launches.py included),
     and every tile end is an interior pixel"""
     r = _r()
     plans = [(name, graphs[model], n, b, r.plan_summary(cc.matrix_config(name))) for name, (mode, model, w, h, n, gap, b, seed) in cc.MATRIX.items()]
     plans += [(cn.case_id(c), cn.net(c[0])[1], c[4], c[5], r.plan_summary(cn.config(*c))) for c in CUSTOM_MATRIX]
+    plans += [(name, graphs[model], n, b, r.plan_summary(cc.batch_config(name))) for name, (mode, model, w, h, n, gap, b, seed) in cc.BATCH_MATRIX.items()]   # tests/test_batch_launches.py: full batches
     halos = set()
     for name, g, n, b, summary in plans:
         levels, launches = cc.parse_plan(summary)

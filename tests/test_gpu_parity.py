@@ -488,10 +488,10 @@ def test_submit_frame_with_an_enlarging_pyramid_level_runs_on_the_device():
 # ------------------------------------------------------------------------------------------
 # frame batching: B frames share one conv launch sequence; per-frame results do not depend on B
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("prec_name,B,N", [("fp16", 3, 1), ("fp32", 2, 2)])
+@pytest.mark.parametrize("prec_name,B,N", [("fp16", 3, 1), ("fp32", 2, 2), ("mixed", 2, 1)])
 def test_frame_batching_is_transparent(prec_name, B, N):
     import caffe_rtpose_amd as r
-    prec = r.PREC_FP16 if prec_name == "fp16" else r.PREC_FP32
+    prec = {"fp16": r.PREC_FP16, "fp32": r.PREC_FP32, "mixed": r.PREC_MIXED}[prec_name]     # mixed: the default, and the benched, mode
     W, H = 320, 176
     e = _engine(net_w=W, net_h=H, num_scales=N, scale_gap=0.25, disp_w=640, disp_h=360, frames_in_flight=2 * B, batch_frames=B, precision=prec)
     imgs = [r.synth_frame(640, 360, i, seed=21) for i in range(2 * B + 2)]   # 2 full batches + a partial one
