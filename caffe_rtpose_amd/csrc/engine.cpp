@@ -2091,6 +2091,10 @@ int rtp_set_thresholds(rtp_engine* e, float nms_threshold, float connect_inter_t
                        int connect_min_subset_cnt, float connect_min_subset_score) {
   SYNC_GUARD;
   if (!e) return RTP_EINVAL;
+  // A pair is accepted with count > inter_min_above of its 10 samples above the threshold (rtpose.cpp:641 / :939).  Below 0 that accepts count == 0, whose
+  // score is 0 / 0: the reference then sorts NaNs with a comparator that is no ordering (undefined).  Nothing is changed by a refused call.
+  if (connect_inter_min_above_threshold < 0)
+    return fail(e, RTP_EINVAL, "rtp_set_thresholds: connect_inter_min_above_threshold %d < 0 accepts pairs without a sample (score 0 / 0)", connect_inter_min_above_threshold);
   if (e->graph_post && !e->ctx.empty()) {  // the post-processing chains live inside the batch graphs: their arguments are baked
     int rc;
     if ((rc = need_idle(e))) return rc;

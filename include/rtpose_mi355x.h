@@ -139,7 +139,9 @@ int rtp_engine_info(const rtp_engine* e, int* num_parts, int* max_peaks, int* he
                     int* low_w, int* low_h);
 
 /* Replaces: the global.* thresholds written by warmup() and the UI thread
- * (rtpose.cpp:212-226) and NmsLayer::SetThreshold (rtpose.cpp:1145). */
+ * (rtpose.cpp:212-226) and NmsLayer::SetThreshold (rtpose.cpp:1145).
+ * connect_inter_min_above_threshold < 0 is refused (RTP_EINVAL, nothing changes): it would accept
+ * pairs with no sample above the threshold, whose score is 0 / 0. */
 int rtp_set_thresholds(rtp_engine* e, float nms_threshold, float connect_inter_threshold,
                        int connect_inter_min_above_threshold, int connect_min_subset_cnt,
                        float connect_min_subset_score);

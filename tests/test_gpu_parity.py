@@ -130,13 +130,16 @@ def test_pooling_fused_into_the_convolution_epilogue_is_bit_identical(prec, mode
 # ------------------------------------------------------------------------------------------
 # ImResize — bit exact
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("model,W,H,N,start,gap", [(0, 656, 368, 1, 1.0, 0.3), (0, 656, 368, 3, 1.0, 0.15),
-                                                    (1, 496, 368, 2, 1.0, 0.3), (0, 64, 48, 2, 1.0, 0.25),
-                                                    # round 5: --start_scale != 1 moves the crop of EVERY scale (imresize_layer.cu:110-113),
-                                                    # portrait / large nets, crops down to 14 x 8 low-res cells
-                                                    (0, 656, 368, 1, 0.8, 0.15), (0, 656, 368, 2, 0.8, 0.15), (0, 656, 368, 3, 0.8, 0.15),
-                                                    (0, 656, 368, 1, 0.65, 0.25), (0, 656, 368, 3, 0.65, 0.25), (1, 496, 368, 2, 0.65, 0.15),
-                                                    (0, 368, 656, 2, 0.8, 0.15), (0, 1312, 736, 2, 0.8, 0.15), (0, 64, 48, 2, 0.7, 0.3)])
+RESIZE_CASES = [(0, 656, 368, 1, 1.0, 0.3), (0, 656, 368, 3, 1.0, 0.15),
+                (1, 496, 368, 2, 1.0, 0.3), (0, 64, 48, 2, 1.0, 0.25),
+                # round 5: --start_scale != 1 moves the crop of EVERY scale (imresize_layer.cu:110-113),
+                # portrait / large nets, crops down to 14 x 8 low-res cells
+                (0, 656, 368, 1, 0.8, 0.15), (0, 656, 368, 2, 0.8, 0.15), (0, 656, 368, 3, 0.8, 0.15),
+                (0, 656, 368, 1, 0.65, 0.25), (0, 656, 368, 3, 0.65, 0.25), (1, 496, 368, 2, 0.65, 0.15),
+                (0, 368, 656, 2, 0.8, 0.15), (0, 1312, 736, 2, 0.8, 0.15), (0, 64, 48, 2, 0.7, 0.3)]
+
+
+@pytest.mark.parametrize("model,W,H,N,start,gap", RESIZE_CASES)
 def test_resize_bit_exact(model, W, H, N, start, gap):
     e = _engine(model=model, net_w=W, net_h=H, num_scales=N, start_scale=start, scale_gap=gap, frames_in_flight=1)
     low = _synth.smooth_field(N * e.heat_channels, H // 8, W // 8, seed=3).reshape(N, e.heat_channels, H // 8, W // 8)
@@ -528,7 +531,7 @@ def test_frame_batching_is_transparent(prec_name, B, N):
 # ------------------------------------------------------------------------------------------
 # production post-processing (no resized map in memory) == oracle ImResize -> Nms -> connect
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("model,W,H,N,start,gap,kind", [
+FUSED_CASES = [
     (0, 656, 368, 1, 1.0, 0.3, "people5"),
     (0, 656, 368, 3, 1.0, 0.15, "people20"),
     (1, 496, 368, 2, 1.0, 0.3, "people4"),
@@ -547,34 +550,27 @@ def test_frame_batching_is_transparent(prec_name, B, N):
     (0, 1312, 736, 1, 0.8, 0.15, "speople5"),
     (0, 368, 656, 1, 1.0, 0.3, "noise"),         # portrait: the first max_peaks maxima lie in the rows the write kernel's `width` bound keeps
     (0, 64, 48, 2, 0.7, 0.3, "noise"),
-])
+]
+
+
+@pytest.mark.parametrize("model,W,H,N,start,gap,kind", FUSED_CASES)
 def test_fused_postproc_from_lowres_bit_exact(model, W, H, N, start, gap, kind):
     e = _engine(model=model, net_w=W, net_h=H, num_scales=N, start_scale=start, scale_gap=gap, frames_in_flight=1)
     tabs = orc.model_tables(model)
     thr = e.get_thresholds()
-    h, w = H // 8, W // 8
-    if kind == "noise":
-        low = (_synth.smooth_field(N * e.heat_channels, h, w, seed=31, scale=1.0).reshape(N, e.heat_channels, h, w)
-               + 0.25 * np.random.default_rng(7).standard_normal((N, e.heat_channels, h, w)).astype(np.float32))
-    elif kind.startswith("speople"):   # the same people at every scale, planted in each scale's crop window
-        import _pincases as pc
-        low = pc.scaled_people(model, tabs, int(kind[7:]), h, w, 44, N, start, gap)
-    else:
-        low, _ = _synth.people_lowres(model, tabs, int(kind[6:]), h, w, seed=44, N=N)
-        low = low.reshape(N, e.heat_channels, h, w)
+    import _postcases as pc
+    low = pc.fused_case_input(model, W, H, N, start, gap, kind)
+    assert low.shape == (N, e.heat_channels, H // 8, W // 8)
     ref_res = orc.imresize(low, W, H, start, gap)[0]
     ref_peaks = orc.nms(ref_res, e.num_parts, e.max_peaks, thr["nms_threshold"])
     peaks, joints, n = e.post_from_lowres(low)
     assert np.array_equal(peaks, ref_peaks)
     if kind == "noise" and W > 100:
         assert ref_peaks[:, 0, 0].max() >= e.max_peaks        # the cap was exercised
-    try:
-        rn, rj = orc.connect(model, ref_res, ref_peaks, e.max_peaks, W, H, 1280, 720, thr)
-    except Exception:
-        rn = None
-    if rn is not None:
-        assert n == rn
-        assert np.array_equal(joints[:n], rj[:n])
+    # (the oracle accepts all of FUSED_CASES: tests/test_postproc_sizes_cpu.py asserts it without a GPU)
+    rn, rj = orc.connect(model, ref_res, ref_peaks, e.max_peaks, W, H, 1280, 720, thr)
+    assert n == rn
+    assert np.array_equal(joints[:n], rj[:n])
     if kind != "noise":
         assert n >= 1
     # and the map-materialising taps agree with it too
