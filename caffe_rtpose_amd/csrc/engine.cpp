@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <fstream>
@@ -48,6 +49,25 @@ size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64
 extern "C" double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 extern "C" int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                                     double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
+
+// The producer computes its level scales from the DOUBLE flags (DEFINE_double start_scale / scale_gap, rtpose.cpp:68-69; `float scale =
+// START_SCALE - i*SCALE_GAP`, :359), rtp_config and rtp_set_scales carry floats (ImResizeLayer's own types).  A float that was a decimal flag
+// (0.225f) widens to 0.22499999403953552, and 1 - 4 * that is 0.10000002 where the flags give 0.1: at a level whose net * s is a multiple
+// of 16 (160 * 0.1) the 16-aligned size would come out one step larger than the reference's and than rtp_preprocess_frame's on the same
+// decimal (32x32 for 16x16 at 5 scales with gap 0.225 and at 16 scales with gap 0.06 on a 160x96 net).  The flag's value is the shortest decimal
+// that rounds to the float: what the caller wrote.  ImResize's crops keep the floats, as the reference's layer does.
+// The result is within half a float ulp of the widened float, and it IS the widened float for values that are exact in binary (1, 0.25, 0.8125).
+// Nine significant digits round-trip every float, so the loop always returns; the line behind it is for a C library that does not.
+// snprintf and strtof / strtod read LC_NUMERIC: another decimal point changes the text, not the value — both sides use the same locale.
+static double producer_flag(float v) {
+  if (!(v == v) || v - v != 0.f) return (double)v;   // NaN / inf: refused by scales_fit
+  char buf[40];
+  for (int prec = 1; prec <= 9; ++prec) {
+    snprintf(buf, sizeof buf, "%.*g", prec, (double)v);
+    if (strtof(buf, nullptr) == v) return strtod(buf, nullptr);
+  }
+  return (double)v;
+}
 
 namespace {
 
@@ -1240,7 +1260,7 @@ int build_prep_tables(rtp_engine* e) {
   std::vector<Host> hs(e->N);
   size_t bytes = 0;
   for (int i = 0; i < e->N; ++i) {
-    const float scale = (float)((double)e->start_scale - i * (double)e->scale_gap);
+    const float scale = (float)(producer_flag(e->start_scale) - i * producer_flag(e->scale_gap));
     Host& h = hs[i];
     h.tw = (int)(16 * std::ceil(e->cfg.net_w * scale / 16));
     h.th = (int)(16 * std::ceil(e->cfg.net_h * scale / 16));
@@ -1946,7 +1966,7 @@ void rtp_engine_destroy(rtp_engine* e) {
 // must fit the net input; NaN / inf never do.  The same test guards ImResize's crops (imresize_layer.cu:110-113: padw >= 0, ow >= 1).
 static bool scales_fit(int net_w, int net_h, int num_scales, float start_scale, float scale_gap, int* bad, float* bad_s) {
   for (int i = 0; i < num_scales; ++i) {
-    const float s = (float)((double)start_scale - i * (double)scale_gap);
+    const float s = (float)(producer_flag(start_scale) - i * producer_flag(scale_gap));
     const bool ok = s > 0.f && 16 * std::ceil(net_w * s / 16) <= net_w && 16 * std::ceil(net_h * s / 16) <= net_h &&
                     16 * std::ceil(net_w * s / 16) >= 16 && 16 * std::ceil(net_h * s / 16) >= 16;
     if (!ok) { if (bad) *bad = i; if (bad_s) *bad_s = s; return false; }
@@ -2208,8 +2228,8 @@ int rtp_submit_frame(rtp_engine* e, const unsigned char* bgr, int w, int h, uint
   } else {  // a pyramid level would have to be enlarged: host restatement (linear fallback) + H2D
     const size_t bytes = (size_t)e->N * 3 * e->cfg.net_h * e->cfg.net_w * sizeof(float);
     float* hin = (float*)((char*)cx.host_in + sj * bytes);
-    rc = rtp_preprocess_frame(bgr, w, h, e->cfg.disp_w, e->cfg.disp_h, e->cfg.net_w, e->cfg.net_h, e->N, e->start_scale, e->scale_gap,
-                              hin, nullptr, frame_scale);
+    rc = rtp_preprocess_frame(bgr, w, h, e->cfg.disp_w, e->cfg.disp_h, e->cfg.net_w, e->cfg.net_h, e->N, producer_flag(e->start_scale),
+                              producer_flag(e->scale_gap), hin, nullptr, frame_scale);
     if (rc) return fail(e, rc, "pre-processing failed (a scale does not fit the net resolution?)");
     HIPCHK(e, hipMemcpyAsync((char*)cx.input + sj * bytes, hin, bytes, hipMemcpyHostToDevice, cx.in_stream));
     cx.in_pending = true;

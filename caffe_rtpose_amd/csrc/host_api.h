@@ -127,6 +127,8 @@ inline void NmsLayer::SetThreshold(float t) {
   rtp_get_thresholds(net_->e_, &a, &b, &c, &d, &e);
   rtp_set_thresholds(net_->e_, t, b, c, d, e);
 }
+// The floats reach rtp_set_scales as they are.  ImResize crops with them; the pyramid LEVEL SIZES are computed, like the reference's producer does from
+// its double flags, from the shortest decimal that rounds to each float (SetScaleGap(0.225f) sizes the levels of --scale_gap 0.225): rtp_config.scale_gap.
 inline void ImResizeLayer::SetStartScale(float s) { net_->start_scale_ = s; if (net_->e_) rtp_set_scales(net_->e_, net_->start_scale_, net_->scale_gap_); }
 inline void ImResizeLayer::SetScaleGap(float g) { net_->scale_gap_ = g; if (net_->e_) rtp_set_scales(net_->e_, net_->start_scale_, net_->scale_gap_); }
 template <> inline std::shared_ptr<NmsLayer> Net::layer_by_name<NmsLayer>(const std::string& name) {

@@ -77,6 +77,11 @@ typedef struct rtp_config {
   int num_scales;          /* --num_scales = blob N (rtpose.cpp:188, 1719)                          */
   float start_scale;       /* --start_scale -> ImResizeLayer::SetStartScale (rtpose.cpp:201)       */
   float scale_gap;         /* --scale_gap   -> ImResizeLayer::SetScaleGap   (rtpose.cpp:202)       */
+                           /* The reference's flags are doubles and its producer sizes level i from the double
+                            * start_scale - i * scale_gap (rtpose.cpp:359).  For the LEVEL SIZES (and the range check)
+                            * these two floats — and rtp_set_scales' arguments — are read as the shortest decimal that
+                            * rounds to the float (0.225f is 0.225, not 0.22499999404): the levels of
+                            * rtp_preprocess_frame called with that decimal.  ImResize's crops use the floats as given. */
   int disp_w, disp_h;      /* --resolution: joints are returned in display coordinates (:1061)     */
   int precision;           /* RTP_PREC_*                                                            */
   int frames_in_flight;    /* >=1: frames that may be submitted before a collect is needed         */
@@ -152,7 +157,8 @@ int rtp_get_thresholds(const rtp_engine* e, float* nms_threshold, float* connect
 /* Replaces: ImResizeLayer::SetStartScale/SetScaleGap (imresize_layer.hpp:11-45).  Every level s = start_scale - i * scale_gap
  * (i < num_scales) must be positive and its 16-aligned size 16 * ceil(net * s / 16) must fit the net input — what the producer CHECKs
  * (rtpose.cpp:363-364) — else RTP_EINVAL and the engine keeps its previous scales; the same test guards rtp_engine_create and
- * rtp_preprocess_frame.  start_scale < 1 is in contract: ImResize then crops every scale incl. the first (imresize_layer.cu:110-113). */
+ * rtp_preprocess_frame.  start_scale < 1 is in contract: ImResize then crops every scale incl. the first (imresize_layer.cu:110-113).
+ * s is computed in double from the shortest decimals that round to the two floats (see rtp_config.scale_gap). */
 int rtp_set_scales(rtp_engine* e, float start_scale, float scale_gap);
 
 /* ---- the per-frame hot loop (rtpose.cpp:1127-1166) ---------------------------------- */

@@ -807,10 +807,10 @@ MATRIX = OrderedDict([   # name -> (mode, model, W, H, num_scales, scale_gap, ba
 ])
 
 
-def matrix_config(name):
-    """the engine configuration of a MATRIX entry"""
+def matrix_config(name, matrix=None):
+    """the engine configuration of a MATRIX entry (or of an entry of a sibling matrix with the same columns: tests/_manycases.py)"""
     import caffe_rtpose_amd as r
-    mode, model, W, H, N, gap, B, wseed = MATRIX[name]
+    mode, model, W, H, N, gap, B, wseed = (MATRIX if matrix is None else matrix)[name]
     prec = {"fp16": r.PREC_FP16, "fp32": r.PREC_FP32, "mixed": r.PREC_MIXED, "f16x3": r.PREC_F16X3}[mode]
     return r.Config(model=model, net_w=W, net_h=H, num_scales=N, scale_gap=gap, precision=prec, frames_in_flight=B, batch_frames=B, synthetic_seed=wseed)
 
@@ -843,10 +843,10 @@ BATCH_MATRIX = OrderedDict([   # name -> (mode, model, W, H, num_scales, scale_g
 BATCH_FLOAT64 = ("mixed_coco_160x96_3s_b2", "mixed_mpi_96x64_b5", "fp32_coco_160x96_2s_b2")   # cases that also run every launch of the full batch against float64
 
 
-def batch_config(name, exec_mode=None, contexts=2):
-    """the engine configuration of a BATCH_MATRIX entry: `contexts` full batches in flight"""
+def batch_config(name, exec_mode=None, contexts=2, matrix=None):
+    """the engine configuration of a BATCH_MATRIX entry (or of a sibling matrix, tests/_manycases.py): `contexts` full batches in flight"""
     import caffe_rtpose_amd as r
-    mode, model, W, H, N, gap, B, wseed = BATCH_MATRIX[name]
+    mode, model, W, H, N, gap, B, wseed = (BATCH_MATRIX if matrix is None else matrix)[name]
     prec = {"fp16": r.PREC_FP16, "fp32": r.PREC_FP32, "mixed": r.PREC_MIXED, "f16x3": r.PREC_F16X3}[mode]
     kw = {} if exec_mode is None else dict(exec_mode=exec_mode)
     return r.Config(model=model, net_w=W, net_h=H, num_scales=N, scale_gap=gap, precision=prec, frames_in_flight=contexts * B, batch_frames=B, synthetic_seed=wseed, **kw)

@@ -15,6 +15,10 @@ behind; the cases are _convcheck.BATCH_MATRIX (tests/test_conv_launches_cpu.py a
 (b) test_every_launch_of_a_full_batch_against_float64: for three cases, one full batch in GRAPH mode and _convcheck.check_plan over all
     N * B images with the bound of tests/_convcheck.py, unchanged.  It never runs the one-frame tap: the independent half.
 
+(c) the same two bodies over tests/_manycases.py BATCH_MATRIX: 10 and 32 images per launch (5 and 16 scales, batch_frames 2) and batch_frames 16
+    (47 frames, a partial batch of 15), every frame tapped alone — image indices past 8, the q / r split of the XCD remap on those grids, the arena
+    seams between up to 32 images, conv_first's H * 32 rows.
+
 Times are printed per case in the `[convcheck]` style; profiles/conv_launch_check.txt has them."""
 import re
 import time
@@ -24,6 +28,7 @@ import pytest
 
 import _batchcheck as bc
 import _convcheck as cc
+import _manycases as mc
 import _synth
 
 pytestmark = pytest.mark.gpu
@@ -73,11 +78,21 @@ def _collect(e, k):
 @pytest.mark.parametrize("exec_mode", ["graph", "eager"])
 @pytest.mark.parametrize("name", list(cc.BATCH_MATRIX))
 def test_batch_blobs_equal_single_frame_blobs(name, exec_mode):
+    _batch_blobs_equal_single_frame_blobs(name, exec_mode, cc.BATCH_MATRIX)
+
+
+@pytest.mark.parametrize("exec_mode", ["graph", "eager"])
+@pytest.mark.parametrize("name", list(mc.BATCH_MATRIX))
+def test_many_image_batch_blobs_equal_single_frame_blobs(name, exec_mode):
+    _batch_blobs_equal_single_frame_blobs(name, exec_mode, mc.BATCH_MATRIX)
+
+
+def _batch_blobs_equal_single_frame_blobs(name, exec_mode, matrix):
     import caffe_rtpose_amd as r
-    mode, model, W, H, N, gap, B, wseed = cc.BATCH_MATRIX[name]
+    mode, model, W, H, N, gap, B, wseed = matrix[name]
     graph = _graph(model)
     t0 = time.time()
-    e = r.Engine(cc.batch_config(name, exec_mode=r.EXEC_GRAPH if exec_mode == "graph" else r.EXEC_EAGER))
+    e = r.Engine(cc.batch_config(name, exec_mode=r.EXEC_GRAPH if exec_mode == "graph" else r.EXEC_EAGER, matrix=matrix))
     t1 = time.time()
     summary = r.plan_summary(e.cfg)
     names = _materialised(e, graph, summary)
@@ -164,11 +179,20 @@ def test_batch_blobs_equal_single_frame_blobs(name, exec_mode):
 
 @pytest.mark.parametrize("name", list(cc.BATCH_FLOAT64))
 def test_every_launch_of_a_full_batch_against_float64(name):
+    _every_launch_of_a_full_batch_against_float64(name, cc.BATCH_MATRIX)
+
+
+@pytest.mark.parametrize("name", list(mc.BATCH_FLOAT64))
+def test_every_launch_of_a_many_image_batch_against_float64(name):
+    _every_launch_of_a_full_batch_against_float64(name, mc.BATCH_MATRIX)
+
+
+def _every_launch_of_a_full_batch_against_float64(name, matrix):
     import caffe_rtpose_amd as r
-    mode, model, W, H, N, gap, B, wseed = cc.BATCH_MATRIX[name]
+    mode, model, W, H, N, gap, B, wseed = matrix[name]
     graph = _graph(model)
     t0 = time.time()
-    e = r.Engine(cc.batch_config(name, exec_mode=r.EXEC_GRAPH))
+    e = r.Engine(cc.batch_config(name, exec_mode=r.EXEC_GRAPH, matrix=matrix))
     t1 = time.time()
     layers = e.conv_layers()
     weights = {n: e.get_conv_weights(i) for i, (n, *_rest) in enumerate(layers)}

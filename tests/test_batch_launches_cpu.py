@@ -6,7 +6,8 @@
 2. The float64 checker over several images per launch: a correct kernel emulated on B * N DIFFERENT images (the first two stages of the 128x32
    plans with batch_frames 2 and 3, every pixel sampled) passes; defects of the kind only a batch can have fail in the images and the class
    they belong to — a frame computed from another frame's input, a grid one workgroup short, a 7x7 halo that reads the previous image's rows,
-   two frames' low-res maps swapped.
+   two frames' low-res maps swapped; and, over TEN images, an image index that is wrong from the 8th image on (what only a launch of many
+   images can have: tests/_manycases.py), sampled as sparsely as on the GPU.
 3. The bitwise comparer (tests/_batchcheck.py) reports a single last-bit difference exactly where it was planted."""
 import numpy as np
 import pytest
@@ -14,6 +15,7 @@ import pytest
 import _batchcheck as bc
 import _convcheck as cc
 import _customnets as cn
+import _manycases as mc
 import _synth
 import test_precision as tp
 
@@ -121,7 +123,7 @@ class _BatchToy:
 
     def plant(self, name, v, **kw):
         L = self.launch[name]
-        assert L.kind == "conv"
+        assert L.kind in ("conv", "first")
         self.em.finish(L, name, v)
         rep = self.check([name], **kw)
         self.em.finish(L, name, self.em.pre[name])
@@ -212,6 +214,47 @@ def test_planted_7x7_halo_rows_read_from_the_previous_image(toys):
     rep = t.plant(name, v)
     assert rep.nfail > 0 and {f.img for f in rep.failures} == {1, 2} and {f.cls for f in rep.failures} == {"border"}, [str(f) for f in rep.failures]
     assert all(f.layer == name and f.y < 3 for f in rep.failures)
+
+
+def test_planted_image_index_wrong_from_the_8th_image_on(toys):
+    """img = (tile / tiles_per_img) & 7: images 8 and 9 of a launch of ten are computed from images 0 and 1.  Nothing below nine images per launch
+    can show it — the matrices of tests/test_batch_launches.py stopped at six.  Sampled as on the GPU (128 // images interior pixels per image)."""
+    B = 10
+    t = toys("fp16", B, W=64, H=32, stop="conv2_2")
+    assert t.frame.shape[0] == B and all(not np.array_equal(t.frame[i], t.frame[i & 7]) for i in (8, 9))
+    reps = t.check(only=list(t.weights) + [p for p in t.graph.pools if p in t.em.hi], n_interior=128 // B)
+    print([repr(rep.launch) for rep in reps])
+    assert len(reps) >= 4 and not [str(f) for rep in reps for f in rep.failures]      # conv1_1 .. conv2_2 and the pooling that the plan has materialised
+    for name in ("conv1_1", "conv2_1"):
+        v = t.em.pre[name].copy()
+        v[8:] = v[:2]
+        rep = t.plant(name, v, n_interior=128 // B)
+        assert rep.nfail > 0 and {f.img for f in rep.failures} == {8, 9} and all(f.layer == name for f in rep.failures), [str(f) for f in rep.failures]
+        v = t.em.pre[name].copy()
+        v[:8] = np.roll(v[:8], 1, axis=0)                                              # (the first eight alone: a defect the older matrices could see)
+        rep = t.plant(name, v, n_interior=128 // B)
+        assert rep.nfail > 0 and {f.img for f in rep.failures} == set(range(8))
+    # the bitwise comparer names the first wrong image of such a batch too
+    blob = t.em.blob("conv2_1")
+    singles = [blob[i:i + 1] for i in range(B)]
+    bad = blob.copy()
+    bad[8:] = bad[:2]
+    d = bc.compare_blob("conv2_1", bad, singles, 1)
+    assert d is not None and (d.frame, d.image) == (8, 8) and bc.compare_blob("conv2_1", blob, singles, 1) is None
+
+
+def test_many_image_batch_cases_are_what_they_are_named_for():
+    """tests/_manycases.py BATCH_MATRIX: (a) at least 10 images per launch from many scales at batch_frames 2, on the ring kernel's 64x128 tile;
+    (b) 32 images per launch; (c) batch_frames 16 at one scale — and the float64 cases are among them"""
+    r = _r()
+    t = mc.BATCH_MATRIX
+    plans = {n: cc.parse_plan(r.plan_summary(cc.batch_config(n, matrix=t)))[1] for n in t}
+    a, b, c = t["fp16_coco_96x64_5s_b2"], t["mixed_coco_64x48_16s_b2"], t["mixed_coco_64x48_b16"]
+    assert a[4] * a[6] >= 10 and a[6] == 2 and any(L.impl == "ring" and L.tile == (64, 128) for L in plans["fp16_coco_96x64_5s_b2"])
+    assert (b[4], b[6]) == (16, 2) and (c[4], c[6]) == (1, 16) and b[2:4] == c[2:4] == (64, 48)
+    assert set(mc.BATCH_FLOAT64) <= set(t) and len(t) == 3
+    for n, la in plans.items():               # every launch of a case holds all its images: wgs is a multiple of the image count
+        assert all(L.wgs % (t[n][4] * t[n][6]) == 0 for L in la if L.kind != "pool"), n
 
 
 def test_planted_swap_of_the_low_res_maps_of_two_frames():

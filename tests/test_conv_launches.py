@@ -16,7 +16,10 @@ sampled pixels; both are printed, profiles/conv_launch_check.txt has them for ev
 A second set of cases (tests/_customnets.py CUSTOM_MATRIX) runs graphs other than the built-in one through proto_path, at sizes of a few
 thousand pixels: 1x1 layers on the register-staged kernel, concat slices at odd channel offsets, output-channel tails other than 19 / 38 / 28,
 7x7 layers below 1/8 resolution, one convolution writing the low-res maps, a tensor with a lo and a q block (tests/test_conv_launches_cpu.py
-asserts what they reach)."""
+asserts what they reach).
+
+A third set (tests/_manycases.py CONV_MATRIX) runs plans of 7, 10 and 13 images per launch — 5 to 13 scales on nets of 64x48 to 160x96 — for
+the seven kernel classes the planner picks only there, the ring kernel's 64x128 tile in every mode among them; same body, same bound."""
 import time
 
 import numpy as np
@@ -24,6 +27,7 @@ import pytest
 
 import _convcheck as cc
 import _customnets as cn
+import _manycases as mc
 import _synth
 
 pytestmark = pytest.mark.gpu
@@ -83,3 +87,11 @@ def test_every_launch_alone_against_float64(name):
 def test_every_launch_of_a_custom_graph_alone_against_float64(case):
     gname, mode, W, H, N, B = case
     _check_every_launch(cn.case_id(case), cn.config(*case), cn.net(gname)[1], mode, N, B, 3)
+
+
+@pytest.mark.parametrize("name", list(mc.CONV_MATRIX))
+def test_every_launch_of_a_many_image_plan_alone_against_float64(name):
+    mode, model, W, H, N, gap, B, wseed = mc.CONV_MATRIX[name]
+    if model not in _graphs:
+        _graphs[model] = cc.builtin_graph(model)
+    _check_every_launch(name, cc.matrix_config(name, mc.CONV_MATRIX), _graphs[model], mode, N, B, 3)

@@ -13,12 +13,16 @@ catches what it is for.
 3. Graphs other than the built-in one (tests/_customnets.py, CUSTOM_MATRIX): the shape-dependent branches of the planner and of the epilogues
    that the built-in plans never take are reached (asserted feature by feature), the tile walks match the plans, a correct kernel emulated
    over every custom graph passes (which proves, among others, that no activation reaches the 112 at which the 2q bound ends), and the
-   defects planted on the new paths fail in the right layer."""
+   defects planted on the new paths fail in the right layer.
+4. Plans of 7 to 13 images per launch (tests/_manycases.py CONV_MATRIX): the seven kernel classes that only such plans run are reached, each by
+   the case named for it and by no plan of the three older matrices; the image counts 7, 10, 13, 16 and 32 occur; grids that are and are not
+   a multiple of 8 per kernel; the tile walks match the plans."""
 import numpy as np
 import pytest
 
 import _convcheck as cc
 import _customnets as cn
+import _manycases as mc
 import _synth
 import test_precision as tp
 
@@ -75,6 +79,8 @@ def test_tile_walks_match_the_workgroup_counts_of_the_plan(graphs):
     plans = [(name, graphs[model], n, b, r.plan_summary(cc.matrix_config(name))) for name, (mode, model, w, h, n, gap, b, seed) in cc.MATRIX.items()]
     plans += [(cn.case_id(c), cn.net(c[0])[1], c[4], c[5], r.plan_summary(cn.config(*c))) for c in CUSTOM_MATRIX]
     plans += [(name, graphs[model], n, b, r.plan_summary(cc.batch_config(name))) for name, (mode, model, w, h, n, gap, b, seed) in cc.BATCH_MATRIX.items()]   # tests/test_batch_launches.py: full batches
+    plans += [(name, graphs[model], n, b, r.plan_summary(cc.matrix_config(name, mc.CONV_MATRIX))) for name, (mode, model, w, h, n, gap, b, seed) in mc.CONV_MATRIX.items()]   # tests/_manycases.py: 7 to 32 images
+    plans += [(name, graphs[model], n, b, r.plan_summary(cc.batch_config(name, matrix=mc.BATCH_MATRIX))) for name, (mode, model, w, h, n, gap, b, seed) in mc.BATCH_MATRIX.items()]
     halos = set()
     for name, g, n, b, summary in plans:
         levels, launches = cc.parse_plan(summary)
@@ -502,3 +508,62 @@ def test_planted_dropped_lo_part_of_the_tensor_with_lo_and_q(custom):
     t.em.lo["f"] = keep
     assert _only(rep, {("f", "f")}), [str(f) for f in rep.failures]
     assert t.check(["f"])[0].nfail == 0
+
+
+# ------------------------------------------------------------------------------------------------------------
+# plans of many images per launch (tests/_manycases.py)
+# ------------------------------------------------------------------------------------------------------------
+def _old_classes(graphs):
+    """kernel classes of every plan of the three older matrices"""
+    r = _r()
+    old = set()
+    for name, t in cc.MATRIX.items():
+        old |= mc.classes(t[0], cc.parse_plan(r.plan_summary(cc.matrix_config(name)))[1])
+    for name, t in cc.BATCH_MATRIX.items():
+        old |= mc.classes(t[0], cc.parse_plan(r.plan_summary(cc.batch_config(name)))[1])
+    for c in CUSTOM_MATRIX:
+        old |= mc.classes(c[1], cc.parse_plan(r.plan_summary(cn.config(*c)))[1])
+    return old
+
+
+def test_many_image_cases_reach_the_seven_classes_no_older_case_runs(graphs):
+    r = _r()
+    old = _old_classes(graphs)
+    assert len(old) == 55
+    plans = {name: cc.parse_plan(r.plan_summary(cc.matrix_config(name, mc.CONV_MATRIX)))[1] for name in mc.CONV_MATRIX}
+    new = {name: mc.classes(mc.CONV_MATRIX[name][0], la) - old for name, la in plans.items()}
+    for cls, case in mc.NEW_CLASSES.items():      # first: a case taken out of CONV_MATRIX fails HERE, with the class it was added for in the message
+        assert cls not in old, f"{cls} is run by an older case"
+        reached_by = {name for name, cl in new.items() if cls in cl}
+        assert reached_by == {case}, f"class {cls} (added for: {case}) is reached by {sorted(reached_by) or 'no case'}"
+    assert len(mc.NEW_CLASSES) == 7 and set(mc.NEW_CLASSES.values()) == set(mc.CONV_MATRIX)
+    assert set().union(*new.values()) == set(mc.NEW_CLASSES)          # ... and the cases add nothing that is not on the list
+    # the ring kernel's 64x128 tile in every mode and pass label
+    assert {(c[0], c[5]) for c in mc.NEW_CLASSES if c[2:4] == ("ring", "64x128")} == {("fp16", "1"), ("fp32", "1"), ("mixed", "1"), ("mixed", "2q"), ("f16x3", "3aw")}
+    # its k-split is on record in the bound: KSPLIT 2, the reduction of one more partial
+    for la in plans.values():
+        for L in la:
+            if L.kind == "conv" and L.tile == (64, 128):
+                assert cc.ksplit_of(L) == 2
+    # the same plan runs the full batches of tests/test_batch_launches.py
+    assert mc.BATCH_MATRIX["fp16_coco_96x64_5s_b2"] == mc.CONV_MATRIX["fp16_coco_96x64_5s_b2"]
+    both = cc.parse_plan(r.plan_summary(cc.batch_config("fp16_coco_96x64_5s_b2", matrix=mc.BATCH_MATRIX)))[1]
+    assert ("fp16", "conv", "ring", "64x128", 128, "1", False) in mc.classes("fp16", both)
+
+
+def test_many_image_cases_reach_the_image_counts_and_grid_remainders(graphs):
+    r = _r()
+    entries = [(t, r.plan_summary(cc.matrix_config(n, mc.CONV_MATRIX))) for n, t in mc.CONV_MATRIX.items()]
+    entries += [(t, r.plan_summary(cc.batch_config(n, matrix=mc.BATCH_MATRIX))) for n, t in mc.BATCH_MATRIX.items()]
+    counts = {t[4] * t[6] for t, _ in entries}
+    assert mc.IMAGE_COUNTS <= counts, mc.IMAGE_COUNTS - counts
+    older = {t[4] * t[6] for t in list(cc.MATRIX.values()) + list(cc.BATCH_MATRIX.values())} | {c[4] * c[5] for c in CUSTOM_MATRIX}
+    assert max(older) == 6                                              # what the suite stopped at
+    assert max(t[4] for t, _ in entries) == 16 and max(t[6] for t, _ in entries) == 16     # the accepted limits of num_scales and batch_frames
+    for impl in ("ring", "reg", "pw2"):      # grids that are and are not a multiple of 8 workgroups, per kernel: the q / r split of the XCD remap
+        rem = {L.wgs % 8 == 0 for _, s in entries for L in cc.parse_plan(s)[1] if L.impl == impl}
+        assert rem == {True, False}, (impl, rem)
+    for t, s in entries:                      # conv_first: one workgroup per image row of every image
+        first = [L for L in cc.parse_plan(s)[1] if L.kind == "first"]
+        assert all(L.wgs == t[3] * t[4] * t[6] for L in first)
+    assert any(L.kind == "first" and L.wgs == 48 * 32 for t, s in entries for L in cc.parse_plan(s)[1])       # 32 images of 48 rows

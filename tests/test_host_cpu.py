@@ -69,6 +69,43 @@ BAD_GEOMETRY = [dict(start_scale=1.2), dict(start_scale=0.0), dict(start_scale=-
                 dict(net_w=650), dict(net_h=100), dict(net_w=0), dict(net_h=-16), dict(num_scales=0), dict(num_scales=17)]
 
 
+def _create_gets_past_the_argument_checks(**kw):
+    """rtp_engine_create with these arguments: True where the geometry is accepted (the engine exists, or only the device is missing: argument errors come
+    before RTP_ENODEV), False where it is refused with RTP_EINVAL"""
+    import caffe_rtpose_amd as r
+    try:
+        r.Engine(r.Config(**{**dict(net_w=160, net_h=96, frames_in_flight=1), **kw})).close()
+    except r.RtpError as err:
+        assert err.code in (r.RTP_EINVAL, -19), err
+        return err.code != r.RTP_EINVAL
+    return True
+
+
+def test_level_scales_are_computed_from_the_decimal_the_float_stands_for():
+    """rtp_config carries start_scale / scale_gap as floats, the reference's producer computes `float scale = START_SCALE - i*SCALE_GAP` from double flags
+    (rtpose.cpp:68-69, 359).  engine.cpp producer_flag reads each float as the shortest decimal that rounds to it, so the engine's range check (and its
+    level sizes, tests/test_many_scales.py) agree with rtp_preprocess_frame on the same decimals — seen here through the range check alone, no device:
+    0.9 - 3 * 0.3 is 1.1e-16 in double, a positive scale (a 16x16 level, as in the reference); the widened floats give 0.89999998 - 3 * 0.30000001 < 0."""
+    import caffe_rtpose_amd as r
+    assert np.float32(np.float64(np.float32(0.9)) - 3 * np.float64(np.float32(0.3))) < 0 < np.float32(0.9 - 3 * 0.3)
+    assert _create_gets_past_the_argument_checks(num_scales=4, start_scale=0.9, scale_gap=0.3)
+    img = np.zeros((48, 64, 3), np.uint8)
+    x, _, _ = r.preprocess_frame(img, 64, 48, 160, 96, 4, 0.9, 0.3)                        # the host function on the decimals: accepted too, last level 16x16
+    assert x.shape == (4, 3, 96, 160) and (x[3, 0] != 0).sum() == 16 * 16
+    # where the decimals give exactly 0 the scale is refused, widened or not: 0.9 - 4 * 0.225, 1 - 4 * 0.25 (exact in binary)
+    assert not _create_gets_past_the_argument_checks(num_scales=5, start_scale=0.9, scale_gap=0.225)
+    assert not _create_gets_past_the_argument_checks(num_scales=5, start_scale=1.0, scale_gap=0.25)
+    assert _create_gets_past_the_argument_checks(num_scales=4, start_scale=1.0, scale_gap=0.25)
+    # floats that are no short decimal (1/3, 0.7 - 2^-24, the float below 1, a nine-digit one) read as themselves to within half an ulp: accepted as before
+    for start, gap in ((1.0, float(np.float32(1) / np.float32(3))), (float(np.nextafter(np.float32(0.7), np.float32(0))), 0.1),
+                       (float(np.nextafter(np.float32(1), np.float32(0))), 0.3), (0.987654321, 0.123456789)):
+        assert _create_gets_past_the_argument_checks(num_scales=3, start_scale=start, scale_gap=gap), (start, gap)
+    # NaN / inf never fit (BAD_GEOMETRY has them one at a time): both at once, and a negative gap that would grow the levels past the net
+    for start, gap in ((float("nan"), float("nan")), (float("inf"), float("inf")), (float("-inf"), 0.3), (1.0, float("inf")), (1.0, -1e-3)):
+        assert not _create_gets_past_the_argument_checks(num_scales=2, start_scale=start, scale_gap=gap), (start, gap)
+    assert _create_gets_past_the_argument_checks(num_scales=1, start_scale=1.0, scale_gap=float("nan")) is False   # 0 * NaN is NaN: a NaN gap is refused at one scale too
+
+
 def test_out_of_contract_scales_and_net_sizes_are_einval_before_any_device_is_touched():
     """The reference CHECKs (rtpose.cpp:363-364: target <= net resolution) and dies inside cv::resize for a scale <= 0; the C ABI returns
     RTP_EINVAL from rtp_engine_create — also where no GPU exists: argument errors come before RTP_ENODEV — and from
