@@ -90,6 +90,7 @@ SIGNATURES = {
     "rtp_busy_probe": (C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.c_int]),
     "rtp_probe_dropped": (C.c_int, [vp, C.POINTER(C.c_long)]),
     "rtp_stamp_probe": (C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.c_int]),
+    "rtp_debug_stream_queues": (C.c_int, [vp, C.c_int, ip, fp, C.c_int, C.POINTER(C.c_long), C.c_int]),
     "rtp_submit": (C.c_int, [vp, fp, C.c_uint64]),
     "rtp_submit_device": (C.c_int, [vp, vp, C.c_uint64]),
     "rtp_submit_frame": (C.c_int, [vp, C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_uint64, fp]),

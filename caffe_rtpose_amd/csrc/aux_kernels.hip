@@ -265,4 +265,19 @@ hipError_t launch_export(int prec, const void* in, Geom g, int Cp, const int* ch
   return hipGetLastError();
 }
 
+// Queue probe (engine.cpp "hardware queues"): ONE wave waits `ticks` of the chip's 100 MHz wall clock (s_memrealtime, the clock KStamp
+// reads) and leaves {start, end}.  The wait ends by the clock alone — it reads no memory — and `ticks` is capped at 10 ms.
+__global__ void __launch_bounds__(64) queue_wait_kernel(long ticks, unsigned long long* out) {
+  if (ticks > 1000000) ticks = 1000000;
+  const unsigned long long t0 = wall_clock64();
+  unsigned long long t = t0;
+  while ((long)(t - t0) < ticks) { __builtin_amdgcn_s_sleep(8); t = wall_clock64(); }
+  if (threadIdx.x == 0) { out[0] = t0; out[1] = t; }
+}
+
+hipError_t launch_queue_wait(long ticks, unsigned long long* out2, hipStream_t stream) {
+  hipLaunchKernelGGL(queue_wait_kernel, dim3(1), dim3(64), 0, stream, ticks, out2);
+  return hipGetLastError();
+}
+
 }  // namespace rtp

@@ -175,6 +175,8 @@ hipError_t launch_maxpool(int prec, const void* in, Geom gi, int Cpi, void* out,
 // q_off != 0 (and no lo block): the exported value is hi + fp8 lo part / 2^12.
 hipError_t launch_export(int prec, const void* in, Geom g, int Cp, const int* chmap_dev, int C, int lo_off, int q_off, float* out,
                          hipStream_t stream);
+// one wave waits `ticks` of the 100 MHz wall clock (at most 10 ms) and writes {start, end} to out2 (queue probe, measurement only)
+hipError_t launch_queue_wait(long ticks, unsigned long long* out2, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------
 // Pre-processing on the device (row a1): see preproc.hip

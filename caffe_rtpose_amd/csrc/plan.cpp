@@ -678,6 +678,72 @@ long step_workgroups(const Plan& p, const Step& s) {
 
 int plan_contexts(int frames_in_flight, int B) { return (frames_in_flight + B - 1) / B + (B > 1 ? 1 : 0); }
 
+// F frames in flight hold the fewest slots of the most contexts when the oldest batch has one frame left and the newest has one frame in:
+// B - 1 empty slots in all, so ceil((F + B - 1) / B) contexts.  open_slot opens the LOWEST idle context, so with in-order collects the
+// contexts from this number on are never opened (tests/test_hwq_placement.py simulates the loop); they exist for out-of-order callers.
+int plan_busy_contexts(int frames_in_flight, int B) { return std::min(plan_contexts(frames_in_flight, B), (frames_in_flight + 2 * B - 2) / B); }
+
+const char* plan_stream_arrangement(int frames_in_flight, int B, int hw_queues) {
+  return (plan_contexts(frames_in_flight, B) <= hw_queues || B == 1) ? "one_per_context" : "per_frame_chains";
+}
+
+// The busy contexts fit the queues and the allocated ones do not; batches of 2 (a conv stream and one chain stream per queue: the candidate
+// pool of engine.cpp place_streams is sized for that), no unused pad streams in between
+bool plan_queue_placement(int frames_in_flight, int B, int hw_queues, int pad_streams) {
+  const int busy = plan_busy_contexts(frames_in_flight, B);
+  return B > 1 && busy <= hw_queues && hw_queues < plan_contexts(frames_in_flight, B) && pad_streams == 0 && B <= 2 && hw_queues <= 16;
+}
+
+// Streams that ran alone on their queue in a pair probe are on different queues; `share[a * n + b]` says that candidates a and b waited for
+// each other (1), ran side by side (0) or that the probe could not tell (-1).  Picks `busy` groups of `per` candidates each such that every
+// group shares one queue and no two groups share one: pick[g * per + j] = candidate index.  False when the map does not allow it.
+bool plan_pick_queue_groups(const std::vector<int>& share, int n, int busy, int per, std::vector<int>* pick) {
+  pick->clear();
+  if (n <= 0 || (int)share.size() != n * n || busy < 1 || per < 1) return false;
+  std::vector<int> cls(n, -1);   // queue class of every candidate: the lowest candidate it shares a queue with
+  for (int a = 0; a < n; ++a) {
+    for (int b = 0; b < a && cls[a] < 0; ++b) {
+      if (share[a * n + b] < 0) return false;
+      if (share[a * n + b] == 1) cls[a] = cls[b];
+    }
+    if (cls[a] < 0) cls[a] = a;
+  }
+  for (int a = 0; a < n; ++a)      // the relation must be an equivalence: anything else is a mis-measurement
+    for (int b = 0; b < a; ++b)
+      if (share[a * n + b] < 0 || (share[a * n + b] == 1) != (cls[a] == cls[b])) return false;
+  for (int rep = 0; rep < n && (int)pick->size() < busy * per; ++rep) {
+    if (cls[rep] != rep) continue;
+    std::vector<int> members;
+    for (int a = rep; a < n && (int)members.size() < per; ++a) if (cls[a] == rep) members.push_back(a);
+    if ((int)members.size() == per) pick->insert(pick->end(), members.begin(), members.end());
+  }
+  if ((int)pick->size() != busy * per) { pick->clear(); return false; }
+  return true;
+}
+
+}  // namespace rtp
+
+// The stream rules above for the tests (host only; not part of the public header).  out = {contexts, busy contexts, 1 where every context
+// has one stream, 1 where the busy contexts' streams are placed on queues of their own}
+extern "C" int rtp_internal_stream_rules(int frames_in_flight, int B, int hw_queues, int pad_streams, int out[4]) {
+  if (frames_in_flight < 1 || B < 1 || hw_queues < 1 || !out) return RTP_EINVAL;
+  out[0] = rtp::plan_contexts(frames_in_flight, B);
+  out[1] = rtp::plan_busy_contexts(frames_in_flight, B);
+  out[2] = !strcmp(rtp::plan_stream_arrangement(frames_in_flight, B, hw_queues), "one_per_context");
+  out[3] = rtp::plan_queue_placement(frames_in_flight, B, hw_queues, pad_streams);
+  return RTP_OK;
+}
+// plan_pick_queue_groups: share = n x n ints (1 one queue, 0 side by side, -1 unknown), pick = busy * per ints; returns 1 / 0
+extern "C" int rtp_internal_pick_queue_groups(const int* share, int n, int busy, int per, int* pick) {
+  if (!share || !pick || n < 1 || n > 64) return RTP_EINVAL;
+  std::vector<int> got;
+  if (!rtp::plan_pick_queue_groups(std::vector<int>(share, share + (size_t)n * n), n, busy, per, &got)) return 0;
+  std::copy(got.begin(), got.end(), pick);
+  return 1;
+}
+
+namespace rtp {
+
 std::string describe_plan(const Plan& p, int N, int B, int frames_in_flight, int hw_queues) {
   std::ostringstream o;
   o << "model " << p.model << " parts " << p.num_parts << " max_peaks " << p.max_peaks << " heat_channels " << p.heat_channels << "\n";
@@ -686,7 +752,10 @@ std::string describe_plan(const Plan& p, int N, int B, int frames_in_flight, int
   o << "arena_bytes " << p.arena_bytes << " weights_bytes " << p.weights_bytes << " tensors " << p.tensors.size() << "\n";
   {  // which streams a batch context gets (alloc_ctx; "hardware queues" above): one for everything when the runtime's hardware queues suffice
     const int nctx = plan_contexts(frames_in_flight, B);
-    o << "streams contexts " << nctx << " hw_queues " << hw_queues << " arrangement " << ((nctx <= hw_queues || B == 1) ? "one_per_context" : "per_frame_chains") << "\n";
+    // busy: the contexts an in-order caller ever opens (plan_busy_contexts); where they fit the queues and the allocated ones do not, the
+    // per-frame chains are placed on their own context's queue (engine.cpp place_streams)
+    o << "streams contexts " << nctx << " hw_queues " << hw_queues << " arrangement " << plan_stream_arrangement(frames_in_flight, B, hw_queues)
+      << " busy " << plan_busy_contexts(frames_in_flight, B) << "\n";
   }
   double gflop = 0, mfma_gflop = 0;
   for (auto& s : p.steps) {

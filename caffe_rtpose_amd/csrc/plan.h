@@ -125,6 +125,12 @@ inline long conv_workgroups(long tiles_per_img, int NI, int coutp, int BN, int n
 long step_workgroups(const Plan& p, const Step& s);   // of a full batch
 
 int plan_contexts(int frames_in_flight, int B);   // batches in flight (+1 being filled)
+int plan_busy_contexts(int frames_in_flight, int B);   // ... of which a caller that collects in order ever opens this many
+const char* plan_stream_arrangement(int frames_in_flight, int B, int hw_queues);   // "one_per_context" / "per_frame_chains"
+// per_frame_chains with the busy contexts' streams placed on hardware queues of their own: busy <= queues < contexts
+bool plan_queue_placement(int frames_in_flight, int B, int hw_queues, int pad_streams);
+// which candidate streams become the busy contexts' streams, from the measured "these two share a queue" map (pure; plan.cpp)
+bool plan_pick_queue_groups(const std::vector<int>& share, int n, int busy, int per, std::vector<int>* pick);
 
 // the text of rtp_plan_summary
 std::string describe_plan(const Plan& p, int N, int B, int frames_in_flight, int hw_queues);

@@ -892,6 +892,21 @@ class Engine:
             lib.rtp_stamp_probe(self.h, -1, _f(out), n)
         return out
 
+    def stream_queues(self, reps=5):
+        """rtp_debug_stream_queues: (owner [(context, frame)] per stream with (-1, 0) = the legacy stream, ratio [n][n] float32 or None when reps = 0, opens per context).
+        ratio[a][b] = median pair time / single wait: ~1 = the two streams run side by side, ~2 = they share a hardware queue."""
+        nctx = 64
+        opens = (C.c_long * nctx)(*([-1] * nctx))
+        n = lib.rtp_debug_stream_queues(self.h, 0, None, None, 0, opens, nctx)
+        if n < 0:
+            raise RtpError(n, lib.rtp_last_error(self.h).decode())
+        owner = (C.c_int * max(n, 1))()
+        ratio = np.zeros((n, n), np.float32)
+        k = lib.rtp_debug_stream_queues(self.h, reps, owner, _f(ratio) if reps else None, n, None, 0)
+        if k < 0:
+            raise RtpError(k, lib.rtp_last_error(self.h).decode())
+        return [(owner[i] // 256, owner[i] % 256) if owner[i] >= 0 else (-1, 0) for i in range(n)], (ratio if reps else None), [o for o in opens if o >= 0]
+
     def bench_dominant_conv(self, iters=50):
         ms = C.c_float()
         fl = C.c_double()

@@ -427,6 +427,16 @@ int rtp_probe_dropped(const rtp_engine* e, long out[3]);
  * assemble kernel, 200 + 2 j + k = frame j's warp / area-pad kernel.  1 - union(spans) / wall = the share of the time with NO kernel on the
  * chip (bench.py `idle_frac_kernel_stamps`).  No reference counterpart (measurement only).  Returns the number of triples. */
 int rtp_stamp_probe(rtp_engine* e, int enable, float* spans, int cap);
+/* Which of the engine's streams share a hardware queue of the HIP runtime, MEASURED (idle engine only, measurement only).  The engine's
+ * distinct streams are numbered context by context: a context's conv stream, then the chain streams of its frames that have one.
+ * owner[k] = 256 * context + frame of stream k (frame 0 = the conv stream); the last stream is the legacy stream, on which the engine's
+ * synchronous hipMemset / hipMemcpy calls run: owner -1.  With reps >= 1 and ratio != NULL every pair (a, b) is timed
+ * `reps` times: a one-workgroup kernel that waits 200 us on the chip's wall clock runs on both streams at once, and
+ * ratio[a * n + b] = median(first start .. last end of the pair) / (one wait alone): about 1 = side by side on different queues, about 2 =
+ * one waited for the other on the same queue.  opens[c] (may be NULL) = batches opened on context c since creation.  Returns n, the
+ * number of streams; fills the arrays only when cap >= n (opens: the first min(opens_cap, contexts) entries), and times nothing when
+ * reps = 0 or ratio = NULL. */
+int rtp_debug_stream_queues(rtp_engine* e, int reps, int* owner, float* ratio, int cap, long* opens, int opens_cap);
 /* Host float -> OCP e4m3 (round to nearest even, clamped to +-448): how the fp8 weight copies of split layers are made. */
 int rtp_debug_f32_to_e4m3(const float* in, unsigned char* out, int n);
 
