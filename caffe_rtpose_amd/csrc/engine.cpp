@@ -12,43 +12,12 @@
 //   * weights are re-laid out per layer for the kernel's [tap][chunk][cout][k] staging order;
 //   * frames_in_flight contexts (stream + arena) let consecutive frames overlap, which is what
 //     fills 256 CUs when one frame's layers are too small to.
-#include <hip/hip_runtime.h>
+// The engine's side of the two GPU codecs lives in engine_jpeg.cpp, the load-time calibration in engine_calib.cpp; what the three files
+// share is in engine_internal.h.
+#include "engine_internal.h"
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <deque>
-#include <fstream>
-#include <map>
-#include <mutex>
-#include <sstream>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "../../include/rtpose_mi355x.h"
-#include "jpeg_plan.h"
-#include "kernels.h"
-#include "netdef.h"
-#include "plan.h"
-
-using namespace rtp;
-
-void rtp_internal_cubic_tab2d(short* tab);
-double rtp_internal_warp_inverse_scale(double s);
-bool rtp_internal_area_fast(int sw, int sh, int dw, int dh, int* ix, int* iy);
-int rtp_internal_area_table(int ssize, int dsize, std::vector<int>* start, std::vector<int>* si, std::vector<float>* alpha);
-void rtp_internal_linear_area_table(int ssize, int dsize, std::vector<int>* tab);
-size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64], unsigned char* header, size_t header_cap,
-                               unsigned short huff_code[4][256], unsigned char huff_size[4][256]);
-extern "C" double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
-extern "C" int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
-                                    double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
+namespace rtp {
+namespace eng __attribute__((visibility("hidden"))) {
 
 // The producer computes its level scales from the DOUBLE flags (DEFINE_double start_scale / scale_gap, rtpose.cpp:68-69; `float scale =
 // START_SCALE - i*SCALE_GAP`, :359), rtp_config and rtp_set_scales carry floats (ImResizeLayer's own types).  A float that was a decimal flag
@@ -59,7 +28,7 @@ extern "C" int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int 
 // The result is within half a float ulp of the widened float, and it IS the widened float for values that are exact in binary (1, 0.25, 0.8125).
 // Nine significant digits round-trip every float, so the loop always returns; the line behind it is for a C library that does not.
 // snprintf and strtof / strtod read LC_NUMERIC: another decimal point changes the text, not the value — both sides use the same locale.
-static double producer_flag(float v) {
+double producer_flag(float v) {
   if (!(v == v) || v - v != 0.f) return (double)v;   // NaN / inf: refused by scales_fit
   char buf[40];
   for (int prec = 1; prec <= 9; ++prec) {
@@ -70,234 +39,10 @@ static double producer_flag(float v) {
 }
 
 namespace {
-
 thread_local std::string g_create_error = "";
-
-// HIP refuses every synchronous legacy-stream operation (hipMemset, hipMemcpy, hipDeviceSynchronize, ...) of ANY thread while ANY
-// stream of the process is capturing a graph ("operation would make the legacy stream depend on a capturing blocking stream"), whatever
-// the capture mode.  One engine per worker thread (rtpose.cpp:1463-1472) means engines are created, captured and torn down concurrently:
-// every capture and every such synchronous operation of this library happens under this one process-wide lock.  The per-frame path
-// (async copies, launches, event waits on the engine's own streams) never takes it.  Found by rtpose.bin --num_gpu 4 --devices 0,0,0,0.
-std::recursive_mutex g_sync_mutex;
-#define SYNC_GUARD std::lock_guard<std::recursive_mutex> sync_guard_(g_sync_mutex)
-
-// The GPU JPEG decoder's buffers (jpeg_dec.hip): one device allocation carved by JdLayout, the pinned staging of what the host sends
-// (the de-stuffed scan with its tables, or the host decoder's coefficients), and a pinned status word the last entropy kernel writes
-struct JdBufs {
-  unsigned char* dev = nullptr;
-  size_t dev_cap = 0;
-  unsigned char* host = nullptr;
-  size_t host_cap = 0;
-  unsigned* status_host = nullptr;
-  unsigned* status_host_dev = nullptr;
-};
-// One planned decode: what to copy, what to launch
-struct JdJob {
-  int path = RTP_JPEG_ENTROPY_HOST;
-  JdLayout L;
-  JdDev d = {};
-  JdRecon g = {};
-  int group = 0, mcus = 0;
-  size_t copy_bytes = 0, copy_dst = 0;   // pinned [0, copy_bytes) -> dev + copy_dst
-  short* coef = nullptr;
-  unsigned char* planes = nullptr;
-};
-constexpr int kJdSubBits = 512;      // S: bits per subsequence (profiles/r09_jpeg_decode.txt)
-constexpr int kJdGroup = 256;        // subsequences per workgroup
-constexpr int kJdMaxGroups = 512;    // most synchronisation launches one decode may enqueue (16 MB of scan at the defaults)
-constexpr size_t kJdStageCap = (size_t)64 << 20;   // staged scans above this take the host entropy path
-
-// One frame's post-processing state (a batch context carries batch_frames of them)
-struct Slot {
-  hipStream_t stream = nullptr;  // resize -> nms -> connect -> D2H of this frame (slot 0 shares the context's stream)
-  bool own_stream = false, preset_stream = false;
-  float* resized = nullptr;
-  float* peaks = nullptr;
-  int* strip_count = nullptr;
-  int* strip_list = nullptr;
-  float* cand_score = nullptr;
-  int* cand_ij = nullptr;
-  int* cand_count = nullptr;
-  int* cand_blk = nullptr;
-  int* conn = nullptr;
-  float* conn_score = nullptr;
-  int* conn_count = nullptr;
-  int* tickets = nullptr;       // connect_chain_kernel's tickets (num_limbs + 1 zeros)
-  float* joints = nullptr;
-  int* num_people = nullptr;
-  float* host_out = nullptr;  // pinned: [1 int as float slot][joints]
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // post start, resize, nms, connect, results on host
-  // deferred pre-processing (rtp_engine::prep_defer): the frame's H2D copy runs on the engine's copy stream; its warp / area kernels are
-  // enqueued on the batch's conv stream once the copy has COMPLETED (polled at the next API call; forced, with a stream wait, at launch)
-  hipEvent_t ev_copy = nullptr;
-  bool copy_pending = false;
-  int pend_w = 0, pend_h = 0;
-  bool pend_yuv = false;                // the staged frame is YUV (rtp_submit_frame_yuv): yuv_dev describes its planes behind the BGR image in frame_dev,
-  YuvView yuv_dev = {};                 // and the conversion kernel runs in front of the warp
-  // rtp_submit_frame_jpeg: the staged frame is a JPEG file's scan (or its coefficients) in jd's pinned buffer; the decode kernels run in
-  // front of the warp and write the BGR image to frame_dev.  jpeg_status: the collect of this frame reads jd's status word.
-  bool pend_jpeg = false, jpeg_status = false;
-  JdBufs jd;
-  JdJob jd_job;
-  unsigned char* frame_dev = nullptr;   // raw u8 frame (device) for rtp_submit_frame
-  unsigned char* frame_host = nullptr;  // pinned staging of the raw frame
-  size_t frame_cap = 0;
-  unsigned char* disp_dev = nullptr;    // display-resolution u8 image
-  const unsigned char* disp_cur = nullptr;  // this frame's display image: disp_dev, or frame_dev itself when the frame already HAS the display size (fit scale 1: the
-                                            // cubic warp samples at integer positions with weights (0, 1, 0, 0) = a copy; skipped, bit for bit the same image)
-  bool has_disp = false;                // disp_dev holds this frame's display image (rtp_submit_frame, device path)
-  unsigned char* render_dev = nullptr;  // cfg.render: display image with the pose overlay
-  unsigned char* render_host = nullptr; // pinned copy of it
-  float* render_tab = nullptr;
-  // rtp_submit_frame_device: ev_ready = the producer's stream at the submit (the staging stream waits on it), ev_read = the caller's frame
-  // has been read (the producer's stream waits on it).  rtp_collect_rendered_device: ev_export = the export of render_dev through the
-  // caller's view is done; while export_pending, the context's next batch (whose render overwrites render_dev) waits on it first.
-  hipEvent_t ev_ready = nullptr, ev_read = nullptr, ev_export = nullptr;
-  bool export_pending = false;
-  // rtp_set_render_jpeg: the GPU encoder's scratch for render_dev (allocated lazily, like render_dev) and its pinned output, which the
-  // encoder's last kernel writes: [jpeg_cap bytes] the file after the header, then its length (4 bytes)
-  JpegBufs jpeg;
-  unsigned char* jpeg_host = nullptr;
-  unsigned char* jpeg_host_dev = nullptr;   // the same memory as the device addresses it
-  size_t jpeg_cap = 0;
-  uint64_t tag = 0;
-  bool busy = false;
-};
-
-// One batch in flight: the conv stack runs once over filled*num_scales images
-struct Ctx {
-  hipStream_t stream = nullptr, spare_stream = nullptr;
-  std::vector<hipStream_t> pad_streams;   // never used: they only take hardware-queue slots in the runtime's round-robin (alloc_ctx)
-  unsigned char* arena = nullptr;
-  float* input = nullptr;     // device NCHW fp32, batch_frames * num_scales images
-  float* host_in = nullptr;   // pinned staging
-  float* lowres = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around the conv stack
-  // Input staging (H2D of a frame, device pre-processing, or the copy of a resident input) runs on its own stream, so that a frame's copy
-  // is under way while earlier batches compute and the conv queue never holds a barrier that waits for PCIe; ev_in = staged input complete
-  hipStream_t in_stream = nullptr;
-  hipEvent_t ev_in = nullptr;
-  bool in_pending = false;
-  std::vector<Slot> slot;
-  int filled = 0;        // frames staged in the open batch
-  bool launched = false;
-  // RTP_EXEC_GRAPH: the whole batch (conv stack, every frame's post-processing chain, D2H) captured once
-  // per (timed?, frames in the batch) and replayed; gev = {before, after} the replay on `stream`
-  hipGraphExec_t gexec[17] = {};
-  hipEvent_t gev[2] = {nullptr, nullptr};
-  hipEvent_t ev_stage0 = nullptr;         // rtp_busy_probe: recorded in front of the batch's first input staging
-  bool stage0_set = false;
-  bool graph_run = false;                 // the batch in flight was ONE graph replay incl. post-processing (collect waits on gev[1])
-  bool graph_conv = false;                // the conv stack was a replay, the post-processing chains were launched eagerly
-  // rtp_get_batch_blob: the batch launch_batch ran last on this context (the one-frame taps record one frame); nothing on the frame path reads it
-  int last_nframes = 0;
-  bool last_own_input = false;            // its conv stack read cx.input (not the caller's tensor of an eager batch_frames 1 rtp_submit_device)
-  std::vector<uint64_t> last_tags;        // in slot order
-  long opens = 0;                         // batches opened on this context (rtp_debug_stream_queues)
-  unsigned long long* stamps = nullptr;   // rtp_stamp_probe: STAMP_SLOTS x {~first workgroup start, last workgroup end} of this context's launches (kernels.h KStamp)
-  bool stamps_dirty = false;
-};
-
 }  // namespace
 
-struct rtp_engine {
-  rtp_config cfg;
-  std::string proto_path, weights_path;
-  NetDef net;
-  Plan plan;   // plan.h: everything build_plan produced for (net, cfg, N, B, mode, split_rules, split_fp8)
-  float nms_threshold = 0.05f, inter_threshold = 0.05f, min_subset_score = 0.4f;
-  int inter_min_above = 9, min_subset_cnt = 3;
-  float start_scale = 1.f, scale_gap = 0.3f;
-  bool weights_pending = false;   // rtp_config.defer_weights: no weights yet (zero arena, no graphs): the net must not run until an import / peer copy
-  bool calib_fell_back = false;   // rtp_calibrate_precision ended in RTP_PREC_F16X3 (its last resort)
-  bool broken = false;   // a re-plan failed and the previous plan could not be restored: no contexts; every entry point fails, destroy works
-  int N = 1;    // images per frame (num_scales)
-  int B = 1;    // frames per batch (cfg.batch_frames)
-  int open_ctx = -1;  // context whose batch is being filled
-  std::vector<std::vector<float>> w_ref, b_ref;           // Caffe layout per conv
-  unsigned char* dweights = nullptr;
-  int* dchmap = nullptr;  // scratch for export
-  std::vector<Ctx> ctx;
-  std::deque<int> fifo;
-  float last_ms[5] = {0, 0, 0, 0, 0};
-  std::string err;
-  bool time_dominant = false;
-  double dom_ms_total = 0;
-  long dom_launches = 0;
-  double dom_ms_pass[4] = {0, 0, 0, 0};   // the same, by MFMA passes of the launch (split-precision layers run 2-3)
-  long dom_n_pass[4] = {0, 0, 0, 0};
-  // rtp_kernel_timing: one HIP event pair around every dominant-class launch (recorded on the launch's own stream; batches are
-  // launched eagerly while it is on).  Nothing here compares clocks of different XCDs.
-  std::vector<hipEvent_t> tev;            // 2 * pairs
-  std::vector<unsigned char> tev_pass;    // MFMA passes (1..3) of the launch behind pair i
-  std::vector<short> tev_step;            // plan step of the launch behind pair i
-  // rtp_busy_probe: when on, every batch's stream-busy spans (first input staging .. end of its conv stack on the batch's stream; start ..
-  // end of each frame's post-processing chain incl. the D2H of the joints on the frame's stream) are read back at collect time as
-  // milliseconds since `busy_base` — an UNPROFILED account of when the engine had work on the GPU (bench.py: gpu_busy)
-  bool busy_probe = false;
-  // rtp_set_render_jpeg: 0 off, else the quality every rendered frame is encoded at on the GPU; the display-size header and quantisers
-  int jpeg_quality = 0;
-  std::vector<unsigned char> jpeg_hdr;
-  JpegQuant jpeg_q;
-  // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
-  JpegBufs jenc;
-  unsigned char* jenc_host = nullptr;
-  unsigned char* jenc_host_dev = nullptr;
-  size_t jenc_cap = 0;
-  hipEvent_t jenc_ev = nullptr;
-  // rtp_decode_jpeg_device: the engine's own decoder buffers; jd_sub_bits / jd_group = S and subsequences per workgroup of every decode
-  // (rtp_internal_jpeg_knobs; tests and the sweep of tools/bench_jpeg_decode.py change them)
-  JdBufs jdec;
-  hipEvent_t jdec_ev = nullptr;
-  int jd_sub_bits = kJdSubBits, jd_group = kJdGroup;
-  hipEvent_t busy_base = nullptr;
-  std::vector<float> busy_spans;          // [n][3]: kind (0 conv stream, 1 post chain), start ms, end ms
-  // rtp_stamp_probe: device-side residency stamps of every kernel of the per-frame path (no profiler, no events)
-  bool stamp_probe = false;
-  unsigned long long stamp_base = 0;      // wall-clock ticks (100 MHz) of the first harvested start
-  std::vector<float> stamp_spans;         // [n][3]: slot id (see stamp_slot), start us, end us relative to stamp_base
-  bool time_all = false;                  // rtp_kernel_timing(3): an event pair around EVERY step of a full batch, not only the dominant class
-  std::vector<double> step_ms;            // per plan step: event-timed milliseconds / launches of the timing pass (rtp_kernel_timing_steps)
-  std::vector<long> step_n;
-  int tev_next = 0;
-  long probe_dropped[3] = {0, 0, 0};      // rtp_probe_dropped: timing pairs not recorded (table full), busy spans dropped (cap), graph-replayed batches the busy probe skipped
-  static const int TEV_PAIRS = 4096;
-  // device-side pre-processing (row a1)
-  const short* warp_tab_dev = nullptr;  // inside prep_tables
-  std::vector<AreaScale> area_scales;   // device pointers inside prep_tables
-  unsigned char* prep_tables = nullptr;
-  bool gpu_prep_ok = false;
-  bool use_graph = true;
-  bool split_fp8 = true;    // RTP_SPLIT_FP8=0: split layers run three fp16 passes everywhere
-  bool graph_post = false;  // RTP_GRAPH_POST=1: also capture the per-frame post-processing chains + D2H into the batch graph
-  // 0 (default) = a batch's inputs are staged on its conv stream; 1 = on a stream of their own (created after all others), 2 = ... of high
-  // priority.  Measured (profiles/r04_input_staging.txt, host u8 frames, 7 in flight): 0: 1045 frames/s, 1: 880-890, 2: 880-990 — the
-  // runtime multiplexes streams onto 4 hardware queues, and a staging stream's barrier (kernel behind a PCIe copy) then blocks whichever
-  // conv / post-processing stream shares its queue.  Experiments build only (RTP_IN_STREAM).
-  // 1 = the connect chain (pairs -> match -> assemble) as ONE launch (connect_chain_kernel: tickets; experiments build, RTP_CHAIN_CONNECT=1).
-  // Bit-identical (GPU test) and no faster: 67.5 vs 67.7 us for one planted person, 97.5 vs 96.5 us on noise maps, 1033 vs 1039 frames/s —
-  // on a chip of 8 XCDs the device-scope release / acquire between the phases is an L2 write-back / invalidate, i.e. what a kernel boundary
-  // costs (with a fence per THREAD instead of per workgroup the first version took 24 us more).  profiles/r04_experiments.txt.
-  int chain_connect = 0;
-  int in_stream_mode = 0;
-  // 1 = deferred pre-processing (experiments build, RTP_PREP_DEFER): a frame's copy goes to a copy-only stream, its kernels are enqueued on
-  // the conv stream once the copy has COMPLETED (polled at the next API call), a full batch whose last frame was just copied is launched at
-  // the next call — so that no kernel of a compute queue sits behind a barrier that waits for PCIe.  Bit-identical (GPU test), and not
-  // adopted: what it gains depends on WHEN the caller makes its next call.  tools/bench_input.py: COCO +0.7 %, MPI (batches of 5) +5 %;
-  // inside bench.py's loop (a collect right behind the submit that completes a batch): COCO -5 %, MPI +-0; waiting for the copy on the
-  // host instead: -23 % (hipEventSynchronize ~0.3 ms per call).  profiles/r04_input_staging.txt.
-  int prep_defer = 0;
-  hipStream_t copy_stream = nullptr;   // H2D copies only (created after every other stream)
-  std::deque<int> pending_launch;      // full batches whose last frame's copy was still in flight when it was committed (launched by pump())
-  int mode = 0;  // rtp_config.precision (RTP_PREC_*); plan.prec selects the kernels' element type (0 fp16, 1 fp32)
-  std::string split_rules;
-  int nctx_full = 1;            // batch contexts of the configured pipeline (a calibration trial runs with one)
-  std::vector<hipStream_t> placed;   // place_streams -> alloc_ctx: the busy contexts' streams, batch_frames per context, each context's on one hardware queue
-  std::string calib_report;     // what rtp_calibrate_precision last did (rtp_calibration_report)
-  std::vector<void*> user_bufs; // rtp_device_alloc allocations still alive
-};
-
-namespace {
+std::recursive_mutex g_sync_mutex;
 
 // Flags of the engine's events.  sync = the event is waited for (by the host or by another stream) after work whose results the waiter reads;
 // the others only take time stamps between launches.  Experiments build: RTP_EV_NOFENCE=1 creates the time-stamp events of the per-frame path
@@ -320,13 +65,7 @@ int fail(rtp_engine* e, int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIPCHK(e, call)                                                                             \
-  do {                                                                                              \
-    hipError_t _s = (call);                                                                         \
-    if (_s != hipSuccess)                                                                           \
-      return fail((e), RTP_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_s), __FILE__, __LINE__); \
-  } while (0)
-
+namespace {
 // ---- weight packing -------------------------------------------------------------------------
 // float -> OCP e4m3 (round to nearest even, subnormals kept, clamped to +-448): what v_cvt_pk_fp8_f32 does after the clamp
 unsigned char f32_to_e4m3(float x) {
@@ -679,9 +418,6 @@ int launch_pw2_step(rtp_engine* e, Ctx& cx, const Step& s, int nimg) {
   return RTP_OK;
 }
 
-}  // namespace
-
-namespace {
 bool is_dominant_class(const rtp_engine* e, const Step& s) {
   if (s.type != 1 || e->plan.dominant_step < 0) return false;
   const ConvOp& a = e->plan.convs[s.a];
@@ -816,10 +552,6 @@ int run_post_fused(rtp_engine* e, Ctx& cx, int sj, hipEvent_t ev_nms) {
   return RTP_OK;
 }
 
-int jpeg_alloc(rtp_engine* e, int w, int h, JpegBufs* b, unsigned char** host, unsigned char** host_dev, size_t* cap);
-void jd_free(JdBufs* b);
-int jd_launch(rtp_engine* e, unsigned long long* stamp, const JdJob& job, const FrameView& dst, hipStream_t stream);
-
 // one batch on one context: conv stack over nframes*num_scales images, then per frame (on the
 // frame slot's stream) resize -> nms -> connect -> D2H of the joints
 int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bool materialize, bool cap, int part = 3) {
@@ -922,7 +654,6 @@ int capture_batch(rtp_engine* e, Ctx& cx, int nframes, hipGraphExec_t* out) {
   return RTP_OK;
 }
 
-int flush_prep(rtp_engine* e, Ctx& cx, bool force);
 int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bool materialize = false) {
   int rc;
   cx.last_nframes = nframes;
@@ -1274,67 +1005,6 @@ int alloc_ctx(rtp_engine* e, Ctx& cx) {
   return RTP_OK;
 }
 
-// ---- the GPU JPEG encoder (jpeg_enc.hip) ----------------------------------------------------------------------------------------
-// A w x h encoder: one device allocation of scratch (with the Huffman code tables, filled here) and one pinned buffer that the last
-// kernel writes: the file after its header, padded to 16 bytes, then the length.  Called under SYNC_GUARD (hipMalloc, hipMemcpy).
-void jpeg_free(JpegBufs* b, unsigned char** host, size_t* cap) {
-  if (b->base) (void)hipFree(b->base);
-  if (*host) (void)hipHostFree(*host);
-  *b = JpegBufs();
-  *host = nullptr;
-  *cap = 0;
-}
-bool jpeg_size_ok(int w, int h) {  // every bit offset of the entropy-coded segment fits 31 bits
-  return w >= 1 && h >= 1 && w <= 65535 && h <= 65535 && (double)((w + 15) / 16) * ((h + 15) / 16) * 6 * kJpegMaxBlockBits < 2147483648.0;
-}
-int jpeg_alloc(rtp_engine* e, int w, int h, JpegBufs* b, unsigned char** host, unsigned char** host_dev, size_t* cap) {
-  jpeg_free(b, host, cap);
-  *host_dev = nullptr;
-  JpegBufs nb;
-  unsigned char* hb = nullptr;
-  unsigned char* hd = nullptr;
-  unsigned char qt[2][64], hdr[1024];
-  JpegHuffTab huff[4];
-  unsigned short code[4][256];
-  unsigned char size[4][256];
-  rtp_internal_jpeg_setup(w, h, 75, qt, hdr, sizeof hdr, code, size);
-  for (int t = 0; t < 4; ++t) { memcpy(huff[t].code, code[t], sizeof code[t]); memcpy(huff[t].size, size[t], sizeof size[t]); }
-  const size_t c = (rtp_jpeg_max_bytes(w, h) + 15) / 16 * 16;   // >= the stuffed data + EOI rounded up to 16 bytes
-  const char* what = "hipMalloc";
-  hipError_t st = hipMalloc(&nb.base, jpeg_bufs_bytes(w, h, nullptr));
-  if (st == hipSuccess) {
-    jpeg_bufs_bytes(w, h, &nb);
-    what = "hipMemcpy";
-    st = hipMemcpy(nb.huff, huff, sizeof huff, hipMemcpyHostToDevice);
-  }
-  if (st == hipSuccess) { what = "hipHostMalloc"; st = hipHostMalloc((void**)&hb, c + 16, hipHostMallocMapped | hipHostMallocCoherent); }
-  if (st == hipSuccess) { what = "hipHostGetDevicePointer"; st = hipHostGetDevicePointer((void**)&hd, hb, 0); }
-  if (st != hipSuccess) {   // nothing half-made stays behind
-    if (nb.base) (void)hipFree(nb.base);
-    if (hb) (void)hipHostFree(hb);
-    return fail(e, RTP_EHIP, "JPEG encoder buffers for %d x %d: %s failed: %s", w, h, what, hipGetErrorString(st));
-  }
-  *b = nb;
-  *host = hb;
-  *host_dev = hd;
-  *cap = c;
-  return RTP_OK;
-}
-// the quantisers of `quality` (jcdctmgr.c divides by 8 Q) and the header of a w x h file
-void jpeg_tables(int w, int h, int quality, JpegQuant* q, std::vector<unsigned char>* hdr) {
-  unsigned char qt[2][64], hb[1024];
-  unsigned short code[4][256];
-  unsigned char size[4][256];
-  const size_t hl = rtp_internal_jpeg_setup(w, h, quality, qt, hb, sizeof hb, code, size);
-  hdr->assign(hb, hb + hl);
-  for (int t = 0; t < 2; ++t)
-    for (int i = 0; i < 64; ++i) {
-      const uint64_t dv = (uint64_t)qt[t][i] << 3;
-      q->recip[t][i] = (unsigned)(((1ull << 32) + dv - 1) / dv);
-      q->half[t][i] = (unsigned short)(dv >> 1);
-    }
-}
-
 void free_ctx(Ctx& cx) {
   if (cx.stream) (void)hipStreamSynchronize(cx.stream);
   if (cx.in_stream && cx.in_stream != cx.stream) { (void)hipStreamSynchronize(cx.in_stream); (void)hipStreamDestroy(cx.in_stream); }
@@ -1367,6 +1037,7 @@ void free_ctx(Ctx& cx) {
   for (hipStream_t d : cx.pad_streams) if (d) (void)hipStreamDestroy(d);
   cx = Ctx();
 }
+}  // namespace
 
 int use_device(rtp_engine* e) {
   if (e->broken) return fail(e, RTP_EHIP, "this engine lost its plan in a failed re-plan and can only be destroyed");
@@ -1374,6 +1045,7 @@ int use_device(rtp_engine* e) {
   return RTP_OK;
 }
 
+namespace {
 // A captured batch graph bakes every by-value kernel argument (ConvParams::wq_exp of the fp8-compensated layers; with
 // RTP_GRAPH_POST=1 also the thresholds and scales of the post-processing chains).  Whoever changes one of those drops the
 // graphs; launch_batch re-captures on the next batch.  Needs an idle engine.
@@ -1515,11 +1187,12 @@ int launch_prep_kernels(rtp_engine* e, Ctx& cx, int sj, int w, int h, hipStream_
   HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, e->cfg.disp_w, e->cfg.disp_h, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, stream));
   return RTP_OK;
 }
+}  // namespace
 
 // raw u8 BGR frame (host), or — yuv != null — the planes of a host YUV frame -> frame slot sj of cx.input on the device
 // jpeg: the frame is the file planned into sl.jd_job (staged in sl.jd's pinned buffer); frame_dev receives the decoded image
-int enqueue_preprocess(rtp_engine* e, Ctx& cx, int sj, const unsigned char* bgr, int w, int h, float* frame_scale, const YuvView* yuv = nullptr,
-                       bool jpeg = false) {
+int enqueue_preprocess(rtp_engine* e, Ctx& cx, int sj, const unsigned char* bgr, int w, int h, float* frame_scale, const YuvView* yuv,
+                       bool jpeg) {
   Slot& sl = cx.slot[sj];
   const size_t fbytes = (size_t)w * h * 3;
   size_t yuv_off = 0;
@@ -1554,134 +1227,6 @@ int enqueue_preprocess(rtp_engine* e, Ctx& cx, int sj, const unsigned char* bgr,
   HIPCHK(e, hipMemcpyAsync(cdst, csrc, cbytes, hipMemcpyHostToDevice, cx.in_stream));
   if ((rc = launch_prep_kernels(e, cx, sj, w, h, cx.in_stream))) return rc;
   cx.in_pending = true;
-  return RTP_OK;
-}
-
-// ---- the GPU JPEG decoder (jpeg_dec.hip) -------------------------------------------------------------------------------------------
-void jd_free(JdBufs* b) {
-  if (b->dev) (void)hipFree(b->dev);
-  if (b->host) (void)hipHostFree(b->host);
-  if (b->status_host) (void)hipHostFree(b->status_host);
-  *b = JdBufs();
-}
-
-// Room in the decoder's buffers; the first `keep` bytes of the pinned buffer survive its growth.  Rare (the first file of a slot, or a
-// larger one): under the creation lock, and hipFree synchronises the device.
-int jd_ensure(rtp_engine* e, JdBufs* b, size_t host_bytes, size_t dev_bytes, size_t keep) {
-  if (host_bytes <= b->host_cap && dev_bytes <= b->dev_cap && b->status_host) return RTP_OK;
-  SYNC_GUARD;
-  if (!b->status_host) {
-    HIPCHK(e, hipHostMalloc((void**)&b->status_host, 64, hipHostMallocDefault));
-    HIPCHK(e, hipHostGetDevicePointer((void**)&b->status_host_dev, b->status_host, 0));
-    *b->status_host = 0xffffffffu;
-  }
-  if (host_bytes > b->host_cap) {
-    const size_t cap = round_up_sz(host_bytes + host_bytes / 4, 4096);
-    unsigned char* nh = nullptr;
-    HIPCHK(e, hipHostMalloc((void**)&nh, cap, hipHostMallocDefault));
-    if (keep && b->host) memcpy(nh, b->host, std::min(keep, b->host_cap));
-    if (b->host) (void)hipHostFree(b->host);
-    b->host = nh; b->host_cap = cap;
-  }
-  if (dev_bytes > b->dev_cap) {
-    const size_t cap = round_up_sz(dev_bytes + dev_bytes / 4, 4096);
-    if (b->dev) (void)hipFree(b->dev);
-    b->dev = nullptr; b->dev_cap = 0;
-    HIPCHK(e, hipMalloc((void**)&b->dev, cap));
-    b->dev_cap = cap;
-  }
-  return RTP_OK;
-}
-
-void jd_fill_recon(const JpegGeom& g, JdRecon* r, long* plane_bytes) {
-  memset(r, 0, sizeof *r);
-  r->W = g.W; r->H = g.H; r->ncomp = g.ncomp; r->rgb = g.rgb; r->hmax = g.hmax; r->vmax = g.vmax;
-  long off = 0;
-  int blocks = 0;
-  for (int c = 0; c < g.ncomp; ++c) {
-    r->h[c] = g.h[c]; r->v[c] = g.v[c]; r->bw[c] = g.bw[c]; r->bh[c] = g.bh[c]; r->dw[c] = g.dw[c]; r->dh[c] = g.dh[c];
-    r->coef_off[c] = blocks;
-    blocks += g.bw[c] * g.bh[c];
-    r->plane_off[c] = off;
-    off += (long)round_up_sz((size_t)g.bw[c] * 8 * g.bh[c] * 8, 256);
-    memcpy(r->qn[c], g.qn[c], sizeof r->qn[c]);
-  }
-  r->blocks = blocks;
-  *plane_bytes = off;
-}
-
-// Parse the file, stage what the device needs in b's pinned buffer and describe the launches in *job.  No HIP work is enqueued.
-// Failures carry the code and the message of rtp_decode_image.
-int jd_plan(rtp_engine* e, const char* fn, const unsigned char* bytes, size_t n, int sub_bits, int group, bool force_host, JdBufs* b, JdJob* job) {
-  int rc;
-  const size_t wcap = std::min(kJdStageCap, round_up_sz(n + n / 2 + 64, 4));
-  if ((rc = jd_ensure(e, b, wcap, 0, 0))) return rc;
-  JpegPlan P;
-  try {
-    rc = jpeg_plan(bytes, n, sub_bits, reinterpret_cast<uint32_t*>(b->host), wcap / 4, force_host, &P);
-  } catch (const std::exception& ex) {
-    return fail(e, RTP_ENOMEM, "%s: %s", fn, ex.what());
-  }
-  if (rc) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
-  // one synchronisation launch is enqueued per workgroup of subsequences: a scan that would need more than kJdMaxGroups of them (a
-  // huge file, or tiny S / group from a test or a sweep) takes the host's entropy decoder instead of flooding the stream
-  if (P.path == RTP_JPEG_ENTROPY_DEVICE && (P.subs.size() + group - 1) / group > (size_t)kJdMaxGroups) {
-    try {
-      rc = jpeg_plan(bytes, n, sub_bits, nullptr, 0, true, &P);
-    } catch (const std::exception& ex) {
-      return fail(e, RTP_ENOMEM, "%s: %s", fn, ex.what());
-    }
-    if (rc) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
-  }
-  long plane_bytes = 0;
-  jd_fill_recon(P.g, &job->g, &plane_bytes);
-  const bool dev = P.path == RTP_JPEG_ENTROPY_DEVICE;
-  job->path = P.path;
-  job->group = group;
-  job->mcus = P.g.mcux * P.g.mcuy;
-  job->L = jd_layout(job->g.blocks, plane_bytes, dev ? P.nwords : 0, dev ? P.segs.size() : 0, dev ? P.subs.size() : 0, group);
-  const JdLayout& L = job->L;
-  const size_t coef_bytes = (size_t)job->g.blocks * 64 * sizeof(short);
-  if ((rc = jd_ensure(e, b, dev ? L.staged : coef_bytes, L.total, dev ? P.nwords * 4 : 0))) return rc;
-  job->coef = reinterpret_cast<short*>(b->dev + L.coef);
-  job->planes = b->dev + L.planes;
-  if (!dev) {
-    memcpy(b->host, P.coef.data(), coef_bytes);
-    job->copy_bytes = coef_bytes; job->copy_dst = L.coef;
-    return RTP_OK;
-  }
-  JdTables* tab = reinterpret_cast<JdTables*>(b->host + L.tab);
-  tab->scan = P.scan;
-  memcpy(tab->dc, P.dc, sizeof tab->dc);
-  memcpy(tab->ac, P.ac, sizeof tab->ac);
-  memcpy(b->host + L.segs, P.segs.data(), P.segs.size() * sizeof(JdSeg));
-  memcpy(b->host + L.subs, P.subs.data(), P.subs.size() * sizeof(JdSub));
-  job->copy_bytes = L.staged; job->copy_dst = 0;
-  JdDev& d = job->d;
-  d.tab = reinterpret_cast<const JdTables*>(b->dev + L.tab);
-  d.segs = reinterpret_cast<const JdSeg*>(b->dev + L.segs);
-  d.subs = reinterpret_cast<const JdSub*>(b->dev + L.subs);
-  d.words = reinterpret_cast<const uint32_t*>(b->dev + L.words);
-  d.nsub = (int)P.subs.size(); d.nwords = (int)P.nwords; d.ngroups = L.ngroups;
-  d.entry = reinterpret_cast<JdState*>(b->dev + L.entry);
-  d.exit_ = reinterpret_cast<JdState*>(b->dev + L.exit_);
-  d.count = reinterpret_cast<int*>(b->dev + L.count);
-  d.excl = reinterpret_cast<int*>(b->dev + L.excl);
-  d.gexit = reinterpret_cast<JdState*>(b->dev + L.gexit);
-  d.flags = reinterpret_cast<int*>(b->dev + L.flags);
-  d.status = reinterpret_cast<unsigned*>(b->dev + L.status);
-  d.status_out = b->status_host_dev;
-  d.coef = job->coef;
-  d.dcsum = reinterpret_cast<int*>(b->dev + L.dcsum);
-  return RTP_OK;
-}
-
-// The kernels of a planned decode on `stream` (behind the copy of its staged bytes): entropy decoding where the device does it,
-// then the reconstruction into the three named channels of dst
-int jd_launch(rtp_engine* e, unsigned long long* stamp, const JdJob& job, const FrameView& dst, hipStream_t stream) {
-  if (job.path == RTP_JPEG_ENTROPY_DEVICE)
-    HIPCHK(e, launch_jpeg_entropy(stamp, job.d, job.group, job.mcus, job.g.ncomp, job.g.blocks, stream));
-  HIPCHK(e, launch_jpeg_reconstruct(stamp, job.g, job.coef, job.planes, dst, stream));
   return RTP_OK;
 }
 
@@ -1742,6 +1287,7 @@ int check_caller_stream(rtp_engine* e, void* stream, const char* fn) {
   return RTP_OK;
 }
 
+namespace {
 // The memory behind the view: device memory of cfg.device_id, every addressed byte inside the allocation that holds data.  A failed
 // query is cleared from HIP's last error, so that the next launch of a valid call does not report it.
 // `what` names the pointer in the messages ("data", "y", "u", "v"); *avail = bytes from p to the end of its allocation.
@@ -1769,6 +1315,7 @@ int check_device_range(rtp_engine* e, const char* fn, const char* what, const vo
     return fail(e, RTP_EINVAL, "%s: the view addresses bytes up to %ld past %s, its allocation ends %zu bytes past %s", fn, hi, what, *avail, what);
   return RTP_OK;
 }
+}  // namespace
 
 int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long hi, int* layout) {
   size_t avail = 0;
@@ -1778,9 +1325,9 @@ int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long h
   return RTP_OK;
 }
 
+namespace {
 // rtp_yuv_view: the field checks of codecs.cpp (no HIP call: also for a NULL engine), then — check_yuv_memory — each plane on its own
 // (y, u and v may be three allocations): device memory of cfg.device_id, the last byte it addresses inside its allocation.
-extern "C" int rtp_internal_yuv_fields(const rtp_yuv_view* v, char* msg, size_t msg_len, long hi[3]);
 int check_yuv_fields(rtp_engine* e, const rtp_yuv_view* v, const char* fn, YuvView* yv, long hi[3]) {
   char msg[256];
   if (rtp_internal_yuv_fields(v, msg, sizeof msg, hi)) return fail(e, RTP_EINVAL, "%s: %s", fn, msg);
@@ -1921,6 +1468,12 @@ int materialize_plan(rtp_engine* e, int nctx, bool capture) {
   return RTP_OK;
 }
 
+// What the engine's plan depends on: the net and config it was created with, and the precision mode / split set calibration may change
+PlanInput plan_input(const rtp_engine* e) {
+  return {&e->net, e->cfg.net_w, e->cfg.net_h, e->N, e->B, e->mode, e->split_rules, e->split_fp8, e->cfg.keep_blobs};
+}
+}  // namespace
+
 // Drop the plan and everything on the device that was laid out for it; the reference weights (w_ref / b_ref), thresholds, scales and
 // the pre-processing tables stay.
 void drop_plan(rtp_engine* e) {
@@ -1934,11 +1487,6 @@ void drop_plan(rtp_engine* e) {
   e->open_ctx = -1;
   e->fifo.clear();
   e->pending_launch.clear();
-}
-
-// What the engine's plan depends on: the net and config it was created with, and the precision mode / split set calibration may change
-PlanInput plan_input(const rtp_engine* e) {
-  return {&e->net, e->cfg.net_w, e->cfg.net_h, e->N, e->B, e->mode, e->split_rules, e->split_fp8, e->cfg.keep_blobs};
 }
 
 // Re-plan an idle engine for another precision mode / split set (load-time calibration).  light = one context, no graph capture.
@@ -1964,6 +1512,8 @@ int need_weights(rtp_engine* e) {
   if (e->weights_pending) return fail(e, RTP_EINVAL, "this engine was created with defer_weights = 1 and has no weights yet: rtp_weight_blob_import or rtp_copy_weights_from first");
   return RTP_OK;
 }
+
+namespace {
 // ... and once the weights are there, the launch graphs of every context are captured (what materialize_plan does for other engines)
 int weights_delivered(rtp_engine* e) {
   if (!e->weights_pending) return RTP_OK;
@@ -1976,6 +1526,7 @@ int weights_delivered(rtp_engine* e) {
         if ((rc = capture_batch(e, c, nf, &c.gexec[nf]))) return rc;
   return RTP_OK;
 }
+}  // namespace
 
 // ---- batching: frames are staged into the open context; a full batch is launched at once ----------
 int open_slot(rtp_engine* e, int* ci, int* sj) {
@@ -1999,6 +1550,8 @@ int open_slot(rtp_engine* e, int* ci, int* sj) {
   *sj = e->ctx[e->open_ctx].filled;
   return RTP_OK;
 }
+
+namespace {
 int launch_open(rtp_engine* e) {
   if (e->open_ctx < 0) return RTP_OK;
   Ctx& cx = e->ctx[e->open_ctx];
@@ -2006,12 +1559,9 @@ int launch_open(rtp_engine* e) {
   if (cx.filled == 0) return RTP_OK;
   return launch_batch(e, cx, cx.filled, cx.input);
 }
-// Deferred pre-processing: launch the full batches that were waiting for their last frame's copy, oldest first.
-//   PUMP_POLL   launch what is ready (hipEventQuery), leave the rest for the next call            — rtp_submit*
-//   PUMP_HOST   wait for the copies ON THE HOST (<= one PCIe copy, ~55 us), then launch             — rtp_collect, which is about to block for a
-//               whole frame anyway: a batch must not sit un-launched behind that wait
-//   PUMP_STREAM launch now, the conv stream waits for the copies                                   — somebody needs this very batch (rtp_flush)
-enum { PUMP_POLL = 0, PUMP_HOST = 1, PUMP_STREAM = 2 };
+}  // namespace
+
+// (the modes: PUMP_* in engine_internal.h)
 int pump(rtp_engine* e, int mode) {
   while (!e->pending_launch.empty()) {
     Ctx& cx = e->ctx[e->pending_launch.front()];
@@ -2045,11 +1595,124 @@ int commit_slot(rtp_engine* e, int ci, int sj, uint64_t tag) {
   return RTP_OK;
 }
 
+// ---- synchronous taps (context 0; require an idle engine) ---------------------------------------
+int need_idle(rtp_engine* e) {
+  if (!e) return RTP_EINVAL;
+  if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "parity taps need an idle engine (collect %zu frames first)", e->fifo.size());
+  int rc;
+  if ((rc = use_device(e))) return rc;
+  for (Ctx& cx : e->ctx)   // the taps reuse context 0's buffers on the host's clock: no export of a rendered image may still read them
+    for (Slot& sl : cx.slot)
+      if (sl.export_pending) {
+        HIPCHK(e, hipEventSynchronize(sl.ev_export));
+        sl.export_pending = false;
+      }
+  return RTP_OK;
+}
+
+namespace {
+// What every submit variant does before it stages its frame: the device, the weights, the batches deferred pre-processing left
+// un-launched, a slot of the open batch, the busy probe's mark in front of the batch's first staging and — frame: the variants that
+// stage a u8 / YUV frame — the kernels of an earlier frame of this batch whose copy is done by now.  device_prep: the variants that
+// read the caller's device memory have no host fallback and refuse where device pre-processing is unavailable.
+int begin_submit(rtp_engine* e, bool frame, bool device_prep, int* ci, int* sj) {
+  int rc;
+  if ((rc = use_device(e))) return rc;
+  if ((rc = need_weights(e))) return rc;
+  if (device_prep && !e->gpu_prep_ok) return fail(e, RTP_EINVAL, "device pre-processing unavailable for this configuration (a level would be enlarged)");
+  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
+  if ((rc = open_slot(e, ci, sj))) return rc;
+  Ctx& cx = e->ctx[*ci];
+  if (e->busy_probe && *sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
+  if (frame && e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;
+  return RTP_OK;
+}
+
+void stage_ms(rtp_engine* e, Ctx& cx, Slot& sl) {
+  if (cx.graph_run) {  // events recorded inside a capture carry no time: only the whole replay is bracketed
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, cx.gev[0], cx.gev[1]);
+    for (int i = 0; i < 4; ++i) e->last_ms[i] = 0.f;
+    e->last_ms[4] = ms;
+    return;
+  }
+  hipEvent_t start = cx.graph_conv ? cx.gev[0] : cx.ev[0];  // the conv stack's own start event lives inside the replay
+  hipEvent_t a[5] = {start, sl.ev[0], sl.ev[1], sl.ev[2], start};
+  hipEvent_t b[5] = {cx.ev[1], sl.ev[1], sl.ev[2], sl.ev[3], sl.ev[4]};
+  for (int i = 0; i < 5; ++i) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, a[i], b[i]);
+    e->last_ms[i] = ms;
+  }
+}
 }  // namespace
+
+int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* rendered, bool want_render) {
+  if (!e) return RTP_EINVAL;
+  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
+  int rc;
+  if ((rc = use_device(e))) return rc;
+  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
+  Ctx& cx = e->ctx[ci];
+  Slot& sl = cx.slot[sj];
+  if (e->prep_defer) {
+    if ((rc = pump(e, PUMP_STREAM))) return rc;   // nothing stays un-launched while this call blocks for a frame (a host-side wait for the copy
+                                                  // was measured: hipEventSynchronize costs ~0.3 ms per call here, 1010 -> 777 frames/s)
+    if (e->open_ctx >= 0 && e->open_ctx != ci && (rc = flush_prep(e, e->ctx[e->open_ctx], false))) return rc;
+  }
+  if (!cx.launched && (rc = launch_open(e))) return rc;  // the oldest frame sits in a partial batch
+  HIPCHK(e, hipEventSynchronize(cx.graph_run ? cx.gev[1] : sl.ev[4]));
+  e->fifo.pop_front();
+  sl.busy = false;
+  bool any = false;
+  for (Slot& s : cx.slot) any = any || s.busy;
+  if (!any) { cx.launched = false; cx.filled = 0; }
+  int n;
+  memcpy(&n, sl.host_out, sizeof(int));
+  if (tag) *tag = sl.tag;
+  stage_ms(e, cx, sl);
+  if (e->busy_probe && e->busy_base && cx.graph_run) e->probe_dropped[2]++;
+  if (e->busy_probe && e->busy_base && !cx.graph_run && e->busy_spans.size() >= 3 * 65536) e->probe_dropped[1]++;
+  if (e->busy_probe && e->busy_base && !cx.graph_run && e->busy_spans.size() < 3 * 65536) {
+    float t0 = 0.f, t1 = 0.f;
+    if (sj == 0 && cx.stage0_set && hipEventElapsedTime(&t0, e->busy_base, cx.ev_stage0) == hipSuccess &&
+        hipEventElapsedTime(&t1, e->busy_base, cx.ev[1]) == hipSuccess) { e->busy_spans.push_back(0.f); e->busy_spans.push_back(t0); e->busy_spans.push_back(t1); }
+    if (hipEventElapsedTime(&t0, e->busy_base, sl.ev[0]) == hipSuccess && hipEventElapsedTime(&t1, e->busy_base, sl.ev[4]) == hipSuccess) {
+      e->busy_spans.push_back(1.f); e->busy_spans.push_back(t0); e->busy_spans.push_back(t1);
+    }
+  }
+  if (sl.jpeg_status) {   // rtp_submit_frame_jpeg: what the entropy kernels found in the scan
+    sl.jpeg_status = false;
+    const unsigned st = *sl.jd.status_host;
+    if (st != 0xffffffffu) {
+      if (num_people) *num_people = 0;
+      return fail(e, RTP_EIO, "rtp_submit_frame_jpeg (tag %llu): %s (block %u of the scan); the frame is dropped", (unsigned long long)sl.tag,
+                  jpeg_entropy_message((int)(st & 3u)), st >> 2);
+    }
+  }
+  if (n < 0) {
+    if (num_people) *num_people = 0;
+    return fail(e, RTP_ERANGE, "connect: a PAF sample coordinate fell outside the net resolution (the reference CHECK-fails here, rtpose.cpp:928)");
+  }
+  if (n > RTP_MAX_PEOPLE) n = RTP_MAX_PEOPLE;
+  if (num_people) *num_people = n;
+  if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->plan.num_parts * 3 * sizeof(float));
+  if (want_render) {
+    if (!e->cfg.render) return fail(e, RTP_EINVAL, "rtp_collect_rendered needs rtp_config.render = 1");
+    if (!sl.has_disp || (rendered && !sl.render_host))
+      return fail(e, RTP_EINVAL, "no display image for this frame: submit it with rtp_submit_frame (device pre-processing)");
+    if (rendered) memcpy(rendered, sl.render_host, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3);
+  }
+  return RTP_OK;
+}
+
+}  // namespace eng
+}  // namespace rtp
 
 // =================================================================================================
 // C-ABI
 // =================================================================================================
+
 extern "C" {
 
 int rtp_config_default(rtp_config* cfg) {
@@ -2243,7 +1906,6 @@ int rtp_engine_info(const rtp_engine* e, int* num_parts, int* max_peaks, int* he
   return RTP_OK;
 }
 
-static int need_idle(rtp_engine* e);
 int rtp_set_thresholds(rtp_engine* e, float nms_threshold, float connect_inter_threshold, int connect_inter_min_above_threshold,
                        int connect_min_subset_cnt, float connect_min_subset_score) {
   SYNC_GUARD;
@@ -2299,12 +1961,8 @@ int rtp_set_scales(rtp_engine* e, float start_scale, float scale_gap) {
 int rtp_submit_device(rtp_engine* e, const float* d_in, uint64_t tag) {
   if (!e || !d_in) return RTP_EINVAL;
   int rc, ci, sj;
-  if ((rc = use_device(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
-  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  if ((rc = begin_submit(e, false, false, &ci, &sj))) return rc;
   Ctx& cx = e->ctx[ci];
-  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
   const size_t bytes = (size_t)e->N * 3 * e->cfg.net_h * e->cfg.net_w * sizeof(float);
   if (e->B == 1 && !e->use_graph) {  // eager: no staging copy, the conv stack reads the caller's tensor
     cx.slot[0].tag = tag;
@@ -2324,12 +1982,8 @@ int rtp_submit_device(rtp_engine* e, const float* d_in, uint64_t tag) {
 int rtp_submit(rtp_engine* e, const float* h_in, uint64_t tag) {
   if (!e || !h_in) return RTP_EINVAL;
   int rc, ci, sj;
-  if ((rc = use_device(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
-  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  if ((rc = begin_submit(e, false, false, &ci, &sj))) return rc;
   Ctx& cx = e->ctx[ci];
-  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
   const size_t bytes = (size_t)e->N * 3 * e->cfg.net_h * e->cfg.net_w * sizeof(float);
   memcpy((char*)cx.host_in + sj * bytes, h_in, bytes);
   if (e->prep_defer) {   // the copy on the copy-only stream; the conv stream learns about it when it has completed (flush_prep / pump)
@@ -2352,13 +2006,8 @@ int rtp_submit(rtp_engine* e, const float* h_in, uint64_t tag) {
 int rtp_submit_frame(rtp_engine* e, const unsigned char* bgr, int w, int h, uint64_t tag, float* frame_scale) {
   if (!e || !bgr || w < 1 || h < 1) return RTP_EINVAL;
   int rc, ci, sj;
-  if ((rc = use_device(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
-  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  if ((rc = begin_submit(e, true, false, &ci, &sj))) return rc;
   Ctx& cx = e->ctx[ci];
-  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
-  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier frame of this batch whose copy is done by now
   cx.slot[sj].has_disp = e->gpu_prep_ok;
   if (e->gpu_prep_ok) {
     if ((rc = enqueue_preprocess(e, cx, sj, bgr, w, h, frame_scale))) return rc;
@@ -2384,14 +2033,8 @@ int rtp_submit_frame_device(rtp_engine* e, const rtp_frame_view* frame, void* st
   if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
   if ((rc = check_caller_stream(e, stream, fn))) return rc;
   if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
-  if ((rc = use_device(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (!e->gpu_prep_ok) return fail(e, RTP_EINVAL, "device pre-processing unavailable for this configuration (a level would be enlarged)");
-  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
-  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  if ((rc = begin_submit(e, true, true, &ci, &sj))) return rc;
   Ctx& cx = e->ctx[ci];
-  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
-  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier host frame of this batch whose copy is done by now
   if ((rc = enqueue_preprocess_view(e, cx, sj, fv, layout, (hipStream_t)stream, frame_scale))) return rc;
   cx.slot[sj].has_disp = true;
   return commit_slot(e, ci, sj, tag);
@@ -2428,13 +2071,8 @@ int rtp_submit_frame_yuv(rtp_engine* e, const rtp_yuv_view* frame, uint64_t tag,
       return fail(e, RTP_ENOMEM, "%s: host conversion: %s", fn, ex.what());
     }
   }
-  if ((rc = use_device(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
-  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  if ((rc = begin_submit(e, true, false, &ci, &sj))) return rc;
   Ctx& cx = e->ctx[ci];
-  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
-  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier frame of this batch whose copy is done by now
   cx.slot[sj].has_disp = true;
   if ((rc = enqueue_preprocess(e, cx, sj, nullptr, yv.w, yv.h, frame_scale, &yv))) return rc;
   return commit_slot(e, ci, sj, tag);
@@ -2450,14 +2088,8 @@ int rtp_submit_frame_yuv_device(rtp_engine* e, const rtp_yuv_view* frame, void* 
   if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
   if ((rc = check_caller_stream(e, stream, fn))) return rc;
   if ((rc = check_yuv_memory(e, fn, yv, hi))) return rc;
-  if ((rc = use_device(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (!e->gpu_prep_ok) return fail(e, RTP_EINVAL, "device pre-processing unavailable for this configuration (a level would be enlarged)");
-  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
-  if ((rc = open_slot(e, &ci, &sj))) return rc;
+  if ((rc = begin_submit(e, true, true, &ci, &sj))) return rc;
   Ctx& cx = e->ctx[ci];
-  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
-  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier host frame of this batch whose copy is done by now
   if ((rc = enqueue_preprocess_yuv_view(e, cx, sj, yv, (hipStream_t)stream, frame_scale))) return rc;
   cx.slot[sj].has_disp = true;
   return commit_slot(e, ci, sj, tag);
@@ -2483,141 +2115,6 @@ int rtp_convert_yuv_device(rtp_engine* e, const rtp_yuv_view* src, const rtp_fra
   return RTP_OK;
 }
 
-// ---- JPEG files decoded on the GPU ---------------------------------------------------------------------------------------------------
-// rtp_decode_jpeg_device with the test knobs: sub_bits = S (0: the engine's), group = subsequences per workgroup (0: the engine's),
-// force_host = 1: the host's entropy decoder whatever the file.  rounds (may be NULL): [0] launches of the synchronisation kernel that
-// did work, [1] launches enqueued.  Not part of the public header.
-extern "C" int rtp_internal_jpeg_decode_device(rtp_engine* e, const unsigned char* jpeg_host, size_t n, const rtp_frame_view* dst, void* stream,
-                                               int sub_bits, int group, int force_host, int* entropy_path, int* rounds) {
-  static const char* fn = "rtp_decode_jpeg_device";
-  FrameView fv;
-  long hi = 0;
-  int rc, layout = LAYOUT_GENERIC;
-  if ((rc = check_view_fields(e, dst, fn, &fv, &hi))) return rc;
-  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
-  if (!jpeg_host) return fail(e, RTP_EINVAL, "%s: NULL file", fn);
-  if (n >= 8 && jpeg_host[0] == 0x89 && jpeg_host[1] == 'P') return fail(e, RTP_EINVAL, "%s: a PNG file (only JPEG is decoded on the GPU: rtp_decode_image)", fn);
-  if (sub_bits <= 0) sub_bits = e->jd_sub_bits;
-  if (group <= 0) group = e->jd_group;
-  if (sub_bits < 32 || sub_bits % 32 || group < 1 || group > 1024) return fail(e, RTP_EINVAL, "%s: S = %d bits (a multiple of 32), %d subsequences per workgroup (1..1024)", fn, sub_bits, group);
-  if ((rc = check_caller_stream(e, stream, fn))) return rc;
-  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
-  if ((rc = use_device(e))) return rc;
-  if (e->jdec_ev) HIPCHK(e, hipEventSynchronize(e->jdec_ev));
-  else HIPCHK(e, hipEventCreateWithFlags(&e->jdec_ev, hipEventDisableTiming));
-  JdJob job;
-  if ((rc = jd_plan(e, fn, jpeg_host, n, sub_bits, group, force_host != 0, &e->jdec, &job))) return rc;
-  if (job.g.W != fv.w || job.g.H != fv.h) return fail(e, RTP_EINVAL, "%s: the destination is %d x %d, the file %d x %d", fn, fv.w, fv.h, job.g.W, job.g.H);
-  if (entropy_path) *entropy_path = job.path;
-  const hipStream_t st = (hipStream_t)stream;
-  *e->jdec.status_host = 0xffffffffu;
-  HIPCHK(e, hipMemcpyAsync(e->jdec.dev + job.copy_dst, e->jdec.host, job.copy_bytes, hipMemcpyHostToDevice, st));
-  if ((rc = jd_launch(e, nullptr, job, fv, st))) return rc;
-  HIPCHK(e, hipEventRecord(e->jdec_ev, st));
-  HIPCHK(e, hipEventSynchronize(e->jdec_ev));
-  if (rounds) {
-    rounds[0] = rounds[1] = 0;
-    if (job.path == RTP_JPEG_ENTROPY_DEVICE) {
-      std::vector<int> flags((size_t)job.d.ngroups);
-      HIPCHK(e, hipMemcpy(flags.data(), job.d.flags, flags.size() * sizeof(int), hipMemcpyDeviceToHost));
-      rounds[1] = job.d.ngroups;
-      for (int r = 0; r < job.d.ngroups; ++r) if (r == 0 || flags[r - 1]) rounds[0] = r + 1;
-    }
-  }
-  const unsigned s = *e->jdec.status_host;
-  if (s != 0xffffffffu) return fail(e, RTP_EIO, "%s: %s", fn, jpeg_entropy_message((int)(s & 3u)));
-  return RTP_OK;
-}
-
-int rtp_decode_jpeg_device(rtp_engine* e, const unsigned char* jpeg_host, size_t n, const rtp_frame_view* dst, void* stream, int* entropy_path) {
-  return rtp_internal_jpeg_decode_device(e, jpeg_host, n, dst, stream, 0, 0, 0, entropy_path, nullptr);
-}
-
-// S and subsequences per workgroup of every later decode of this engine (0: back to the defaults)
-extern "C" int rtp_internal_jpeg_knobs(rtp_engine* e, int sub_bits, int group) {
-  if (!e) return RTP_EINVAL;
-  if (sub_bits < 0 || sub_bits % 32 || group < 0 || group > 1024) return fail(e, RTP_EINVAL, "rtp_internal_jpeg_knobs: S = %d, group = %d", sub_bits, group);
-  e->jd_sub_bits = sub_bits ? sub_bits : kJdSubBits;
-  e->jd_group = group ? group : kJdGroup;
-  return RTP_OK;
-}
-
-// The reconstruction kernels alone: coefficient blocks (host, component after component, natural order) and natural-order 16-bit
-// quantisers -> the view.  The device counterpart of codecs.cpp's rtp_internal_jpeg_reconstruct_host.
-extern "C" int rtp_internal_jpeg_geom(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, rtp::JpegGeom* g);
-extern "C" int rtp_internal_jpeg_reconstruct_device(rtp_engine* e, int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb,
-                                                    const short* coef_host, const rtp_frame_view* dst, void* stream) {
-  static const char* fn = "rtp_internal_jpeg_reconstruct_device";
-  FrameView fv;
-  long hi = 0;
-  int rc, layout = LAYOUT_GENERIC;
-  if ((rc = check_view_fields(e, dst, fn, &fv, &hi))) return rc;
-  if (!e || !coef_host) return fail(e, RTP_EINVAL, "%s: NULL argument", fn);
-  JpegGeom g;
-  if ((rc = rtp_internal_jpeg_geom(W, H, ncomp, hv, qn, rgb, &g))) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
-  if (fv.w != W || fv.h != H) return fail(e, RTP_EINVAL, "%s: the destination is %d x %d, the image %d x %d", fn, fv.w, fv.h, W, H);
-  if ((rc = check_caller_stream(e, stream, fn))) return rc;
-  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
-  if ((rc = use_device(e))) return rc;
-  if (e->jdec_ev) HIPCHK(e, hipEventSynchronize(e->jdec_ev));
-  else HIPCHK(e, hipEventCreateWithFlags(&e->jdec_ev, hipEventDisableTiming));
-  JdJob job;
-  long plane_bytes = 0;
-  jd_fill_recon(g, &job.g, &plane_bytes);
-  job.L = jd_layout(job.g.blocks, plane_bytes, 0, 0, 0, 1);
-  const size_t coef_bytes = (size_t)job.g.blocks * 64 * sizeof(short);
-  if ((rc = jd_ensure(e, &e->jdec, coef_bytes, job.L.total, 0))) return rc;
-  memcpy(e->jdec.host, coef_host, coef_bytes);
-  job.coef = reinterpret_cast<short*>(e->jdec.dev + job.L.coef);
-  job.planes = e->jdec.dev + job.L.planes;
-  const hipStream_t st = (hipStream_t)stream;
-  HIPCHK(e, hipMemcpyAsync(job.coef, e->jdec.host, coef_bytes, hipMemcpyHostToDevice, st));
-  if ((rc = jd_launch(e, nullptr, job, fv, st))) return rc;
-  HIPCHK(e, hipEventRecord(e->jdec_ev, st));
-  HIPCHK(e, hipEventSynchronize(e->jdec_ev));
-  return RTP_OK;
-}
-
-// rtp_submit_frame on the pixels rtp_decode_image makes of the file: the scan (or the host decoder's coefficients) crosses PCIe, the
-// decode kernels run in front of the warp.
-int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t n, uint64_t tag, float* frame_scale, int* w, int* h) {
-  static const char* fn = "rtp_submit_frame_jpeg";
-  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
-  if (!jpeg_host) return fail(e, RTP_EINVAL, "%s: NULL file", fn);
-  int rc, ci, sj;
-  const bool png = n >= 8 && jpeg_host[0] == 0x89 && jpeg_host[1] == 'P';
-  if (!e->gpu_prep_ok || png) {   // the host fallback of rtp_submit_frame, on the decoded pixels (a PNG file always is decoded there)
-    try {   // (nothing may unwind through the C boundary)
-      int iw = 0, ih = 0;
-      if ((rc = rtp_decode_image(jpeg_host, n, nullptr, 0, &iw, &ih))) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
-      std::vector<unsigned char> bgr((size_t)iw * ih * 3);
-      if ((rc = rtp_decode_image(jpeg_host, n, bgr.data(), bgr.size(), &iw, &ih))) return fail(e, rc, "%s: %s", fn, rtp_codec_last_error());
-      if (w) *w = iw;
-      if (h) *h = ih;
-      return rtp_submit_frame(e, bgr.data(), iw, ih, tag, frame_scale);
-    } catch (const std::exception& ex) {
-      return fail(e, RTP_ENOMEM, "%s: host decoding: %s", fn, ex.what());
-    }
-  }
-  if ((rc = use_device(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (e->prep_defer && (rc = pump(e, PUMP_POLL))) return rc;
-  if ((rc = open_slot(e, &ci, &sj))) return rc;
-  Ctx& cx = e->ctx[ci];
-  Slot& sl = cx.slot[sj];
-  // everything that can refuse the file happens before the slot is committed: a failed call leaves the open batch as it was
-  if ((rc = jd_plan(e, fn, jpeg_host, n, e->jd_sub_bits, e->jd_group, false, &sl.jd, &sl.jd_job))) return rc;
-  if (w) *w = sl.jd_job.g.W;
-  if (h) *h = sl.jd_job.g.H;
-  if (e->busy_probe && sj == 0 && (rc = busy_mark_stage0(e, cx))) return rc;
-  if (e->prep_defer && (rc = flush_prep(e, cx, false))) return rc;   // an earlier frame of this batch whose copy is done by now
-  sl.has_disp = true;
-  *sl.jd.status_host = 0xffffffffu;
-  if ((rc = enqueue_preprocess(e, cx, sj, nullptr, sl.jd_job.g.W, sl.jd_job.g.H, frame_scale, nullptr, true))) return rc;
-  sl.jpeg_status = sl.jd_job.path == RTP_JPEG_ENTROPY_DEVICE;
-  return commit_slot(e, ci, sj, tag);
-}
-
 // Launch a partially filled batch now (end of stream, or a latency-sensitive caller).
 int rtp_flush(rtp_engine* e) {
   if (!e) return RTP_EINVAL;
@@ -2627,7 +2124,6 @@ int rtp_flush(rtp_engine* e) {
   return launch_open(e);
 }
 
-static int need_idle(rtp_engine* e);
 // Parity tap: the device pre-processing alone (net input and display image back on the host).
 int rtp_debug_preprocess(rtp_engine* e, const unsigned char* bgr, int w, int h, float* net_input, unsigned char* display_bgr, float* frame_scale) {
   SYNC_GUARD;
@@ -2647,25 +2143,6 @@ int rtp_debug_preprocess(rtp_engine* e, const unsigned char* bgr, int w, int h, 
 
 int rtp_in_flight(const rtp_engine* e) { return e ? (int)e->fifo.size() : 0; }
 
-static void stage_ms(rtp_engine* e, Ctx& cx, Slot& sl) {
-  if (cx.graph_run) {  // events recorded inside a capture carry no time: only the whole replay is bracketed
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, cx.gev[0], cx.gev[1]);
-    for (int i = 0; i < 4; ++i) e->last_ms[i] = 0.f;
-    e->last_ms[4] = ms;
-    return;
-  }
-  hipEvent_t start = cx.graph_conv ? cx.gev[0] : cx.ev[0];  // the conv stack's own start event lives inside the replay
-  hipEvent_t a[5] = {start, sl.ev[0], sl.ev[1], sl.ev[2], start};
-  hipEvent_t b[5] = {cx.ev[1], sl.ev[1], sl.ev[2], sl.ev[3], sl.ev[4]};
-  for (int i = 0; i < 5; ++i) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a[i], b[i]);
-    e->last_ms[i] = ms;
-  }
-}
-
-static int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* rendered, bool want_render);
 int rtp_collect(rtp_engine* e, uint64_t* tag, float* joints, int* num_people) { return collect_impl(e, tag, joints, num_people, nullptr, false); }
 // rtp_collect + the display-resolution frame with the pose overlay (the image the reference hands to
 // cv::imwrite under --write_frames --no_text, rtpose.cpp:1179-1199, 1286-1293).  Needs
@@ -2675,64 +2152,6 @@ int rtp_collect_rendered(rtp_engine* e, uint64_t* tag, float* joints, int* num_p
     return fail(e, RTP_EINVAL, "rtp_collect_rendered: JPEG mode is on (rtp_set_render_jpeg %d), so the raw frame never reaches the host: "
                 "collect with rtp_collect_rendered_jpeg, or rtp_collect_rendered_device", e->jpeg_quality);
   return collect_impl(e, tag, joints, num_people, display_bgr, true);
-}
-static int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* rendered, bool want_render) {
-  if (!e) return RTP_EINVAL;
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  int rc;
-  if ((rc = use_device(e))) return rc;
-  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
-  Ctx& cx = e->ctx[ci];
-  Slot& sl = cx.slot[sj];
-  if (e->prep_defer) {
-    if ((rc = pump(e, PUMP_STREAM))) return rc;   // nothing stays un-launched while this call blocks for a frame (a host-side wait for the copy
-                                                  // was measured: hipEventSynchronize costs ~0.3 ms per call here, 1010 -> 777 frames/s)
-    if (e->open_ctx >= 0 && e->open_ctx != ci && (rc = flush_prep(e, e->ctx[e->open_ctx], false))) return rc;
-  }
-  if (!cx.launched && (rc = launch_open(e))) return rc;  // the oldest frame sits in a partial batch
-  HIPCHK(e, hipEventSynchronize(cx.graph_run ? cx.gev[1] : sl.ev[4]));
-  e->fifo.pop_front();
-  sl.busy = false;
-  bool any = false;
-  for (Slot& s : cx.slot) any = any || s.busy;
-  if (!any) { cx.launched = false; cx.filled = 0; }
-  int n;
-  memcpy(&n, sl.host_out, sizeof(int));
-  if (tag) *tag = sl.tag;
-  stage_ms(e, cx, sl);
-  if (e->busy_probe && e->busy_base && cx.graph_run) e->probe_dropped[2]++;
-  if (e->busy_probe && e->busy_base && !cx.graph_run && e->busy_spans.size() >= 3 * 65536) e->probe_dropped[1]++;
-  if (e->busy_probe && e->busy_base && !cx.graph_run && e->busy_spans.size() < 3 * 65536) {
-    float t0 = 0.f, t1 = 0.f;
-    if (sj == 0 && cx.stage0_set && hipEventElapsedTime(&t0, e->busy_base, cx.ev_stage0) == hipSuccess &&
-        hipEventElapsedTime(&t1, e->busy_base, cx.ev[1]) == hipSuccess) { e->busy_spans.push_back(0.f); e->busy_spans.push_back(t0); e->busy_spans.push_back(t1); }
-    if (hipEventElapsedTime(&t0, e->busy_base, sl.ev[0]) == hipSuccess && hipEventElapsedTime(&t1, e->busy_base, sl.ev[4]) == hipSuccess) {
-      e->busy_spans.push_back(1.f); e->busy_spans.push_back(t0); e->busy_spans.push_back(t1);
-    }
-  }
-  if (sl.jpeg_status) {   // rtp_submit_frame_jpeg: what the entropy kernels found in the scan
-    sl.jpeg_status = false;
-    const unsigned st = *sl.jd.status_host;
-    if (st != 0xffffffffu) {
-      if (num_people) *num_people = 0;
-      return fail(e, RTP_EIO, "rtp_submit_frame_jpeg (tag %llu): %s (block %u of the scan); the frame is dropped", (unsigned long long)sl.tag,
-                  jpeg_entropy_message((int)(st & 3u)), st >> 2);
-    }
-  }
-  if (n < 0) {
-    if (num_people) *num_people = 0;
-    return fail(e, RTP_ERANGE, "connect: a PAF sample coordinate fell outside the net resolution (the reference CHECK-fails here, rtpose.cpp:928)");
-  }
-  if (n > RTP_MAX_PEOPLE) n = RTP_MAX_PEOPLE;
-  if (num_people) *num_people = n;
-  if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->plan.num_parts * 3 * sizeof(float));
-  if (want_render) {
-    if (!e->cfg.render) return fail(e, RTP_EINVAL, "rtp_collect_rendered needs rtp_config.render = 1");
-    if (!sl.has_disp || (rendered && !sl.render_host))
-      return fail(e, RTP_EINVAL, "no display image for this frame: submit it with rtp_submit_frame (device pre-processing)");
-    if (rendered) memcpy(rendered, sl.render_host, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3);
-  }
-  return RTP_OK;
 }
 
 // rtp_collect_rendered with the image exported through a view of the caller's device memory.  Every refusal happens before the frame is
@@ -2768,110 +2187,9 @@ int rtp_collect_rendered_device(rtp_engine* e, uint64_t* tag, float* joints, int
   return RTP_OK;
 }
 
-// ---- JPEG files encoded on the GPU (jpeg_enc.hip: the bytes of rtp_encode_jpeg) ------------------------------------------------
-int rtp_set_render_jpeg(rtp_engine* e, int quality) {
-  if (!e) return fail(nullptr, RTP_EINVAL, "rtp_set_render_jpeg: NULL engine");
-  if (quality < 0 || quality > 100) return fail(e, RTP_EINVAL, "rtp_set_render_jpeg: quality %d (0 = off, 1..100)", quality);
-  if (quality && !e->cfg.render) return fail(e, RTP_EINVAL, "rtp_set_render_jpeg needs rtp_config.render >= 1");
-  if (quality && !jpeg_size_ok(e->cfg.disp_w, e->cfg.disp_h))
-    return fail(e, RTP_EINVAL, "rtp_set_render_jpeg: a %d x %d display image is too large for the GPU encoder", e->cfg.disp_w, e->cfg.disp_h);
-  if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "rtp_set_render_jpeg: %zu frames in flight (collect them first)", e->fifo.size());
-  if (quality) {
-    jpeg_tables(e->cfg.disp_w, e->cfg.disp_h, quality, &e->jpeg_q, &e->jpeg_hdr);
-    SYNC_GUARD;   // the raw frames' pinned copies are not written in JPEG mode (the engine is idle: no copy into them is pending)
-    for (Ctx& cx : e->ctx)
-      for (Slot& sl : cx.slot)
-        if (sl.render_host) { HIPCHK(e, hipHostFree(sl.render_host)); sl.render_host = nullptr; }
-  }
-  e->jpeg_quality = quality;
-  return RTP_OK;
-}
-
-// rtp_collect_rendered with the JPEG file of the rendered frame.  Every refusal happens before the frame is taken off the FIFO.
-int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* jpeg_host, size_t capacity,
-                              size_t* jpeg_bytes) {
-  static const char* fn = "rtp_collect_rendered_jpeg";
-  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
-  if (!e->jpeg_quality) return fail(e, RTP_EINVAL, "%s: JPEG mode is off (rtp_set_render_jpeg)", fn);
-  const size_t need = rtp_jpeg_max_bytes(e->cfg.disp_w, e->cfg.disp_h);
-  if (!jpeg_host || capacity < need)
-    return fail(e, RTP_EINVAL, "%s: capacity %zu, need rtp_jpeg_max_bytes(%d, %d) = %zu", fn, jpeg_host ? capacity : (size_t)0, e->cfg.disp_w,
-                e->cfg.disp_h, need);
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
-  Slot& sl = e->ctx[ci].slot[sj];
-  if (!sl.has_disp) return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", fn);
-  int rc;
-  if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
-  unsigned n = 0;
-  memcpy(&n, sl.jpeg_host + sl.jpeg_cap, sizeof n);
-  const size_t hl = e->jpeg_hdr.size();
-  if (hl + n > capacity) return fail(e, RTP_EHIP, "%s: the encoder reported %u bytes, more than its bound", fn, n);
-  memcpy(jpeg_host, e->jpeg_hdr.data(), hl);
-  memcpy(jpeg_host + hl, sl.jpeg_host, n);
-  if (jpeg_bytes) *jpeg_bytes = hl + n;
-  return RTP_OK;
-}
-
-// rtp_encode_jpeg on the pixels of a view of device memory, ordered after the work queued on `stream`; returns with the file on the host.
-// The engine's own scratch: frames in flight are not touched.
-int rtp_encode_jpeg_device(rtp_engine* e, const rtp_frame_view* src, int quality, void* stream, unsigned char* jpeg_host, size_t capacity,
-                           size_t* jpeg_bytes) {
-  static const char* fn = "rtp_encode_jpeg_device";
-  FrameView fv;
-  long hi = 0;
-  int rc, layout = LAYOUT_GENERIC;
-  if ((rc = check_view_fields(e, src, fn, &fv, &hi))) return rc;
-  if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
-  if ((rc = check_caller_stream(e, stream, fn))) return rc;
-  if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
-  if (!jpeg_size_ok(fv.w, fv.h)) return fail(e, RTP_EINVAL, "%s: a %d x %d frame is too large for the GPU encoder", fn, fv.w, fv.h);
-  if ((rc = use_device(e))) return rc;
-  if (quality < 1) quality = 1;
-  if (quality > 100) quality = 100;
-  if (e->jenc.w != fv.w || e->jenc.h != fv.h) {
-    SYNC_GUARD;
-    if (e->jenc_ev) HIPCHK(e, hipEventSynchronize(e->jenc_ev));
-    if ((rc = jpeg_alloc(e, fv.w, fv.h, &e->jenc, &e->jenc_host, &e->jenc_host_dev, &e->jenc_cap))) return rc;
-  }
-  if (!e->jenc_ev) HIPCHK(e, hipEventCreateWithFlags(&e->jenc_ev, hipEventDisableTiming));
-  JpegQuant q;
-  std::vector<unsigned char> hdr;
-  jpeg_tables(fv.w, fv.h, quality, &q, &hdr);
-  const hipStream_t st = (hipStream_t)stream;
-  HIPCHK(e, launch_jpeg_encode(nullptr, fv, q, e->jenc, e->jenc_host_dev, reinterpret_cast<unsigned*>(e->jenc_host_dev + e->jenc_cap), st));
-  HIPCHK(e, hipEventRecord(e->jenc_ev, st));
-  HIPCHK(e, hipEventSynchronize(e->jenc_ev));
-  unsigned n = 0;
-  memcpy(&n, e->jenc_host + e->jenc_cap, sizeof n);
-  const size_t total = hdr.size() + n;
-  if (jpeg_bytes) *jpeg_bytes = total;
-  if (jpeg_host) {
-    if (capacity < total) return fail(e, RTP_EINVAL, "%s: output buffer too small (%zu bytes, the file has %zu)", fn, capacity, total);
-    memcpy(jpeg_host, hdr.data(), hdr.size());
-    memcpy(jpeg_host + hdr.size(), e->jenc_host, n);
-  }
-  return RTP_OK;
-}
-
 int rtp_last_stage_ms(const rtp_engine* e, float ms[5]) {
   if (!e || !ms) return RTP_EINVAL;
   memcpy(ms, e->last_ms, sizeof e->last_ms);
-  return RTP_OK;
-}
-
-// ---- synchronous taps (context 0; require an idle engine) ---------------------------------------
-static int need_idle(rtp_engine* e) {
-  if (!e) return RTP_EINVAL;
-  if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "parity taps need an idle engine (collect %zu frames first)", e->fifo.size());
-  int rc;
-  if ((rc = use_device(e))) return rc;
-  for (Ctx& cx : e->ctx)   // the taps reuse context 0's buffers on the host's clock: no export of a rendered image may still read them
-    for (Slot& sl : cx.slot)
-      if (sl.export_pending) {
-        HIPCHK(e, hipEventSynchronize(sl.ev_export));
-        sl.export_pending = false;
-      }
   return RTP_OK;
 }
 
@@ -3658,179 +2976,6 @@ int rtp_device_local_cpus(int device_id, char* buf, size_t buflen) {
   if (line.size() + 1 > buflen) return RTP_ERANGE;
   memcpy(buf, line.c_str(), line.size() + 1);
   return (int)line.size();
-}
-
-// ---- load-time precision calibration ----------------------------------------------------------------
-// The default split set of RTP_PREC_MIXED was chosen on one synthetic weight set.  Trained weights arrive through
-// CopyTrainedLayersFrom (net.cpp:750-803) with another spectrum; this measures the set on the weights that are LOADED:
-//   reference  = the same frames through RTP_PREC_F16X3 (every layer as hi + lo fp16 pairs: 1e-5 of the map maximum vs fp32),
-//   candidate  = the current mixed plan;  err = max |candidate - reference| / max |reference|  over the final maps.
-// While err > target, every layer group that is not split yet is tried on top of the current set and the one that lowers the
-// error most is promoted; when every group is in and the error still exceeds the target the engine falls back to F16X3.
-int rtp_calibrate_precision(rtp_engine* e, const float* frames_host, int nframes, float target, char* rules_out, size_t rules_len,
-                            float* err_before, float* err_after) {
-  // (no process-wide lock across this function: every re-plan and every tap below takes g_sync_mutex for its own captures / synchronous
-  // calls, so other engines of the process — rtpose.bin --num_gpu N --calibrate K — interleave with the trials instead of queueing behind
-  // the dozens of seconds a calibration can take)
-  int rc;
-  if ((rc = need_idle(e))) return rc;
-  if ((rc = need_weights(e))) return rc;
-  if (e->mode == RTP_PREC_F16X3 && e->calib_fell_back) {   // an earlier calibration ended in the parity-grade mode: nothing is left to adjust
-    if (err_before) *err_before = 0.f;
-    if (err_after) *err_after = 0.f;
-    if (rules_out && rules_len) snprintf(rules_out, rules_len, "@f16x3");
-    e->calib_report += "; called again: already RTP_PREC_F16X3 (every layer runs three fp16 passes), nothing to adjust";
-    return RTP_OK;
-  }
-  if (e->mode != RTP_PREC_MIXED) return fail(e, RTP_EINVAL, "rtp_calibrate_precision adjusts the split set of RTP_PREC_MIXED (engine precision is %d)", e->mode);
-  if (nframes < 1 || nframes > 64) return fail(e, RTP_EINVAL, "calibration frames %d out of range [1, 64]", nframes);
-  if (!(target > 0.f)) target = 0.7e-3f;
-  const size_t in_floats = (size_t)e->N * 3 * e->cfg.net_h * e->cfg.net_w;
-  const size_t low_floats = (size_t)e->N * e->plan.heat_channels * e->plan.low_h * e->plan.low_w;
-  std::vector<float> synth;
-  if (!frames_host) {  // what process_and_pad_image makes of a u8 frame: v / 256 - 0.5 (rtpose.cpp:259), seeded
-    synth.resize(in_floats * nframes);
-    uint64_t st = 0x9E3779B97F4A7C15ull ^ e->cfg.synthetic_seed;
-    for (float& v : synth) { st = st * 6364136223846793005ull + 1442695040888963407ull; v = (float)((st >> 56) & 0xff) / 256.0f - 0.5f; }
-    frames_host = synth.data();
-  }
-  std::vector<float> ref(low_floats * nframes), got(low_floats);
-  auto run = [&](const float* x, float* out) { return rtp_forward_heatmaps(e, x, out); };
-  const std::string base_rules = e->split_rules;
-  // a failure half way (a trial plan that does not fit the device, a HIP error) must not leave the caller with a one-context trial engine:
-  // put the plan it came with back (best effort) and report the original error
-  auto bail = [&](int code) {
-    const std::string msg = e->err;
-    if (replan(e, RTP_PREC_MIXED, base_rules, false) != RTP_OK) {
-      // the restore failed too (e.g. the same out-of-memory condition): the engine has NO plan.  Mark it: every entry point that would
-      // touch a context reports RTP_EHIP instead of dereferencing an empty vector; rtp_engine_destroy still works.
-      drop_plan(e);
-      e->broken = true;
-      e->err = msg + " (and the engine's previous plan could not be restored: the engine is unusable, destroy it)";
-      return code;
-    }
-    e->err = msg;
-    return code;
-  };
-  // reference maps
-  if ((rc = replan(e, RTP_PREC_F16X3, base_rules, true))) return bail(rc);
-  for (int f = 0; f < nframes; ++f)
-    if ((rc = run(frames_host + (size_t)f * in_floats, ref.data() + (size_t)f * low_floats))) return bail(rc);
-  double norm = 0;
-  for (float v : ref) norm = std::max(norm, (double)std::fabs(v));
-  if (!(norm > 0) || !std::isfinite(norm)) {
-    if (bail(RTP_ERANGE) && e->broken) return RTP_ERANGE;
-    return fail(e, RTP_ERANGE, "calibration: the reference maps are %s (weights / frames out of range for fp16 storage?)", norm > 0 ? "not finite" : "all zero");
-  }
-  auto measure = [&](double* err) -> int {
-    double m = 0;
-    for (int f = 0; f < nframes; ++f) {
-      int r2 = run(frames_host + (size_t)f * in_floats, got.data());
-      if (r2) return r2;
-      const float* rf = ref.data() + (size_t)f * low_floats;
-      for (size_t i = 0; i < low_floats; ++i) {
-        const double d = std::fabs((double)got[i] - (double)rf[i]);
-        m = (d == d) ? std::max(m, d) : 1e30;   // NaN counts as unbounded
-      }
-    }
-    *err = m / norm;
-    return RTP_OK;
-  };
-  std::ostringstream rep;
-  std::string rules = base_rules;
-  double err = 0;
-  if ((rc = replan(e, RTP_PREC_MIXED, rules, true))) return bail(rc);
-  if ((rc = measure(&err))) return bail(rc);
-  if (err_before) *err_before = (float)err;
-  rep << "target " << target << "; frames " << nframes << "; set \"" << rules << "\" err " << err;
-  // the layer groups a rule can name: trunk blocks by their "convN_" prefix, stage 1, the refinement stages (from the MIXED plan's flags)
-  std::vector<std::string> all_groups;
-  {
-    auto add = [&](const std::string& g) { if (std::find(all_groups.begin(), all_groups.end(), g) == all_groups.end()) all_groups.push_back(g); };
-    for (auto& c : e->plan.convs) {
-      const size_t st = c.name.find("_stage");
-      if (st != std::string::npos) { size_t en = st + 6; while (en < c.name.size() && isdigit((unsigned char)c.name[en])) ++en; add("*" + c.name.substr(st, en - st) + "_"); }
-      else { const size_t us = c.name.find('_'); add(us == std::string::npos ? c.name : c.name.substr(0, us + 1)); }
-    }
-  }
-  auto in_group = [](const std::string& g, const ConvOp& c) { return g[0] == '*' ? c.name.find(g.substr(1)) != std::string::npos : c.name.compare(0, g.size(), g) == 0; };
-  auto open_groups = [&](bool want_h8) {   // groups with a layer that is not fully split yet (stage 1) / that still runs an fp8 chunk (stage 2)
-    std::vector<std::string> gs;
-    for (auto& g : all_groups) {
-      bool open = false;
-      for (auto& c : e->plan.convs) if (in_group(g, c) && (want_h8 ? c.h8 : !(c.split_w && (c.split_a || c.first)))) open = true;
-      if (open) gs.push_back(g);
-    }
-    return gs;
-  };
-  // stage 1: promote un-split groups, the one that lowers the error most first
-  std::vector<std::string> groups = open_groups(false);
-  while (err > target && !groups.empty()) {
-    int best = -1;
-    double best_err = 1e300;
-    for (size_t g = 0; g < groups.size(); ++g) {
-      double eg = 0;
-      if ((rc = replan(e, RTP_PREC_MIXED, rules + "," + groups[g], true))) return bail(rc);
-      if ((rc = measure(&eg))) return bail(rc);
-      rep << "; try +" << groups[g] << " -> " << eg;
-      if (eg < best_err) { best_err = eg; best = (int)g; }
-    }
-    rules += "," + groups[best];
-    rep << "; promote " << groups[best];
-    groups.erase(groups.begin() + best);
-    err = best_err;
-  }
-  // stage 2: every group is split and the target is still missed — the fp8 correction chunks are the limit (e4m3 operands: activations
-  // beyond +-112 or rounding errors beyond their range saturate; 3 mantissa bits).  Groups switch to fp16 correction passes (":x"),
-  // ranked by what the switch gains alone, applied cumulatively until the target holds.
-  if (err > target) {
-    if ((rc = replan(e, RTP_PREC_MIXED, rules, true))) return bail(rc);
-    std::vector<std::string> hg = open_groups(true);
-    std::vector<std::pair<double, std::string>> gain;
-    for (auto& g : hg) {
-      double eg = 0;
-      if ((rc = replan(e, RTP_PREC_MIXED, rules + "," + g + ":x", true))) return bail(rc);
-      if ((rc = measure(&eg))) return bail(rc);
-      rep << "; try " << g << ":x -> " << eg;
-      gain.push_back({eg, g});
-    }
-    std::sort(gain.begin(), gain.end());
-    for (auto& ge : gain) {
-      if (err <= target) break;
-      rules += "," + ge.second + ":x";
-      if ((rc = replan(e, RTP_PREC_MIXED, rules, true))) return bail(rc);
-      if ((rc = measure(&err))) return bail(rc);
-      rep << "; switch " << ge.second << ":x -> " << err;
-    }
-  }
-  int final_mode = RTP_PREC_MIXED;
-  if (err > target) {   // every layer runs three fp16 passes already where it can: the parity-grade mode for all of them
-    final_mode = RTP_PREC_F16X3;
-    rep << "; err " << err << " > target with every group switched: falling back to RTP_PREC_F16X3";
-    err = 0;
-  }
-  if ((rc = replan(e, final_mode, final_mode == RTP_PREC_MIXED ? rules : base_rules, false))) return bail(rc);
-  e->calib_fell_back = final_mode == RTP_PREC_F16X3;   // (rtp_get_split_layers then reports precision RTP_PREC_F16X3 next to the caller's own rule list: the rules do not apply in that mode)
-  if (final_mode == RTP_PREC_MIXED && (rc = measure(&err))) return bail(rc);
-  if (err_after) *err_after = (float)err;
-  rep << "; final " << (final_mode == RTP_PREC_MIXED ? "mixed" : "f16x3") << " set \"" << rules << "\" err " << err;
-  e->calib_report = rep.str();
-  if (rules_out && rules_len) snprintf(rules_out, rules_len, "%s", final_mode == RTP_PREC_MIXED ? rules.c_str() : "@f16x3");
-  return RTP_OK;
-}
-const char* rtp_calibration_report(const rtp_engine* e) { return e ? e->calib_report.c_str() : ""; }
-// The split set in force (rule list of rtp_config.split_layers syntax) and the precision mode (a calibration may have changed both).
-int rtp_get_split_layers(const rtp_engine* e, char* buf, size_t buflen, int* precision) {
-  if (!e) return RTP_EINVAL;
-  if (precision) *precision = e->mode;
-  if (buf && buflen) {
-    if (e->split_rules.size() + 1 > buflen) {   // never a silently truncated rule list: the receiver would build another plan
-      buf[0] = 0;
-      return fail(const_cast<rtp_engine*>(e), RTP_ERANGE, "rtp_get_split_layers: the rule list needs %zu bytes, the buffer has %zu", e->split_rules.size() + 1, buflen);
-    }
-    snprintf(buf, buflen, "%s", e->split_rules.c_str());
-  }
-  return RTP_OK;
 }
 
 // ---- one-time weight distribution (optional; nothing here is on the per-frame path) -------------------------

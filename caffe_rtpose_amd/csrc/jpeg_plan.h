@@ -1,4 +1,4 @@
-// jpeg_plan.h — what codecs.cpp's JPEG parser hands to the GPU decoder (engine.cpp, jpeg_dec.hip): geometry, quantisers, colour
+// jpeg_plan.h — what codecs.cpp's JPEG parser hands to the GPU decoder (engine_jpeg.cpp, jpeg_dec.hip): geometry, quantisers, colour
 // model, and either the staged scan with its subsequence tables (entropy decoding on the device) or the coefficients the host's own
 // entropy decoder produced (progressive, multi-scan and every irregular file).  Host only.
 #pragma once

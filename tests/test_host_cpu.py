@@ -3,6 +3,7 @@ logic behind it (graph builder / prototxt parser / plan / caffemodel IO / JSON /
 model tables / std::sort replica) agrees with the oracle and with fixtures derived from the
 reference.  No compute kernels are called here."""
 import ctypes as C
+import glob
 import json
 import os
 import re
@@ -48,7 +49,10 @@ def test_production_library_has_no_experiment_knobs():
     removed = {b"RTP_RING_VAR", b"RTP_FORCE_CFG", b"RTP_TILE_OVERRIDE", b"RTP_DIAG_SKIP_POST", b"RTP_RING_SB", b"RTP_RING_SPEC", b"RTP_POST_CUS", b"RTP_NMS_PROBE",
                b"RTP_SPLIT_LAYERS", b"RTP_HALO_SHARED", b"RTP_HALF_CHIP", b"RTP_GRAPH_POST", b"RTP_STREAM_PLAN", b"RTP_MATCH_WGS"}
     assert os.path.exists(exp) and removed <= names(exp)            # the experiments build still has them (tools/, tests of the variants)
-    src = "".join(open(os.path.join(ROOT, "caffe_rtpose_amd", "csrc", f)).read() for f in ("engine.cpp", "plan.cpp", "conv_ring.hip"))
+    csrc = os.path.join(ROOT, "caffe_rtpose_amd", "csrc")
+    engine = sorted(glob.glob(os.path.join(csrc, "engine*.cpp")))                          # engine.cpp and every engine_*.cpp
+    assert os.path.join(csrc, "engine.cpp") in engine
+    src = "".join(open(f).read() for f in engine + [os.path.join(csrc, "plan.cpp"), os.path.join(csrc, "conv_ring.hip")])
     assert re.findall(r"[^_A-Z]getenv\(\"(RTP_[A-Z_]+)\"\)", src.replace("#ifdef RTP_EXPERIMENTS", "")) .count("RTP_EXEC") == 1
 
 
