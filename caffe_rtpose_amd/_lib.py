@@ -170,6 +170,16 @@ SIGNATURES = {
     "rtp_video_read_jpeg": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(C.c_size_t)]),
     "rtp_decode_jpeg_device": (C.c_int, [vp, C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(rtp_frame_view), vp, ip]),
     "rtp_submit_frame_jpeg": (C.c_int, [vp, C.POINTER(C.c_ubyte), C.c_size_t, C.c_uint64, fp, ip, ip]),
+    "rtp_convert_bgr_to_yuv": (C.c_int, [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_long, C.POINTER(rtp_yuv_view)]),
+    "rtp_yuv_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "rtp_video_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtp_video_write_yuv": (C.c_int, [vp, C.POINTER(rtp_yuv_view)]),
+    "rtp_video_write_jpeg": (C.c_int, [vp, C.POINTER(C.c_ubyte), C.c_size_t]),
+    "rtp_video_finish": (C.c_int, [vp]),
+    "rtp_convert_to_yuv_device": (C.c_int, [vp, C.POINTER(rtp_frame_view), C.POINTER(rtp_yuv_view), vp]),
+    "rtp_set_render_yuv": (C.c_int, [vp, C.c_int]),
+    "rtp_collect_rendered_yuv": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(C.c_ubyte), C.c_size_t]),
+    "rtp_collect_rendered_yuv_device": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(rtp_yuv_view), vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

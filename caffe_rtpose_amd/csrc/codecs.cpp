@@ -26,6 +26,7 @@
 #include <cstring>
 #include <exception>
 #include <fstream>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -1324,6 +1325,131 @@ int rtp_convert_yuv(const rtp_yuv_view* v, unsigned char* out_bgr, size_t capaci
     }
   }
   return RTP_OK;
+}
+
+// The other direction, and the one definition of it (the GPU kernels of yuv_export.hip restate it): luma per pixel, chroma from the
+// rounded mean of each cell's pixels, coordinates clamped to the last column / row.  No clamp: over the whole BGR cube Y stays in
+// 16..235 and U, V in 16..240.
+int rtp_convert_bgr_to_yuv(const unsigned char* bgr, int w, int h, long row_stride, const rtp_yuv_view* v) {
+  char msg[256];
+  long hi[3];
+  if (rtp_internal_yuv_fields(v, msg, sizeof msg, hi)) return cfail(RTP_EINVAL, std::string("rtp_convert_bgr_to_yuv: ") + msg);
+  if (!bgr) return cfail(RTP_EINVAL, "rtp_convert_bgr_to_yuv: NULL image");
+  if (w != v->width || h != v->height)
+    return cfail(RTP_EINVAL, "rtp_convert_bgr_to_yuv: the image is " + std::to_string(w) + " x " + std::to_string(h) + ", the view " +
+                                 std::to_string(v->width) + " x " + std::to_string(v->height));
+  if (row_stride < 3L * w) return cfail(RTP_EINVAL, "rtp_convert_bgr_to_yuv: row_stride " + std::to_string(row_stride) + " is below 3 * width");
+  unsigned char* Y = (unsigned char*)v->y;
+  unsigned char* U = (unsigned char*)v->u;
+  unsigned char* V = (unsigned char*)v->v;
+  for (int y = 0; y < h; ++y) {
+    const unsigned char* p = bgr + (size_t)y * row_stride;
+    unsigned char* yr = Y + (size_t)y * v->y_stride;
+    for (int x = 0; x < w; ++x, p += 3) yr[x] = (unsigned char)(((66 * p[2] + 129 * p[1] + 25 * p[0] + 128) >> 8) + 16);
+  }
+  if (!U) return RTP_OK;
+  const int sx = v->chroma_shift_x, sy = v->chroma_shift_y, sh = sx + sy, half = (1 << sh) >> 1;
+  const int cw = (w + sx) >> sx, ch = (h + sy) >> sy;
+  for (int cy = 0; cy < ch; ++cy)
+    for (int cx = 0; cx < cw; ++cx) {
+      int s[3] = {0, 0, 0};
+      for (int dy = 0; dy <= sy; ++dy)
+        for (int dx = 0; dx <= sx; ++dx) {
+          const int yy = std::min((cy << sy) + dy, h - 1), xx = std::min((cx << sx) + dx, w - 1);
+          const unsigned char* p = bgr + (size_t)yy * row_stride + (size_t)xx * 3;
+          s[0] += p[0]; s[1] += p[1]; s[2] += p[2];
+        }
+      const int b = (s[0] + half) >> sh, g = (s[1] + half) >> sh, r = (s[2] + half) >> sh;
+      const size_t c = (size_t)cy * v->uv_stride + (size_t)cx * v->uv_pixel_stride;
+      U[c] = (unsigned char)(((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128);
+      V[c] = (unsigned char)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128);
+    }
+  return RTP_OK;
+}
+
+size_t rtp_yuv_bytes(int w, int h, int chroma) {
+  if (w < 1 || h < 1) return 0;
+  const size_t W = (size_t)w, H = (size_t)h, cw = (W + 1) / 2, chh = (H + 1) / 2;
+  switch (chroma) {
+    case 420: return W * H + 2 * cw * chh;
+    case 422: return W * H + 2 * cw * H;
+    case 444: return 3 * W * H;
+    case 400: return W * H;
+    default: return 0;
+  }
+}
+
+// ---- stream writers: Y4M (8-bit 4:2:0) and raw MJPEG, append only (the path may be a FIFO feeding an encoder) ----
+struct rtp_video_out {
+  int kind = 0, w = 0, h = 0;
+  FILE* f = nullptr;
+  bool failed = false;
+  std::vector<unsigned char> row;
+};
+
+int rtp_video_create(const char* path, int w, int h, int kind, int fps_num, int fps_den, rtp_video_out** out) {
+  if (!path || !out) return cfail(RTP_EINVAL, "rtp_video_create: NULL argument");
+  *out = nullptr;
+  if (kind != RTP_VIDEO_Y4M && kind != RTP_VIDEO_MJPEG) return cfail(RTP_EINVAL, "rtp_video_create: kind " + std::to_string(kind) + " (RTP_VIDEO_Y4M or RTP_VIDEO_MJPEG)");
+  if (w < 1 || h < 1 || (long long)w * h > kMaxPixels || fps_num < 1 || fps_den < 1)
+    return cfail(RTP_EINVAL, "rtp_video_create: " + std::to_string(w) + " x " + std::to_string(h) + " at " + std::to_string(fps_num) + ":" + std::to_string(fps_den) + " frames/s");
+  FILE* f = fopen(path, "wb");
+  if (!f) return cfail(RTP_EIO, std::string("cannot create ") + path);
+  rtp_video_out* o = new (std::nothrow) rtp_video_out();
+  if (!o) { fclose(f); return cfail(RTP_ENOMEM, "rtp_video_create: out of memory"); }
+  o->kind = kind; o->w = w; o->h = h; o->f = f;
+  // the chroma samples are box averages, i.e. centre sited: the "jpeg" siting (rtp_video_open reads every C420* tag)
+  if (kind == RTP_VIDEO_Y4M && fprintf(f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg\n", w, h, fps_num, fps_den) < 0) o->failed = true;
+  *out = o;
+  return RTP_OK;
+}
+
+int rtp_video_write_yuv(rtp_video_out* o, const rtp_yuv_view* v) {
+  char msg[256];
+  long hi[3];
+  if (!o) return cfail(RTP_EINVAL, "rtp_video_write_yuv: NULL writer");
+  if (rtp_internal_yuv_fields(v, msg, sizeof msg, hi)) return cfail(RTP_EINVAL, std::string("rtp_video_write_yuv: ") + msg);
+  if (o->kind != RTP_VIDEO_Y4M) return cfail(RTP_EINVAL, "rtp_video_write_yuv: an MJPEG writer takes JPEG files (rtp_video_write_jpeg)");
+  if (v->width != o->w || v->height != o->h || !v->u || v->chroma_shift_x != 1 || v->chroma_shift_y != 1)
+    return cfail(RTP_EINVAL, "rtp_video_write_yuv: the stream holds 4:2:0 frames of " + std::to_string(o->w) + " x " + std::to_string(o->h));
+  if (o->failed) return cfail(RTP_EIO, "rtp_video_write_yuv: an earlier write failed");
+  const int cw = (o->w + 1) / 2, ch = (o->h + 1) / 2;
+  bool ok = fwrite("FRAME\n", 1, 6, o->f) == 6;
+  for (int y = 0; ok && y < o->h; ++y) ok = fwrite((const unsigned char*)v->y + (size_t)y * v->y_stride, 1, (size_t)o->w, o->f) == (size_t)o->w;
+  try {
+    o->row.resize((size_t)cw);
+  } catch (const std::exception&) {
+    return cfail(RTP_ENOMEM, "rtp_video_write_yuv: out of memory");
+  }
+  for (int p = 0; p < 2; ++p) {
+    const unsigned char* base = (const unsigned char*)(p ? v->v : v->u);
+    for (int y = 0; ok && y < ch; ++y) {
+      const unsigned char* r = base + (size_t)y * v->uv_stride;
+      for (int x = 0; x < cw; ++x) o->row[x] = r[(size_t)x * v->uv_pixel_stride];
+      ok = fwrite(o->row.data(), 1, (size_t)cw, o->f) == (size_t)cw;
+    }
+  }
+  if (!ok) { o->failed = true; return cfail(RTP_EIO, "rtp_video_write_yuv: write failed"); }
+  return RTP_OK;
+}
+
+int rtp_video_write_jpeg(rtp_video_out* o, const unsigned char* bytes, size_t n) {
+  if (!o || !bytes) return cfail(RTP_EINVAL, "rtp_video_write_jpeg: NULL argument");
+  if (o->kind != RTP_VIDEO_MJPEG) return cfail(RTP_EINVAL, "rtp_video_write_jpeg: a Y4M writer takes planes (rtp_video_write_yuv)");
+  if (n < 4 || bytes[0] != 0xFF || bytes[1] != 0xD8 || bytes[n - 2] != 0xFF || bytes[n - 1] != 0xD9)
+    return cfail(RTP_EINVAL, "rtp_video_write_jpeg: not one JPEG file (SOI .. EOI)");
+  if (o->failed) return cfail(RTP_EIO, "rtp_video_write_jpeg: an earlier write failed");
+  if (fwrite(bytes, 1, n, o->f) != n) { o->failed = true; return cfail(RTP_EIO, "rtp_video_write_jpeg: write failed"); }
+  return RTP_OK;
+}
+
+int rtp_video_finish(rtp_video_out* o) {
+  if (!o) return RTP_EINVAL;
+  bool ok = !o->failed;
+  if (fflush(o->f) != 0) ok = false;
+  if (fclose(o->f) != 0) ok = false;
+  delete o;
+  return ok ? RTP_OK : cfail(RTP_EIO, "rtp_video_finish: a write to the stream failed");
 }
 
 int rtp_video_chroma(const rtp_video* v) { return v && v->kind == 1 ? v->chroma : 0; }

@@ -12,8 +12,8 @@
 //   * weights are re-laid out per layer for the kernel's [tap][chunk][cout][k] staging order;
 //   * frames_in_flight contexts (stream + arena) let consecutive frames overlap, which is what
 //     fills 256 CUs when one frame's layers are too small to.
-// The engine's side of the two GPU codecs lives in engine_jpeg.cpp, the load-time calibration in engine_calib.cpp; what the three files
-// share is in engine_internal.h.
+// The engine's side of the two GPU codecs lives in engine_jpeg.cpp, the YUV output in engine_yuv.cpp, the load-time calibration in
+// engine_calib.cpp; what the four files share is in engine_internal.h.
 #include "engine_internal.h"
 
 namespace rtp {
@@ -247,11 +247,14 @@ int upload_all_weights(rtp_engine* e) {
 // Residency-stamp slots of one batch context: [0, 64) plan steps (conv stack), 64 + 8 j + {0 strip, 1 write, 2 pairs, 3 match, 4 assemble}
 // = frame j's post-processing chain, 64 + 8 j + 5 = the export of its rendered image (rtp_collect_rendered_device), 64 + 8 j + 6 = the
 // JPEG encoding of its rendered image (rtp_set_render_jpeg; all seven launches), 200 + 2 j + {0 warp or import of a device frame,
-// 1 area/pad} = frame j's device pre-processing.
+// 1 area/pad} = frame j's device pre-processing; 64 + 8 j + 7 = the conversion of frame j's rendered image to YUV planes (rtp_set_render_yuv,
+// rtp_collect_rendered_yuv_device; engine_yuv.cpp).
 constexpr int STAMP_SLOTS = 256;
+}  // namespace
 unsigned long long* stamp_slot(const rtp_engine* e, const Ctx& cx, int idx) {
   return (e->stamp_probe && cx.stamps && idx >= 0 && idx < STAMP_SLOTS) ? cx.stamps + 2 * (size_t)idx : nullptr;
 }
+namespace {
 // the stamps of the batch that last ran on `cx` (complete: the context is idle) -> e->stamp_spans; slots zeroed for the next batch
 int stamp_harvest(rtp_engine* e, Ctx& cx) {
   if (!cx.stamps || !cx.stamps_dirty) return RTP_OK;
@@ -613,7 +616,9 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
         vp.model = e->plan.model; vp.part_to_show = e->cfg.render - 1;
         HIPCHK(e, launch_render_view(vp, sl.stream));
       }
-      if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
+      if (e->yuv_mode) {  // rtp_set_render_yuv: only the planes cross PCIe
+        if ((rc = yuv_out_launch(e, cx, j))) return rc;
+      } else if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
         if (!sl.jpeg.base) {
           SYNC_GUARD;
           if ((rc = jpeg_alloc(e, e->cfg.disp_w, e->cfg.disp_h, &sl.jpeg, &sl.jpeg_host, &sl.jpeg_host_dev, &sl.jpeg_cap))) return rc;
@@ -622,7 +627,7 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
         HIPCHK(e, launch_jpeg_encode(stamp_slot(e, cx, 64 + 8 * j + 6), fv, e->jpeg_q, sl.jpeg, sl.jpeg_host_dev,
                                      reinterpret_cast<unsigned*>(sl.jpeg_host_dev + sl.jpeg_cap), sl.stream));
       } else {
-        if (!sl.render_host) {   // freed while JPEG mode was on
+        if (!sl.render_host) {   // freed while JPEG or YUV mode was on
           SYNC_GUARD;
           HIPCHK(e, hipHostMalloc((void**)&sl.render_host, dbytes, hipHostMallocDefault));
         }
@@ -1018,6 +1023,8 @@ void free_ctx(Ctx& cx) {
     for (void* p : dptrs) if (p) (void)hipFree(p);
     if (sl.frame_host) (void)hipHostFree(sl.frame_host);
     if (sl.render_host) (void)hipHostFree(sl.render_host);
+    if (sl.yuv_out_dev) (void)hipFree(sl.yuv_out_dev);
+    if (sl.yuv_out_host) (void)hipHostFree(sl.yuv_out_host);
     jpeg_free(&sl.jpeg, &sl.jpeg_host, &sl.jpeg_cap);
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
@@ -1325,7 +1332,6 @@ int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long h
   return RTP_OK;
 }
 
-namespace {
 // rtp_yuv_view: the field checks of codecs.cpp (no HIP call: also for a NULL engine), then — check_yuv_memory — each plane on its own
 // (y, u and v may be three allocations): device memory of cfg.device_id, the last byte it addresses inside its allocation.
 int check_yuv_fields(rtp_engine* e, const rtp_yuv_view* v, const char* fn, YuvView* yv, long hi[3]) {
@@ -1345,6 +1351,8 @@ int check_yuv_memory(rtp_engine* e, const char* fn, const YuvView& yv, const lon
   if (yv.v && (rc = check_device_range(e, fn, "v", yv.v, hi[2], &avail))) return rc;
   return RTP_OK;
 }
+
+namespace {
 
 // A caller's device frame -> frame slot sj of cx.input.  The display image is always the slot's own disp_dev (area_pad and the renderer
 // read it after this call has released the caller's memory): the import kernel when the frame has the display size, else the cubic warp
@@ -2151,6 +2159,9 @@ int rtp_collect_rendered(rtp_engine* e, uint64_t* tag, float* joints, int* num_p
   if (e && e->jpeg_quality)
     return fail(e, RTP_EINVAL, "rtp_collect_rendered: JPEG mode is on (rtp_set_render_jpeg %d), so the raw frame never reaches the host: "
                 "collect with rtp_collect_rendered_jpeg, or rtp_collect_rendered_device", e->jpeg_quality);
+  if (e && e->yuv_mode)
+    return fail(e, RTP_EINVAL, "rtp_collect_rendered: YUV mode is on (rtp_set_render_yuv %d), so the raw frame never reaches the host: "
+                "collect with rtp_collect_rendered_yuv, or rtp_collect_rendered_device / rtp_collect_rendered_yuv_device", e->yuv_mode);
   return collect_impl(e, tag, joints, num_people, display_bgr, true);
 }
 

@@ -1,4 +1,4 @@
-// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_calib.cpp) share: the frame slot, the batch context and
+// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_calib.cpp) share: the frame slot, the batch context and
 // rtp_engine itself, the error / lock macros, and the declarations of every helper one of those files defines and another one calls.
 // Internal: only the engine's own files include it (it opens namespace rtp for them); nothing here is part of the library's ABI.
 #pragma once
@@ -131,6 +131,10 @@ struct Slot {
   unsigned char* jpeg_host = nullptr;
   unsigned char* jpeg_host_dev = nullptr;   // the same memory as the device addresses it
   size_t jpeg_cap = 0;
+  // rtp_set_render_yuv: the planar 4:2:0 planes of render_dev (Y, U, V, pitches = plane widths; allocated lazily, like render_dev) and
+  // their pinned copy, the only bytes of the rendered frame that cross PCIe in that mode
+  unsigned char* yuv_out_dev = nullptr;
+  unsigned char* yuv_out_host = nullptr;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -214,6 +218,7 @@ struct rtp_engine {
   int jpeg_quality = 0;
   std::vector<unsigned char> jpeg_hdr;
   JpegQuant jpeg_q;
+  int yuv_mode = 0;   // rtp_set_render_yuv: 0 off, 420 = every rendered frame leaves as planar 4:2:0 planes (engine_yuv.cpp)
   // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
   JpegBufs jenc;
   unsigned char* jenc_host = nullptr;
@@ -293,6 +298,9 @@ int flush_prep(rtp_engine* e, Ctx& cx, bool force);
 int check_view_fields(rtp_engine* e, const rtp_frame_view* v, const char* fn, FrameView* fv, long* hi);
 int check_caller_stream(rtp_engine* e, void* stream, const char* fn);
 int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long hi, int* layout);
+int check_yuv_fields(rtp_engine* e, const rtp_yuv_view* v, const char* fn, YuvView* yv, long hi[3]);
+int check_yuv_memory(rtp_engine* e, const char* fn, const YuvView& yv, const long hi[3]);
+unsigned long long* stamp_slot(const rtp_engine* e, const Ctx& cx, int idx);
 void drop_plan(rtp_engine* e);
 int replan(rtp_engine* e, int mode, const std::string& rules, bool light);
 int busy_mark_stage0(rtp_engine* e, Ctx& cx);
@@ -314,6 +322,10 @@ void jpeg_free(JpegBufs* b, unsigned char** host, size_t* cap);
 int jpeg_alloc(rtp_engine* e, int w, int h, JpegBufs* b, unsigned char** host, unsigned char** host_dev, size_t* cap);
 void jd_free(JdBufs* b);
 int jd_launch(rtp_engine* e, unsigned long long* stamp, const JdJob& job, const FrameView& dst, hipStream_t stream);
+
+// engine_yuv.cpp
+YuvView yuv_out_view(unsigned char* planes, int w, int h);
+int yuv_out_launch(rtp_engine* e, Ctx& cx, int sj);
 
 }  // namespace eng
 }  // namespace rtp

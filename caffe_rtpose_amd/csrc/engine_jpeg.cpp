@@ -347,6 +347,7 @@ int rtp_set_render_jpeg(rtp_engine* e, int quality) {
   if (!e) return fail(nullptr, RTP_EINVAL, "rtp_set_render_jpeg: NULL engine");
   if (quality < 0 || quality > 100) return fail(e, RTP_EINVAL, "rtp_set_render_jpeg: quality %d (0 = off, 1..100)", quality);
   if (quality && !e->cfg.render) return fail(e, RTP_EINVAL, "rtp_set_render_jpeg needs rtp_config.render >= 1");
+  if (quality && e->yuv_mode) return fail(e, RTP_EINVAL, "rtp_set_render_jpeg: YUV mode is on (rtp_set_render_yuv %d): one renderer mode at a time", e->yuv_mode);
   if (quality && !jpeg_size_ok(e->cfg.disp_w, e->cfg.disp_h))
     return fail(e, RTP_EINVAL, "rtp_set_render_jpeg: a %d x %d display image is too large for the GPU encoder", e->cfg.disp_w, e->cfg.disp_h);
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "rtp_set_render_jpeg: %zu frames in flight (collect them first)", e->fifo.size());

@@ -237,6 +237,13 @@ int yuv_layout(const YuvView& s, const FrameView& d);
 inline FrameView packed_bgr_view(unsigned char* p, int w, int h) { return FrameView{p, w, h, 3L * w, 3, {0, 1, 2}}; }
 // YUV (BT.601 limited range, the integer arithmetic of codecs.cpp rtp_convert_yuv) -> the three named channels of the view (s.w x s.h)
 hipError_t launch_yuv_import(unsigned long long* stamp, const YuvView& s, const FrameView& d, int layout, hipStream_t stream);
+// The other direction (yuv_export.hip): the three named channels of the view -> the planes of d (written; d.w x d.h = s.w x s.h), the
+// integer arithmetic of codecs.cpp rtp_convert_bgr_to_yuv.  yuv_export_layout returns a YuvLayout value: the 4:2:0 layouts (one thread
+// per 4 x 2 luma block: two rows of three dword loads, two dword luma stores, 16-bit or dword chroma stores) only for a packed-BGR
+// source (pix 3, offsets 0 1 2, data and row 4-byte aligned), w % 4 == 0, h % 2 == 0 and planes aligned as yuv_layout asks of them;
+// GENERIC: one thread per chroma cell, byte loads and stores.
+int yuv_export_layout(const FrameView& s, const YuvView& d);
+hipError_t launch_yuv_export(unsigned long long* stamp, const FrameView& s, const YuvView& d, int layout, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------
 // JPEG encoder (rtp_encode_jpeg_device, rtp_set_render_jpeg): jpeg_enc.hip, the bytes of codecs.cpp's rtp_encode_jpeg

@@ -42,6 +42,9 @@ int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* 
 int rtp_submit_frame_yuv(rtp_engine* e, const rtp_yuv_view* frame_host, uint64_t tag, float* frame_scale) __attribute__((weak));
 // (nor a JPEG entry: without it every file is decoded on the producer side, as with --host_decode)
 int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t n, uint64_t tag, float* frame_scale, int* w, int* h) __attribute__((weak));
+// (nor the YUV mode of the renderer: --write_video x.y4m then needs --host_video, as under --dry_engine)
+int rtp_set_render_yuv(rtp_engine* e, int chroma) __attribute__((weak));
+int rtp_collect_rendered_yuv(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* planes_host, size_t capacity) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -57,6 +60,13 @@ double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::
 struct Flags {
   bool host_preprocess = false;
   bool host_jpeg = false;        // --write_frames: encode on the host (rtp_encode_jpeg on an encoder pool) instead of on the GPU
+  // --write_video FILE.y4m|FILE.mjpeg|FILE.mjpg: the rendered frames as ONE stream (rtp_video_create), written in order by the display
+  // thread.  .y4m: the renderer's YUV mode, only the 4:2:0 planes cross PCIe; .mjpeg: its JPEG mode at the quality of --write_frames.
+  // --host_video: the raw frames cross PCIe and are converted (rtp_convert_bgr_to_yuv) / encoded (rtp_encode_jpeg) by the display thread
+  // instead: the same bytes, and the only path under --dry_engine.
+  std::string write_video;
+  int video_fps = 30;
+  bool host_video = false;
   bool host_yuv = false;         // --video x.y4m: convert every frame to BGR on the producer thread (rtp_video_read) instead of on the GPU
   // JPEG files are decoded on the GPU (rtp_submit_frame_jpeg: only the file crosses PCIe) or on the producer side (rtp_decode_image).
   // Default by source (profiles/r09_jpeg_decode.txt): --video x.mjpeg on the GPU (one producer thread decodes a video), --image_dir on
@@ -90,14 +100,14 @@ struct Flags {
 };
 
 int parse_flags(int argc, char** argv, Flags& F) {
-  std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video},
+  std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video}, {"write_video", &F.write_video},
       {"image_dir", &F.image_dir}, {"caffemodel", &F.caffemodel}, {"caffeproto", &F.caffeproto}, {"resolution", &F.resolution},
       {"net_resolution", &F.net_resolution}, {"camera_resolution", &F.camera_resolution}, {"precision", &F.precision}, {"model", &F.model}, {"devices", &F.devices}};
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
-      {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}};
+      {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}};
   std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display},
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -145,6 +155,11 @@ void usage() {
          "  --write_frames draws the pose overlay only: the FPS / people-count text of the reference (cv::putText, rtpose.cpp:1319-1333) is not\n"
          "  drawn, i.e. --no_text is implied.  Its JPEG files (quality 98) are encoded on the GPU and only the files cross PCIe;\n"
          "  --host_jpeg copies the raw frames to the host and encodes them there on 8 threads instead (the same bytes).\n"
+         "  --write_video FILE.y4m|FILE.mjpeg|FILE.mjpg [--video_fps N (30)] writes the same rendered frames as ONE stream, in frame order.\n"
+         "  .y4m: converted to YUV 4:2:0 on the GPU (BT.601 limited range), only the planes cross PCIe; not together with --write_frames (one\n"
+         "  renderer mode at a time).  .mjpeg / .mjpg: the JPEG files of --write_frames one after the other (may be combined with it).\n"
+         "  --host_video copies the raw frames to the host and converts / encodes them there instead (the same bytes; the only path under\n"
+         "  --dry_engine).  Without --no_frame_drops the stream simply holds the frames that were processed: dropped frames leave no gap.\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
          "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
          "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
@@ -181,6 +196,7 @@ struct Frame {
   bool mono = false;
   std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
   bool rendered_jpeg = false;
+  bool rendered_yuv = false;            // --write_video x.y4m: rendered holds the frame's 4:2:0 planes (rtp_collect_rendered_yuv)
   int img_w = 0, img_h = 0;
   double commit_time = 0, preprocessed_time = 0, gpu_fetched_time = 0, gpu_computed_time = 0, buffer_start_time = 0, buffer_end_time = 0;
   int index = 0, numPeople = 0, video_frame_number = 0;
@@ -195,6 +211,9 @@ struct Global {
   BlockingQueue<Frame> input_queue, output_queue, output_queue_ordered;
   BlockingQueue<EncodeJob> encode_queue;  // --write_frames: JPEG encoding is spread over a few threads (files are independent)
   std::atomic<bool> encode_done{false};
+  rtp_video_out* video_out = nullptr;     // --write_video: written by the display thread only
+  int video_kind = 0;                     // RTP_VIDEO_Y4M / RTP_VIDEO_MJPEG
+  std::atomic<bool> video_failed{false};
   std::priority_queue<int, std::vector<int>, std::greater<int>> dropped_index;
   std::mutex mutex;
   std::atomic<bool> quit_threads{false};
@@ -414,7 +433,8 @@ void worker(int widx, int device, int* status) {
   cfg.precision = F.precision == "fp32" ? RTP_PREC_FP32 : F.precision == "fp16" ? RTP_PREC_FP16 : F.precision == "f16x3" ? RTP_PREC_F16X3 : RTP_PREC_MIXED;
   cfg.frames_in_flight = F.frames_in_flight;
   cfg.batch_frames = F.batch_frames;
-  cfg.render = F.write_frames.empty() ? 0 : 1 + F.part_to_show;  // render() of rtpose.cpp:270-299: pose overlay or a --part_to_show view
+  const bool want_render = !F.write_frames.empty() || !F.write_video.empty();
+  cfg.render = !want_render ? 0 : 1 + F.part_to_show;  // render() of rtpose.cpp:270-299: pose overlay or a --part_to_show view
   cfg.calibrate_frames = F.calibrate;
   rtp_engine* e = nullptr;
   const bool dry = F.dry_engine > 0;
@@ -446,13 +466,31 @@ void worker(int widx, int device, int* status) {
     return;
   }
   // --write_frames: the files are encoded on the GPU (quality 98, rtpose.cpp:1367-1381) unless --host_jpeg; --dry_engine has no GPU
-  const bool gpu_jpeg = !dry && !F.write_frames.empty() && !F.host_jpeg;
+  // --write_video x.mjpeg takes the same files (main() refuses the combinations in which one output wants the GPU's and the other the host's)
+  const bool gpu_jpeg = !dry && ((!F.write_frames.empty() && !F.host_jpeg) || (G.video_kind == RTP_VIDEO_MJPEG && !F.host_video));
+  // --write_video x.y4m: the renderer's YUV mode unless --host_video
+  const bool gpu_yuv = !dry && G.video_kind == RTP_VIDEO_Y4M && !F.host_video;
+  if (gpu_yuv) {
+    const char* err = !rtp_set_render_yuv || !rtp_collect_rendered_yuv ? "this binary was linked without the engine's YUV output"
+                      : rtp_set_render_yuv(e, 420) != RTP_OK            ? rtp_last_error(e) : nullptr;
+    if (err) {   // never a quiet fall-back to the host conversion: --host_video asks for it
+      fprintf(stderr, "GPU %d: --write_video: %s\n", device, err);
+      *status = 1;
+      G.quit_threads = true;
+      rtp_engine_destroy(e);
+      return;
+    }
+  }
+  if (!F.write_video.empty() && widx == 0)
+    fprintf(stderr, "--write_video: frames %s\n", gpu_yuv ? "converted to YUV 4:2:0 on the GPU (rtp_collect_rendered_yuv)"
+                                                  : gpu_jpeg ? "encoded on the GPU (rtp_collect_rendered_jpeg)"
+                                                             : "converted / encoded on the host (--host_video)");
   std::vector<unsigned char> jpeg_buf(gpu_jpeg ? rtp_jpeg_max_bytes(DISP_W, DISP_H) : 0);
   if (gpu_jpeg) {
     const char* err = !rtp_set_render_jpeg || !rtp_collect_rendered_jpeg ? "this binary was linked without the engine's GPU JPEG encoder"
                       : rtp_set_render_jpeg(e, 98) != RTP_OK              ? rtp_last_error(e) : nullptr;
     if (err) {   // never a quiet fall-back to the host encoders: --host_jpeg asks for them
-      fprintf(stderr, "GPU %d: --write_frames: %s\n", device, err);
+      fprintf(stderr, "GPU %d: %s: %s\n", device, F.write_frames.empty() ? "--write_video" : "--write_frames", err);
       *status = 1;
       G.quit_threads = true;
       rtp_engine_destroy(e);
@@ -521,10 +559,11 @@ void worker(int widx, int device, int* status) {
     int n = 0;
     Frame fr = std::move(inflight.front());
     inflight.pop_front();
-    if (!F.write_frames.empty() && !gpu_jpeg) fr.rendered.resize((size_t)DISP_W * DISP_H * 3);
+    if (want_render && !gpu_jpeg) fr.rendered.resize(gpu_yuv ? rtp_yuv_bytes(DISP_W, DISP_H, 420) : (size_t)DISP_W * DISP_H * 3);
     size_t jpeg_bytes = 0;
     const int rc = dry ? dry_collect(fr, joints.data(), &n)
-                   : F.write_frames.empty() ? rtp_collect(e, &tag, joints.data(), &n)
+                   : !want_render ? rtp_collect(e, &tag, joints.data(), &n)
+                   : gpu_yuv ? rtp_collect_rendered_yuv(e, &tag, joints.data(), &n, fr.rendered.data(), fr.rendered.size())
                    : gpu_jpeg ? rtp_collect_rendered_jpeg(e, &tag, joints.data(), &n, jpeg_buf.data(), jpeg_buf.size(), &jpeg_bytes)
                               : rtp_collect_rendered(e, &tag, joints.data(), &n, fr.rendered.data());
     if (rc != RTP_OK) { fprintf(stderr, "GPU %d frame %d: %s\n", device, fr.index, rtp_last_error(e)); n = 0; }
@@ -547,6 +586,11 @@ void worker(int widx, int device, int* status) {
         fr.rendered = black_jpeg;
       }
       fr.rendered_jpeg = !fr.rendered.empty();
+    }
+    if (gpu_yuv) {
+      // a frame whose collect failed: the host path converts the zero-filled frame it is handed, so this path writes those planes
+      if (rc != RTP_OK) { memset(fr.rendered.data(), 16, (size_t)DISP_W * DISP_H); memset(fr.rendered.data() + (size_t)DISP_W * DISP_H, 128, fr.rendered.size() - (size_t)DISP_W * DISP_H); }
+      fr.rendered_yuv = true;
     }
     fr.numPeople = n;
     fr.joints.assign(joints.begin(), joints.begin() + (size_t)n * num_parts * 3);
@@ -713,6 +757,7 @@ void writer(std::atomic<bool>* reorder_done) {
   int counter = 1;
   double last_time = wall();
   std::vector<char> buf(1 << 20);
+  std::vector<unsigned char> video_buf;   // --write_video --host_video: the frame's planes / its JPEG file
   while (true) {
     Frame fr;
     if (!G.output_queue_ordered.try_pop(&fr)) {
@@ -722,6 +767,32 @@ void writer(std::atomic<bool>* reorder_done) {
     }
     double t_commit = fr.commit_time, t_pre = fr.preprocessed_time, t_fetch = fr.gpu_fetched_time, t_done = fr.gpu_computed_time, t_b0 = fr.buffer_start_time, t_b1 = fr.buffer_end_time;
     const int f_index = fr.index, f_np = fr.numPeople;
+    if (G.video_out && !fr.rendered.empty() && !G.video_failed.load()) {   // --write_video: this thread sees the frames in order
+      int vrc;
+      if (G.video_kind == RTP_VIDEO_Y4M) {
+        const size_t ysz = (size_t)DISP_W * DISP_H, csz = (size_t)((DISP_W + 1) / 2) * ((DISP_H + 1) / 2);
+        rtp_yuv_view yv;
+        memset(&yv, 0, sizeof yv);
+        yv.struct_size = sizeof yv;
+        yv.matrix = RTP_YUV_BT601_LIMITED;
+        yv.width = DISP_W; yv.height = DISP_H;
+        yv.chroma_shift_x = yv.chroma_shift_y = 1;
+        yv.y_stride = DISP_W; yv.uv_stride = (DISP_W + 1) / 2; yv.uv_pixel_stride = 1;
+        unsigned char* planes = fr.rendered.data();
+        if (!fr.rendered_yuv) { video_buf.resize(ysz + 2 * csz); planes = video_buf.data(); }
+        yv.y = planes; yv.u = planes + ysz; yv.v = planes + ysz + csz;
+        vrc = fr.rendered_yuv ? RTP_OK : rtp_convert_bgr_to_yuv(fr.rendered.data(), DISP_W, DISP_H, 3L * DISP_W, &yv);   // --host_video
+        if (vrc == RTP_OK) vrc = rtp_video_write_yuv(G.video_out, &yv);
+      } else {
+        if (!fr.rendered_jpeg) {   // --host_video: encoded here, once; --write_frames then writes the same file
+          video_buf.resize(rtp_jpeg_max_bytes(DISP_W, DISP_H));
+          const long nb = rtp_encode_jpeg(fr.rendered.data(), DISP_W, DISP_H, 98, video_buf.data(), video_buf.size());
+          if (nb > 0) { fr.rendered.assign(video_buf.begin(), video_buf.begin() + nb); fr.rendered_jpeg = true; }
+        }
+        vrc = fr.rendered_jpeg ? rtp_video_write_jpeg(G.video_out, fr.rendered.data(), fr.rendered.size()) : RTP_EINVAL;
+      }
+      if (vrc != RTP_OK) { fprintf(stderr, "--write_video: frame %d: %s\n", fr.index, rtp_codec_last_error()); G.video_failed = true; }
+    }
     if (!F.write_frames.empty() && !fr.rendered.empty()) {  // cv::imwrite(fname, wrap_frame, {JPEG_QUALITY, 98}), rtpose.cpp:1367-1381
       char fname[1024];
       if (F.image_dir.empty()) snprintf(fname, sizeof fname, "%s/frame%06d.jpg", F.write_frames.c_str(), fr.video_frame_number);
@@ -825,6 +896,28 @@ int main(int argc, char** argv) {
     if ((int)devs.size() != F.num_gpu) { fprintf(stderr, "--devices names %zu devices but --num_gpu is %d\n", devs.size(), F.num_gpu); return 1; }
   }
   G.per_worker.assign(F.num_gpu, 0);
+  if (!F.write_video.empty()) {
+    const size_t dot = F.write_video.find_last_of('.');
+    std::string ext = dot == std::string::npos ? "" : F.write_video.substr(dot);
+    for (char& ch : ext) ch = (char)tolower((unsigned char)ch);
+    G.video_kind = ext == ".y4m" ? RTP_VIDEO_Y4M : (ext == ".mjpeg" || ext == ".mjpg") ? RTP_VIDEO_MJPEG : 0;
+    if (!G.video_kind) { fprintf(stderr, "--write_video %s: the suffix chooses the format: .y4m, .mjpeg or .mjpg\n", F.write_video.c_str()); return 1; }
+    if (F.video_fps < 1) { fprintf(stderr, "--video_fps must be >= 1\n"); return 1; }
+    if (F.host_preprocess) { fprintf(stderr, "--write_video needs the device pre-processing path (drop --host_preprocess)\n"); return 1; }
+    if (G.video_kind == RTP_VIDEO_Y4M && !F.write_frames.empty()) {
+      fprintf(stderr, "--write_video %s cannot be combined with --write_frames: one renderer mode is active at a time (YUV planes or JPEG files); "
+                      "write an .mjpeg video next to the frames, or run twice\n", F.write_video.c_str());
+      return 1;
+    }
+    if (G.video_kind == RTP_VIDEO_MJPEG && !F.write_frames.empty() && !(F.dry_engine > 0) && F.host_jpeg != F.host_video) {
+      fprintf(stderr, "--write_frames with --write_video x.mjpeg: both take the same files, so give --host_jpeg and --host_video together or neither\n");
+      return 1;
+    }
+    if (rtp_video_create(F.write_video.c_str(), DISP_W, DISP_H, G.video_kind, F.video_fps, 1, &G.video_out) != RTP_OK) {
+      fprintf(stderr, "--write_video: %s\n", rtp_codec_last_error());
+      return 1;
+    }
+  }
   if (!F.write_frames.empty() && F.host_preprocess) { fprintf(stderr, "--write_frames needs the device pre-processing path (drop --host_preprocess)\n"); return 1; }
 
   const double t0 = wall();
@@ -843,12 +936,14 @@ int main(int argc, char** argv) {
   reo.join();
   reorder_done = true;
   wr.join();
+  if (G.video_out && rtp_video_finish(G.video_out) != RTP_OK) { fprintf(stderr, "--write_video: %s\n", rtp_codec_last_error()); G.video_failed = true; }
   G.encode_done = true;
   for (auto& t : encoders) t.join();
   G.json_done = true;
   for (auto& t : jsonw) t.join();
   int rc = 0;
   for (int s : status) rc |= s;
+  if (G.video_failed.load()) rc |= 1;
   const double dt = wall() - t0;
   for (int g = 0; g < F.num_gpu; ++g) fprintf(stderr, "worker %d (GPU %d) processed %d frames\n", g, devs[g], G.per_worker[g]);
   if (F.share_weights) fprintf(stderr, "share_weights: %d worker(s) took worker 0's packed weights\n", G.weights_shared.load());

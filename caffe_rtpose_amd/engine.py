@@ -1,5 +1,6 @@
 """ctypes mirror of include/rtpose_mi355x.h (numpy in / numpy out).  Plumbing only."""
 import ctypes as C
+import os
 import sys
 
 import numpy as np
@@ -414,6 +415,104 @@ def convert_yuv(y, u, v=None, *, interleaved_order="uv"):
     return out
 
 
+def yuv_bytes(w, h, chroma=420):
+    """rtp_yuv_bytes: bytes of a w x h frame's planes without pitches (chroma 420, 422, 444 or 400); 0 for bad arguments."""
+    return int(lib.rtp_yuv_bytes(int(w), int(h), int(chroma)))
+
+
+def convert_bgr_to_yuv(bgr, chroma=420, *, out=None, interleaved_order="uv"):
+    """rtp_convert_bgr_to_yuv: a BGR HWC u8 host image (any row pitch) -> planes, BT.601 limited range — the bytes every YUV output
+    of the library holds.  chroma 420, 422, 444 or 400 (luma only): returns new (y, u, v) numpy planes (u = v = None for 400).
+    out = (y, u, v), (y, uv) or (y, None) as yuv_view takes them: the conversion is written into those host planes (pitched,
+    interleaved, ...) instead, and `out` is returned."""
+    img = np.asarray(bgr)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.strides[2] != 1 or (img.shape[1] > 1 and img.strides[1] != 3) or img.strides[0] < 0:
+        img = np.ascontiguousarray(bgr, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"shape {img.shape}: (H, W, 3)")
+    h, w = img.shape[:2]
+    if out is None:
+        shifts = {420: (1, 1), 422: (1, 0), 444: (0, 0), 400: None}.get(int(chroma), 0)
+        if shifts == 0:
+            raise ValueError(f"chroma {chroma!r}: 420, 422, 444 or 400")
+        y = np.empty((h, w), np.uint8)
+        if shifts is None:
+            out = (y, None, None)
+        else:
+            cs = ((h + shifts[1]) >> shifts[1], (w + shifts[0]) >> shifts[0])
+            out = (y, np.empty(cs, np.uint8), np.empty(cs, np.uint8))
+    planes = tuple(out) + (None,) * (3 - len(out))
+    f = yuv_view(planes[0], planes[1], planes[2], interleaved_order=interleaved_order)
+    if f["device"]:
+        raise TypeError("convert_bgr_to_yuv takes host arrays (device frames: Engine.convert_to_yuv_device)")
+    s = _yuv_struct(f)
+    rc = lib.rtp_convert_bgr_to_yuv(C.cast(img.ctypes.data, C.POINTER(C.c_ubyte)), w, h, img.strides[0] if h > 1 else 3 * w, C.byref(s))
+    if rc:
+        raise RtpError(rc, lib.rtp_codec_last_error().decode())
+    return out
+
+
+VIDEO_Y4M, VIDEO_MJPEG = 1, 2   # RTP_VIDEO_*
+
+
+class VideoWriter:
+    """rtp_video_create: an append-only Y4M (8-bit 4:2:0) or raw MJPEG stream that Video reads back; the path may be a FIFO.
+
+    kind: VIDEO_Y4M / VIDEO_MJPEG, or None = by the suffix (.y4m, .mjpeg / .mjpg).  fps: an int or a (num, den) pair."""
+
+    def __init__(self, path, w, h, kind=None, fps=30):
+        if kind is None:
+            suffix = os.path.splitext(str(path))[1].lower()
+            kind = {".y4m": VIDEO_Y4M, ".mjpeg": VIDEO_MJPEG, ".mjpg": VIDEO_MJPEG}.get(suffix)
+            if kind is None:
+                raise ValueError(f"{path}: the suffix names no format (.y4m, .mjpeg, .mjpg): pass kind")
+        num, den = fps if isinstance(fps, (tuple, list)) else (fps, 1)
+        self.h = C.c_void_p()
+        self.kind, self.w, self.h_ = int(kind), int(w), int(h)
+        rc = lib.rtp_video_create(str(path).encode(), self.w, self.h_, self.kind, int(num), int(den), C.byref(self.h))
+        if rc:
+            self.h = C.c_void_p()
+            raise RtpError(rc, lib.rtp_codec_last_error().decode())
+
+    def write_yuv(self, y, u, v=None, *, interleaved_order="uv"):
+        """rtp_video_write_yuv: one 4:2:0 frame from host planes (see yuv_view; any pitches, planar or interleaved)."""
+        f = yuv_view(y, u, v, interleaved_order=interleaved_order)
+        if f["device"]:
+            raise TypeError("VideoWriter.write_yuv takes host planes")
+        s = _yuv_struct(f)
+        rc = lib.rtp_video_write_yuv(self.h, C.byref(s))
+        if rc:
+            raise RtpError(rc, lib.rtp_codec_last_error().decode())
+
+    def write_bgr(self, bgr, quality=98):
+        """One BGR HWC u8 host frame, converted (Y4M: convert_bgr_to_yuv) or encoded (MJPEG: encode_jpeg) on the host."""
+        if self.kind == VIDEO_Y4M:
+            self.write_yuv(*convert_bgr_to_yuv(bgr, 420))
+        else:
+            self.write_jpeg(encode_jpeg(bgr, quality))
+
+    def write_jpeg(self, data):
+        """rtp_video_write_jpeg: append one JPEG file (bytes)."""
+        buf = (C.c_ubyte * len(data)).from_buffer_copy(data)
+        rc = lib.rtp_video_write_jpeg(self.h, buf, len(data))
+        if rc:
+            raise RtpError(rc, lib.rtp_codec_last_error().decode())
+
+    def close(self):
+        """rtp_video_finish: flush and close; raises RtpError(RTP_EIO) if a write to the stream failed."""
+        if self.h:
+            h, self.h = self.h, C.c_void_p()
+            rc = lib.rtp_video_finish(h)
+            if rc:
+                raise RtpError(rc, lib.rtp_codec_last_error().decode())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def video_chroma(video):
     """rtp_video_chroma: 420, 422, 444 or 400 for a Y4M Video, 0 for anything else."""
     return int(lib.rtp_video_chroma(video.h))
@@ -645,6 +744,50 @@ class Engine:
         nb = C.c_size_t()
         self._chk(lib.rtp_collect_rendered_jpeg(self.h, C.byref(tag), _f(joints), C.byref(n), _u8(out), out.size, C.byref(nb)))
         return tag.value, n.value, joints[: n.value].copy(), out[: nb.value].tobytes()
+
+    def convert_to_yuv_device(self, frame, y, u, v=None, stream=None, order="bgr", *, interleaved_order="uv"):
+        """rtp_convert_to_yuv_device: the u8 device frame `frame` (see frame_view) -> the device planes (see yuv_view; v = None:
+        interleaved or luma only) of the same size, the bytes of convert_bgr_to_yuv, on the GPU in order with `stream`."""
+        f = yuv_view(y, u, v, interleaved_order=interleaved_order)
+        if not f["device"]:
+            raise TypeError("convert_to_yuv_device takes device planes (host arrays: convert_bgr_to_yuv)")
+        d = _yuv_struct(f)
+        s = _view_struct(frame_view(frame, order))
+        st, _ = _stream_of(frame, stream)
+        self._chk(lib.rtp_convert_to_yuv_device(self.h, C.byref(s), C.byref(d), st))
+
+    def set_render_yuv(self, chroma):
+        """rtp_set_render_yuv: 0 off, 420 = every rendered frame leaves as planar 4:2:0 planes; collect with collect_rendered_yuv."""
+        self._chk(lib.rtp_set_render_yuv(self.h, int(chroma)))
+
+    def collect_rendered_yuv(self):
+        """rtp_collect_rendered_yuv: (tag, joints, y, u, v) of the oldest frame: joints of the people found, and the rendered
+        frame's planes (views of one buffer laid out as a Y4M FRAME payload)."""
+        tag = C.c_uint64()
+        n = C.c_int()
+        joints = np.zeros((MAX_PEOPLE, self.num_parts, 3), np.float32)
+        w, h = self.cfg.c.disp_w, self.cfg.c.disp_h
+        cw, ch = (w + 1) // 2, (h + 1) // 2
+        buf = np.empty(yuv_bytes(w, h, 420), np.uint8)
+        self._chk(lib.rtp_collect_rendered_yuv(self.h, C.byref(tag), _f(joints), C.byref(n), _u8(buf), buf.size))
+        y = buf[: w * h].reshape(h, w)
+        u = buf[w * h: w * h + cw * ch].reshape(ch, cw)
+        v = buf[w * h + cw * ch:].reshape(ch, cw)
+        return tag.value, joints[: n.value].copy(), y, u, v
+
+    def collect_rendered_yuv_device(self, y, u, v=None, stream=None, *, interleaved_order="uv"):
+        """rtp_collect_rendered_yuv_device: the rendered display image converted into the caller's device planes (disp_w x disp_h,
+        see yuv_view: e.g. a pitched NV12 surface); work queued on `stream` afterwards sees them.  Returns (tag, num_people, joints)."""
+        f = yuv_view(y, u, v, interleaved_order=interleaved_order)
+        if not f["device"]:
+            raise TypeError("collect_rendered_yuv_device takes device planes (host planes: collect_rendered_yuv)")
+        s = _yuv_struct(f)
+        st, _ = _stream_of(y, stream)
+        tag = C.c_uint64()
+        n = C.c_int()
+        joints = np.zeros((MAX_PEOPLE, self.num_parts, 3), np.float32)
+        self._chk(lib.rtp_collect_rendered_yuv_device(self.h, C.byref(tag), _f(joints), C.byref(n), C.byref(s), st))
+        return tag.value, n.value, joints[: n.value].copy()
 
     def encode_jpeg_device(self, obj, quality=98, stream=None, order="bgr"):
         """rtp_encode_jpeg_device: encode_jpeg of a u8 frame in device memory (see frame_view), on the GPU after the work queued on

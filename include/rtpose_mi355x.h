@@ -355,6 +355,33 @@ typedef struct rtp_yuv_view {
  * (arithmetic shift).  This is what rtp_video_read makes of a Y4M frame, and what the GPU entries below compute bit for bit.
  * RTP_EINVAL + rtp_codec_last_error for a view that fails the field checks or a capacity below the image. */
 int rtp_convert_yuv(const rtp_yuv_view* host, unsigned char* bgr_out, size_t capacity);
+/* The other direction: packed u8 BGR (w x h, rows row_stride >= 3 w bytes apart) -> the planes dst_host describes (same size; planar or
+ * interleaved, 4:2:0 / 4:2:2 / 4:4:4 or luma only, any pitches; pitch padding is not written).  BT.601 limited range, integers only,
+ * arithmetic shifts:
+ *   Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel;
+ *   U = ((-38 R' - 74 G' + 112 B' + 128) >> 8) + 128, V = ((112 R' - 94 G' - 18 B' + 128) >> 8) + 128 per chroma sample, where
+ *   (R', G', B') is the rounded mean of the sample's cell: (sum + 2) >> 2 of 2 x 2 pixels, (sum + 1) >> 1 of 2 x 1, the pixel itself at
+ *   4:4:4; coordinates are clamped to the last column / row, so an odd edge cell repeats its last pixel.
+ * Y stays in 16..235 and U, V in 16..240 without a clamp; rtp_convert_yuv of the 4:4:4 result is within 3 of every source channel.
+ * This is the definition of every YUV output of the library: the GPU entries below write these bytes.  RTP_EINVAL +
+ * rtp_codec_last_error for a view that fails the field checks of rtp_convert_yuv, a size other than the view's, or row_stride < 3 w. */
+int rtp_convert_bgr_to_yuv(const unsigned char* bgr, int w, int h, long row_stride, const rtp_yuv_view* dst_host);
+/* Bytes of a w x h frame's planes without pitches (Y, U, V; chroma planes of (w + 1) / 2 columns and, at 4:2:0, (h + 1) / 2 rows):
+ * chroma = 420, 422, 444 or 400 (luma only).  Host only; 0 for a size below 1 or any other chroma. */
+size_t rtp_yuv_bytes(int w, int h, int chroma);
+/* Stream writers for the two container-less formats rtp_video_open reads (cv::VideoWriter has no counterpart in the reference, which
+ * stops at --write_frames).  Append only, never seeking: path may be a FIFO that feeds an encoder.  RTP_VIDEO_Y4M: 8-bit 4:2:0
+ * ("C420jpeg": the chroma samples are centre sited box averages), one "FRAME" line + the planes without pitches per
+ * rtp_video_write_yuv (refused for a view of another size or chroma); RTP_VIDEO_MJPEG: the JPEG files of rtp_video_write_jpeg one after
+ * the other.  A write of the other kind is refused (RTP_EINVAL, nothing written).  rtp_video_finish flushes, closes and frees the
+ * writer whatever it returns: RTP_EIO if any write to the stream failed.  RTP_EIO from rtp_video_create: the file cannot be created. */
+#define RTP_VIDEO_Y4M 1
+#define RTP_VIDEO_MJPEG 2
+typedef struct rtp_video_out rtp_video_out;
+int rtp_video_create(const char* path, int w, int h, int kind, int fps_num, int fps_den, rtp_video_out** out);
+int rtp_video_write_yuv(rtp_video_out* o, const rtp_yuv_view* host);
+int rtp_video_write_jpeg(rtp_video_out* o, const unsigned char* bytes, size_t n);
+int rtp_video_finish(rtp_video_out* o);
 /* cv::VideoCapture(path) (rtpose.cpp:402-411, 431) for the container-less formats decodable here:
  * Y4M (YUV4MPEG2, 8 bit) and raw MJPEG streams.  nframes may be NULL; rtp_video_read returns
  * RTP_EAGAIN at the end of the stream. */
@@ -509,7 +536,7 @@ int rtp_encode_jpeg_device(rtp_engine* e, const rtp_frame_view* src, int quality
 /* JPEG mode of the renderer.  0: off (the default).  1..100: every rendered frame (overlay or part_to_show view) is encoded on
  * the GPU at this quality right after the render kernel, and only the file is copied to the host; collect it with
  * rtp_collect_rendered_jpeg (rtp_collect_rendered is refused, rtp_collect_rendered_device still works).  Refused: render == 0 or
- * quality outside 0..100 (RTP_EINVAL), frames in flight (RTP_EAGAIN). */
+ * quality outside 0..100, YUV mode on (rtp_set_render_yuv: one mode at a time) (RTP_EINVAL), frames in flight (RTP_EAGAIN). */
 int rtp_set_render_jpeg(rtp_engine* e, int quality);
 
 /* = rtp_collect_rendered with the JPEG file of the rendered frame in place of the raw image (*jpeg_bytes = its length).
@@ -537,6 +564,31 @@ int rtp_submit_frame_yuv_device(rtp_engine* e, const rtp_yuv_view* frame_dev, vo
  * image (NULL: the null stream, and the image is complete when the call returns).  Uses no frame slot: frames in flight are not
  * disturbed. */
 int rtp_convert_yuv_device(rtp_engine* e, const rtp_yuv_view* src_dev, const rtp_frame_view* dst_dev, void* stream);
+
+/* ---- YUV planes out, converted on the GPU (yuv_export.hip): byte for byte what rtp_convert_bgr_to_yuv writes ---------------------- */
+
+/* The conversion alone, the other way round: the three named channels of src_dev -> the planes of dst_dev (same width and height;
+ * pitch padding is not written), both in device memory and checked as for rtp_convert_yuv_device.  Same `stream` contract.  Uses no
+ * frame slot: frames in flight are not disturbed. */
+int rtp_convert_to_yuv_device(rtp_engine* e, const rtp_frame_view* src_dev, const rtp_yuv_view* dst_dev, void* stream);
+
+/* YUV mode of the renderer.  0: off (the default).  420: every rendered frame (overlay or part_to_show view) is converted to planar
+ * 4:2:0 on the GPU right after the render kernel, and only the planes are copied to the host (rtp_yuv_bytes(disp_w, disp_h, 420)
+ * bytes instead of 3 per pixel); collect them with rtp_collect_rendered_yuv (rtp_collect_rendered is refused,
+ * rtp_collect_rendered_device and rtp_collect_rendered_yuv_device still work).  Refused: render == 0, any other chroma value, JPEG
+ * mode on (RTP_EINVAL; rtp_set_render_jpeg is refused likewise while this mode is on), frames in flight (RTP_EAGAIN). */
+int rtp_set_render_yuv(rtp_engine* e, int chroma);
+
+/* = rtp_collect_rendered with the planes of the rendered frame in place of the raw image: Y (disp_w x disp_h), then U, then V
+ * ((disp_w + 1) / 2 x (disp_h + 1) / 2 each), pitches = plane widths — the payload of a Y4M FRAME.  Refused before the frame leaves
+ * the FIFO (RTP_EINVAL): YUV mode off, capacity < rtp_yuv_bytes(disp_w, disp_h, 420), an oldest frame without a display image. */
+int rtp_collect_rendered_yuv(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* planes_host, size_t capacity);
+
+/* = rtp_collect_rendered_device with the rendered frame converted into the caller's planes (disp_w x disp_h; e.g. the pitched NV12
+ * surface of a hardware encoder): the checks and the `stream` contract of that entry, the view checked as in
+ * rtp_convert_to_yuv_device.  Works in every mode of the renderer. */
+int rtp_collect_rendered_yuv_device(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, const rtp_yuv_view* out_dev,
+                                    void* stream);
 
 /* ---- JPEG files, decoded on the GPU (jpeg_dec.hip): byte for byte the pixels of rtp_decode_image ---------------------- */
 
