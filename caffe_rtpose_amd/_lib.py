@@ -71,6 +71,25 @@ class rtp_yuv_view(C.Structure):
     ]
 
 
+class rtp_maps_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("grid", C.c_int),
+        ("format", C.c_int),
+        ("channels", C.POINTER(C.c_int)),
+        ("num_channels", C.c_int),
+    ]
+
+
+class rtp_maps_view(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("data", C.c_void_p),
+        ("channel_stride", C.c_long),
+        ("row_stride", C.c_long),
+    ]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 vp = C.c_void_p
@@ -180,6 +199,13 @@ SIGNATURES = {
     "rtp_set_render_yuv": (C.c_int, [vp, C.c_int]),
     "rtp_collect_rendered_yuv": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(C.c_ubyte), C.c_size_t]),
     "rtp_collect_rendered_yuv_device": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(rtp_yuv_view), vp]),
+    "rtp_set_maps_output": (C.c_int, [vp, C.POINTER(rtp_maps_config)]),
+    "rtp_maps_info": (C.c_int, [vp, ip, ip, C.POINTER(C.c_size_t)]),
+    "rtp_peek_maps": (C.c_int, [vp, C.POINTER(C.c_uint64), vp, C.c_size_t]),
+    "rtp_peek_maps_device": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(rtp_maps_view), vp]),
+    "rtp_maps_from_lowres": (C.c_int, [vp, fp, vp, C.c_size_t]),
+    "rtp_maps_quantize_u8": (C.c_int, [fp, C.c_size_t, C.c_int, C.POINTER(C.c_ubyte)]),
+    "rtp_maps_to_f16": (C.c_int, [fp, C.c_size_t, C.POINTER(C.c_uint16)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

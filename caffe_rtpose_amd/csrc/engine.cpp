@@ -634,6 +634,7 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
         HIPCHK(e, hipMemcpyAsync(sl.render_host, sl.render_dev, dbytes, hipMemcpyDeviceToHost, sl.stream));
       }
     }
+    if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // rtp_set_maps_output: the frame's maps -> its pinned buffer (engine_maps.cpp)
     HIPCHK(e, hipMemcpyAsync(sl.host_out + 4, sl.joints, jbytes, hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(e, hipMemcpyAsync(sl.host_out, sl.num_people, sizeof(int), hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(e, hipEventRecord(sl.ev[4], sl.stream));
@@ -670,6 +671,12 @@ int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bo
       HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_export, 0));
       sl.export_pending = false;
     }
+  for (Slot& sl : cx.slot)   // ... or its low-res maps are still being read by rtp_peek_maps_device on a caller's stream: this batch's conv stack overwrites them
+    if (sl.maps_export_pending) {
+      HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_maps_export, 0));
+      sl.maps_export_pending = false;
+    }
+  if (e->maps_on && (rc = maps_ensure(e, cx, nframes))) return rc;   // maps mode: the slots' buffers exist before anything is launched or captured
   if (e->prep_defer && (rc = flush_prep(e, cx, true))) return rc;
   if (cx.in_pending) {   // the batch's inputs were staged on the staging stream: the conv stream starts when the last of them is complete
     if (cx.in_stream != cx.stream) {
@@ -1017,7 +1024,8 @@ void free_ctx(Ctx& cx) {
   for (Slot& sl : cx.slot) {
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     if (sl.export_pending) (void)hipEventSynchronize(sl.ev_export);   // an export on the caller's stream may still read render_dev
-    for (hipEvent_t ev : {sl.ev_ready, sl.ev_read, sl.ev_export}) if (ev) (void)hipEventDestroy(ev);
+    if (sl.maps_export_pending) (void)hipEventSynchronize(sl.ev_maps_export);   // ... or the context's low-res maps (rtp_peek_maps_device)
+    for (hipEvent_t ev : {sl.ev_ready, sl.ev_read, sl.ev_export, sl.ev_maps_export}) if (ev) (void)hipEventDestroy(ev);
     void* dptrs[] = {sl.resized, sl.peaks, sl.strip_count, sl.strip_list, sl.cand_score, sl.cand_ij, sl.cand_count, sl.cand_blk, sl.conn, sl.conn_score,
                      sl.conn_count, sl.tickets, sl.joints, sl.num_people, sl.frame_dev, sl.disp_dev, sl.render_dev, sl.render_tab};
     for (void* p : dptrs) if (p) (void)hipFree(p);
@@ -1025,6 +1033,7 @@ void free_ctx(Ctx& cx) {
     if (sl.render_host) (void)hipHostFree(sl.render_host);
     if (sl.yuv_out_dev) (void)hipFree(sl.yuv_out_dev);
     if (sl.yuv_out_host) (void)hipHostFree(sl.yuv_out_host);
+    maps_free(sl);
     jpeg_free(&sl.jpeg, &sl.jpeg_host, &sl.jpeg_cap);
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
@@ -1052,7 +1061,6 @@ int use_device(rtp_engine* e) {
   return RTP_OK;
 }
 
-namespace {
 // A captured batch graph bakes every by-value kernel argument (ConvParams::wq_exp of the fp8-compensated layers; with
 // RTP_GRAPH_POST=1 also the thresholds and scales of the post-processing chains).  Whoever changes one of those drops the
 // graphs; launch_batch re-captures on the next batch.  Needs an idle engine.
@@ -1065,6 +1073,7 @@ int invalidate_graphs(rtp_engine* e) {
   return RTP_OK;
 }
 
+namespace {
 // INTER_AREA tables of every pyramid level (display resolution -> 16*ceil(net*s/16)) + cubic table
 int build_prep_tables(rtp_engine* e) {
   SYNC_GUARD;
@@ -1294,7 +1303,6 @@ int check_caller_stream(rtp_engine* e, void* stream, const char* fn) {
   return RTP_OK;
 }
 
-namespace {
 // The memory behind the view: device memory of cfg.device_id, every addressed byte inside the allocation that holds data.  A failed
 // query is cleared from HIP's last error, so that the next launch of a valid call does not report it.
 // `what` names the pointer in the messages ("data", "y", "u", "v"); *avail = bytes from p to the end of its allocation.
@@ -1322,7 +1330,6 @@ int check_device_range(rtp_engine* e, const char* fn, const char* what, const vo
     return fail(e, RTP_EINVAL, "%s: the view addresses bytes up to %ld past %s, its allocation ends %zu bytes past %s", fn, hi, what, *avail, what);
   return RTP_OK;
 }
-}  // namespace
 
 int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long hi, int* layout) {
   size_t avail = 0;
@@ -1615,6 +1622,12 @@ int need_idle(rtp_engine* e) {
         HIPCHK(e, hipEventSynchronize(sl.ev_export));
         sl.export_pending = false;
       }
+  for (Ctx& cx : e->ctx)
+    for (Slot& sl : cx.slot)
+      if (sl.maps_export_pending) {
+        HIPCHK(e, hipEventSynchronize(sl.ev_maps_export));
+        sl.maps_export_pending = false;
+      }
   return RTP_OK;
 }
 
@@ -1655,7 +1668,8 @@ void stage_ms(rtp_engine* e, Ctx& cx, Slot& sl) {
 }
 }  // namespace
 
-int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* rendered, bool want_render) {
+// Blocks until the oldest frame in flight is finished (its batch is launched first where it is still open); the frame stays in the FIFO
+int wait_oldest(rtp_engine* e, int* ci_out, int* sj_out) {
   if (!e) return RTP_EINVAL;
   if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
   int rc;
@@ -1670,6 +1684,16 @@ int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, u
   }
   if (!cx.launched && (rc = launch_open(e))) return rc;  // the oldest frame sits in a partial batch
   HIPCHK(e, hipEventSynchronize(cx.graph_run ? cx.gev[1] : sl.ev[4]));
+  *ci_out = ci;
+  *sj_out = sj;
+  return RTP_OK;
+}
+
+int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* rendered, bool want_render) {
+  int rc, ci = 0, sj = 0;
+  if ((rc = wait_oldest(e, &ci, &sj))) return rc;
+  Ctx& cx = e->ctx[ci];
+  Slot& sl = cx.slot[sj];
   e->fifo.pop_front();
   sl.busy = false;
   bool any = false;

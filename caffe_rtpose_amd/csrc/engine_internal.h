@@ -1,4 +1,4 @@
-// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_calib.cpp) share: the frame slot, the batch context and
+// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_calib.cpp) share: the frame slot, the batch context and
 // rtp_engine itself, the error / lock macros, and the declarations of every helper one of those files defines and another one calls.
 // Internal: only the engine's own files include it (it opens namespace rtp for them); nothing here is part of the library's ABI.
 #pragma once
@@ -135,6 +135,14 @@ struct Slot {
   // their pinned copy, the only bytes of the rendered frame that cross PCIe in that mode
   unsigned char* yuv_out_dev = nullptr;
   unsigned char* yuv_out_host = nullptr;
+  // rtp_set_maps_output: the frame's chosen maps in the chosen format (allocated lazily, like render_dev) and their pinned copy.
+  // rtp_peek_maps_device: ev_maps_export = the kernel that reads this frame's low-res maps on the caller's stream is done; while
+  // maps_export_pending, the context's next batch (whose conv stack overwrites the low-res maps) waits on it first.
+  unsigned char* maps_dev = nullptr;
+  unsigned char* maps_host = nullptr;
+  size_t maps_cap = 0;
+  hipEvent_t ev_maps_export = nullptr;
+  bool maps_export_pending = false;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -219,6 +227,10 @@ struct rtp_engine {
   std::vector<unsigned char> jpeg_hdr;
   JpegQuant jpeg_q;
   int yuv_mode = 0;   // rtp_set_render_yuv: 0 off, 420 = every rendered frame leaves as planar 4:2:0 planes (engine_yuv.cpp)
+  // rtp_set_maps_output (engine_maps.cpp): maps mode on, its grid / format (RTP_MAPS_*) and the chosen channels in output order
+  bool maps_on = false;
+  int maps_grid = 0, maps_format = 0;
+  std::vector<int> maps_chan;
   // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
   JpegBufs jenc;
   unsigned char* jenc_host = nullptr;
@@ -288,6 +300,9 @@ namespace eng __attribute__((visibility("hidden"))) {
   } while (0)
 
 // engine.cpp
+int invalidate_graphs(rtp_engine* e);
+int check_device_range(rtp_engine* e, const char* fn, const char* what, const void* p, long hi, size_t* avail);
+int wait_oldest(rtp_engine* e, int* ci, int* sj);
 double producer_flag(float v);
 unsigned event_flags(bool sync);
 int fail(rtp_engine* e, int code, const char* fmt, ...);
@@ -326,6 +341,11 @@ int jd_launch(rtp_engine* e, unsigned long long* stamp, const JdJob& job, const 
 // engine_yuv.cpp
 YuvView yuv_out_view(unsigned char* planes, int w, int h);
 int yuv_out_launch(rtp_engine* e, Ctx& cx, int sj);
+
+// engine_maps.cpp
+int maps_ensure(rtp_engine* e, Ctx& cx, int nframes);
+int maps_launch(rtp_engine* e, Ctx& cx, int sj);
+void maps_free(Slot& sl);
 
 }  // namespace eng
 }  // namespace rtp

@@ -1,6 +1,7 @@
 // host_util.cpp — the host-only pieces of the path behind the C-ABI: model descriptor tables,
-// default thresholds, process_and_pad_image and the JSON body.  No GPU needed.
+// default thresholds, process_and_pad_image, the JSON body and the narrow formats of maps mode.  No GPU needed.
 #include <charconv>
+#include <cmath>
 #include <cstring>
 #include <sstream>
 #include <string>
@@ -104,6 +105,49 @@ long rtp_format_json(char* buf, size_t buflen, const float* joints, int num_peop
   if (!ok) return RTP_ERANGE;
   *p = 0;
   return (long)(p - buf);
+}
+
+// The two narrow formats of maps mode (maps_export.hip computes the same bits on the device).  Each float operation is spelled as
+// one statement: a multiply never feeds an add here, so no build of this file can contract one into an FMA.
+int rtp_maps_quantize_u8(const float* v, size_t n, int is_paf, unsigned char* out) {
+  if ((!v || !out) && n) return RTP_EINVAL;
+  for (size_t i = 0; i < n; ++i) {
+    float s;
+    if (is_paf) {
+      const float t = v[i] + 1.f;
+      s = t * 127.5f;
+    } else {
+      s = v[i] * 255.f;
+    }
+    const float lo = fmaxf(s, 0.f);   // NaN -> 0
+    const float hi = fminf(lo, 255.f);
+    out[i] = (unsigned char)rintf(hi);  // round half to even (the default rounding mode)
+  }
+  return RTP_OK;
+}
+
+// float -> IEEE binary16, round to nearest even, in integer arithmetic on the bits
+int rtp_maps_to_f16(const float* v, size_t n, uint16_t* out) {
+  if ((!v || !out) && n) return RTP_EINVAL;
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t b;
+    memcpy(&b, &v[i], 4);
+    const uint32_t sign = (b >> 16) & 0x8000u, a = b & 0x7fffffffu;
+    uint32_t h;
+    if (a > 0x7f800000u) h = 0x7e00u | ((a >> 13) & 0x1ffu);          // NaN (quiet, some payload kept)
+    else if (a >= 0x47800000u) h = 0x7c00u;                            // >= 65536 (65520 .. 65536 round up through the carry below), inf
+    else if (a >= 0x38800000u) {                                       // normal in binary16: drop 13 mantissa bits, carry may reach the exponent / inf
+      const uint32_t m = a - 0x38000000u;                              // re-biased exponent (127 -> 15)
+      h = (m + 0xfffu + ((m >> 13) & 1u)) >> 13;
+    } else if (a >= 0x33000000u) {                                     // denormal in binary16: 2^-25 <= |v| < 2^-14
+      const int shift = 126 - (int)(a >> 23);                          // mantissa with its hidden bit, shifted to units of 2^-24: 14 .. 24 bits dropped
+      const uint32_t m = (a & 0x7fffffu) | 0x800000u;
+      const uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+      h = q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u);
+    } else h = 0;                                                      // below half of the smallest denormal
+    out[i] = (uint16_t)(sign | h);
+  }
+  return RTP_OK;
 }
 
 }  // extern "C"

@@ -350,6 +350,29 @@ struct ResizeParams {
 };
 hipError_t launch_resize(const ResizeParams& p, hipStream_t stream);
 
+// Maps mode (maps_export.hip, rtp_set_maps_output): selected channels of a frame's maps, converted and written through a pitched view.
+//   grid 0 (RTP_MAPS_GRID_NET):    plane k = channel chan[k] of the resized map (r.th x r.tw), the arithmetic of resize_kernel bit for bit
+//   grid 1 (RTP_MAPS_GRID_LOWRES): plane n * nch + k = channel chan[k] of scale n of r.src (r.h x r.w), as it stands
+// Element (x, y) of plane z is at dst + z * channel_stride + y * row_stride + x * (1 u8 | 2 f16 | 4 f32) bytes; pitch padding is never
+// written.  format 2 (RTP_MAPS_U8) quantises channels <= num_parts as rintf(clamp(v * 255, 0, 255)) and the PAF channels behind
+// them as rintf(clamp((v + 1) * 127.5, 0, 255)), NaN -> 0 (rtp_maps_quantize_u8); format 1 rounds to binary16, nearest even.
+// wide = 1: groups of 4 consecutive outputs of a row leave as one 4 / 8 / 16-byte store (NET), typed element stores (LOWRES);
+// maps_export_wide says where that is allowed.  wide = 0: every element leaves byte by byte (any address, any pitch).
+#define RTP_MAPS_MAX_CHANNELS 70   // RTP_MAX_NUM_PARTS
+struct MapsParams {
+  ResizeParams r;            // r.src = the frame's low-res maps, r.dst unused
+  unsigned char* dst;
+  long channel_stride, row_stride;
+  int grid, format, nch, num_parts, wide;
+  unsigned short chan[RTP_MAPS_MAX_CHANNELS];
+  unsigned long long* stamp;  // kernel residency slot (KStamp) or null
+};
+inline int maps_elem_bytes(int format) { return format == 2 ? 1 : format == 1 ? 2 : 4; }
+// NET: data, both strides and the row's bytes are multiples of one 4-output group (4 u8 / 8 f16 / 16 f32 bytes) and width % 4 == 0;
+// LOWRES: data and both strides are multiples of the element size
+int maps_export_wide(int grid, int format, int width, const void* data, long channel_stride, long row_stride);
+hipError_t launch_maps_export(const MapsParams& p, hipStream_t stream);
+
 struct NmsParams {
   const float* src;  // resized map [src_planes][H][W]
   float* peaks;      // [num_parts][max_peaks+1][3]  (in/out)

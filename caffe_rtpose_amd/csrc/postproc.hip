@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "resize_math.h"
 #include "stdsort_replica.h"
 
 // No packed-f32 VALU (v_pk_add/mul/fma_f32) in these kernels: this file is built with
@@ -43,27 +44,7 @@ namespace rtp {
 // ---------------------------------------------------------------------------------------
 // ImResize
 // ---------------------------------------------------------------------------------------
-// imresize_layer.cu:14-17 with C++'s usual arithmetic conversions spelled out, in two halves: the three sub-expressions that do
-// not depend on the fraction (8 consecutive outputs along an axis share them), and the evaluation at a fraction.  Same
-// operations in the same order as the one-piece expression (no contraction in this file): cubic_interp IS this pair.
-struct CubicCoef { float a; double b; float c; float v1; };
-__device__ __forceinline__ CubicCoef cubic_coef(float v0, float v1, float v2, float v3) {
-  CubicCoef k;
-  k.a = (-0.5f * v0 + 1.5f * v1 - 1.5f * v2 + 0.5f * v3);
-  k.b = ((double)(v0 - 2.5f * v1) + 2.0 * (double)v2 - 0.5 * (double)v3);
-  k.c = (-0.5f * v0 + 0.5f * v2);
-  k.v1 = v1;
-  return k;
-}
-__device__ __forceinline__ float cubic_eval(const CubicCoef& k, float dx) {
-  const float t1 = k.a * dx * dx * dx;
-  const double t2 = k.b * (double)dx * (double)dx;
-  const float t3 = k.c * dx;
-  return (float)((((double)t1 + t2) + (double)t3) + (double)k.v1);
-}
-__device__ __forceinline__ float cubic_interp(float v0, float v1, float v2, float v3, float dx) {
-  return cubic_eval(cubic_coef(v0, v1, v2, v3), dx);
-}
+// cubic_coef / cubic_eval / cubic_interp and the 8 x 8 output block of resize_kernel: resize_math.h (shared with maps_export.hip)
 
 // Geometry of scale n (imresize_layer.cu:99-131)
 struct ScaleGeo {
@@ -154,87 +135,16 @@ __device__ __forceinline__ float resized_at(const ScaleGeo* geo, const ResizePar
   return resized_from(geo, p.num, p.src + (long)c * plane, (long)p.C * plane, y, x);
 }
 
-// One thread = an 8x8 block of outputs of one channel: x0 = 8k-4, y0 = 8m-4.  For the full-size
-// scale such a block shares ONE 4x4 low-res neighbourhood, so the 4 row interpolations t[i] of an
-// output column are computed once and reused by the 8 output rows (1.5 cubic evaluations per output
-// instead of 5) and the 16 neighbours are loaded once per block.  Per-output arithmetic and
-// rounding are exactly the reference kernel's; whenever the neighbourhood of an output differs
-// from the previous one (other scales, borders) it is simply recomputed.
+// One thread = an 8x8 block of outputs of one channel: x0 = 8k-4, y0 = 8m-4 (resize_block8, resize_math.h: the full-size scale
+// shares one 4x4 low-res neighbourhood per block, 1.5 cubic evaluations per output instead of 5).
 __global__ __launch_bounds__(128) void resize_kernel(ResizeParams p) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;  // 8-wide column strip
   const int x0 = 8 * k - 4;
   const int y0 = 8 * (int)blockIdx.y - 4;
   const int c = blockIdx.z;
   if (x0 >= p.tw) return;
-  const long plane = (long)p.h * p.w;
-  const float* src_c = p.src + (long)c * plane;
-  const long src_offset = (long)p.C * plane;
   float sum[8][8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum[r][j] = 0.f;
-  for (int n = 0; n < p.num; ++n) {
-    const int padw = (int)floorf((float)(p.w / 2) * (1 - p.start_scale + n * p.scale_gap));
-    const int padh = (int)floorf((float)(p.h / 2) * (1 - p.start_scale + n * p.scale_gap));
-    const int ow = p.w - 2 * padw, oh = p.h - 2 * padh;
-    const float* sp = src_c + n * src_offset;
-    const float offset_x = (float)((double)(p.tw / (float)ow / 2) - 0.5);
-    const float offset_y = (float)((double)(p.th / (float)oh / 2) - 0.5);
-    const int rw = ow + 2 * padw;
-    float t[4][8];   // row interpolations of the current y-neighbourhood, per output column
-    int prev_y = -1;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int y = y0 + r;
-      if (y < 0 || y >= p.th) continue;
-      const float y_on = (y - offset_y) * ((float)oh / p.th);
-      int yn1 = (int)((double)y_on + 1e-5);
-      yn1 = (yn1 < 0) ? 0 : yn1;
-      const float dy = y_on - yn1;
-      if (yn1 != prev_y) {
-        prev_y = yn1;
-        int yn[4];
-        yn[0] = ((yn1 - 1 < 0) ? yn1 : (yn1 - 1)) + padh;
-        yn[2] = (yn1 + 1 >= oh) ? (oh - 1) : (yn1 + 1);
-        yn[3] = ((yn[2] + 1 >= oh) ? (oh - 1) : (yn[2] + 1)) + padh;
-        yn[1] = yn1 + padh;
-        yn[2] += padh;
-        float v[4][4];
-        int prev_x = -1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int x = x0 + j;
-          if (x < 0 || x >= p.tw) continue;
-          const float x_on = (x - offset_x) * ((float)ow / p.tw);
-          int xn1 = (int)((double)x_on + 1e-5);
-          xn1 = (xn1 < 0) ? 0 : xn1;
-          const float dx = x_on - xn1;
-          if (xn1 != prev_x) {
-            prev_x = xn1;
-            const int xn0 = ((xn1 - 1 < 0) ? xn1 : (xn1 - 1)) + padw;
-            const int xn2 = (xn1 + 1 >= ow) ? (ow - 1) : (xn1 + 1);
-            const int xn3 = ((xn2 + 1 >= ow) ? (ow - 1) : (xn2 + 1)) + padw;
-            const int xa = xn1 + padw, xb = xn2 + padw;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float* rr = sp + yn[i] * rw;
-              v[i][0] = rr[xn0]; v[i][1] = rr[xa]; v[i][2] = rr[xb]; v[i][3] = rr[xn3];
-            }
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) t[i][j] = cubic_interp(v[i][0], v[i][1], v[i][2], v[i][3], dx);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int x = x0 + j;
-        if (x < 0 || x >= p.tw) continue;
-        const float d = cubic_interp(t[0][j], t[1][j], t[2][j], t[3][j], dy);
-        sum[r][j] = sum[r][j] + d;
-      }
-    }
-  }
+  resize_block8(p, p.src + (long)c * p.h * p.w, x0, y0, sum);
   float* o = p.dst + (long)c * p.th * p.tw;
 #pragma unroll
   for (int r = 0; r < 8; ++r) {

@@ -45,6 +45,9 @@ int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t 
 // (nor the YUV mode of the renderer: --write_video x.y4m then needs --host_video, as under --dry_engine)
 int rtp_set_render_yuv(rtp_engine* e, int chroma) __attribute__((weak));
 int rtp_collect_rendered_yuv(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* planes_host, size_t capacity) __attribute__((weak));
+// (nor maps mode: --write_heatmaps then runs only under --dry_engine)
+int rtp_set_maps_output(rtp_engine* e, const rtp_maps_config* cfg) __attribute__((weak));
+int rtp_peek_maps(rtp_engine* e, uint64_t* tag, void* maps_host, size_t capacity) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -75,6 +78,10 @@ struct Flags {
   bool fullscreen = false, no_frame_drops = false, no_display = false, no_text = false, logtostderr = false;
   int part_to_show = 0, camera = 0, start_frame = 0, start_device = 0, num_gpu = 1, num_scales = 1;
   std::string write_frames, write_json, video, image_dir;
+  // --write_heatmaps PREFIX: every frame's maps (maps mode of the engine: u8 on the net grid) as PREFIX%06d.pgm, binary P5 of net_w x
+  // nch * net_h with channel k in rows [k * net_h, (k + 1) * net_h), written in frame order by the display thread.
+  // --heatmap_channels parts|bkg|parts+bkg|pafs|all chooses the channels (the reference's --heatmaps_add_parts / _bkg / _PAFs).
+  std::string write_heatmaps, heatmap_channels = "parts+bkg";
   std::string caffemodel = "model/coco/pose_iter_440000.caffemodel", caffeproto = "model/coco/pose_deploy_linevec.prototxt";
   std::string resolution = "1280x720", net_resolution = "656x368", camera_resolution = "1280x720";
   double start_scale = 1, scale_gap = 0.3;
@@ -100,7 +107,7 @@ struct Flags {
 };
 
 int parse_flags(int argc, char** argv, Flags& F) {
-  std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video}, {"write_video", &F.write_video},
+  std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video}, {"write_video", &F.write_video}, {"write_heatmaps", &F.write_heatmaps}, {"heatmap_channels", &F.heatmap_channels},
       {"image_dir", &F.image_dir}, {"caffemodel", &F.caffemodel}, {"caffeproto", &F.caffeproto}, {"resolution", &F.resolution},
       {"net_resolution", &F.net_resolution}, {"camera_resolution", &F.camera_resolution}, {"precision", &F.precision}, {"model", &F.model}, {"devices", &F.devices}};
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
@@ -160,6 +167,10 @@ void usage() {
          "  renderer mode at a time).  .mjpeg / .mjpg: the JPEG files of --write_frames one after the other (may be combined with it).\n"
          "  --host_video copies the raw frames to the host and converts / encodes them there instead (the same bytes; the only path under\n"
          "  --dry_engine).  Without --no_frame_drops the stream simply holds the frames that were processed: dropped frames leave no gap.\n"
+         "  --write_heatmaps PREFIX [--heatmap_channels parts|bkg|parts+bkg|pafs|all (parts+bkg)] writes every frame's part-confidence maps /\n"
+         "  PAFs at net resolution as PREFIX%%06d.pgm (binary P5, net_w x channels * net_h, channel k in rows [k * net_h, (k + 1) * net_h)), in frame\n"
+         "  order: u8, confidence and background as round(255 v), PAF channels as round(127.5 (v + 1)); evaluated and quantised on the GPU\n"
+         "  (maps mode of the engine), only the bytes cross PCIe.  Under --dry_engine the files hold zeros.\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
          "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
          "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
@@ -194,6 +205,7 @@ struct Frame {
   bool yuv = false;                // image = Y (img_w x img_h), then U and V ((img_w + sx) >> sx by (img_h + sy) >> sy each; none for mono)
   int chroma_sx = 0, chroma_sy = 0;
   bool mono = false;
+  std::vector<unsigned char> heatmaps;  // --write_heatmaps: the frame's u8 maps [nch][net_h][net_w] (rtp_peek_maps)
   std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
   bool rendered_jpeg = false;
   bool rendered_yuv = false;            // --write_video x.y4m: rendered holds the frame's 4:2:0 planes (rtp_collect_rendered_yuv)
@@ -516,9 +528,35 @@ void worker(int widx, int device, int* status) {
     }
     if (widx != 0) { share_done_guard.armed = false; G.share_done++; }   // through with worker 0's engine
   }
-  int num_parts = F.model == "mpi" ? 15 : 18;
-  if (!dry) rtp_engine_info(e, &num_parts, nullptr, nullptr, nullptr, nullptr);
+  int num_parts = F.model == "mpi" ? 15 : 18, heat_channels = F.model == "mpi" ? 44 : 57;
+  if (!dry) rtp_engine_info(e, &num_parts, nullptr, &heat_channels, nullptr, nullptr);
   G.num_parts.store(num_parts);
+  // --write_heatmaps: maps mode, u8 on the net grid; concat_stage7 holds the parts, the background, then the PAF channels
+  size_t heat_bytes = 0;
+  if (!F.write_heatmaps.empty()) {
+    std::vector<int> chan;
+    const std::string& hc = F.heatmap_channels;
+    if (hc == "parts" || hc == "parts+bkg" || hc == "all") for (int c = 0; c < num_parts; ++c) chan.push_back(c);
+    if (hc == "bkg" || hc == "parts+bkg" || hc == "all") chan.push_back(num_parts);
+    if (hc == "pafs" || hc == "all") for (int c = num_parts + 1; c < heat_channels; ++c) chan.push_back(c);
+    heat_bytes = chan.size() * (size_t)NET_W * NET_H;
+    if (!dry) {
+      rtp_maps_config mc;
+      memset(&mc, 0, sizeof mc);
+      mc.struct_size = sizeof mc;
+      mc.grid = RTP_MAPS_GRID_NET; mc.format = RTP_MAPS_U8;
+      mc.channels = chan.data(); mc.num_channels = (int)chan.size();
+      const char* err = !rtp_set_maps_output || !rtp_peek_maps ? "this binary was linked without the engine's maps mode"
+                        : rtp_set_maps_output(e, &mc) != RTP_OK ? rtp_last_error(e) : nullptr;
+      if (err) {
+        fprintf(stderr, "GPU %d: --write_heatmaps: %s\n", device, err);
+        *status = 1;
+        G.quit_threads = true;
+        rtp_engine_destroy(e);
+        return;
+      }
+    }
+  }
   // --dry_engine: what the engine costs the HOST per frame (the staging copy of rtp_submit_frame, the joints copy of
   // rtp_collect) and when a frame completes (RATE frames/s, at least two frame times after its submit)
   std::vector<unsigned char> dry_staging;
@@ -561,6 +599,13 @@ void worker(int widx, int device, int* status) {
     inflight.pop_front();
     if (want_render && !gpu_jpeg) fr.rendered.resize(gpu_yuv ? rtp_yuv_bytes(DISP_W, DISP_H, 420) : (size_t)DISP_W * DISP_H * 3);
     size_t jpeg_bytes = 0;
+    if (heat_bytes) {   // the maps of the oldest frame, which the collect below then takes off the engine's FIFO (--dry_engine: zeros)
+      fr.heatmaps.assign(heat_bytes, 0);
+      if (!dry && rtp_peek_maps(e, &tag, fr.heatmaps.data(), fr.heatmaps.size()) != RTP_OK) {
+        fprintf(stderr, "GPU %d frame %d: --write_heatmaps: %s\n", device, fr.index, rtp_last_error(e));
+        fr.heatmaps.assign(heat_bytes, 0);
+      }
+    }
     const int rc = dry ? dry_collect(fr, joints.data(), &n)
                    : !want_render ? rtp_collect(e, &tag, joints.data(), &n)
                    : gpu_yuv ? rtp_collect_rendered_yuv(e, &tag, joints.data(), &n, fr.rendered.data(), fr.rendered.size())
@@ -793,6 +838,18 @@ void writer(std::atomic<bool>* reorder_done) {
       }
       if (vrc != RTP_OK) { fprintf(stderr, "--write_video: frame %d: %s\n", fr.index, rtp_codec_last_error()); G.video_failed = true; }
     }
+    if (!F.write_heatmaps.empty() && !fr.heatmaps.empty()) {   // this thread sees the frames in order
+      char fname[1024];
+      snprintf(fname, sizeof fname, "%s%06d.pgm", F.write_heatmaps.c_str(), fr.video_frame_number);
+      FILE* f = fopen(fname, "wb");
+      if (f) {
+        fprintf(f, "P5\n%d %d\n255\n", NET_W, (int)(fr.heatmaps.size() / (size_t)NET_W));
+        fwrite(fr.heatmaps.data(), 1, fr.heatmaps.size(), f);
+        fclose(f);
+      } else fprintf(stderr, "cannot create %s\n", fname);
+      fr.heatmaps.clear();
+      fr.heatmaps.shrink_to_fit();
+    }
     if (!F.write_frames.empty() && !fr.rendered.empty()) {  // cv::imwrite(fname, wrap_frame, {JPEG_QUALITY, 98}), rtpose.cpp:1367-1381
       char fname[1024];
       if (F.image_dir.empty()) snprintf(fname, sizeof fname, "%s/frame%06d.jpg", F.write_frames.c_str(), fr.video_frame_number);
@@ -870,6 +927,10 @@ int main(int argc, char** argv) {
   }
   for (const std::string* d : {&F.write_frames, &F.write_json})
     if (!d->empty() && !mkdir_p(*d)) { fprintf(stderr, "Could not write to or create directory %s\n", d->c_str()); return 1; }
+  if (F.heatmap_channels != "parts" && F.heatmap_channels != "bkg" && F.heatmap_channels != "parts+bkg" && F.heatmap_channels != "pafs" && F.heatmap_channels != "all") {
+    fprintf(stderr, "--heatmap_channels must be parts, bkg, parts+bkg, pafs or all\n");
+    return 1;
+  }
   if (F.num_gpu < 1) { fprintf(stderr, "--num_gpu must be >= 1\n"); return 1; }
   if (F.precision != "mixed" && F.precision != "fp16" && F.precision != "f16x3" && F.precision != "fp32") { fprintf(stderr, "--precision must be mixed, fp16, f16x3 or fp32\n"); return 1; }
   if (F.frames_in_flight < 1 || F.frames_in_flight > 64) { fprintf(stderr, "--frames_in_flight must be in [1, 64]\n"); return 1; }

@@ -5,12 +5,16 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
 EXEC_GRAPH, EXEC_EAGER = 0, 1
 MAX_PEOPLE = 96
+MAX_NUM_PARTS = 70
+MAPS_GRIDS = {"net": 0, "lowres": 1}              # RTP_MAPS_GRID_*
+MAPS_FORMATS = {"f32": 0, "f16": 1, "u8": 2}      # RTP_MAPS_F32 / F16 / U8
+_MAPS_DTYPES = {0: np.float32, 1: np.float16, 2: np.uint8}
 
 
 # error codes of include/rtpose_mi355x.h
@@ -539,6 +543,56 @@ def video_read_yuv(video):
     return y, plane(s.u, ch, cw, s.uv_stride), plane(s.v, ch, cw, s.uv_stride)
 
 
+def maps_quantize_u8(v, is_paf):
+    """rtp_maps_quantize_u8: the u8 format of maps mode on the host, rint(clip(v * 255, 0, 255)) for confidence and background
+    channels, rint(clip((v + 1) * 127.5, 0, 255)) for PAF channels (is_paf), float32 arithmetic, ties to even, NaN -> 0."""
+    a = np.ascontiguousarray(v, np.float32)
+    out = np.empty(a.shape, np.uint8)
+    rc = lib.rtp_maps_quantize_u8(_f(a), a.size, 1 if is_paf else 0, _u8(out))
+    if rc:
+        raise RtpError(rc, "rtp_maps_quantize_u8")
+    return out
+
+
+def maps_to_f16(v):
+    """rtp_maps_to_f16: float32 -> IEEE binary16, round to nearest even (the f16 format of maps mode), as a float16 array."""
+    a = np.ascontiguousarray(v, np.float32)
+    out = np.empty(a.shape, np.uint16)
+    rc = lib.rtp_maps_to_f16(_f(a), a.size, out.ctypes.data_as(C.POINTER(C.c_uint16)))
+    if rc:
+        raise RtpError(rc, "rtp_maps_to_f16")
+    return out.view(np.float16)
+
+
+def maps_view(obj, shape, dtype):
+    """The rtp_maps_view fields of a device array that receives maps of `shape` (4 dims, leading 1s allowed to be absent in obj) and
+    `dtype`, from its __cuda_array_interface__ (nothing touches the GPU): strides are taken from it, so a window of a larger
+    tensor keeps its parent's pitches.  Elements of a row must be adjacent; planes (and, on the LOWRES grid, scales) evenly spaced."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TypeError(f"{type(obj).__name__} has no __cuda_array_interface__: device arrays only (host arrays: peek_maps)")
+    dt = np.dtype(dtype)
+    if np.dtype(cai["typestr"]) != dt:
+        raise ValueError(f"dtype {cai['typestr']}: the maps are {dt.str}")
+    want = tuple(int(d) for d in shape)
+    have = tuple(int(d) for d in cai["shape"])
+    while len(have) < 4:
+        have = (1,) + have
+    if have != want:
+        raise ValueError(f"shape {tuple(cai['shape'])}: the maps have {want}")
+    strides = cai.get("strides")
+    if strides is None:   # C-contiguous
+        strides = tuple(int(np.prod(cai["shape"][i + 1:])) * dt.itemsize for i in range(len(cai["shape"])))
+    strides = tuple(int(x) for x in strides)
+    strides = (0,) * (4 - len(strides)) + strides
+    ss, cs, rs, es = strides
+    if want[3] > 1 and es != dt.itemsize:
+        raise ValueError(f"element stride {es}: the elements of a row must be adjacent")
+    if want[0] > 1 and ss != want[1] * cs:
+        raise ValueError(f"scale stride {ss} is not {want[1]} channel strides of {cs}: planes must be evenly spaced")
+    return dict(data=int(cai["data"][0]), channel_stride=cs, row_stride=rs)
+
+
 def _stream_of(obj, stream):
     """(handle or None, torch default stream?) of the stream a device frame is ordered on.  stream: a torch.cuda.Stream, a raw
     hipStream_t as int, or None = torch's current stream of a tensor's device, else the interface's `stream` entry, else NULL."""
@@ -788,6 +842,77 @@ class Engine:
         joints = np.zeros((MAX_PEOPLE, self.num_parts, 3), np.float32)
         self._chk(lib.rtp_collect_rendered_yuv_device(self.h, C.byref(tag), _f(joints), C.byref(n), C.byref(s), st))
         return tag.value, n.value, joints[: n.value].copy()
+
+    # ---- maps mode
+    def set_maps_output(self, grid="net", fmt="u8", channels=None):
+        """rtp_set_maps_output: every frame's chosen maps leave the engine (peek_maps / peek_maps_device in front of the frame's
+        collect).  grid "net" ([nch][net_h][net_w], the values of resize()) or "lowres" ([N][nch][low_h][low_w], the values of
+        forward_heatmaps()); fmt "f32", "f16" or "u8"; channels: indices into the heat channels in output order (None = all).
+        grid=None switches the mode off.  Arguments are checked here, before the library is called."""
+        if grid is None:
+            self._chk(lib.rtp_set_maps_output(self.h, None))
+            return
+        if grid not in MAPS_GRIDS:
+            raise ValueError(f"grid {grid!r}: 'net' or 'lowres'")
+        if fmt not in MAPS_FORMATS:
+            raise ValueError(f"fmt {fmt!r}: 'f32', 'f16' or 'u8'")
+        cfg = rtp_maps_config()
+        cfg.struct_size = C.sizeof(rtp_maps_config)
+        cfg.grid, cfg.format = MAPS_GRIDS[grid], MAPS_FORMATS[fmt]
+        if channels is not None:
+            ch = [int(c) for c in channels]
+            if not 1 <= len(ch) <= MAX_NUM_PARTS:
+                raise ValueError(f"{len(ch)} channels: 1 .. {MAX_NUM_PARTS}")
+            bad = [c for c in ch if not 0 <= c < self.heat_channels]
+            if bad:
+                raise ValueError(f"channels {bad} outside [0, {self.heat_channels})")
+            arr = (C.c_int * len(ch))(*ch)
+            cfg.channels, cfg.num_channels = arr, len(ch)
+        self._chk(lib.rtp_set_maps_output(self.h, C.byref(cfg)))
+
+    def maps_info(self):
+        """rtp_maps_info: (shape of one frame's maps as 4 ints, numpy dtype, bytes)."""
+        shape = (C.c_int * 4)()
+        fmt = C.c_int()
+        nb = C.c_size_t()
+        rc = lib.rtp_maps_info(self.h, shape, C.byref(fmt), C.byref(nb))
+        if rc:
+            raise RtpError(rc, "maps mode is off (set_maps_output)")
+        return tuple(shape), np.dtype(_MAPS_DTYPES[fmt.value]), nb.value
+
+    def peek_maps(self, out=None):
+        """rtp_peek_maps: (tag, maps) of the oldest frame in flight, which stays in flight: collect it afterwards.  out: a
+        C-contiguous array of the shape and dtype of maps_info to fill (a loop that reuses one spares a fresh allocation per frame)."""
+        shape, dt, nb = self.maps_info()
+        if out is None:
+            out = np.empty(shape, dt)
+        elif not (isinstance(out, np.ndarray) and out.shape == shape and out.dtype == dt and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
+            raise ValueError(f"out must be a writeable C-contiguous {dt} array of shape {shape}")
+        tag = C.c_uint64()
+        self._chk(lib.rtp_peek_maps(self.h, C.byref(tag), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return tag.value, out
+
+    def peek_maps_device(self, out, stream=None):
+        """rtp_peek_maps_device: the oldest frame's maps written into `out` (a device array of the shape and dtype of maps_info,
+        leading 1s optional, any pitches: see maps_view); work queued on `stream` afterwards sees them.  Returns the tag."""
+        shape, dt, _ = self.maps_info()
+        f = maps_view(out, shape, dt)
+        v = rtp_maps_view()
+        v.struct_size = C.sizeof(rtp_maps_view)
+        v.data, v.channel_stride, v.row_stride = f["data"], f["channel_stride"], f["row_stride"]
+        st, _ = _stream_of(out, stream)
+        tag = C.c_uint64()
+        self._chk(lib.rtp_peek_maps_device(self.h, C.byref(tag), C.byref(v), st))
+        return tag.value
+
+    def maps_from_lowres(self, lowres):
+        """rtp_maps_from_lowres: the maps of the current mode for the given low-res maps (parity tap, idle engine)."""
+        lowres = np.ascontiguousarray(lowres, np.float32)
+        assert lowres.shape == (self.N, self.heat_channels, self.low_h, self.low_w), lowres.shape
+        shape, dt, _ = self.maps_info()
+        out = np.empty(shape, dt)
+        self._chk(lib.rtp_maps_from_lowres(self.h, _f(lowres), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
 
     def encode_jpeg_device(self, obj, quality=98, stream=None, order="bgr"):
         """rtp_encode_jpeg_device: encode_jpeg of a u8 frame in device memory (see frame_view), on the GPU after the work queued on

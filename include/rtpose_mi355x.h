@@ -614,6 +614,67 @@ int rtp_decode_jpeg_device(rtp_engine* e, const unsigned char* jpeg_host, size_t
  * *w, *h (may be NULL) = the file's size.  Where the device pre-processing cannot run the file is decoded on the host. */
 int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t n, uint64_t tag, float* frame_scale, int* w, int* h);
 
+/* ---- maps mode: a frame's part-confidence maps and PAFs from the async path (maps_export.hip) -------------------------- */
+
+/* The engine computes heat_channels maps per frame (rtp_engine_info; COCO 57: 18 parts, background, 38 PAF channels).  Maps mode
+ * hands chosen channels of every submitted frame to the caller.  Off by default, and then nothing about the engine changes.  On:
+ * each frame's post-processing chain gains ONE kernel on the frame's own stream, which evaluates the chosen channels straight
+ * from the low-res maps (the fp32 resized map is never written), converts them and writes a per-slot buffer that is copied to
+ * pinned host memory behind it.  Frames submitted as net inputs (rtp_submit, rtp_submit_device) get maps too. */
+#define RTP_MAPS_GRID_NET 0    /* [nch][net_h][net_w]: the resized_map blob (ImResize over all scales), the values rtp_resize returns, bit for bit */
+#define RTP_MAPS_GRID_LOWRES 1 /* [num_scales][nch][low_h][low_w]: concat_stage7 as rtp_forward_heatmaps returns it */
+#define RTP_MAPS_F32 0
+#define RTP_MAPS_F16 1         /* IEEE binary16, round to nearest even (rtp_maps_to_f16) */
+#define RTP_MAPS_U8 2          /* rtp_maps_quantize_u8 */
+typedef struct rtp_maps_config {
+  unsigned int struct_size; /* sizeof(rtp_maps_config) */
+  int grid, format;         /* RTP_MAPS_GRID_*, RTP_MAPS_F32 / F16 / U8 */
+  const int* channels;      /* indices into concat_stage7, in output order: any order, repeats allowed (copied by the call); NULL = all heat_channels */
+  int num_channels;         /* 1 .. RTP_MAX_NUM_PARTS (ignored when channels == NULL) */
+} rtp_maps_config;
+
+/* Switches maps mode on (or changes it), NULL cfg = off.  Thresholds and scales may change while it is on (rtp_set_scales changes the
+ * maps as it changes ImResize).  Refused, with the engine unchanged: wrong struct_size, unknown grid or format, num_channels out of
+ * range, a channel outside [0, heat_channels) (RTP_EINVAL); frames in flight (RTP_EAGAIN). */
+int rtp_set_maps_output(rtp_engine* e, const rtp_maps_config* cfg);
+
+/* shape = {1, nch, net_h, net_w} (NET) or {num_scales, nch, low_h, low_w} (LOWRES), *format, *bytes = the dense payload of one
+ * frame (any of the three may be NULL).  RTP_EINVAL while the mode is off. */
+int rtp_maps_info(const rtp_engine* e, int shape[4], int* format, size_t* bytes);
+
+/* Blocks until the OLDEST frame in flight is finished (a partial batch is launched, exactly as rtp_collect does) and copies its maps
+ * (dense, the shape of rtp_maps_info) and its tag.  The frame STAYS in flight: follow with whichever rtp_collect* the frame needs.
+ * Peeking twice returns the same maps.  Refused: mode off, maps_host NULL or capacity < bytes, a deferred-weights engine without
+ * weights (RTP_EINVAL); nothing in flight (RTP_EAGAIN). */
+int rtp_peek_maps(rtp_engine* e, uint64_t* tag, void* maps_host, size_t capacity);
+
+/* Where rtp_peek_maps_device writes: element (x, y) of plane z (NET: z = output channel; LOWRES: z = scale * nch + output channel)
+ * is at data + z * channel_stride + y * row_stride + x * element size, strides in bytes, row_stride >= width * element size,
+ * channel_stride >= height * row_stride.  Bytes between rows and between planes are never written. */
+typedef struct rtp_maps_view {
+  unsigned int struct_size; /* sizeof(rtp_maps_view) */
+  void* data;               /* device memory of cfg.device_id */
+  long channel_stride, row_stride;
+} rtp_maps_view;
+
+/* = rtp_peek_maps with the maps written by the kernel itself into the caller's device memory, checked like an rtp_frame_view (device
+ * memory of cfg.device_id, the last addressed byte inside its allocation) before anything is launched.  `stream` as in
+ * rtp_collect_rendered_device: NULL = the maps are complete on return; else they are written in `stream`'s order (which must not
+ * be capturing), and the engine's next batch on that frame slot waits for the write.  Any address and pitch is accepted;
+ * naturally aligned views are written with wide stores.  The kernel runs a second time for this call (the caller's memory is not
+ * known when the batch is launched); the frame's copy to pinned host memory has run as for rtp_peek_maps. */
+int rtp_peek_maps_device(rtp_engine* e, uint64_t* tag, const rtp_maps_view* out_dev, void* stream);
+
+/* Parity tap like rtp_post_from_lowres (idle engine, context 0): the maps of the current mode for the given low-res maps
+ * [num_scales][heat_channels][low_h][low_w]. */
+int rtp_maps_from_lowres(rtp_engine* e, const float* lowres_host, void* maps_host, size_t capacity);
+
+/* Host only: the one definition of the two narrow formats.  u8, in float arithmetic: q = rintf(fminf(fmaxf(s, 0.f), 255.f)) with
+ * s = v * 255.f for confidence and background channels (is_paf 0: channel <= num_parts) and s = (v + 1.f) * 127.5f for PAF channels
+ * (is_paf 1); ties round to even, NaN gives 0.  f16: IEEE binary16 bits, round to nearest even, NaN stays NaN. */
+int rtp_maps_quantize_u8(const float* v, size_t n, int is_paf, unsigned char* out);
+int rtp_maps_to_f16(const float* v, size_t n, uint16_t* out);
+
 #ifdef __cplusplus
 }
 #endif
