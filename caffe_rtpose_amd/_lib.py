@@ -90,6 +90,29 @@ class rtp_maps_view(C.Structure):
     ]
 
 
+class rtp_crops_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("crop_w", C.c_int),
+        ("crop_h", C.c_int),
+        ("max_crops", C.c_int),
+        ("parts", C.POINTER(C.c_int)),
+        ("num_parts", C.c_int),
+        ("min_score", C.c_float),
+        ("min_parts", C.c_int),
+        ("margin", C.c_float),
+        ("layout", C.c_int),
+    ]
+
+
+class rtp_crops_view(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("data", C.c_void_p),
+        ("crop_stride", C.c_long),
+    ]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 vp = C.c_void_p
@@ -206,6 +229,13 @@ SIGNATURES = {
     "rtp_maps_from_lowres": (C.c_int, [vp, fp, vp, C.c_size_t]),
     "rtp_maps_quantize_u8": (C.c_int, [fp, C.c_size_t, C.c_int, C.POINTER(C.c_ubyte)]),
     "rtp_maps_to_f16": (C.c_int, [fp, C.c_size_t, C.POINTER(C.c_uint16)]),
+    "rtp_crop_people": (C.c_int, [C.POINTER(C.c_ubyte), C.c_int, C.c_int, fp, C.c_int, C.c_int, C.POINTER(rtp_crops_config), fp, C.POINTER(C.c_ubyte)]),
+    "rtp_set_crops_output": (C.c_int, [vp, C.POINTER(rtp_crops_config)]),
+    "rtp_crops_info": (C.c_int, [vp, ip, ip, ip, ip, C.POINTER(C.c_size_t)]),
+    "rtp_peek_crops": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.POINTER(C.c_ubyte), C.c_int, ip]),
+    "rtp_peek_crops_device": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.c_int, C.POINTER(rtp_crops_view), vp]),
+    "rtp_crops_from_joints": (C.c_int, [vp, C.POINTER(C.c_ubyte), fp, C.c_int, fp, ip, C.POINTER(C.c_ubyte), C.c_int]),
+    "rtp_crops_head_parts": (C.c_int, [C.c_int, ip]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

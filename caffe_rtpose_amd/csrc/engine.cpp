@@ -635,6 +635,7 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
       }
     }
     if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // rtp_set_maps_output: the frame's maps -> its pinned buffer (engine_maps.cpp)
+    if (e->crops_on && (rc = crops_launch(e, cx, j))) return rc;   // rtp_set_crops_output: the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
     HIPCHK(e, hipMemcpyAsync(sl.host_out + 4, sl.joints, jbytes, hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(e, hipMemcpyAsync(sl.host_out, sl.num_people, sizeof(int), hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(e, hipEventRecord(sl.ev[4], sl.stream));
@@ -650,7 +651,7 @@ int capture_batch(rtp_engine* e, Ctx& cx, int nframes, hipGraphExec_t* out) {
   SYNC_GUARD;
   hipGraph_t g = nullptr;
   HIPCHK(e, hipStreamBeginCapture(cx.stream, hipStreamCaptureModeThreadLocal));
-  const int rc = launch_batch_body(e, cx, nframes, cx.input, false, true, e->graph_post ? 3 : 1);
+  const int rc = launch_batch_body(e, cx, nframes, cx.input, false, true, e->graph_post && !e->crops_on ? 3 : 1);   // (crops mode: see launch_batch)
   const hipError_t s = hipStreamEndCapture(cx.stream, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
   if (s != hipSuccess || !g) return fail(e, RTP_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(s));
@@ -677,6 +678,7 @@ int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bo
       sl.maps_export_pending = false;
     }
   if (e->maps_on && (rc = maps_ensure(e, cx, nframes))) return rc;   // maps mode: the slots' buffers exist before anything is launched or captured
+  if (e->crops_on && (rc = crops_ensure(e, cx, nframes))) return rc;   // crops mode likewise
   if (e->prep_defer && (rc = flush_prep(e, cx, true))) return rc;
   if (cx.in_pending) {   // the batch's inputs were staged on the staging stream: the conv stream starts when the last of them is complete
     if (cx.in_stream != cx.stream) {
@@ -699,7 +701,10 @@ int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bo
   if (!cx.gexec[nframes] && (rc = capture_batch(e, cx, nframes, &cx.gexec[nframes]))) return rc;
   HIPCHK(e, hipEventRecord(cx.gev[0], cx.stream));
   HIPCHK(e, hipGraphLaunch(cx.gexec[nframes], cx.stream));
-  if (!e->graph_post) {  // the conv stack is one replay; every frame's short post-processing chain is launched eagerly on its slot's stream
+  // the conv stack is one replay; every frame's short post-processing chain is launched eagerly on its slot's stream.  Crops mode keeps
+  // the chains out of the graphs under RTP_GRAPH_POST=1 too: the crops kernel reads disp_cur, which differs from frame to frame
+  // (rtp_set_crops_output dropped the graphs that held them)
+  if (!e->graph_post || e->crops_on) {
     if ((rc = launch_batch_body(e, cx, nframes, cx.input, false, false, 2))) return rc;
     cx.graph_run = false;            // collect waits for the frame's own event, not for the whole batch
     cx.graph_conv = true;
@@ -1025,7 +1030,8 @@ void free_ctx(Ctx& cx) {
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     if (sl.export_pending) (void)hipEventSynchronize(sl.ev_export);   // an export on the caller's stream may still read render_dev
     if (sl.maps_export_pending) (void)hipEventSynchronize(sl.ev_maps_export);   // ... or the context's low-res maps (rtp_peek_maps_device)
-    for (hipEvent_t ev : {sl.ev_ready, sl.ev_read, sl.ev_export, sl.ev_maps_export}) if (ev) (void)hipEventDestroy(ev);
+    if (sl.crops_export_pending) (void)hipEventSynchronize(sl.ev_crops_export);   // ... or the frame's display image (rtp_peek_crops_device)
+    for (hipEvent_t ev : {sl.ev_ready, sl.ev_read, sl.ev_export, sl.ev_maps_export, sl.ev_crops_export}) if (ev) (void)hipEventDestroy(ev);
     void* dptrs[] = {sl.resized, sl.peaks, sl.strip_count, sl.strip_list, sl.cand_score, sl.cand_ij, sl.cand_count, sl.cand_blk, sl.conn, sl.conn_score,
                      sl.conn_count, sl.tickets, sl.joints, sl.num_people, sl.frame_dev, sl.disp_dev, sl.render_dev, sl.render_tab};
     for (void* p : dptrs) if (p) (void)hipFree(p);
@@ -1034,6 +1040,7 @@ void free_ctx(Ctx& cx) {
     if (sl.yuv_out_dev) (void)hipFree(sl.yuv_out_dev);
     if (sl.yuv_out_host) (void)hipHostFree(sl.yuv_out_host);
     maps_free(sl);
+    crops_free(sl);
     jpeg_free(&sl.jpeg, &sl.jpeg_host, &sl.jpeg_cap);
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
@@ -1563,6 +1570,8 @@ int open_slot(rtp_engine* e, int* ci, int* sj) {
   }
   *ci = e->open_ctx;
   *sj = e->ctx[e->open_ctx].filled;
+  Ctx& oc = e->ctx[*ci];
+  if (oc.slot[*sj].crops_export_pending) return crops_wait_export(e, oc, oc.slot[*sj], false);   // rtp_peek_crops_device still reads the slot's last frame on a caller's stream
   return RTP_OK;
 }
 
@@ -1628,6 +1637,9 @@ int need_idle(rtp_engine* e) {
         HIPCHK(e, hipEventSynchronize(sl.ev_maps_export));
         sl.maps_export_pending = false;
       }
+  for (Ctx& cx : e->ctx)
+    for (Slot& sl : cx.slot)
+      if (sl.crops_export_pending && (rc = crops_wait_export(e, cx, sl, true))) return rc;
   return RTP_OK;
 }
 

@@ -1,5 +1,6 @@
 // host_util.cpp — the host-only pieces of the path behind the C-ABI: model descriptor tables,
-// default thresholds, process_and_pad_image, the JSON body and the narrow formats of maps mode.  No GPU needed.
+// default thresholds, process_and_pad_image, the JSON body, the narrow formats of maps mode and the boxes and pixels of
+// crops mode (rtp_crop_people).  No GPU needed.
 #include <charconv>
 #include <cmath>
 #include <cstring>
@@ -148,6 +149,131 @@ int rtp_maps_to_f16(const float* v, size_t n, uint16_t* out) {
     out[i] = (uint16_t)(sign | h);
   }
   return RTP_OK;
+}
+
+}  // extern "C"
+
+// ---- crops mode: the one definition of its arithmetic (crops.hip computes the same bits on the device) ------------------------------
+
+// What is wrong with the configuration for a model of model_parts parts, or nullptr.  The engine's switch reports the same text.
+extern "C" const char* rtp_internal_crops_check(const rtp_crops_config* c, int model_parts) {
+  if (!c) return "NULL rtp_crops_config";
+  if (c->struct_size != sizeof(rtp_crops_config)) return "rtp_crops_config.struct_size is not this library's sizeof(rtp_crops_config)";
+  if (model_parts < 1 || model_parts > RTP_MAX_NUM_PARTS) return "num_parts outside 1 .. RTP_MAX_NUM_PARTS";
+  if (c->crop_w < RTP_CROP_MIN_SIZE || c->crop_w > RTP_CROP_MAX_SIZE) return "crop_w outside 8 .. 512";
+  if (c->crop_h < RTP_CROP_MIN_SIZE || c->crop_h > RTP_CROP_MAX_SIZE) return "crop_h outside 8 .. 512";
+  if (c->max_crops < 1 || c->max_crops > RTP_MAX_PEOPLE) return "max_crops outside 1 .. RTP_MAX_PEOPLE";
+  if (!(c->min_score >= 0.f) || std::isinf(c->min_score)) return "min_score must be a finite number >= 0";
+  if (c->min_parts < 1) return "min_parts must be >= 1";
+  if (!(c->margin >= 0.f && c->margin <= 16.f)) return "margin outside 0 .. 16";
+  if (c->layout != RTP_CROPS_HWC_BGR && c->layout != RTP_CROPS_CHW_RGB) return "layout is neither RTP_CROPS_HWC_BGR nor RTP_CROPS_CHW_RGB";
+  if (c->parts) {
+    if (c->num_parts < 1 || c->num_parts > RTP_MAX_NUM_PARTS) return "the part list's num_parts outside 1 .. RTP_MAX_NUM_PARTS";
+    for (int i = 0; i < c->num_parts; ++i)
+      if (c->parts[i] < 0 || c->parts[i] >= model_parts) return "a listed part is outside the model's parts";
+  }
+  return nullptr;
+}
+
+// rtp_crops_head_parts: nose, eyes and ears (COCO), head and neck (MPI)
+extern "C" int rtp_crops_head_parts(int model, int parts[8]) {
+  static const int coco[5] = {0, 14, 15, 16, 17}, mpi[2] = {0, 1};
+  const bool c = model == RTP_MODEL_COCO_18;
+  if (!c && model != RTP_MODEL_MPI_15) return RTP_EINVAL;
+  const int n = c ? 5 : 2;
+  memcpy(parts, c ? coco : mpi, n * sizeof(int));
+  return n;
+}
+
+extern "C" {
+
+int rtp_crop_people(const unsigned char* display_bgr, int w, int h, const float* joints, int num_people, int num_parts,
+                    const rtp_crops_config* cfg, float* boxes, unsigned char* crops) {
+#pragma clang fp contract(off)
+  if (rtp_internal_crops_check(cfg, num_parts) || !boxes || w < 1 || h < 1 || w > 32768 || h > 32768 || num_people < 0) return RTP_EINVAL;
+  if ((num_people > 0 && !joints) || (crops && !display_bgr)) return RTP_EINVAL;
+  const int n = num_people < cfg->max_crops ? num_people : cfg->max_crops;
+  const int nlist = cfg->parts ? cfg->num_parts : num_parts;
+  const int cw = cfg->crop_w, ch = cfg->crop_h;
+  const size_t crop_bytes = (size_t)cw * ch * 3;
+  const float fcw = (float)cw, fch = (float)ch;
+  for (int k = 0; k < n; ++k) {
+    const float* jp = joints + (size_t)k * num_parts * 3;
+    float* rec = boxes + (size_t)k * RTP_CROP_BOX_FLOATS;
+    unsigned char* out = crops ? crops + (size_t)k * crop_bytes : nullptr;
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    int count = 0;
+    for (int i = 0; i < nlist; ++i) {
+      const int p = cfg->parts ? cfg->parts[i] : i;
+      const float s = jp[3 * p + 2];
+      if (!(s > cfg->min_score) || !std::isfinite(jp[3 * p]) || !std::isfinite(jp[3 * p + 1])) continue;
+      const float x = jp[3 * p] + 0.0f, y = jp[3 * p + 1] + 0.0f;
+      x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+      ++count;
+    }
+    bool valid = count >= cfg->min_parts;
+    float left = 0.f, top = 0.f, bw = 0.f, bh = 0.f;
+    if (valid) {
+      const float sx = x0 + x1, sy = y0 + y1;
+      const float cx = sx * 0.5f, cy = sy * 0.5f;
+      bw = x1 - x0; bh = y1 - y0;
+      const bool finite = std::isfinite(bw) && std::isfinite(bh);
+      const float gm = cfg->margin * fmaxf(bw, bh);
+      const float g = gm * 2.0f;
+      const float wg = bw + g, hg = bh + g;
+      bw = fmaxf(wg, 1.0f); bh = fmaxf(hg, 1.0f);
+      const float wn = bh * fcw;
+      const float wa = wn / fch;
+      if (wa > bw) bw = wa;
+      else { const float hn = bw * fch; bh = hn / fcw; }
+      const float hw = bw * 0.5f, hh = bh * 0.5f;
+      left = cx - hw; top = cy - hh;
+      const float right = left + bw, bottom = top + bh;
+      const float lim = 1048576.0f;
+      valid = finite && fabsf(left) <= lim && fabsf(top) <= lim && fabsf(right) <= lim && fabsf(bottom) <= lim;
+    }
+    if (!valid) {
+      rec[0] = rec[1] = rec[2] = rec[3] = 0.f; rec[4] = (float)count; rec[5] = 0.f;
+      if (out) memset(out, 0, crop_bytes);
+      continue;
+    }
+    rec[0] = left; rec[1] = top; rec[2] = bw; rec[3] = bh; rec[4] = (float)count; rec[5] = 1.f;
+    if (!out) continue;
+    const float lq = left * 65536.0f, tq = top * 65536.0f;
+    const float stx = bw / fcw, sty = bh / fch;
+    const float dxq = stx * 65536.0f, dyq = sty * 65536.0f;
+    const long long ox = (long long)rintf(lq), oy = (long long)rintf(tq);
+    const long long dx = (long long)rintf(dxq), dy = (long long)rintf(dyq);
+    const int Sx = dx <= 98304 ? 1 : dx <= 196608 ? 2 : 4, Sy = dy <= 98304 ? 1 : dy <= 196608 ? 2 : 4;
+    const long long half = (long long)Sx * Sy * 2097152, den = (long long)Sx * Sy * 4194304;
+    for (int j = 0; j < ch; ++j)
+      for (int i = 0; i < cw; ++i) {
+        long long T[3] = {0, 0, 0};
+        for (int b = 0; b < Sy; ++b) {
+          const long long py = oy + j * dy + ((2 * b + 1) * dy) / (2 * Sy) - 32768;
+          const long long Y = py >> 16, fy = ((py & 65535) + 16) >> 5;
+          for (int a = 0; a < Sx; ++a) {
+            const long long px = ox + i * dx + ((2 * a + 1) * dx) / (2 * Sx) - 32768;
+            const long long X = px >> 16, fx = ((px & 65535) + 16) >> 5;
+            for (int c = 0; c < 3; ++c) {
+              long long p[2][2];
+              for (int r = 0; r < 2; ++r)
+                for (int q = 0; q < 2; ++q) {
+                  const long long yy = Y + r, xx = X + q;
+                  p[r][q] = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? display_bgr[((size_t)yy * w + xx) * 3 + c] : 0;
+                }
+              T[c] += (2048 - fy) * ((2048 - fx) * p[0][0] + fx * p[0][1]) + fy * ((2048 - fx) * p[1][0] + fx * p[1][1]);
+            }
+          }
+        }
+        for (int c = 0; c < 3; ++c) {
+          const unsigned char v = (unsigned char)((T[c] + half) / den);
+          if (cfg->layout == RTP_CROPS_HWC_BGR) out[((size_t)j * cw + i) * 3 + c] = v;
+          else out[((size_t)(2 - c) * ch + j) * cw + i] = v;
+        }
+      }
+  }
+  return n;
 }
 
 }  // extern "C"

@@ -373,6 +373,31 @@ inline int maps_elem_bytes(int format) { return format == 2 ? 1 : format == 1 ? 
 int maps_export_wide(int grid, int format, int width, const void* data, long channel_stride, long row_stride);
 hipError_t launch_maps_export(const MapsParams& p, hipStream_t stream);
 
+// Crops mode (crops.hip, rtp_set_crops_output): one box per person from the joints connect_assemble_kernel left in device memory, and
+// the display image resampled into fixed-size slots; boxes and pixels are rtp_crop_people's bit for bit (include/rtpose_mi355x.h
+// spells out the arithmetic).  One launch per frame, grid (tiles of one crop, max_crops); *num_people is read on the device
+// (negative = connect's error code = 0 people) and the workgroups of slots >= min(*num_people, max_crops) leave at once.
+//   src == nullptr: boxes only (a frame without a display image), a grid of (1, max_crops)
+//   boxes == nullptr: pixels only (rtp_peek_crops_device runs the kernel again into a caller's memory)
+// Crop k starts at dst + k * crop_stride.  One pixel per thread.  wide = 1: a workgroup's 256 pixels are gathered in LDS and leave as
+// 16-byte stores; crops_wide says where that is allowed.  wide = 0: three byte stores per thread (any address and stride).
+#define RTP_CROPS_MAX_PARTS 70   // RTP_MAX_NUM_PARTS
+struct CropsParams {
+  const unsigned char* src;  // display image, u8 BGR HWC (device)
+  int w, h;
+  const float* joints;       // [max_people][num_parts][3]
+  const int* num_people;
+  float* boxes;              // [max_crops][6] records
+  unsigned char* dst;
+  long crop_stride;
+  int num_parts, nlist, min_parts, crop_w, crop_h, max_crops, layout, wide;
+  float min_score, margin;
+  unsigned char list[RTP_CROPS_MAX_PARTS];
+};
+// data and crop_stride multiples of 16, crop_w a multiple of 16 (then crop_w * 3 and every plane are too)
+int crops_wide(int crop_w, const void* data, long crop_stride);
+hipError_t launch_crops(const CropsParams& p, hipStream_t stream);
+
 struct NmsParams {
   const float* src;  // resized map [src_planes][H][W]
   float* peaks;      // [num_parts][max_peaks+1][3]  (in/out)

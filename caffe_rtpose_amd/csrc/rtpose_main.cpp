@@ -48,6 +48,9 @@ int rtp_collect_rendered_yuv(rtp_engine* e, uint64_t* tag, float* joints, int* n
 // (nor maps mode: --write_heatmaps then runs only under --dry_engine)
 int rtp_set_maps_output(rtp_engine* e, const rtp_maps_config* cfg) __attribute__((weak));
 int rtp_peek_maps(rtp_engine* e, uint64_t* tag, void* maps_host, size_t capacity) __attribute__((weak));
+// (nor crops mode: --write_crops then writes box files without boxes, as under --dry_engine)
+int rtp_set_crops_output(rtp_engine* e, const rtp_crops_config* cfg) __attribute__((weak));
+int rtp_peek_crops(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_boxes, unsigned char* crops_host, int capacity, int* has_pixels) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -82,6 +85,13 @@ struct Flags {
   // nch * net_h with channel k in rows [k * net_h, (k + 1) * net_h), written in frame order by the display thread.
   // --heatmap_channels parts|bkg|parts+bkg|pafs|all chooses the channels (the reference's --heatmaps_add_parts / _bkg / _PAFs).
   std::string write_heatmaps, heatmap_channels = "parts+bkg";
+  // --write_crops PREFIX: every frame's per-person crops of the un-rendered display image (crops mode of the engine) as
+  // PREFIX%06d_%02d.ppm (binary P6, one file per slot that has a box; %02d = the person's index in the frame's joints) and one
+  // PREFIX%06d_boxes.json per frame, written in frame order by the display thread.
+  // --crop_size WxH, --crop_parts all|head|p0,p1,.. (the parts that span a box), --crop_margin F, --max_crops N
+  std::string write_crops, crop_size = "128x128", crop_parts = "all";
+  double crop_margin = 0.15;
+  int max_crops = 16;
   std::string caffemodel = "model/coco/pose_iter_440000.caffemodel", caffeproto = "model/coco/pose_deploy_linevec.prototxt";
   std::string resolution = "1280x720", net_resolution = "656x368", camera_resolution = "1280x720";
   double start_scale = 1, scale_gap = 0.3;
@@ -108,12 +118,13 @@ struct Flags {
 
 int parse_flags(int argc, char** argv, Flags& F) {
   std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video}, {"write_video", &F.write_video}, {"write_heatmaps", &F.write_heatmaps}, {"heatmap_channels", &F.heatmap_channels},
+      {"write_crops", &F.write_crops}, {"crop_size", &F.crop_size}, {"crop_parts", &F.crop_parts},
       {"image_dir", &F.image_dir}, {"caffemodel", &F.caffemodel}, {"caffeproto", &F.caffeproto}, {"resolution", &F.resolution},
       {"net_resolution", &F.net_resolution}, {"camera_resolution", &F.camera_resolution}, {"precision", &F.precision}, {"model", &F.model}, {"devices", &F.devices}};
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
-      {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}};
-  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}};
+      {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}, {"max_crops", &F.max_crops}};
+  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}};
   std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
@@ -171,6 +182,12 @@ void usage() {
          "  PAFs at net resolution as PREFIX%%06d.pgm (binary P5, net_w x channels * net_h, channel k in rows [k * net_h, (k + 1) * net_h)), in frame\n"
          "  order: u8, confidence and background as round(255 v), PAF channels as round(127.5 (v + 1)); evaluated and quantised on the GPU\n"
          "  (maps mode of the engine), only the bytes cross PCIe.  Under --dry_engine the files hold zeros.\n"
+         "  --write_crops PREFIX [--crop_size WxH (128x128)] [--crop_parts all|head|p0,p1,.. (all)] [--crop_margin F (0.15)] [--max_crops N (16)]\n"
+         "  writes a fixed-size crop of the un-rendered display image around each of the first N people as PREFIX%%06d_%%02d.ppm (binary P6;\n"
+         "  %%02d = the person's index; only people with a box get a file) and every frame's boxes as PREFIX%%06d_boxes.json, in frame order.\n"
+         "  The box spans the listed parts (head = nose, eyes and ears; MPI: head and neck), grown by F * its larger side and widened to the\n"
+         "  crop's aspect; boxes and crops are computed on the GPU (crops mode of the engine) and equal rtp_crop_people bit for bit.\n"
+         "  With --host_preprocess the engine never sees the display image: boxes only.  Under --dry_engine the box files hold no boxes.\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
          "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
          "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
@@ -206,6 +223,9 @@ struct Frame {
   int chroma_sx = 0, chroma_sy = 0;
   bool mono = false;
   std::vector<unsigned char> heatmaps;  // --write_heatmaps: the frame's u8 maps [nch][net_h][net_w] (rtp_peek_maps)
+  std::vector<float> crop_boxes;        // --write_crops: the frame's box records [crop_n][RTP_CROP_BOX_FLOATS] and its crops (HWC BGR; empty
+  std::vector<unsigned char> crops;     // for a frame without a display image) (rtp_peek_crops); crop_n < 0: not a --write_crops run
+  int crop_n = -1;
   std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
   bool rendered_jpeg = false;
   bool rendered_yuv = false;            // --write_video x.y4m: rendered holds the frame's 4:2:0 planes (rtp_collect_rendered_yuv)
@@ -557,6 +577,41 @@ void worker(int widx, int device, int* status) {
       }
     }
   }
+  // --write_crops: crops mode, HWC BGR crops (the writer swaps to the RGB of a PPM file)
+  int crop_w = 0, crop_h = 0;
+  if (!F.write_crops.empty()) {
+    rtp_crops_config cc;
+    memset(&cc, 0, sizeof cc);
+    cc.struct_size = sizeof cc;
+    sscanf(F.crop_size.c_str(), "%dx%d", &cc.crop_w, &cc.crop_h);
+    crop_w = cc.crop_w; crop_h = cc.crop_h;
+    cc.max_crops = F.max_crops; cc.min_score = 0.f; cc.min_parts = 1; cc.margin = (float)F.crop_margin; cc.layout = RTP_CROPS_HWC_BGR;
+    std::vector<int> parts;
+    if (F.crop_parts == "head") {
+      int hp[8];
+      const int nh = rtp_crops_head_parts(num_parts == 15 ? RTP_MODEL_MPI_15 : RTP_MODEL_COCO_18, hp);
+      parts.assign(hp, hp + std::max(nh, 0));
+    } else if (F.crop_parts != "all") {
+      for (const char* q = F.crop_parts.c_str(); *q;) {
+        char* end = nullptr;
+        parts.push_back((int)strtol(q, &end, 10));
+        if (end == q) { parts.back() = -1; break; }
+        q = *end == ',' ? end + 1 : end;
+      }
+    }
+    if (!parts.empty()) { cc.parts = parts.data(); cc.num_parts = (int)parts.size(); }
+    if (!dry) {
+      const char* err = !rtp_set_crops_output || !rtp_peek_crops ? "this binary was linked without the engine's crops mode"
+                        : rtp_set_crops_output(e, &cc) != RTP_OK ? rtp_last_error(e) : nullptr;
+      if (err) {
+        fprintf(stderr, "GPU %d: --write_crops: %s\n", device, err);
+        *status = 1;
+        G.quit_threads = true;
+        rtp_engine_destroy(e);
+        return;
+      }
+    }
+  }
   // --dry_engine: what the engine costs the HOST per frame (the staging copy of rtp_submit_frame, the joints copy of
   // rtp_collect) and when a frame completes (RATE frames/s, at least two frame times after its submit)
   std::vector<unsigned char> dry_staging;
@@ -604,6 +659,20 @@ void worker(int widx, int device, int* status) {
       if (!dry && rtp_peek_maps(e, &tag, fr.heatmaps.data(), fr.heatmaps.size()) != RTP_OK) {
         fprintf(stderr, "GPU %d frame %d: --write_heatmaps: %s\n", device, fr.index, rtp_last_error(e));
         fr.heatmaps.assign(heat_bytes, 0);
+      }
+    }
+    if (crop_w) {   // likewise the boxes and crops of the oldest frame (--dry_engine: no boxes)
+      fr.crop_n = 0;
+      if (!dry) {
+        fr.crop_boxes.assign((size_t)F.max_crops * RTP_CROP_BOX_FLOATS, 0.f);
+        fr.crops.assign((size_t)F.max_crops * crop_w * crop_h * 3, 0);
+        int has_pixels = 0;
+        if (rtp_peek_crops(e, &tag, fr.crop_boxes.data(), &fr.crop_n, fr.crops.data(), F.max_crops, &has_pixels) != RTP_OK) {
+          fprintf(stderr, "GPU %d frame %d: --write_crops: %s\n", device, fr.index, rtp_last_error(e));
+          fr.crop_n = 0;
+        }
+        fr.crop_boxes.resize((size_t)fr.crop_n * RTP_CROP_BOX_FLOATS);
+        fr.crops.resize(has_pixels ? (size_t)fr.crop_n * crop_w * crop_h * 3 : 0);
       }
     }
     const int rc = dry ? dry_collect(fr, joints.data(), &n)
@@ -850,6 +919,39 @@ void writer(std::atomic<bool>* reorder_done) {
       fr.heatmaps.clear();
       fr.heatmaps.shrink_to_fit();
     }
+    if (!F.write_crops.empty() && fr.crop_n >= 0) {   // (in frame order too)
+      char fname[1024];
+      int cw = 0, ch = 0;
+      sscanf(F.crop_size.c_str(), "%dx%d", &cw, &ch);
+      const size_t cb = (size_t)cw * ch * 3;
+      std::vector<unsigned char> rgb(cb);
+      snprintf(fname, sizeof fname, "%s%06d_boxes.json", F.write_crops.c_str(), fr.video_frame_number);
+      FILE* f = fopen(fname, "wb");
+      if (f) {
+        fprintf(f, "{\n\"frame\":%d,\n\"crop_w\":%d,\n\"crop_h\":%d,\n\"boxes\":[", fr.video_frame_number, cw, ch);
+        for (int k = 0; k < fr.crop_n; ++k) {
+          const float* b = &fr.crop_boxes[(size_t)k * RTP_CROP_BOX_FLOATS];
+          fprintf(f, "%s\n{\"person\":%d,\"left\":%.9g,\"top\":%.9g,\"width\":%.9g,\"height\":%.9g,\"parts\":%d,\"valid\":%d}", k ? "," : "", k, (double)b[0], (double)b[1],
+                  (double)b[2], (double)b[3], (int)b[4], (int)b[5]);
+        }
+        fprintf(f, "\n]\n}\n");
+        fclose(f);
+      } else fprintf(stderr, "cannot create %s\n", fname);
+      for (int k = 0; k < fr.crop_n && !fr.crops.empty(); ++k) {
+        if (fr.crop_boxes[(size_t)k * RTP_CROP_BOX_FLOATS + 5] == 0.f) continue;   // no box: no file
+        const unsigned char* src = &fr.crops[(size_t)k * cb];
+        for (size_t q = 0; q < cb; q += 3) { rgb[q] = src[q + 2]; rgb[q + 1] = src[q + 1]; rgb[q + 2] = src[q]; }
+        snprintf(fname, sizeof fname, "%s%06d_%02d.ppm", F.write_crops.c_str(), fr.video_frame_number, k);
+        FILE* g = fopen(fname, "wb");
+        if (g) {
+          fprintf(g, "P6\n%d %d\n255\n", cw, ch);
+          fwrite(rgb.data(), 1, cb, g);
+          fclose(g);
+        } else fprintf(stderr, "cannot create %s\n", fname);
+      }
+      fr.crops.clear();
+      fr.crops.shrink_to_fit();
+    }
     if (!F.write_frames.empty() && !fr.rendered.empty()) {  // cv::imwrite(fname, wrap_frame, {JPEG_QUALITY, 98}), rtpose.cpp:1367-1381
       char fname[1024];
       if (F.image_dir.empty()) snprintf(fname, sizeof fname, "%s/frame%06d.jpg", F.write_frames.c_str(), fr.video_frame_number);
@@ -930,6 +1032,16 @@ int main(int argc, char** argv) {
   if (F.heatmap_channels != "parts" && F.heatmap_channels != "bkg" && F.heatmap_channels != "parts+bkg" && F.heatmap_channels != "pafs" && F.heatmap_channels != "all") {
     fprintf(stderr, "--heatmap_channels must be parts, bkg, parts+bkg, pafs or all\n");
     return 1;
+  }
+  if (!F.write_crops.empty()) {
+    int cw = 0, ch = 0;
+    char tail = 0;
+    if (sscanf(F.crop_size.c_str(), "%dx%d%c", &cw, &ch, &tail) != 2 || cw < RTP_CROP_MIN_SIZE || ch < RTP_CROP_MIN_SIZE || cw > RTP_CROP_MAX_SIZE || ch > RTP_CROP_MAX_SIZE) {
+      fprintf(stderr, "--crop_size must be WxH with both in [%d, %d]\n", RTP_CROP_MIN_SIZE, RTP_CROP_MAX_SIZE);
+      return 1;
+    }
+    if (F.max_crops < 1 || F.max_crops > RTP_MAX_PEOPLE) { fprintf(stderr, "--max_crops must be in [1, %d]\n", RTP_MAX_PEOPLE); return 1; }
+    if (!(F.crop_margin >= 0 && F.crop_margin <= 16)) { fprintf(stderr, "--crop_margin must be in [0, 16]\n"); return 1; }
   }
   if (F.num_gpu < 1) { fprintf(stderr, "--num_gpu must be >= 1\n"); return 1; }
   if (F.precision != "mixed" && F.precision != "fp16" && F.precision != "f16x3" && F.precision != "fp32") { fprintf(stderr, "--precision must be mixed, fp16, f16x3 or fp32\n"); return 1; }

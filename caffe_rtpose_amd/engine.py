@@ -5,7 +5,7 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -15,6 +15,8 @@ MAX_NUM_PARTS = 70
 MAPS_GRIDS = {"net": 0, "lowres": 1}              # RTP_MAPS_GRID_*
 MAPS_FORMATS = {"f32": 0, "f16": 1, "u8": 2}      # RTP_MAPS_F32 / F16 / U8
 _MAPS_DTYPES = {0: np.float32, 1: np.float16, 2: np.uint8}
+CROPS_LAYOUTS = {"hwc_bgr": 0, "chw_rgb": 1}      # RTP_CROPS_HWC_BGR / CHW_RGB
+CROP_BOX_FLOATS = 6                               # left, top, width, height, counting parts, valid
 
 
 # error codes of include/rtpose_mi355x.h
@@ -593,6 +595,62 @@ def maps_view(obj, shape, dtype):
     return dict(data=int(cai["data"][0]), channel_stride=cs, row_stride=rs)
 
 
+def crops_head_parts(model):
+    """The part indices of --crop_parts head: nose, eyes and ears (COCO), head and neck (MPI)."""
+    parts = (C.c_int * 8)()
+    n = lib.rtp_crops_head_parts(int(model), parts)
+    if n < 0:
+        raise RtpError(n, "bad model")
+    return list(parts)[:n]
+
+
+def _crops_config(crop_w, crop_h, max_crops, parts, min_score, min_parts, margin, layout):
+    """(rtp_crops_config, what keeps its part list alive); layout: a CROPS_LAYOUTS name or its number"""
+    cfg = rtp_crops_config()
+    cfg.struct_size = C.sizeof(rtp_crops_config)
+    cfg.crop_w, cfg.crop_h, cfg.max_crops = int(crop_w), int(crop_h), int(max_crops)
+    cfg.min_score, cfg.min_parts, cfg.margin = float(min_score), int(min_parts), float(margin)
+    if isinstance(layout, str):
+        if layout not in CROPS_LAYOUTS:
+            raise ValueError(f"layout {layout!r}: 'hwc_bgr' or 'chw_rgb'")
+        layout = CROPS_LAYOUTS[layout]
+    cfg.layout = int(layout)
+    keep = None
+    if parts is not None:
+        keep = (C.c_int * max(len(parts), 1))(*[int(p) for p in parts])
+        cfg.parts, cfg.num_parts = keep, len(parts)
+    return cfg, keep
+
+
+def _crops_shape(crop_w, crop_h, layout):
+    return (crop_h, crop_w, 3) if layout == 0 else (3, crop_h, crop_w)
+
+
+def crop_people(display_bgr, joints, num_parts, crop_w, crop_h, max_crops=MAX_PEOPLE, parts=None, min_score=0.0, min_parts=1, margin=0.0,
+                layout="hwc_bgr", pixels=True):
+    """rtp_crop_people, the host definition of crops mode: (boxes [n][6], crops [n][crop_h][crop_w][3] or [n][3][crop_h][crop_w]) for
+    joints [people][num_parts][3] on the u8 BGR display image; n = min(people, max_crops).  pixels=False: boxes only (crops None,
+    display_bgr may be None)."""
+    cfg, keep = _crops_config(crop_w, crop_h, max_crops, parts, min_score, min_parts, margin, layout)
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, int(num_parts), 3)
+    people = j.shape[0]
+    n = min(people, max(int(max_crops), 0))
+    boxes = np.zeros((n, CROP_BOX_FLOATS), np.float32)
+    img, w, h = None, 1, 1
+    if display_bgr is not None:
+        img = np.ascontiguousarray(display_bgr, np.uint8)
+        h, w = img.shape[:2]
+    crops = np.zeros((n,) + _crops_shape(int(crop_w), int(crop_h), cfg.layout), np.uint8) if pixels else None
+    jj = j if people else np.zeros((1, int(num_parts), 3), np.float32)
+    bb = boxes if n else np.zeros((1, CROP_BOX_FLOATS), np.float32)
+    rc = lib.rtp_crop_people(_u8(img) if img is not None else None, w, h, _f(jj), people, int(num_parts), C.byref(cfg), _f(bb),
+                             _u8(crops if n else np.zeros(1, np.uint8)) if pixels else None)
+    if rc < 0:
+        raise RtpError(rc, "rtp_crop_people: an argument is out of range")
+    assert rc == n
+    return boxes, crops
+
+
 def _stream_of(obj, stream):
     """(handle or None, torch default stream?) of the stream a device frame is ordered on.  stream: a torch.cuda.Stream, a raw
     hipStream_t as int, or None = torch's current stream of a tensor's device, else the interface's `stream` entry, else NULL."""
@@ -913,6 +971,82 @@ class Engine:
         out = np.empty(shape, dt)
         self._chk(lib.rtp_maps_from_lowres(self.h, _f(lowres), out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
+
+    # ---- crops mode
+    def set_crops_output(self, crop_w=None, crop_h=None, max_crops=16, parts=None, min_score=0.0, min_parts=1, margin=0.0, layout="hwc_bgr"):
+        """rtp_set_crops_output: every frame's per-person boxes and fixed-size crops of the display image leave the engine
+        (peek_crops / peek_crops_device in front of the frame's collect).  parts: the part indices that span a box (None = all,
+        crops_head_parts(model) = the head); a part counts when its score > min_score; fewer than min_parts counting parts: no
+        box; margin: every side moves out by margin * max(width, height).  crop_w=None switches the mode off."""
+        if crop_w is None:
+            self._chk(lib.rtp_set_crops_output(self.h, None))
+            return
+        cfg, keep = _crops_config(crop_w, crop_h, max_crops, parts, min_score, min_parts, margin, layout)
+        self._chk(lib.rtp_set_crops_output(self.h, C.byref(cfg)))
+
+    def crops_info(self):
+        """rtp_crops_info: dict(crop_w, crop_h, max_crops, layout, crop_bytes, shape of one crop)."""
+        w, h, m, lay = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        nb = C.c_size_t()
+        rc = lib.rtp_crops_info(self.h, C.byref(w), C.byref(h), C.byref(m), C.byref(lay), C.byref(nb))
+        if rc:
+            raise RtpError(rc, "crops mode is off (set_crops_output)")
+        return dict(crop_w=w.value, crop_h=h.value, max_crops=m.value, layout=lay.value, crop_bytes=nb.value,
+                    shape=_crops_shape(w.value, h.value, lay.value))
+
+    def peek_crops(self, pixels=True):
+        """rtp_peek_crops: (tag, boxes [n][6], crops [n] + shape, or None for a frame without a display image or pixels=False) of
+        the oldest frame in flight, which stays in flight: collect it afterwards."""
+        info = self.crops_info()
+        cap = info["max_crops"]
+        boxes = np.zeros((cap, CROP_BOX_FLOATS), np.float32)
+        crops = np.zeros((cap,) + info["shape"], np.uint8) if pixels else None
+        tag = C.c_uint64()
+        n, has = C.c_int(), C.c_int()
+        self._chk(lib.rtp_peek_crops(self.h, C.byref(tag), _f(boxes), C.byref(n), _u8(crops) if pixels else None, cap, C.byref(has)))
+        return tag.value, boxes[: n.value].copy(), (crops[: n.value].copy() if pixels and has.value else None)
+
+    def peek_crops_device(self, out, stream=None):
+        """rtp_peek_crops_device: the oldest frame's crops written into `out`, a u8 device array ([max_crops] + the crop's shape, the
+        crops evenly spaced, each one dense: a window of a larger tensor keeps its stride); work queued on `stream` afterwards
+        sees them.  Returns (tag, boxes [n][6])."""
+        info = self.crops_info()
+        cai = getattr(out, "__cuda_array_interface__", None)
+        if cai is None:
+            raise TypeError(f"{type(out).__name__} has no __cuda_array_interface__: device arrays only (host arrays: peek_crops)")
+        want = (info["max_crops"],) + info["shape"]
+        if np.dtype(cai["typestr"]) != np.uint8 or tuple(int(d) for d in cai["shape"]) != want:
+            raise ValueError(f"{cai['typestr']} {tuple(cai['shape'])}: the crops are uint8 {want}")
+        strides = cai.get("strides")
+        dense = tuple(int(np.prod(want[i + 1:])) for i in range(4))
+        strides = dense if strides is None else tuple(int(x) for x in strides)
+        if strides[1:] != dense[1:]:
+            raise ValueError(f"strides {strides}: every crop must be dense ({dense[1:]})")
+        v = rtp_crops_view()
+        v.struct_size = C.sizeof(rtp_crops_view)
+        v.data, v.crop_stride = int(cai["data"][0]), strides[0]
+        st, _ = _stream_of(out, stream)
+        boxes = np.zeros((info["max_crops"], CROP_BOX_FLOATS), np.float32)
+        tag = C.c_uint64()
+        n = C.c_int()
+        self._chk(lib.rtp_peek_crops_device(self.h, C.byref(tag), _f(boxes), C.byref(n), info["max_crops"], C.byref(v), st))
+        return tag.value, boxes[: n.value].copy()
+
+    def crops_from_joints(self, display_bgr, joints, pixels=True):
+        """rtp_crops_from_joints: (boxes, crops) of the current mode for the given display image and joints [people][num_parts][3]
+        through the kernel of the async path (parity tap, idle engine)."""
+        info = self.crops_info()
+        img = np.ascontiguousarray(display_bgr, np.uint8)
+        assert img.shape == (self.cfg.c.disp_h, self.cfg.c.disp_w, 3), img.shape
+        j = np.ascontiguousarray(joints, np.float32).reshape(-1, self.num_parts, 3)
+        people = j.shape[0]
+        cap = info["max_crops"]
+        boxes = np.zeros((cap, CROP_BOX_FLOATS), np.float32)
+        crops = np.zeros((cap,) + info["shape"], np.uint8) if pixels else None
+        n = C.c_int()
+        jj = j if people else np.zeros((1, self.num_parts, 3), np.float32)
+        self._chk(lib.rtp_crops_from_joints(self.h, _u8(img), _f(jj), people, _f(boxes), C.byref(n), _u8(crops) if pixels else None, cap))
+        return boxes[: n.value].copy(), (crops[: n.value].copy() if pixels else None)
 
     def encode_jpeg_device(self, obj, quality=98, stream=None, order="bgr"):
         """rtp_encode_jpeg_device: encode_jpeg of a u8 frame in device memory (see frame_view), on the GPU after the work queued on

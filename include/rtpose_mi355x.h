@@ -675,6 +675,122 @@ int rtp_maps_from_lowres(rtp_engine* e, const float* lowres_host, void* maps_hos
 int rtp_maps_quantize_u8(const float* v, size_t n, int is_paf, unsigned char* out);
 int rtp_maps_to_f16(const float* v, size_t n, uint16_t* out);
 
+/* ---- crops mode: per-person boxes and fixed-size crops of the display image (crops.hip) ------------------------------- */
+
+/* A second stage per person (hands, faces, re-identification, a top-down refiner) wants a fixed-size patch around each person or
+ * around a group of parts.  Crops mode hands every submitted frame's boxes and crops to the caller.  Off by default, and then
+ * nothing about the engine changes.  On: each frame's post-processing chain gains ONE kernel on the frame's own stream behind the
+ * connect kernels.  It reads num_people and the joints in device memory (no host synchronisation), derives a box per person and
+ * resamples the frame's un-rendered display image into max_crops fixed-size slots.  Slot k belongs to person k (no compaction);
+ * n = min(num_people, max_crops) slots are produced.  rtp_crop_people is the one definition of the arithmetic; the kernel's boxes
+ * and pixels equal it bit for bit.
+ *
+ * THE BOX, in float32, every operation rounded on its own (no fused multiply-add), in exactly this order:
+ *   A list entry p of person k counts when score > min_score and x and y are finite (a NaN score never counts).  A repeated entry
+ *   counts once per repeat.  count = the number of counting entries; count < min_parts: the slot has no box.
+ *   Every counting x and y is first taken as x + 0.0f (so that -0 is +0 and min / max do not depend on the order).
+ *   x0 = min x, x1 = max x, y0 = min y, y1 = max y
+ *   cx = (x0 + x1) * 0.5f            cy = (y0 + y1) * 0.5f
+ *   w = x1 - x0                      h = y1 - y0
+ *   (an infinite w or h, the overflow of two huge coordinates: the slot has no box)
+ *   g = (margin * fmaxf(w, h)) * 2.0f
+ *   w = fmaxf(w + g, 1.0f)           h = fmaxf(h + g, 1.0f)
+ *   wa = (h * (float)crop_w) / (float)crop_h
+ *   if (wa > w) w = wa;  else h = (w * (float)crop_h) / (float)crop_w;
+ *   left = cx - w * 0.5f             top = cy - h * 0.5f
+ *   right = left + w                 bottom = top + h
+ *   The box is NOT clipped to the image.  Unless |left|, |top|, |right| and |bottom| are all <= 1048576.0f (2^20; an infinity or a
+ *   NaN from an overflow fails this), the slot has no box.
+ * The record of slot k, RTP_CROP_BOX_FLOATS floats: {left, top, w, h, (float)count, valid (1.0f or 0.0f)}; a slot without a box
+ * holds {0, 0, 0, 0, count, 0}.  Coordinates are display pixels with pixel (c, r) covering [c, c + 1) x [r, r + 1).
+ *
+ * THE PIXELS, integers only past these four conversions (Q16, int64):
+ *   ox = (int64)rintf(left * 65536.0f)                    oy = (int64)rintf(top * 65536.0f)
+ *   dx = (int64)rintf((w / (float)crop_w) * 65536.0f)     dy = (int64)rintf((h / (float)crop_h) * 65536.0f)
+ *   Sx = dx <= 98304 ? 1 : dx <= 196608 ? 2 : 4 (a step of <= 1.5, <= 3, more pixels); Sy likewise from dy.
+ *   Output pixel (i, j) is the mean of Sx x Sy bilinear samples.  Sample (a, b), a < Sx, b < Sy, lies at the sub-cell centre
+ *     px = ox + i * dx + ((2 * a + 1) * dx) / (2 * Sx) - 32768      py = oy + j * dy + ((2 * b + 1) * dy) / (2 * Sy) - 32768
+ *   (Q16 pixel-index coordinates; the divisions are exact shifts of non-negative numbers), reads the four taps at columns
+ *   X = px >> 16 (floor) and X + 1 and rows Y = py >> 16 and Y + 1, with 11-bit weights per axis
+ *     fx = ((px & 65535) + 16) >> 5 (0 .. 2048), weights (2048 - fx, fx); fy likewise,
+ *   and is worth  (2048 - fy) * ((2048 - fx) * p[Y][X] + fx * p[Y][X+1]) + fy * ((2048 - fx) * p[Y+1][X] + fx * p[Y+1][X+1]).
+ *   A tap outside the image reads 0 in all three channels (constant border).  The samples are summed (T) and
+ *     value = (T + Sx * Sy * 2097152) / (Sx * Sy * 4194304)   (round half up; a shift).
+ *   A box as large as the crop at an integer position is therefore a plain copy, and a box larger than the crop is box-filtered.
+ * The crop of a slot without a box is all zeros.  Crop k occupies crop_w * crop_h * 3 bytes:
+ *   RTP_CROPS_HWC_BGR: [crop_h][crop_w][3], the display image's channel order;  RTP_CROPS_CHW_RGB: [3][crop_h][crop_w], planes R, G, B. */
+#define RTP_CROPS_HWC_BGR 0
+#define RTP_CROPS_CHW_RGB 1
+#define RTP_CROP_BOX_FLOATS 6
+#define RTP_CROP_MIN_SIZE 8
+#define RTP_CROP_MAX_SIZE 512
+typedef struct rtp_crops_config {
+  unsigned int struct_size; /* sizeof(rtp_crops_config) */
+  int crop_w, crop_h;       /* RTP_CROP_MIN_SIZE .. RTP_CROP_MAX_SIZE each */
+  int max_crops;            /* 1 .. RTP_MAX_PEOPLE */
+  const int* parts;         /* part indices that span the box, any order, repeats allowed (copied by the call); NULL = all parts */
+  int num_parts;            /* 1 .. RTP_MAX_NUM_PARTS (ignored when parts == NULL) */
+  float min_score;          /* >= 0 */
+  int min_parts;            /* >= 1 */
+  float margin;             /* >= 0, <= 16 */
+  int layout;               /* RTP_CROPS_HWC_BGR | RTP_CROPS_CHW_RGB, u8 both */
+} rtp_crops_config;
+
+/* Host only (no engine, no GPU): the definition above.  display_bgr: u8 HWC BGR of w x h; joints [num_people][num_parts][3] as
+ * rtp_collect returns them (num_parts here = the model's parts per person).  Writes n = min(num_people, cfg->max_crops) box records
+ * and, unless crops is NULL, n crops of crop_w * crop_h * 3 bytes each; nothing behind them.  display_bgr may be NULL when crops is.
+ * Returns n, or RTP_EINVAL: a NULL cfg / boxes, wrong struct_size, w or h < 1 or > 32768, num_people < 0, num_parts outside
+ * 1 .. RTP_MAX_NUM_PARTS, a configuration field out of its range, a listed part outside [0, num_parts), NULL joints with people,
+ * NULL display_bgr with crops. */
+int rtp_crop_people(const unsigned char* display_bgr, int w, int h, const float* joints, int num_people, int num_parts,
+                    const rtp_crops_config* cfg, float* boxes, unsigned char* crops);
+
+/* Host only: the part indices of a head box for rtp_crops_config.parts (rtpose.bin --crop_parts head): nose, eyes and ears for
+ * RTP_MODEL_COCO_18 (5), head and neck for RTP_MODEL_MPI_15 (2).  Returns their number, or RTP_EINVAL for another model. */
+int rtp_crops_head_parts(int model, int parts[8]);
+
+/* Switches crops mode on (or changes it), NULL cfg = off.  Refused, with the engine unchanged: wrong struct_size, a size, count,
+ * margin, min_score, min_parts or layout out of range, a listed part outside the model's parts (RTP_EINVAL); frames in flight
+ * (RTP_EAGAIN).  Under the experiments build's RTP_GRAPH_POST=1 the post-processing chains are launched eagerly while the mode is on. */
+int rtp_set_crops_output(rtp_engine* e, const rtp_crops_config* cfg);
+
+/* The current mode (any pointer may be NULL); *crop_bytes = crop_w * crop_h * 3.  RTP_EINVAL while the mode is off. */
+int rtp_crops_info(const rtp_engine* e, int* crop_w, int* crop_h, int* max_crops, int* layout, size_t* crop_bytes);
+
+/* Blocks until the OLDEST frame in flight is finished (as rtp_collect does) and hands out its tag, *num_boxes = n, n box records
+ * into boxes_host and, where the frame has a display image (*has_pixels = 1: rtp_submit_frame* frames; 0: rtp_submit,
+ * rtp_submit_device) and crops_host is not NULL, n dense crops into crops_host.  capacity = the number of records / crops the two
+ * buffers hold; bytes behind the n written ones are untouched.  The frame STAYS in flight: follow with whichever rtp_collect* it
+ * needs; peeking twice returns the same.  The crops come from the un-rendered display image whatever the renderer does.
+ * Refused: mode off, NULL boxes_host or num_boxes, a deferred-weights engine without weights (RTP_EINVAL); nothing in flight
+ * (RTP_EAGAIN); capacity < n (RTP_ERANGE, *num_boxes = n, nothing else written; the frame stays peekable). */
+int rtp_peek_crops(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_boxes, unsigned char* crops_host, int capacity,
+                   int* has_pixels);
+
+/* Where rtp_peek_crops_device writes: crop k starts at data + k * crop_stride, crop_stride >= crop bytes.  Bytes between crops
+ * are never written.  All max_crops slots must lie inside the allocation (n is not known when the view is checked). */
+typedef struct rtp_crops_view {
+  unsigned int struct_size; /* sizeof(rtp_crops_view) */
+  void* data;               /* device memory of cfg.device_id */
+  long crop_stride;
+} rtp_crops_view;
+
+/* = rtp_peek_crops with the n crops written by the kernel itself into the caller's device memory, checked like an rtp_frame_view
+ * (device memory of cfg.device_id, the last addressed byte inside its allocation) before anything is launched; the box records
+ * still go to host memory (capacity as above).  `stream` as in rtp_peek_maps_device: NULL = the crops are complete on return;
+ * else they are written in `stream`'s order (which must not be capturing), and the next frame staged on that frame slot waits
+ * for the write.  Any address and stride is accepted; where data and crop_stride are multiples of 16 and crop_w is one too, every
+ * lane stores 16 bytes at a time.  Also refused: a frame without a display image (RTP_EINVAL; rtp_peek_crops gives its boxes). */
+int rtp_peek_crops_device(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_boxes, int capacity, const rtp_crops_view* out_dev,
+                          void* stream);
+
+/* Parity tap like rtp_render (idle engine, context 0): the kernel of the async path on caller data.  display_bgr_host: u8 HWC BGR
+ * of cfg.disp_w x cfg.disp_h; joints_host [num_people][num_parts][3], num_people <= RTP_MAX_PEOPLE.  Writes
+ * n = min(num_people, max_crops) records and crops (crops_host may be NULL), capacity as in rtp_peek_crops; returns RTP_OK and
+ * *num_boxes = n. */
+int rtp_crops_from_joints(rtp_engine* e, const unsigned char* display_bgr_host, const float* joints_host, int num_people,
+                          float* boxes_host, int* num_boxes, unsigned char* crops_host, int capacity);
+
 #ifdef __cplusplus
 }
 #endif
