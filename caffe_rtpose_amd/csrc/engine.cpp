@@ -244,22 +244,62 @@ int upload_all_weights(rtp_engine* e) {
 }
 
 // ---- launches -------------------------------------------------------------------------------
-// Residency-stamp slots of one batch context: [0, 64) plan steps (conv stack), 64 + 8 j + {0 strip, 1 write, 2 pairs, 3 match, 4 assemble}
-// = frame j's post-processing chain, 64 + 8 j + 5 = the export of its rendered image (rtp_collect_rendered_device), 64 + 8 j + 6 = the
-// JPEG encoding of its rendered image (rtp_set_render_jpeg; all seven launches), 200 + 2 j + {0 warp or import of a device frame,
-// 1 area/pad} = frame j's device pre-processing; 64 + 8 j + 7 = the conversion of frame j's rendered image to YUV planes (rtp_set_render_yuv,
-// rtp_collect_rendered_yuv_device; engine_yuv.cpp).
-constexpr int STAMP_SLOTS = 256;
+constexpr int STAMP_SLOTS = 256;   // (what each one is: StampKind, engine_internal.h)
 }  // namespace
 unsigned long long* stamp_slot(const rtp_engine* e, const Ctx& cx, int idx) {
   return (e->stamp_probe && cx.stamps && idx >= 0 && idx < STAMP_SLOTS) ? cx.stamps + 2 * (size_t)idx : nullptr;
 }
+unsigned long long* frame_stamp(const rtp_engine* e, const Ctx& cx, int sj, StampKind kind) {
+  return stamp_slot(e, cx, kind < STAMP_WARP ? 64 + 8 * sj + kind : kind < STAMP_JPEG_DEC ? 200 + 2 * sj + (kind - STAMP_WARP) : 232 + sj);
+}
+
+// ---- ExportFence (engine_internal.h) ----------------------------------------------------------
+int fence_arm(rtp_engine* e, ExportFence& f, hipStream_t st, bool null_stream) {
+  if (!f.ev) HIPCHK(e, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+  if (f.pending) HIPCHK(e, hipStreamWaitEvent(st, f.ev, 0));   // an earlier read of this frame on another stream: the record below then covers both
+  HIPCHK(e, hipEventRecord(f.ev, st));
+  f.pending = true;
+  return null_stream ? fence_wait_host(e, f) : RTP_OK;
+}
+int fence_wait_streams(rtp_engine* e, ExportFence& f, std::initializer_list<hipStream_t> streams) {
+  if (!f.pending) return RTP_OK;
+  for (hipStream_t s : streams) if (s) HIPCHK(e, hipStreamWaitEvent(s, f.ev, 0));
+  f.pending = false;
+  return RTP_OK;
+}
+int fence_wait_host(rtp_engine* e, ExportFence& f) {
+  if (!f.pending) return RTP_OK;
+  HIPCHK(e, hipEventSynchronize(f.ev));
+  f.pending = false;
+  return RTP_OK;
+}
+void fence_destroy(ExportFence& f) {
+  (void)fence_wait_host(nullptr, f);
+  if (f.ev) (void)hipEventDestroy(f.ev);
+  f = ExportFence();
+}
+void RenderOut::free() {
+  for (void* p : {(void*)dev, (void*)tab, (void*)yuv_dev}) if (p) (void)hipFree(p);
+  for (void* p : {(void*)host, (void*)yuv_host}) if (p) (void)hipHostFree(p);
+  jpeg_free(&jpeg, &jpeg_host, &jpeg_cap);
+  dev = host = yuv_dev = yuv_host = jpeg_host_dev = nullptr;
+  tab = nullptr;
+}
+int render_host_release(rtp_engine* e) {
+  SYNC_GUARD;   // (the engine is idle: no copy into them is pending)
+  for (Ctx& cx : e->ctx)
+    for (Slot& sl : cx.slot)
+      if (sl.render.host) { HIPCHK(e, hipHostFree(sl.render.host)); sl.render.host = nullptr; }
+  return RTP_OK;
+}
+
 namespace {
 // the stamps of the batch that last ran on `cx` (complete: the context is idle) -> e->stamp_spans; slots zeroed for the next batch
 int stamp_harvest(rtp_engine* e, Ctx& cx) {
   if (!cx.stamps || !cx.stamps_dirty) return RTP_OK;
-  for (Slot& sl : cx.slot)   // an export on the caller's stream stamps slot 64 + 8 j + 5 (a host wait: probe runs only)
-    if (sl.export_pending) HIPCHK(e, hipEventSynchronize(sl.ev_export));
+  int rc;
+  for (Slot& sl : cx.slot)   // an export on the caller's stream stamps STAMP_EXPORT / STAMP_YUV_OUT (a host wait: probe runs only)
+    if ((rc = fence_wait_host(e, sl.render.fence))) return rc;
   std::vector<unsigned long long> h(2 * STAMP_SLOTS);
   // on the context's own stream, which is idle here: the legacy stream shares a hardware queue with a busy context where queues are
   // scarce ("hardware queues" below), and a synchronous copy there waits behind that context's kernels (6 % of the wall with no kernel
@@ -510,7 +550,7 @@ NmsParams nms_params(rtp_engine* e, Ctx& cx, int sj) {
   np.max_peaks = e->plan.max_peaks; np.nstrips = e->plan.nstrips; np.strip_rows = e->plan.strip_rows; np.threshold = e->nms_threshold;
   np.probe = nullptr;
   np.clear_flag = nullptr;
-  np.stamp = stamp_slot(e, cx, 64 + 8 * sj);
+  np.stamp = frame_stamp(e, cx, sj, STAMP_STRIP);
   return np;
 }
 int run_nms(rtp_engine* e, Ctx& cx, int sj = 0) {
@@ -528,7 +568,7 @@ ConnectParams connect_params(rtp_engine* e, Ctx& cx, int sj) {
   cp.max_peaks = e->plan.max_peaks; cp.net_w = e->cfg.net_w; cp.net_h = e->cfg.net_h; cp.disp_w = e->cfg.disp_w; cp.disp_h = e->cfg.disp_h;
   cp.inter_threshold = e->inter_threshold; cp.inter_min_above = e->inter_min_above; cp.min_subset_cnt = e->min_subset_cnt;
   cp.min_subset_score = e->min_subset_score; cp.max_people = RTP_MAX_PEOPLE;
-  cp.stamp = stamp_slot(e, cx, 64 + 8 * sj + 2);
+  cp.stamp = frame_stamp(e, cx, sj, STAMP_PAIRS);
   {
     static const char* pf = RTP_EXP_ENV("RTP_PAIRS_FULL");
     cp.pairs_full = (pf && pf[0] == '1') ? 1 : 0;
@@ -555,6 +595,80 @@ int run_post_fused(rtp_engine* e, Ctx& cx, int sj, hipEvent_t ev_nms) {
   return RTP_OK;
 }
 
+// ---- the output stage: what leaves a frame slot besides the joints ---------------------------
+// the renderer's buffers of one slot: the image, the limb table and (host) the raw image's pinned copy; under SYNC_GUARD
+int render_buffers(rtp_engine* e, RenderOut& r, bool host) {
+  const size_t dbytes = (size_t)e->cfg.disp_w * e->cfg.disp_h * 3;
+  if (!r.dev) HIPCHK(e, hipMalloc((void**)&r.dev, dbytes));
+  if (!r.tab) HIPCHK(e, hipMalloc((void**)&r.tab, render_tab_floats(RTP_MAX_PEOPLE) * sizeof(float)));
+  if (host && !r.host) HIPCHK(e, hipHostMalloc((void**)&r.host, dbytes, hipHostMallocDefault));
+  return RTP_OK;
+}
+// render() of rtpose.cpp:270-299 on the slot's stream: `src` -> render.dev, the pose overlay of the slot's joints (part_to_show 0;
+// renderFunctions.cu) or a --part_to_show view of its net-resolution maps
+int render_launch(rtp_engine* e, Slot& sl, const unsigned char* src, int part_to_show, int googly) {
+  if (part_to_show == 0) {
+    RenderParams rp;
+    rp.src = src; rp.dst = sl.render.dev; rp.w = e->cfg.disp_w; rp.h = e->cfg.disp_h;
+    rp.poses = sl.joints; rp.num_people = sl.num_people; rp.tab = sl.render.tab;
+    rp.model = e->plan.model; rp.googly = googly; rp.max_people = RTP_MAX_PEOPLE;
+    HIPCHK(e, launch_render(rp, sl.stream));
+  } else {
+    RenderViewParams vp;
+    vp.src = src; vp.dst = sl.render.dev; vp.w = e->cfg.disp_w; vp.h = e->cfg.disp_h;
+    vp.maps = sl.resized; vp.net_w = e->cfg.net_w; vp.net_h = e->cfg.net_h;
+    vp.model = e->plan.model; vp.part_to_show = part_to_show;
+    HIPCHK(e, launch_render_view(vp, sl.stream));
+  }
+  return RTP_OK;
+}
+
+// Every output buffer the batch's first nframes slots write in the modes that are on (render.host again after JPEG or YUV mode was
+// switched off): the one place the frame path allocates, before anything is launched or captured; only a batch that allocates locks.
+int frame_outputs_ensure(rtp_engine* e, Ctx& cx, int nframes) {
+  int rc;
+  const bool yuv = e->yuv_mode != 0, jpeg = !yuv && e->jpeg_quality != 0;
+  for (int j = 0; e->cfg.render && j < nframes; ++j) {
+    RenderOut& r = cx.slot[j].render;
+    if (!cx.slot[j].has_disp) continue;   // (nothing is rendered for a frame submitted as a net input)
+    if (r.dev && r.tab && (yuv ? r.yuv_dev != nullptr : jpeg ? r.jpeg.base != nullptr : r.host != nullptr)) continue;
+    SYNC_GUARD;
+    if ((rc = render_buffers(e, r, !yuv && !jpeg))) return rc;
+    if (yuv && !r.yuv_dev) {
+      const size_t bytes = rtp_yuv_bytes(e->cfg.disp_w, e->cfg.disp_h, 420);
+      HIPCHK(e, hipMalloc((void**)&r.yuv_dev, bytes));
+      HIPCHK(e, hipHostMalloc((void**)&r.yuv_host, bytes, hipHostMallocDefault));
+    }
+    if (jpeg && !r.jpeg.base && (rc = jpeg_alloc(e, e->cfg.disp_w, e->cfg.disp_h, &r.jpeg, &r.jpeg_host, &r.jpeg_host_dev, &r.jpeg_cap))) return rc;
+  }
+  if (e->maps_on && (rc = maps_ensure(e, cx, nframes))) return rc;
+  if (e->crops_on && (rc = crops_ensure(e, cx, nframes))) return rc;
+  return RTP_OK;
+}
+
+// Frame j's outputs on its slot's stream, between its connect kernels and its last event; allocates nothing (frame_outputs_ensure did).
+// materialized = the chain built the frame's net-resolution maps, which a --part_to_show view reads and the production path never builds.
+int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
+  int rc;
+  Slot& sl = cx.slot[j];
+  RenderOut& r = sl.render;
+  if (e->cfg.render && sl.has_disp) {
+    if (e->cfg.render > 1 && !materialized && (rc = run_resize(e, cx, j))) return rc;
+    if ((rc = render_launch(e, sl, sl.disp_cur, e->cfg.render - 1, 0))) return rc;
+    if (e->yuv_mode) {  // rtp_set_render_yuv: only the planes cross PCIe
+      if ((rc = yuv_out_launch(e, cx, j))) return rc;
+    } else if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
+      HIPCHK(e, launch_jpeg_encode(frame_stamp(e, cx, j, STAMP_JPEG_ENC), packed_bgr_view(r.dev, e->cfg.disp_w, e->cfg.disp_h), e->jpeg_q, r.jpeg,
+                                   r.jpeg_host_dev, reinterpret_cast<unsigned*>(r.jpeg_host_dev + r.jpeg_cap), sl.stream));
+    } else {
+      HIPCHK(e, hipMemcpyAsync(r.host, r.dev, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3, hipMemcpyDeviceToHost, sl.stream));
+    }
+  }
+  if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // the frame's maps -> its pinned buffer (engine_maps.cpp)
+  if (e->crops_on && (rc = crops_launch(e, cx, j))) return rc;   // the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
+  return RTP_OK;
+}
+
 // one batch on one context: conv stack over nframes*num_scales images, then per frame (on the
 // frame slot's stream) resize -> nms -> connect -> D2H of the joints
 int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bool materialize, bool cap, int part = 3) {
@@ -572,6 +686,7 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
     static const char* diag = RTP_EXP_ENV("RTP_DIAG_SKIP_POST");  // diagnosis only: 1 = no connect, 2 = no post-processing at all (both through the
     const int skip = diag ? atoi(diag) : 0;                  // materialised map); 3..6 = production kernels: 3 nms only, 4 + pairs, 5 + match, 6 all
     static const char* unf = RTP_EXP_ENV("RTP_POST_UNFUSED");  // experiments: production path through the materialised map
+    const bool materialized = materialize || skip || (unf && unf[0] == '1');
     HIPCHK(e, hipEventRecord(sl.ev[0], sl.stream));
     if (skip >= 3) {
       const ResizeParams rp = resize_params(e, cx, j);
@@ -583,7 +698,7 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
         cp.diag_stages = skip - 3;   // 1 pairs, 2 + match, 3 + assemble
         HIPCHK(e, launch_connect_fused(cp, rp, sl.stream));
       }
-    } else if (materialize || skip || (unf && unf[0] == '1')) {
+    } else if (materialized) {
       if (skip < 2 && (rc = run_resize(e, cx, j))) return rc;
       HIPCHK(e, hipEventRecord(sl.ev[1], sl.stream));
       if (skip < 2 && (rc = run_nms(e, cx, j))) return rc;
@@ -594,48 +709,7 @@ int launch_batch_body(rtp_engine* e, Ctx& cx, int nframes, const float* input_de
       if ((rc = run_post_fused(e, cx, j, sl.ev[2]))) return rc;
     }
     HIPCHK(e, hipEventRecord(sl.ev[3], sl.stream));
-    if (e->cfg.render && sl.has_disp) {  // pose overlay on the display image (renderFunctions.cu, part_to_show == 0)
-      const size_t dbytes = (size_t)e->cfg.disp_w * e->cfg.disp_h * 3;
-      if (!sl.render_dev) {
-        SYNC_GUARD;
-        HIPCHK(e, hipMalloc((void**)&sl.render_dev, dbytes));
-        HIPCHK(e, hipHostMalloc((void**)&sl.render_host, dbytes, hipHostMallocDefault));
-        HIPCHK(e, hipMalloc((void**)&sl.render_tab, render_tab_floats(RTP_MAX_PEOPLE) * sizeof(float)));
-      }
-      if (e->cfg.render == 1) {
-        RenderParams rp;
-        rp.src = sl.disp_cur; rp.dst = sl.render_dev; rp.w = e->cfg.disp_w; rp.h = e->cfg.disp_h;
-        rp.poses = sl.joints; rp.num_people = sl.num_people; rp.tab = sl.render_tab;
-        rp.model = e->plan.model; rp.googly = 0; rp.max_people = RTP_MAX_PEOPLE;
-        HIPCHK(e, launch_render(rp, sl.stream));
-      } else {  // --part_to_show view: needs the frame's net-resolution maps, which the production path never builds
-        if (!(materialize || skip || (unf && unf[0] == '1')) && (rc = run_resize(e, cx, j))) return rc;
-        RenderViewParams vp;
-        vp.src = sl.disp_cur; vp.dst = sl.render_dev; vp.w = e->cfg.disp_w; vp.h = e->cfg.disp_h;
-        vp.maps = sl.resized; vp.net_w = e->cfg.net_w; vp.net_h = e->cfg.net_h;
-        vp.model = e->plan.model; vp.part_to_show = e->cfg.render - 1;
-        HIPCHK(e, launch_render_view(vp, sl.stream));
-      }
-      if (e->yuv_mode) {  // rtp_set_render_yuv: only the planes cross PCIe
-        if ((rc = yuv_out_launch(e, cx, j))) return rc;
-      } else if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
-        if (!sl.jpeg.base) {
-          SYNC_GUARD;
-          if ((rc = jpeg_alloc(e, e->cfg.disp_w, e->cfg.disp_h, &sl.jpeg, &sl.jpeg_host, &sl.jpeg_host_dev, &sl.jpeg_cap))) return rc;
-        }
-        const FrameView fv = {sl.render_dev, e->cfg.disp_w, e->cfg.disp_h, 3L * e->cfg.disp_w, 3L, {0L, 1L, 2L}};
-        HIPCHK(e, launch_jpeg_encode(stamp_slot(e, cx, 64 + 8 * j + 6), fv, e->jpeg_q, sl.jpeg, sl.jpeg_host_dev,
-                                     reinterpret_cast<unsigned*>(sl.jpeg_host_dev + sl.jpeg_cap), sl.stream));
-      } else {
-        if (!sl.render_host) {   // freed while JPEG or YUV mode was on
-          SYNC_GUARD;
-          HIPCHK(e, hipHostMalloc((void**)&sl.render_host, dbytes, hipHostMallocDefault));
-        }
-        HIPCHK(e, hipMemcpyAsync(sl.render_host, sl.render_dev, dbytes, hipMemcpyDeviceToHost, sl.stream));
-      }
-    }
-    if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // rtp_set_maps_output: the frame's maps -> its pinned buffer (engine_maps.cpp)
-    if (e->crops_on && (rc = crops_launch(e, cx, j))) return rc;   // rtp_set_crops_output: the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
+    if ((rc = frame_outputs_launch(e, cx, j, materialized))) return rc;
     HIPCHK(e, hipMemcpyAsync(sl.host_out + 4, sl.joints, jbytes, hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(e, hipMemcpyAsync(sl.host_out, sl.num_people, sizeof(int), hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(e, hipEventRecord(sl.ev[4], sl.stream));
@@ -667,18 +741,12 @@ int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bo
   cx.last_own_input = input_dev == cx.input;
   cx.last_tags.resize(nframes);
   for (int j = 0; j < nframes; ++j) cx.last_tags[j] = cx.slot[j].tag;
-  for (Slot& sl : cx.slot)   // the previous batch's rendered images are still being exported on a caller's stream: this batch renders over them
-    if (sl.export_pending) {
-      HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_export, 0));
-      sl.export_pending = false;
-    }
-  for (Slot& sl : cx.slot)   // ... or its low-res maps are still being read by rtp_peek_maps_device on a caller's stream: this batch's conv stack overwrites them
-    if (sl.maps_export_pending) {
-      HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_maps_export, 0));
-      sl.maps_export_pending = false;
-    }
-  if (e->maps_on && (rc = maps_ensure(e, cx, nframes))) return rc;   // maps mode: the slots' buffers exist before anything is launched or captured
-  if (e->crops_on && (rc = crops_ensure(e, cx, nframes))) return rc;   // crops mode likewise
+  for (Slot& sl : cx.slot) {   // a caller's stream still exports the previous batch's rendered images (this batch renders over them), or still
+                               // reads its low-res maps (rtp_peek_maps_device; this batch's conv stack overwrites them).  (The crops fence: open_slot)
+    if ((rc = fence_wait_streams(e, sl.render.fence, {cx.stream}))) return rc;
+    if ((rc = fence_wait_streams(e, sl.maps.fence, {cx.stream}))) return rc;
+  }
+  if ((rc = frame_outputs_ensure(e, cx, nframes))) return rc;
   if (e->prep_defer && (rc = flush_prep(e, cx, true))) return rc;
   if (cx.in_pending) {   // the batch's inputs were staged on the staging stream: the conv stream starts when the last of them is complete
     if (cx.in_stream != cx.stream) {
@@ -924,11 +992,8 @@ int alloc_slot(rtp_engine* e, Ctx& cx, Slot& sl, bool share_stream) {
     HIPCHK(e, hipHostMalloc((void**)&sl.frame_host, cbytes, hipHostMallocDefault));
     sl.frame_cap = cbytes;
     HIPCHK(e, hipMalloc((void**)&sl.disp_dev, fbytes));
-    if (e->cfg.render) {
-      HIPCHK(e, hipMalloc((void**)&sl.render_dev, fbytes));
-      HIPCHK(e, hipHostMalloc((void**)&sl.render_host, fbytes, hipHostMallocDefault));
-      HIPCHK(e, hipMalloc((void**)&sl.render_tab, render_tab_floats(RTP_MAX_PEOPLE) * sizeof(float)));
-    }
+    int rc;
+    if (e->cfg.render && (rc = render_buffers(e, sl.render, true))) return rc;
   }
   return RTP_OK;
 }
@@ -1028,20 +1093,15 @@ void free_ctx(Ctx& cx) {
   if (cx.ev_in) (void)hipEventDestroy(cx.ev_in);
   for (Slot& sl : cx.slot) {
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-    if (sl.export_pending) (void)hipEventSynchronize(sl.ev_export);   // an export on the caller's stream may still read render_dev
-    if (sl.maps_export_pending) (void)hipEventSynchronize(sl.ev_maps_export);   // ... or the context's low-res maps (rtp_peek_maps_device)
-    if (sl.crops_export_pending) (void)hipEventSynchronize(sl.ev_crops_export);   // ... or the frame's display image (rtp_peek_crops_device)
-    for (hipEvent_t ev : {sl.ev_ready, sl.ev_read, sl.ev_export, sl.ev_maps_export, sl.ev_crops_export}) if (ev) (void)hipEventDestroy(ev);
+    for (ExportFence* f : {&sl.render.fence, &sl.maps.fence, &sl.crops.fence}) fence_destroy(*f);   // (a caller's stream may still read the slot's buffers: waits)
+    for (hipEvent_t ev : {sl.ev_ready, sl.ev_read}) if (ev) (void)hipEventDestroy(ev);
     void* dptrs[] = {sl.resized, sl.peaks, sl.strip_count, sl.strip_list, sl.cand_score, sl.cand_ij, sl.cand_count, sl.cand_blk, sl.conn, sl.conn_score,
-                     sl.conn_count, sl.tickets, sl.joints, sl.num_people, sl.frame_dev, sl.disp_dev, sl.render_dev, sl.render_tab};
+                     sl.conn_count, sl.tickets, sl.joints, sl.num_people, sl.frame_dev, sl.disp_dev};
     for (void* p : dptrs) if (p) (void)hipFree(p);
     if (sl.frame_host) (void)hipHostFree(sl.frame_host);
-    if (sl.render_host) (void)hipHostFree(sl.render_host);
-    if (sl.yuv_out_dev) (void)hipFree(sl.yuv_out_dev);
-    if (sl.yuv_out_host) (void)hipHostFree(sl.yuv_out_host);
-    maps_free(sl);
-    crops_free(sl);
-    jpeg_free(&sl.jpeg, &sl.jpeg_host, &sl.jpeg_cap);
+    sl.render.free();
+    sl.maps.free();
+    sl.crops.free();
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
     for (int i = 0; i < 5; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
@@ -1196,18 +1256,18 @@ int launch_prep_kernels(rtp_engine* e, Ctx& cx, int sj, int w, int h, hipStream_
   float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
   if (sl.pend_yuv) {
     const FrameView bgr = packed_bgr_view(sl.frame_dev, w, h);
-    HIPCHK(e, launch_yuv_import(stamp_slot(e, cx, 200 + 2 * sj), sl.yuv_dev, bgr, yuv_layout(sl.yuv_dev, bgr), stream));
+    HIPCHK(e, launch_yuv_import(frame_stamp(e, cx, sj, STAMP_WARP), sl.yuv_dev, bgr, yuv_layout(sl.yuv_dev, bgr), stream));
   }
   if (sl.pend_jpeg) {
     int rc;
-    if ((rc = jd_launch(e, stamp_slot(e, cx, 232 + sj), sl.jd_job, packed_bgr_view(sl.frame_dev, w, h), stream))) return rc;
+    if ((rc = jd_launch(e, frame_stamp(e, cx, sj, STAMP_JPEG_DEC), sl.jd_job, packed_bgr_view(sl.frame_dev, w, h), stream))) return rc;
   }
   if (w == e->cfg.disp_w && h == e->cfg.disp_h) sl.disp_cur = sl.frame_dev;   // identity warp (20 us per 720p frame saved)
   else {
     sl.disp_cur = sl.disp_dev;
-    HIPCHK(e, launch_warp(stamp_slot(e, cx, 200 + 2 * sj), sl.frame_dev, w, h, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, e->cfg.disp_w, e->cfg.disp_h, stream));
+    HIPCHK(e, launch_warp(frame_stamp(e, cx, sj, STAMP_WARP), sl.frame_dev, w, h, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, e->cfg.disp_w, e->cfg.disp_h, stream));
   }
-  HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, e->cfg.disp_w, e->cfg.disp_h, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, stream));
+  HIPCHK(e, launch_area_pad(frame_stamp(e, cx, sj, STAMP_AREA_PAD), sl.disp_cur, e->cfg.disp_w, e->cfg.disp_h, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, stream));
   return RTP_OK;
 }
 }  // namespace
@@ -1384,7 +1444,7 @@ int enqueue_preprocess_view(rtp_engine* e, Ctx& cx, int sj, const FrameView& v, 
     HIPCHK(e, hipEventRecord(sl.ev_ready, producer));
     HIPCHK(e, hipStreamWaitEvent(cx.in_stream, sl.ev_ready, 0));
   }
-  unsigned long long* st = stamp_slot(e, cx, 200 + 2 * sj);
+  unsigned long long* st = frame_stamp(e, cx, sj, STAMP_WARP);
   if (v.w == dw && v.h == dh) HIPCHK(e, launch_frame_import(st, v, layout, sl.disp_dev, cx.in_stream));
   else HIPCHK(e, launch_warp_view(st, v, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, dw, dh, cx.in_stream));
   sl.disp_cur = sl.disp_dev;
@@ -1393,7 +1453,7 @@ int enqueue_preprocess_view(rtp_engine* e, Ctx& cx, int sj, const FrameView& v, 
     HIPCHK(e, hipStreamWaitEvent(producer, sl.ev_read, 0));
   }
   float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
-  HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, dw, dh, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
+  HIPCHK(e, launch_area_pad(frame_stamp(e, cx, sj, STAMP_AREA_PAD), sl.disp_cur, dw, dh, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
   cx.in_pending = true;
   return RTP_OK;
 }
@@ -1418,7 +1478,7 @@ int enqueue_preprocess_yuv_view(rtp_engine* e, Ctx& cx, int sj, const YuvView& v
     HIPCHK(e, hipEventRecord(sl.ev_ready, producer));
     HIPCHK(e, hipStreamWaitEvent(cx.in_stream, sl.ev_ready, 0));
   }
-  unsigned long long* st = stamp_slot(e, cx, 200 + 2 * sj);
+  unsigned long long* st = frame_stamp(e, cx, sj, STAMP_WARP);
   const FrameView bgr = packed_bgr_view(same ? sl.disp_dev : sl.frame_dev, v.w, v.h);
   HIPCHK(e, launch_yuv_import(st, v, bgr, yuv_layout(v, bgr), cx.in_stream));
   if (producer) {
@@ -1428,7 +1488,7 @@ int enqueue_preprocess_yuv_view(rtp_engine* e, Ctx& cx, int sj, const YuvView& v
   if (!same) HIPCHK(e, launch_warp(st, sl.frame_dev, v.w, v.h, rtp_internal_warp_inverse_scale(s), e->warp_tab_dev, sl.disp_dev, dw, dh, cx.in_stream));
   sl.disp_cur = sl.disp_dev;
   float* dst = cx.input + (size_t)sj * e->N * 3 * e->cfg.net_h * e->cfg.net_w;
-  HIPCHK(e, launch_area_pad(stamp_slot(e, cx, 200 + 2 * sj + 1), sl.disp_cur, dw, dh, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
+  HIPCHK(e, launch_area_pad(frame_stamp(e, cx, sj, STAMP_AREA_PAD), sl.disp_cur, dw, dh, e->area_scales.data(), e->N, dst, e->cfg.net_w, e->cfg.net_h, cx.in_stream));
   cx.in_pending = true;
   return RTP_OK;
 }
@@ -1551,6 +1611,15 @@ int weights_delivered(rtp_engine* e) {
 }  // namespace
 
 // ---- batching: frames are staged into the open context; a full batch is launched at once ----------
+// The FIFO of frames in flight holds (context, slot) as one int: written by fifo_push, read by oldest_frame, nowhere else
+static void fifo_push(rtp_engine* e, int ci, int sj) { e->fifo.push_back(ci * 64 + sj); }
+int oldest_frame(rtp_engine* e, const char* has_disp_fn, int* ci, int* sj) {
+  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
+  *ci = e->fifo.front() / 64, *sj = e->fifo.front() % 64;
+  if (has_disp_fn && !e->ctx[*ci].slot[*sj].has_disp)
+    return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", has_disp_fn);
+  return RTP_OK;
+}
 int open_slot(rtp_engine* e, int* ci, int* sj) {
   if (e->open_ctx < 0) {
     for (size_t i = 0; i < e->ctx.size() && e->open_ctx < 0; ++i) {
@@ -1571,8 +1640,10 @@ int open_slot(rtp_engine* e, int* ci, int* sj) {
   *ci = e->open_ctx;
   *sj = e->ctx[e->open_ctx].filled;
   Ctx& oc = e->ctx[*ci];
-  if (oc.slot[*sj].crops_export_pending) return crops_wait_export(e, oc, oc.slot[*sj], false);   // rtp_peek_crops_device still reads the slot's last frame on a caller's stream
-  return RTP_OK;
+  Slot& sl = oc.slot[*sj];
+  // rtp_peek_crops_device may still read the slot's last frame (display image and joints) on a caller's stream: the streams that stage
+  // and compute the next one wait for it
+  return fence_wait_streams(e, sl.crops.fence, {oc.stream, oc.in_stream != oc.stream ? oc.in_stream : nullptr, e->copy_stream, sl.stream != oc.stream ? sl.stream : nullptr});
 }
 
 namespace {
@@ -1606,7 +1677,7 @@ int commit_slot(rtp_engine* e, int ci, int sj, uint64_t tag) {
   cx.slot[sj].tag = tag;
   cx.slot[sj].busy = true;
   cx.filled = sj + 1;
-  e->fifo.push_back(ci * 64 + sj);
+  fifo_push(e, ci, sj);
   if (cx.filled == e->B) {
     if (e->prep_defer && e->B > 1 && cx.slot[sj].copy_pending) {   // the frame that completes the batch was copied a moment ago: launch at the next call
       e->open_ctx = -1;
@@ -1625,21 +1696,10 @@ int need_idle(rtp_engine* e) {
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "parity taps need an idle engine (collect %zu frames first)", e->fifo.size());
   int rc;
   if ((rc = use_device(e))) return rc;
-  for (Ctx& cx : e->ctx)   // the taps reuse context 0's buffers on the host's clock: no export of a rendered image may still read them
+  for (Ctx& cx : e->ctx)   // the taps reuse context 0's buffers on the host's clock: no export or peek on a caller's stream may still read them
     for (Slot& sl : cx.slot)
-      if (sl.export_pending) {
-        HIPCHK(e, hipEventSynchronize(sl.ev_export));
-        sl.export_pending = false;
-      }
-  for (Ctx& cx : e->ctx)
-    for (Slot& sl : cx.slot)
-      if (sl.maps_export_pending) {
-        HIPCHK(e, hipEventSynchronize(sl.ev_maps_export));
-        sl.maps_export_pending = false;
-      }
-  for (Ctx& cx : e->ctx)
-    for (Slot& sl : cx.slot)
-      if (sl.crops_export_pending && (rc = crops_wait_export(e, cx, sl, true))) return rc;
+      for (ExportFence* f : {&sl.render.fence, &sl.maps.fence, &sl.crops.fence})
+        if ((rc = fence_wait_host(e, *f))) return rc;
   return RTP_OK;
 }
 
@@ -1683,10 +1743,9 @@ void stage_ms(rtp_engine* e, Ctx& cx, Slot& sl) {
 // Blocks until the oldest frame in flight is finished (its batch is launched first where it is still open); the frame stays in the FIFO
 int wait_oldest(rtp_engine* e, int* ci_out, int* sj_out) {
   if (!e) return RTP_EINVAL;
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  int rc;
+  int rc, ci = 0, sj = 0;
+  if ((rc = oldest_frame(e, nullptr, &ci, &sj))) return rc;
   if ((rc = use_device(e))) return rc;
-  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
   Ctx& cx = e->ctx[ci];
   Slot& sl = cx.slot[sj];
   if (e->prep_defer) {
@@ -1743,9 +1802,9 @@ int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, u
   if (joints) memcpy(joints, sl.host_out + 4, (size_t)n * e->plan.num_parts * 3 * sizeof(float));
   if (want_render) {
     if (!e->cfg.render) return fail(e, RTP_EINVAL, "rtp_collect_rendered needs rtp_config.render = 1");
-    if (!sl.has_disp || (rendered && !sl.render_host))
+    if (!sl.has_disp || (rendered && !sl.render.host))
       return fail(e, RTP_EINVAL, "no display image for this frame: submit it with rtp_submit_frame (device pre-processing)");
-    if (rendered) memcpy(rendered, sl.render_host, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3);
+    if (rendered) memcpy(rendered, sl.render.host, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3);
   }
   return RTP_OK;
 }
@@ -2013,7 +2072,7 @@ int rtp_submit_device(rtp_engine* e, const float* d_in, uint64_t tag) {
     cx.slot[0].busy = true;
     cx.slot[0].has_disp = false;
     cx.filled = 1;
-    e->fifo.push_back(ci * 64);
+    fifo_push(e, ci, 0);
     e->open_ctx = -1;
     return launch_batch(e, cx, 1, d_in);
   }
@@ -2216,22 +2275,14 @@ int rtp_collect_rendered_device(rtp_engine* e, uint64_t* tag, float* joints, int
   if (fv.w != e->cfg.disp_w || fv.h != e->cfg.disp_h)
     return fail(e, RTP_EINVAL, "%s: the output view is %d x %d, the display image %d x %d", fn, fv.w, fv.h, e->cfg.disp_w, e->cfg.disp_h);
   if ((rc = check_view_memory(e, fn, fv, hi, &layout))) return rc;
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
+  int ci = 0, sj = 0;
+  if ((rc = oldest_frame(e, fn, &ci, &sj))) return rc;
+  if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
   Ctx& cx = e->ctx[ci];
   Slot& sl = cx.slot[sj];
-  if (!sl.has_disp) return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", fn);
-  if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : sl.stream;
-  if (!sl.ev_export) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_export, hipEventDisableTiming));
-  HIPCHK(e, launch_frame_export(stamp_slot(e, cx, 64 + 8 * sj + 5), sl.render_dev, fv, layout, st));
-  HIPCHK(e, hipEventRecord(sl.ev_export, st));
-  sl.export_pending = true;
-  if (!stream) {
-    HIPCHK(e, hipEventSynchronize(sl.ev_export));
-    sl.export_pending = false;
-  }
-  return RTP_OK;
+  HIPCHK(e, launch_frame_export(frame_stamp(e, cx, sj, STAMP_EXPORT), sl.render.dev, fv, layout, st));
+  return fence_arm(e, sl.render.fence, st, !stream);
 }
 
 int rtp_last_stage_ms(const rtp_engine* e, float ms[5]) {
@@ -2387,34 +2438,20 @@ int rtp_render(rtp_engine* e, const unsigned char* display_bgr, const float* joi
     return fail(e, RTP_EINVAL, "part_to_show %d is outside the model's %d maps", part_to_show, e->plan.heat_channels);
   Ctx& cx = e->ctx[0];
   Slot& sl = cx.slot[0];
-  const int w = e->cfg.disp_w, h = e->cfg.disp_h;
-  const size_t dbytes = (size_t)w * h * 3;
-  if (!sl.render_dev) {
-    HIPCHK(e, hipMalloc((void**)&sl.render_dev, dbytes));
-    HIPCHK(e, hipHostMalloc((void**)&sl.render_host, dbytes, hipHostMallocDefault));
-    HIPCHK(e, hipMalloc((void**)&sl.render_tab, render_tab_floats(RTP_MAX_PEOPLE) * sizeof(float)));
-  }
+  const size_t dbytes = (size_t)e->cfg.disp_w * e->cfg.disp_h * 3;
+  if ((rc = render_buffers(e, sl.render, false))) return rc;
   if (!sl.disp_dev) HIPCHK(e, hipMalloc((void**)&sl.disp_dev, dbytes));
   HIPCHK(e, hipMemcpy(sl.disp_dev, display_bgr, dbytes, hipMemcpyHostToDevice));
   if (part_to_show == 0) {
     const int n = std::min(num_people, (int)RTP_MAX_PEOPLE);
     if (n > 0) HIPCHK(e, hipMemcpy(sl.joints, joints, (size_t)n * e->plan.num_parts * 3 * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(sl.num_people, &n, sizeof(int), hipMemcpyHostToDevice));
-    RenderParams rp;
-    rp.src = sl.disp_dev; rp.dst = sl.render_dev; rp.w = w; rp.h = h;
-    rp.poses = sl.joints; rp.num_people = sl.num_people; rp.tab = sl.render_tab;
-    rp.model = e->plan.model; rp.googly = googly ? 1 : 0; rp.max_people = RTP_MAX_PEOPLE;
-    HIPCHK(e, launch_render(rp, sl.stream));
   } else {
     HIPCHK(e, hipMemcpy(sl.resized, resized_host, (size_t)e->plan.heat_channels * e->cfg.net_h * e->cfg.net_w * sizeof(float), hipMemcpyHostToDevice));
-    RenderViewParams vp;
-    vp.src = sl.disp_dev; vp.dst = sl.render_dev; vp.w = w; vp.h = h;
-    vp.maps = sl.resized; vp.net_w = e->cfg.net_w; vp.net_h = e->cfg.net_h;
-    vp.model = e->plan.model; vp.part_to_show = part_to_show;
-    HIPCHK(e, launch_render_view(vp, sl.stream));
   }
+  if ((rc = render_launch(e, sl, sl.disp_dev, part_to_show, googly ? 1 : 0))) return rc;
   HIPCHK(e, hipStreamSynchronize(sl.stream));
-  HIPCHK(e, hipMemcpy(out_bgr, sl.render_dev, dbytes, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(out_bgr, sl.render.dev, dbytes, hipMemcpyDeviceToHost));
   return RTP_OK;
 }
 

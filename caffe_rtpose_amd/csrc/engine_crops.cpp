@@ -25,13 +25,13 @@ int crops_enqueue(rtp_engine* e, Ctx& cx, int sj, float* boxes, unsigned char* d
   p.wide = p.dst ? crops_wide(c.crop_w, p.dst, crop_stride) : 0;
   p.min_score = c.min_score; p.margin = c.margin;
   for (int i = 0; i < p.nlist; ++i) p.list[i] = (unsigned char)e->crops_list[i];
-  HIPCHK(e, launch_crops(p, stream));   // no residency stamp: every slot of a frame's chain is taken (stamp_slot: 64 + 8 * sj + 0..7)
+  HIPCHK(e, launch_crops(p, stream));   // no residency stamp: every slot of a frame's chain is taken (StampKind: 64 + 8 * sj + 0..7)
   return RTP_OK;
 }
 
 void crops_free_all(rtp_engine* e) {
   for (Ctx& cx : e->ctx)
-    for (Slot& sl : cx.slot) crops_free(sl);
+    for (Slot& sl : cx.slot) sl.crops.free();
 }
 
 // rtp_crops_view against the current mode: fields only (no HIP call); *hi = the highest byte offset from data the view addresses
@@ -66,63 +66,46 @@ int frame_boxes(rtp_engine* e, const char* fn, const Slot& sl, int capacity, int
 
 }  // namespace
 
-void crops_free(Slot& sl) {
-  if (sl.crops_boxes_dev) (void)hipFree(sl.crops_boxes_dev);
-  if (sl.crops_boxes_host) (void)hipHostFree(sl.crops_boxes_host);
-  if (sl.crops_dev) (void)hipFree(sl.crops_dev);
-  if (sl.crops_host) (void)hipHostFree(sl.crops_host);
-  sl.crops_boxes_dev = nullptr;
-  sl.crops_boxes_host = nullptr;
-  sl.crops_dev = nullptr;
-  sl.crops_host = nullptr;
-  sl.crops_dst = nullptr;
+void CropsOut::free() {
+  if (boxes_dev) (void)hipFree(boxes_dev);
+  if (boxes_host) (void)hipHostFree(boxes_host);
+  if (dev) (void)hipFree(dev);
+  if (host) (void)hipHostFree(host);
+  boxes_dev = boxes_host = nullptr;
+  dev = host = dst = nullptr;
 }
 
-// The buffers of the first nframes slots, before their batch is launched (or captured: no allocation inside a capture)
+// The buffers of the first nframes slots, before their batch is launched (frame_outputs_ensure, and the taps)
 int crops_ensure(rtp_engine* e, Ctx& cx, int nframes) {
   const size_t bytes = crop_bytes(e) * e->crops_cfg.max_crops;
   for (int j = 0; j < nframes; ++j) {
-    Slot& sl = cx.slot[j];
-    if (sl.crops_dst) continue;
+    CropsOut& c = cx.slot[j].crops;
+    if (c.dst) continue;
     SYNC_GUARD;
-    HIPCHK(e, hipMalloc((void**)&sl.crops_boxes_dev, boxes_bytes(e)));
-    HIPCHK(e, hipHostMalloc((void**)&sl.crops_boxes_host, boxes_bytes(e), hipHostMallocDefault));
+    HIPCHK(e, hipMalloc((void**)&c.boxes_dev, boxes_bytes(e)));
+    HIPCHK(e, hipHostMalloc((void**)&c.boxes_host, boxes_bytes(e), hipHostMallocDefault));
     if (e->crops_direct) {   // the kernel stores across PCIe: only real crops travel
-      HIPCHK(e, hipHostMalloc((void**)&sl.crops_host, bytes, hipHostMallocMapped));
-      HIPCHK(e, hipHostGetDevicePointer((void**)&sl.crops_dst, sl.crops_host, 0));
+      HIPCHK(e, hipHostMalloc((void**)&c.host, bytes, hipHostMallocMapped));
+      HIPCHK(e, hipHostGetDevicePointer((void**)&c.dst, c.host, 0));
     } else {
-      HIPCHK(e, hipMalloc((void**)&sl.crops_dev, bytes));
-      HIPCHK(e, hipHostMalloc((void**)&sl.crops_host, bytes, hipHostMallocDefault));
-      sl.crops_dst = sl.crops_dev;
+      HIPCHK(e, hipMalloc((void**)&c.dev, bytes));
+      HIPCHK(e, hipHostMalloc((void**)&c.host, bytes, hipHostMallocDefault));
+      c.dst = c.dev;
     }
   }
   return RTP_OK;
 }
 
-// launch_batch_body: frame sj's boxes and crops -> the slot's buffers -> pinned memory, on the frame's own stream behind the connect
+// frame_outputs_launch: frame sj's boxes and crops -> the slot's buffers -> pinned memory, on the frame's own stream behind the connect
 // kernels and in front of the frame's last event.  A frame without a display image gets boxes only.
 int crops_launch(rtp_engine* e, Ctx& cx, int sj) {
   Slot& sl = cx.slot[sj];
-  sl.crops_pixels = sl.has_disp && sl.disp_cur;
+  sl.crops.pixels = sl.has_disp && sl.disp_cur;
   int rc;
-  if ((rc = crops_enqueue(e, cx, sj, sl.crops_boxes_dev, sl.crops_pixels ? sl.crops_dst : nullptr, (long)crop_bytes(e), sl.stream))) return rc;
-  HIPCHK(e, hipMemcpyAsync(sl.crops_boxes_host, sl.crops_boxes_dev, boxes_bytes(e), hipMemcpyDeviceToHost, sl.stream));
-  if (sl.crops_pixels && !e->crops_direct)
-    HIPCHK(e, hipMemcpyAsync(sl.crops_host, sl.crops_dev, crop_bytes(e) * e->crops_cfg.max_crops, hipMemcpyDeviceToHost, sl.stream));
-  return RTP_OK;
-}
-
-// An rtp_peek_crops_device on a caller's stream may still read the slot's display image and joints: the next frame staged on the slot
-// waits for it on the streams that stage and compute it (host = false), an idle-engine entry or the teardown on the host
-int crops_wait_export(rtp_engine* e, Ctx& cx, Slot& sl, bool host) {
-  if (host) HIPCHK(e, hipEventSynchronize(sl.ev_crops_export));
-  else {
-    HIPCHK(e, hipStreamWaitEvent(cx.stream, sl.ev_crops_export, 0));
-    if (cx.in_stream && cx.in_stream != cx.stream) HIPCHK(e, hipStreamWaitEvent(cx.in_stream, sl.ev_crops_export, 0));
-    if (e->copy_stream) HIPCHK(e, hipStreamWaitEvent(e->copy_stream, sl.ev_crops_export, 0));
-    if (sl.stream && sl.stream != cx.stream) HIPCHK(e, hipStreamWaitEvent(sl.stream, sl.ev_crops_export, 0));
-  }
-  sl.crops_export_pending = false;
+  if ((rc = crops_enqueue(e, cx, sj, sl.crops.boxes_dev, sl.crops.pixels ? sl.crops.dst : nullptr, (long)crop_bytes(e), sl.stream))) return rc;
+  HIPCHK(e, hipMemcpyAsync(sl.crops.boxes_host, sl.crops.boxes_dev, boxes_bytes(e), hipMemcpyDeviceToHost, sl.stream));
+  if (sl.crops.pixels && !e->crops_direct)
+    HIPCHK(e, hipMemcpyAsync(sl.crops.host, sl.crops.dev, crop_bytes(e) * e->crops_cfg.max_crops, hipMemcpyDeviceToHost, sl.stream));
   return RTP_OK;
 }
 
@@ -155,8 +138,7 @@ extern "C" int rtp_internal_crops_direct(rtp_engine* e, int on) {
     SYNC_GUARD;
     int rc;
     if ((rc = need_idle(e))) return rc;
-    for (Ctx& cx : e->ctx)
-      for (Slot& sl : cx.slot) crops_free(sl);
+    crops_free_all(e);
   }
   e->crops_direct = on ? 1 : 0;
   return RTP_OK;
@@ -184,14 +166,14 @@ extern "C" int rtp_internal_crops_time(rtp_engine* e, const unsigned char* displ
   hipEvent_t ev[2];
   HIPCHK(e, hipEventCreate(&ev[0]));
   HIPCHK(e, hipEventCreate(&ev[1]));
-  for (int i = 0; i < 3 && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.crops_boxes_dev, sl.crops_dst, (long)crop_bytes(e), sl.stream);   // warm-up
+  for (int i = 0; i < 3 && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.crops.boxes_dev, sl.crops.dst, (long)crop_bytes(e), sl.stream);   // warm-up
   // a wave that waits 4 ms holds the stream while the train is enqueued, so that the event pair brackets device work only
   unsigned long long* hold = nullptr;
   hipError_t s = hipMalloc((void**)&hold, 2 * sizeof(unsigned long long));
   if (s == hipSuccess) s = hipStreamSynchronize(sl.stream);
   if (s == hipSuccess) s = launch_queue_wait(400000, hold, sl.stream);
   if (s == hipSuccess) s = hipEventRecord(ev[0], sl.stream);
-  for (int i = 0; i < launches && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.crops_boxes_dev, sl.crops_dst, (long)crop_bytes(e), sl.stream);
+  for (int i = 0; i < launches && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.crops.boxes_dev, sl.crops.dst, (long)crop_bytes(e), sl.stream);
   if (s == hipSuccess) s = hipEventRecord(ev[1], sl.stream);
   if (s == hipSuccess) s = hipEventSynchronize(ev[1]);
   float ms = 0.f;
@@ -255,14 +237,13 @@ int rtp_peek_crops(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_box
   if (!e) return fail(nullptr, RTP_EINVAL, "%s: NULL engine", fn);
   int rc, ci = 0, sj = 0;
   if ((rc = peek_checks(e, fn, boxes_host, num_boxes, capacity))) return rc;
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  if ((rc = wait_oldest(e, &ci, &sj))) return rc;
+  if ((rc = wait_oldest(e, &ci, &sj))) return rc;   // (refuses "nothing in flight" before it waits)
   const Slot& sl = e->ctx[ci].slot[sj];
   if ((rc = frame_boxes(e, fn, sl, capacity, num_boxes))) return rc;
   const int n = *num_boxes;
-  memcpy(boxes_host, sl.crops_boxes_host, (size_t)n * RTP_CROP_BOX_FLOATS * sizeof(float));
-  if (sl.crops_pixels && crops_host) memcpy(crops_host, sl.crops_host, (size_t)n * crop_bytes(e));
-  if (has_pixels) *has_pixels = sl.crops_pixels ? 1 : 0;
+  memcpy(boxes_host, sl.crops.boxes_host, (size_t)n * RTP_CROP_BOX_FLOATS * sizeof(float));
+  if (sl.crops.pixels && crops_host) memcpy(crops_host, sl.crops.host, (size_t)n * crop_bytes(e));
+  if (has_pixels) *has_pixels = sl.crops.pixels ? 1 : 0;
   if (tag) *tag = sl.tag;
   return RTP_OK;
 }
@@ -280,20 +261,15 @@ int rtp_peek_crops_device(rtp_engine* e, uint64_t* tag, float* boxes_host, int* 
   if ((rc = check_caller_stream(e, stream, fn))) return rc;
   if ((rc = use_device(e))) return rc;
   if ((rc = check_device_range(e, fn, "data", out_dev->data, hi, &avail))) return rc;
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  if ((rc = wait_oldest(e, &ci, &sj))) return rc;
+  if ((rc = wait_oldest(e, &ci, &sj))) return rc;   // (refuses "nothing in flight" before it waits)
   Ctx& cx = e->ctx[ci];
   Slot& sl = cx.slot[sj];
-  if (!sl.crops_pixels) return fail(e, RTP_EINVAL, "%s: the frame has no display image (it was submitted as a net input): rtp_peek_crops gives its boxes", fn);
+  if (!sl.crops.pixels) return fail(e, RTP_EINVAL, "%s: the frame has no display image (it was submitted as a net input): rtp_peek_crops gives its boxes", fn);
   if ((rc = frame_boxes(e, fn, sl, capacity, num_boxes))) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : sl.stream;
-  if (!sl.ev_crops_export) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_crops_export, hipEventDisableTiming));
-  if (sl.crops_export_pending) HIPCHK(e, hipStreamWaitEvent(st, sl.ev_crops_export, 0));   // an earlier peek of this frame on another stream: the event below then covers both
   if ((rc = crops_enqueue(e, cx, sj, nullptr, (unsigned char*)out_dev->data, out_dev->crop_stride, st))) return rc;
-  HIPCHK(e, hipEventRecord(sl.ev_crops_export, st));
-  sl.crops_export_pending = true;
-  if (!stream && (rc = crops_wait_export(e, cx, sl, true))) return rc;
-  memcpy(boxes_host, sl.crops_boxes_host, (size_t)*num_boxes * RTP_CROP_BOX_FLOATS * sizeof(float));
+  if ((rc = fence_arm(e, sl.crops.fence, st, !stream))) return rc;
+  memcpy(boxes_host, sl.crops.boxes_host, (size_t)*num_boxes * RTP_CROP_BOX_FLOATS * sizeof(float));
   if (tag) *tag = sl.tag;
   return RTP_OK;
 }
@@ -327,8 +303,8 @@ int rtp_crops_from_joints(rtp_engine* e, const unsigned char* display_bgr_host, 
   if ((rc = crops_launch(e, cx, 0))) return rc;
   HIPCHK(e, hipStreamSynchronize(sl.stream));
   sl.has_disp = false;
-  memcpy(boxes_host, sl.crops_boxes_host, (size_t)n * RTP_CROP_BOX_FLOATS * sizeof(float));
-  if (crops_host) memcpy(crops_host, sl.crops_host, (size_t)n * crop_bytes(e));
+  memcpy(boxes_host, sl.crops.boxes_host, (size_t)n * RTP_CROP_BOX_FLOATS * sizeof(float));
+  if (crops_host) memcpy(crops_host, sl.crops.host, (size_t)n * crop_bytes(e));
   return RTP_OK;
 }
 

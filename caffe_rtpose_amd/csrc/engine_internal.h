@@ -14,6 +14,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <sstream>
@@ -80,6 +81,48 @@ constexpr int kJdGroup = 256;        // subsequences per workgroup
 constexpr int kJdMaxGroups = 512;    // most synchronisation launches one decode may enqueue (16 MB of scan at the defaults)
 constexpr size_t kJdStageCap = (size_t)64 << 20;   // staged scans above this take the host entropy path
 
+// A caller's stream may still be reading one of a slot's buffers (an export or a device peek was enqueued on it): ev = recorded behind
+// that read; while `pending`, whoever writes the buffer next waits on it first.  Only fence_* (below) create, record or wait for ev.
+struct ExportFence { hipEvent_t ev = nullptr; bool pending = false; };
+
+// cfg.render: the display image with the pose overlay, and the form it leaves in.  `fence` (rtp_collect_rendered_device,
+// rtp_collect_rendered_yuv_device): the export of `dev` through the caller's view is done; the context's next batch, whose render
+// overwrites `dev`, waits on it first.
+struct RenderOut {
+  unsigned char *dev = nullptr, *host = nullptr;   // host: pinned copy of it (raw mode only: freed while JPEG or YUV mode is on)
+  float* tab = nullptr;
+  // rtp_set_render_jpeg: the GPU encoder's scratch for `dev` and its pinned output, which the encoder's last kernel writes:
+  // [jpeg_cap bytes] the file after the header, then its length (4 bytes)
+  JpegBufs jpeg;
+  unsigned char *jpeg_host = nullptr, *jpeg_host_dev = nullptr;   // (_dev: the same memory as the device addresses it)
+  size_t jpeg_cap = 0;
+  // rtp_set_render_yuv: the planar 4:2:0 planes of `dev` (Y, U, V, pitches = plane widths) and their pinned copy, the only bytes of
+  // the rendered frame that cross PCIe in that mode
+  unsigned char *yuv_dev = nullptr, *yuv_host = nullptr;
+  ExportFence fence;
+  void free();   // the buffers (engine.cpp); the fence stays
+};
+// rtp_set_maps_output: the frame's chosen maps in the chosen format and their pinned copy.  `fence` (rtp_peek_maps_device): the kernel
+// that reads this frame's low-res maps on the caller's stream is done; the context's next batch, whose conv stack overwrites the
+// low-res maps, waits on it first.
+struct MapsOut {
+  unsigned char *dev = nullptr, *host = nullptr;
+  size_t cap = 0;
+  ExportFence fence;
+  void free();   // the buffers (engine_maps.cpp); the fence stays
+};
+// rtp_set_crops_output: the frame's box records and crops and their pinned copies; dst = where the chain's kernel stores the crops
+// (dev, or the mapped pinned buffer itself: rtp_engine::crops_direct).  pixels = the frame in flight had a display image.  `fence`
+// (rtp_peek_crops_device): the kernel that reads this frame's display image and joints on the caller's stream is done; the next frame
+// staged on this slot, whose copy overwrites the image, waits on it first.
+struct CropsOut {
+  float *boxes_dev = nullptr, *boxes_host = nullptr;
+  unsigned char *dev = nullptr, *host = nullptr, *dst = nullptr;
+  bool pixels = false;
+  ExportFence fence;
+  void free();   // the buffers (engine_crops.cpp); the fence stays
+};
+
 // One frame's post-processing state (a batch context carries batch_frames of them)
 struct Slot {
   hipStream_t stream = nullptr;  // resize -> nms -> connect -> D2H of this frame (slot 0 shares the context's stream)
@@ -119,45 +162,12 @@ struct Slot {
   const unsigned char* disp_cur = nullptr;  // this frame's display image: disp_dev, or frame_dev itself when the frame already HAS the display size (fit scale 1: the
                                             // cubic warp samples at integer positions with weights (0, 1, 0, 0) = a copy; skipped, bit for bit the same image)
   bool has_disp = false;                // disp_dev holds this frame's display image (rtp_submit_frame, device path)
-  unsigned char* render_dev = nullptr;  // cfg.render: display image with the pose overlay
-  unsigned char* render_host = nullptr; // pinned copy of it
-  float* render_tab = nullptr;
   // rtp_submit_frame_device: ev_ready = the producer's stream at the submit (the staging stream waits on it), ev_read = the caller's frame
-  // has been read (the producer's stream waits on it).  rtp_collect_rendered_device: ev_export = the export of render_dev through the
-  // caller's view is done; while export_pending, the context's next batch (whose render overwrites render_dev) waits on it first.
-  hipEvent_t ev_ready = nullptr, ev_read = nullptr, ev_export = nullptr;
-  bool export_pending = false;
-  // rtp_set_render_jpeg: the GPU encoder's scratch for render_dev (allocated lazily, like render_dev) and its pinned output, which the
-  // encoder's last kernel writes: [jpeg_cap bytes] the file after the header, then its length (4 bytes)
-  JpegBufs jpeg;
-  unsigned char* jpeg_host = nullptr;
-  unsigned char* jpeg_host_dev = nullptr;   // the same memory as the device addresses it
-  size_t jpeg_cap = 0;
-  // rtp_set_render_yuv: the planar 4:2:0 planes of render_dev (Y, U, V, pitches = plane widths; allocated lazily, like render_dev) and
-  // their pinned copy, the only bytes of the rendered frame that cross PCIe in that mode
-  unsigned char* yuv_out_dev = nullptr;
-  unsigned char* yuv_out_host = nullptr;
-  // rtp_set_maps_output: the frame's chosen maps in the chosen format (allocated lazily, like render_dev) and their pinned copy.
-  // rtp_peek_maps_device: ev_maps_export = the kernel that reads this frame's low-res maps on the caller's stream is done; while
-  // maps_export_pending, the context's next batch (whose conv stack overwrites the low-res maps) waits on it first.
-  unsigned char* maps_dev = nullptr;
-  unsigned char* maps_host = nullptr;
-  size_t maps_cap = 0;
-  hipEvent_t ev_maps_export = nullptr;
-  bool maps_export_pending = false;
-  // rtp_set_crops_output: the frame's box records and crops (allocated by crops_ensure before the batch is launched) and their pinned
-  // copies; crops_dst = where the chain's kernel stores the crops (crops_dev, or the mapped pinned buffer itself: rtp_engine::crops_direct).
-  // crops_pixels = the frame in flight had a display image.  rtp_peek_crops_device: ev_crops_export = the kernel that reads this
-  // frame's display image and joints on the caller's stream is done; while crops_export_pending, the next frame staged on this slot
-  // (whose copy overwrites the image) waits on it first.
-  float* crops_boxes_dev = nullptr;
-  float* crops_boxes_host = nullptr;
-  unsigned char* crops_dev = nullptr;
-  unsigned char* crops_host = nullptr;
-  unsigned char* crops_dst = nullptr;
-  bool crops_pixels = false;
-  hipEvent_t ev_crops_export = nullptr;
-  bool crops_export_pending = false;
+  // has been read (the producer's stream waits on it)
+  hipEvent_t ev_ready = nullptr, ev_read = nullptr;
+  RenderOut render;   // what leaves the slot besides the joints, by output mode (above)
+  MapsOut maps;
+  CropsOut crops;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -337,7 +347,15 @@ int check_caller_stream(rtp_engine* e, void* stream, const char* fn);
 int check_view_memory(rtp_engine* e, const char* fn, const FrameView& fv, long hi, int* layout);
 int check_yuv_fields(rtp_engine* e, const rtp_yuv_view* v, const char* fn, YuvView* yv, long hi[3]);
 int check_yuv_memory(rtp_engine* e, const char* fn, const YuvView& yv, const long hi[3]);
+// Residency-stamp slots of one batch context (rtp_stamp_probe reports these numbers): [0, 64) plan steps (conv stack); 64 + 8 j + k =
+// frame j's post-processing chain and outputs, k = {0 strip, 1 write, 2 pairs, 3 match, 4 assemble} (the nms and connect launches take the
+// first of theirs), 5 the export of its rendered image (rtp_collect_rendered_device), 6 its JPEG encoding (rtp_set_render_jpeg; all seven
+// launches), 7 its conversion to YUV planes (rtp_set_render_yuv, rtp_collect_rendered_yuv_device); 200 + 2 j + {0 warp, or import of a
+// device / YUV frame, 1 area/pad} = frame j's device pre-processing; 232 + j = the decode of frame j's JPEG file.
+enum StampKind { STAMP_STRIP = 0, STAMP_PAIRS = 2, STAMP_EXPORT = 5, STAMP_JPEG_ENC = 6, STAMP_YUV_OUT = 7,   // 64 + 8 j + kind
+                 STAMP_WARP = 8, STAMP_AREA_PAD = 9, STAMP_JPEG_DEC = 10 };                                     // 200 + 2 j + (kind - 8); 232 + j
 unsigned long long* stamp_slot(const rtp_engine* e, const Ctx& cx, int idx);
+unsigned long long* frame_stamp(const rtp_engine* e, const Ctx& cx, int sj, StampKind kind);
 void drop_plan(rtp_engine* e);
 int replan(rtp_engine* e, int mode, const std::string& rules, bool light);
 int busy_mark_stage0(rtp_engine* e, Ctx& cx);
@@ -353,6 +371,15 @@ int pump(rtp_engine* e, int mode);
 int commit_slot(rtp_engine* e, int ci, int sj, uint64_t tag);
 int need_idle(rtp_engine* e);
 int collect_impl(rtp_engine* e, uint64_t* tag, float* joints, int* num_people, unsigned char* rendered, bool want_render);
+// The oldest frame in flight, not waited for: refuses "nothing in flight" and, has_disp_fn != nullptr, a frame without a display image
+int oldest_frame(rtp_engine* e, const char* has_disp_fn, int* ci, int* sj);
+// ExportFence: arm = `st` has just been given a read (null_stream: the caller passed none, so the read is waited for here); wait_streams =
+// the writer's streams (nullptr entries are skipped) wait for a pending read; wait_host = the host does; destroy = wait_host, drop the event
+int fence_arm(rtp_engine* e, ExportFence& f, hipStream_t st, bool null_stream);
+int fence_wait_streams(rtp_engine* e, ExportFence& f, std::initializer_list<hipStream_t> streams);
+int fence_wait_host(rtp_engine* e, ExportFence& f);
+void fence_destroy(ExportFence& f);
+int render_host_release(rtp_engine* e);   // rtp_set_render_jpeg / _yuv: the raw frames' pinned copies are not written in those modes
 
 // engine_jpeg.cpp
 void jpeg_free(JpegBufs* b, unsigned char** host, size_t* cap);
@@ -367,13 +394,10 @@ int yuv_out_launch(rtp_engine* e, Ctx& cx, int sj);
 // engine_maps.cpp
 int maps_ensure(rtp_engine* e, Ctx& cx, int nframes);
 int maps_launch(rtp_engine* e, Ctx& cx, int sj);
-void maps_free(Slot& sl);
 
 // engine_crops.cpp
 int crops_ensure(rtp_engine* e, Ctx& cx, int nframes);
 int crops_launch(rtp_engine* e, Ctx& cx, int sj);
-int crops_wait_export(rtp_engine* e, Ctx& cx, Slot& sl, bool host);
-void crops_free(Slot& sl);
 
 }  // namespace eng
 }  // namespace rtp

@@ -353,10 +353,8 @@ int rtp_set_render_jpeg(rtp_engine* e, int quality) {
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "rtp_set_render_jpeg: %zu frames in flight (collect them first)", e->fifo.size());
   if (quality) {
     jpeg_tables(e->cfg.disp_w, e->cfg.disp_h, quality, &e->jpeg_q, &e->jpeg_hdr);
-    SYNC_GUARD;   // the raw frames' pinned copies are not written in JPEG mode (the engine is idle: no copy into them is pending)
-    for (Ctx& cx : e->ctx)
-      for (Slot& sl : cx.slot)
-        if (sl.render_host) { HIPCHK(e, hipHostFree(sl.render_host)); sl.render_host = nullptr; }
+    int rc;
+    if ((rc = render_host_release(e))) return rc;
   }
   e->jpeg_quality = quality;
   return RTP_OK;
@@ -372,18 +370,16 @@ int rtp_collect_rendered_jpeg(rtp_engine* e, uint64_t* tag, float* joints, int* 
   if (!jpeg_host || capacity < need)
     return fail(e, RTP_EINVAL, "%s: capacity %zu, need rtp_jpeg_max_bytes(%d, %d) = %zu", fn, jpeg_host ? capacity : (size_t)0, e->cfg.disp_w,
                 e->cfg.disp_h, need);
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
-  Slot& sl = e->ctx[ci].slot[sj];
-  if (!sl.has_disp) return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", fn);
-  int rc;
+  int rc, ci = 0, sj = 0;
+  if ((rc = oldest_frame(e, fn, &ci, &sj))) return rc;
   if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
+  const RenderOut& r = e->ctx[ci].slot[sj].render;
   unsigned n = 0;
-  memcpy(&n, sl.jpeg_host + sl.jpeg_cap, sizeof n);
+  memcpy(&n, r.jpeg_host + r.jpeg_cap, sizeof n);
   const size_t hl = e->jpeg_hdr.size();
   if (hl + n > capacity) return fail(e, RTP_EHIP, "%s: the encoder reported %u bytes, more than its bound", fn, n);
   memcpy(jpeg_host, e->jpeg_hdr.data(), hl);
-  memcpy(jpeg_host + hl, sl.jpeg_host, n);
+  memcpy(jpeg_host + hl, r.jpeg_host, n);
   if (jpeg_bytes) *jpeg_bytes = hl + n;
   return RTP_OK;
 }

@@ -49,14 +49,9 @@ int maps_enqueue(rtp_engine* e, Ctx& cx, int sj, unsigned char* dst, long channe
   p.grid = e->maps_grid; p.format = e->maps_format; p.nch = (int)e->maps_chan.size(); p.num_parts = e->plan.num_parts;
   p.wide = maps_export_wide(e->maps_grid, e->maps_format, g.W, dst, channel_stride, row_stride);
   for (int i = 0; i < p.nch; ++i) p.chan[i] = (unsigned short)e->maps_chan[i];
-  p.stamp = nullptr;   // every residency slot of a frame's chain is taken (stamp_slot: 64 + 8 * sj + 0..7)
+  p.stamp = nullptr;   // every residency slot of a frame's chain is taken (StampKind: 64 + 8 * sj + 0..7)
   HIPCHK(e, launch_maps_export(p, stream));
   return RTP_OK;
-}
-
-void maps_free_all(rtp_engine* e) {
-  for (Ctx& cx : e->ctx)
-    for (Slot& sl : cx.slot) maps_free(sl);
 }
 
 // rtp_maps_view against the current mode: fields only (no HIP call); *hi = the highest byte offset from data the view addresses
@@ -86,42 +81,41 @@ int peek_checks(rtp_engine* e, const char* fn) {
 
 }  // namespace
 
-void maps_free(Slot& sl) {
-  if (sl.maps_dev) (void)hipFree(sl.maps_dev);
-  if (sl.maps_host) (void)hipHostFree(sl.maps_host);
-  sl.maps_dev = nullptr;
-  sl.maps_host = nullptr;
-  sl.maps_cap = 0;
+void MapsOut::free() {
+  if (dev) (void)hipFree(dev);
+  if (host) (void)hipHostFree(host);
+  dev = host = nullptr;
+  cap = 0;
 }
 
-// The buffers of the first nframes slots, before their batch is launched (or captured: no allocation inside a capture)
+// The buffers of the first nframes slots, before their batch is launched (frame_outputs_ensure, and the tap)
 int maps_ensure(rtp_engine* e, Ctx& cx, int nframes) {
   const size_t bytes = maps_geo(e).bytes;
   const bool copy = maps_is_lowres_copy(e);
   for (int j = 0; j < nframes; ++j) {
-    Slot& sl = cx.slot[j];
-    if (sl.maps_host && (copy || sl.maps_dev)) continue;
+    MapsOut& m = cx.slot[j].maps;
+    if (m.host && (copy || m.dev)) continue;
     SYNC_GUARD;
-    if (!copy && !sl.maps_dev) HIPCHK(e, hipMalloc((void**)&sl.maps_dev, bytes));
-    if (!sl.maps_host) HIPCHK(e, hipHostMalloc((void**)&sl.maps_host, bytes, hipHostMallocDefault));
-    sl.maps_cap = bytes;
+    if (!copy && !m.dev) HIPCHK(e, hipMalloc((void**)&m.dev, bytes));
+    if (!m.host) HIPCHK(e, hipHostMalloc((void**)&m.host, bytes, hipHostMallocDefault));
+    m.cap = bytes;
   }
   return RTP_OK;
 }
 
-// launch_batch_body: frame sj's maps -> the slot's device buffer -> its pinned buffer, on the frame's own stream behind the
+// frame_outputs_launch: frame sj's maps -> the slot's device buffer -> its pinned buffer, on the frame's own stream behind the
 // post-processing chain and in front of the frame's last event
 int maps_launch(rtp_engine* e, Ctx& cx, int sj) {
   Slot& sl = cx.slot[sj];
   const MapsGeo g = maps_geo(e);
   if (maps_is_lowres_copy(e)) {
-    HIPCHK(e, hipMemcpyAsync(sl.maps_host, cx.lowres + (size_t)sj * lowres_floats(e), g.bytes, hipMemcpyDeviceToHost, sl.stream));
+    HIPCHK(e, hipMemcpyAsync(sl.maps.host, cx.lowres + (size_t)sj * lowres_floats(e), g.bytes, hipMemcpyDeviceToHost, sl.stream));
     return RTP_OK;
   }
   const long rs = (long)g.W * (long)g.elem;
   int rc;
-  if ((rc = maps_enqueue(e, cx, sj, sl.maps_dev, rs * g.H, rs, sl.stream))) return rc;
-  HIPCHK(e, hipMemcpyAsync(sl.maps_host, sl.maps_dev, g.bytes, hipMemcpyDeviceToHost, sl.stream));
+  if ((rc = maps_enqueue(e, cx, sj, sl.maps.dev, rs * g.H, rs, sl.stream))) return rc;
+  HIPCHK(e, hipMemcpyAsync(sl.maps.host, sl.maps.dev, g.bytes, hipMemcpyDeviceToHost, sl.stream));
   return RTP_OK;
 }
 
@@ -176,7 +170,8 @@ int rtp_set_maps_output(rtp_engine* e, const rtp_maps_config* cfg) {
     int rc;
     if ((rc = need_idle(e))) return rc;   // (also: no rtp_peek_maps_device of the old mode is still reading the low-res maps)
     if (e->graph_post && (rc = invalidate_graphs(e))) return rc;   // the chains live inside the batch graphs: the new kernel must join or leave them
-    maps_free_all(e);
+    for (Ctx& cx : e->ctx)
+      for (Slot& sl : cx.slot) sl.maps.free();
   }
   e->maps_on = cfg != nullptr;
   e->maps_grid = cfg ? cfg->grid : 0;
@@ -203,10 +198,9 @@ int rtp_peek_maps(rtp_engine* e, uint64_t* tag, void* maps_host, size_t capacity
   if ((rc = peek_checks(e, fn))) return rc;
   const MapsGeo g = maps_geo(e);
   if (!maps_host || capacity < g.bytes) return fail(e, RTP_EINVAL, "%s: capacity %zu, the maps have %zu bytes (rtp_maps_info)", fn, maps_host ? capacity : (size_t)0, g.bytes);
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  if ((rc = wait_oldest(e, &ci, &sj))) return rc;
+  if ((rc = wait_oldest(e, &ci, &sj))) return rc;   // (refuses "nothing in flight" before it waits)
   const Slot& sl = e->ctx[ci].slot[sj];
-  memcpy(maps_host, sl.maps_host, g.bytes);
+  memcpy(maps_host, sl.maps.host, g.bytes);
   if (tag) *tag = sl.tag;
   return RTP_OK;
 }
@@ -225,20 +219,12 @@ int rtp_peek_maps_device(rtp_engine* e, uint64_t* tag, const rtp_maps_view* out_
   if ((rc = check_caller_stream(e, stream, fn))) return rc;
   if ((rc = use_device(e))) return rc;
   if ((rc = check_device_range(e, fn, "data", out_dev->data, hi, &avail))) return rc;
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  if ((rc = wait_oldest(e, &ci, &sj))) return rc;
+  if ((rc = wait_oldest(e, &ci, &sj))) return rc;   // (refuses "nothing in flight" before it waits)
   Ctx& cx = e->ctx[ci];
   Slot& sl = cx.slot[sj];
   hipStream_t st = stream ? (hipStream_t)stream : sl.stream;
-  if (!sl.ev_maps_export) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_maps_export, hipEventDisableTiming));
-  if (sl.maps_export_pending) HIPCHK(e, hipStreamWaitEvent(st, sl.ev_maps_export, 0));   // an earlier peek of this frame on another stream: the event below then covers both
   if ((rc = maps_enqueue(e, cx, sj, (unsigned char*)out_dev->data, out_dev->channel_stride, out_dev->row_stride, st))) return rc;
-  HIPCHK(e, hipEventRecord(sl.ev_maps_export, st));
-  sl.maps_export_pending = true;
-  if (!stream) {
-    HIPCHK(e, hipEventSynchronize(sl.ev_maps_export));
-    sl.maps_export_pending = false;
-  }
+  if ((rc = fence_arm(e, sl.maps.fence, st, !stream))) return rc;
   if (tag) *tag = sl.tag;
   return RTP_OK;
 }
@@ -259,7 +245,7 @@ int rtp_maps_from_lowres(rtp_engine* e, const float* lowres, void* maps_host, si
   if ((rc = maps_ensure(e, cx, 1))) return rc;
   if ((rc = maps_launch(e, cx, 0))) return rc;
   HIPCHK(e, hipStreamSynchronize(sl.stream));
-  memcpy(maps_host, sl.maps_host, g.bytes);
+  memcpy(maps_host, sl.maps.host, g.bytes);
   return RTP_OK;
 }
 

@@ -18,20 +18,15 @@ YuvView yuv_out_view(unsigned char* planes, int w, int h) {
   return v;
 }
 
-// rtp_set_render_yuv: frame sj's rendered image -> its planes -> the slot's pinned buffer, on the frame's own stream behind the render kernel
+// rtp_set_render_yuv: frame sj's rendered image -> its planes -> the slot's pinned buffer, on the frame's own stream behind the render
+// kernel (the buffers: frame_outputs_ensure)
 int yuv_out_launch(rtp_engine* e, Ctx& cx, int sj) {
   Slot& sl = cx.slot[sj];
   const int w = e->cfg.disp_w, h = e->cfg.disp_h;
-  const size_t bytes = rtp_yuv_bytes(w, h, 420);
-  if (!sl.yuv_out_dev) {
-    SYNC_GUARD;
-    HIPCHK(e, hipMalloc((void**)&sl.yuv_out_dev, bytes));
-    HIPCHK(e, hipHostMalloc((void**)&sl.yuv_out_host, bytes, hipHostMallocDefault));
-  }
-  const FrameView src = packed_bgr_view(sl.render_dev, w, h);
-  const YuvView dst = yuv_out_view(sl.yuv_out_dev, w, h);
-  HIPCHK(e, launch_yuv_export(stamp_slot(e, cx, 64 + 8 * sj + 7), src, dst, yuv_export_layout(src, dst), sl.stream));
-  HIPCHK(e, hipMemcpyAsync(sl.yuv_out_host, sl.yuv_out_dev, bytes, hipMemcpyDeviceToHost, sl.stream));
+  const FrameView src = packed_bgr_view(sl.render.dev, w, h);
+  const YuvView dst = yuv_out_view(sl.render.yuv_dev, w, h);
+  HIPCHK(e, launch_yuv_export(frame_stamp(e, cx, sj, STAMP_YUV_OUT), src, dst, yuv_export_layout(src, dst), sl.stream));
+  HIPCHK(e, hipMemcpyAsync(sl.render.yuv_host, sl.render.yuv_dev, rtp_yuv_bytes(w, h, 420), hipMemcpyDeviceToHost, sl.stream));
   return RTP_OK;
 }
 
@@ -83,12 +78,8 @@ int rtp_set_render_yuv(rtp_engine* e, int chroma) {
   if (chroma && e->jpeg_quality)
     return fail(e, RTP_EINVAL, "rtp_set_render_yuv: JPEG mode is on (rtp_set_render_jpeg %d): one renderer mode at a time", e->jpeg_quality);
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "rtp_set_render_yuv: %zu frames in flight (collect them first)", e->fifo.size());
-  if (chroma) {
-    SYNC_GUARD;   // the raw frames' pinned copies are not written in YUV mode (the engine is idle: no copy into them is pending)
-    for (Ctx& cx : e->ctx)
-      for (Slot& sl : cx.slot)
-        if (sl.render_host) { HIPCHK(e, hipHostFree(sl.render_host)); sl.render_host = nullptr; }
-  }
+  int rc;
+  if (chroma && (rc = render_host_release(e))) return rc;
   e->yuv_mode = chroma;
   return RTP_OK;
 }
@@ -102,13 +93,10 @@ int rtp_collect_rendered_yuv(rtp_engine* e, uint64_t* tag, float* joints, int* n
   if (!planes_host || capacity < need)
     return fail(e, RTP_EINVAL, "%s: capacity %zu, need rtp_yuv_bytes(%d, %d, 420) = %zu", fn, planes_host ? capacity : (size_t)0, e->cfg.disp_w,
                 e->cfg.disp_h, need);
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
-  Slot& sl = e->ctx[ci].slot[sj];
-  if (!sl.has_disp) return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", fn);
-  int rc;
+  int rc, ci = 0, sj = 0;
+  if ((rc = oldest_frame(e, fn, &ci, &sj))) return rc;
   if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
-  memcpy(planes_host, sl.yuv_out_host, need);
+  memcpy(planes_host, e->ctx[ci].slot[sj].render.yuv_host, need);
   return RTP_OK;
 }
 
@@ -127,23 +115,15 @@ int rtp_collect_rendered_yuv_device(rtp_engine* e, uint64_t* tag, float* joints,
   if (yv.w != e->cfg.disp_w || yv.h != e->cfg.disp_h)
     return fail(e, RTP_EINVAL, "%s: the output view is %d x %d, the display image %d x %d", fn, yv.w, yv.h, e->cfg.disp_w, e->cfg.disp_h);
   if ((rc = check_yuv_memory(e, fn, yv, hi))) return rc;
-  if (e->fifo.empty()) return fail(e, RTP_EAGAIN, "nothing in flight");
-  const int ci = e->fifo.front() / 64, sj = e->fifo.front() % 64;
+  int ci = 0, sj = 0;
+  if ((rc = oldest_frame(e, fn, &ci, &sj))) return rc;
+  if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
   Ctx& cx = e->ctx[ci];
   Slot& sl = cx.slot[sj];
-  if (!sl.has_disp) return fail(e, RTP_EINVAL, "%s: the oldest frame has no display image (submitted as a net input): collect it with rtp_collect", fn);
-  if ((rc = collect_impl(e, tag, joints, num_people, nullptr, true))) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : sl.stream;
-  if (!sl.ev_export) HIPCHK(e, hipEventCreateWithFlags(&sl.ev_export, hipEventDisableTiming));
-  const FrameView src = packed_bgr_view(sl.render_dev, e->cfg.disp_w, e->cfg.disp_h);
-  HIPCHK(e, launch_yuv_export(stamp_slot(e, cx, 64 + 8 * sj + 7), src, yv, yuv_export_layout(src, yv), st));
-  HIPCHK(e, hipEventRecord(sl.ev_export, st));
-  sl.export_pending = true;
-  if (!stream) {
-    HIPCHK(e, hipEventSynchronize(sl.ev_export));
-    sl.export_pending = false;
-  }
-  return RTP_OK;
+  const FrameView src = packed_bgr_view(sl.render.dev, e->cfg.disp_w, e->cfg.disp_h);
+  HIPCHK(e, launch_yuv_export(frame_stamp(e, cx, sj, STAMP_YUV_OUT), src, yv, yuv_export_layout(src, yv), st));
+  return fence_arm(e, sl.render.fence, st, !stream);
 }
 
 }  // extern "C"
