@@ -113,6 +113,30 @@ class rtp_crops_view(C.Structure):
     ]
 
 
+class rtp_track_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("min_score", C.c_float),
+        ("min_parts", C.c_int),
+        ("min_common", C.c_int),
+        ("max_cost", C.c_float),
+        ("max_misses", C.c_int),
+    ]
+
+
+class rtp_track_state(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("num_parts", C.c_int),
+        ("next_id", C.c_uint),
+        ("frames", C.c_uint),
+        ("id", C.c_int * 128),
+        ("hits", C.c_int * 128),
+        ("misses", C.c_int * 128),
+        ("joints", C.c_float * (128 * 70 * 3)),
+    ]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 vp = C.c_void_p
@@ -236,6 +260,16 @@ SIGNATURES = {
     "rtp_peek_crops_device": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, ip, C.c_int, C.POINTER(rtp_crops_view), vp]),
     "rtp_crops_from_joints": (C.c_int, [vp, C.POINTER(C.c_ubyte), fp, C.c_int, fp, ip, C.POINTER(C.c_ubyte), C.c_int]),
     "rtp_crops_head_parts": (C.c_int, [C.c_int, ip]),
+    "rtp_track_config_default": (C.c_int, [C.POINTER(rtp_track_config)]),
+    "rtp_track_state_init": (C.c_int, [C.POINTER(rtp_track_state), C.c_int]),
+    "rtp_track_update": (C.c_int, [C.POINTER(rtp_track_state), C.POINTER(rtp_track_config), fp, C.c_int, ip]),
+    "rtp_set_tracking": (C.c_int, [vp, C.POINTER(rtp_track_config)]),
+    "rtp_track_reset": (C.c_int, [vp]),
+    "rtp_track_get_state": (C.c_int, [vp, C.POINTER(rtp_track_state)]),
+    "rtp_track_set_state": (C.c_int, [vp, C.POINTER(rtp_track_state)]),
+    "rtp_peek_tracks": (C.c_int, [vp, C.POINTER(C.c_uint64), ip, ip, C.c_int]),
+    "rtp_track_from_joints": (C.c_int, [vp, fp, C.c_int, ip, ip, C.c_int]),
+    "rtp_format_json_tracked": (C.c_long, [C.c_char_p, C.c_size_t, fp, C.c_int, C.c_int, C.c_float, ip]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -643,6 +643,7 @@ int frame_outputs_ensure(rtp_engine* e, Ctx& cx, int nframes) {
   }
   if (e->maps_on && (rc = maps_ensure(e, cx, nframes))) return rc;
   if (e->crops_on && (rc = crops_ensure(e, cx, nframes))) return rc;
+  if (e->track_on && (rc = track_ensure(e, cx, nframes))) return rc;
   return RTP_OK;
 }
 
@@ -666,6 +667,11 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
   }
   if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // the frame's maps -> its pinned buffer (engine_maps.cpp)
   if (e->crops_on && (rc = crops_launch(e, cx, j))) return rc;   // the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
+  // the frame's people against the engine's track table (engine_track.cpp).  Only a frame in flight (rtp_submit*) advances the tracker:
+  // the synchronous taps, calibration and the profiling passes run this chain on an idle engine, whose slots are not busy.  The kernels
+  // of consecutive frames are chained in LAUNCH order, which is submit order: batches are launched in the order they were filled and
+  // launch_batch_body walks a batch's slots in slot order.
+  if (e->track_on && sl.busy && (rc = track_launch(e, cx, j))) return rc;
   return RTP_OK;
 }
 
@@ -725,7 +731,7 @@ int capture_batch(rtp_engine* e, Ctx& cx, int nframes, hipGraphExec_t* out) {
   SYNC_GUARD;
   hipGraph_t g = nullptr;
   HIPCHK(e, hipStreamBeginCapture(cx.stream, hipStreamCaptureModeThreadLocal));
-  const int rc = launch_batch_body(e, cx, nframes, cx.input, false, true, e->graph_post && !e->crops_on ? 3 : 1);   // (crops mode: see launch_batch)
+  const int rc = launch_batch_body(e, cx, nframes, cx.input, false, true, e->graph_post && !e->crops_on && !e->track_on ? 3 : 1);   // (crops and tracking mode: see launch_batch)
   const hipError_t s = hipStreamEndCapture(cx.stream, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
   if (s != hipSuccess || !g) return fail(e, RTP_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(s));
@@ -771,8 +777,9 @@ int launch_batch(rtp_engine* e, Ctx& cx, int nframes, const float* input_dev, bo
   HIPCHK(e, hipGraphLaunch(cx.gexec[nframes], cx.stream));
   // the conv stack is one replay; every frame's short post-processing chain is launched eagerly on its slot's stream.  Crops mode keeps
   // the chains out of the graphs under RTP_GRAPH_POST=1 too: the crops kernel reads disp_cur, which differs from frame to frame
-  // (rtp_set_crops_output dropped the graphs that held them)
-  if (!e->graph_post || e->crops_on) {
+  // (rtp_set_crops_output dropped the graphs that held them).  Tracking mode likewise: the wait in front of a frame's track kernel names
+  // the event of whichever frame was launched before it
+  if (!e->graph_post || e->crops_on || e->track_on) {
     if ((rc = launch_batch_body(e, cx, nframes, cx.input, false, false, 2))) return rc;
     cx.graph_run = false;            // collect waits for the frame's own event, not for the whole batch
     cx.graph_conv = true;
@@ -1102,6 +1109,7 @@ void free_ctx(Ctx& cx) {
     sl.render.free();
     sl.maps.free();
     sl.crops.free();
+    sl.track.free();
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
     for (int i = 0; i < 5; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
@@ -1563,6 +1571,7 @@ void drop_plan(rtp_engine* e) {
   (void)hipSetDevice(e->cfg.device_id);
   (void)hipDeviceSynchronize();
   for (auto& c : e->ctx) free_ctx(c);
+  track_forget_chain(e);
   e->ctx.clear();
   if (e->dweights) { (void)hipFree(e->dweights); e->dweights = nullptr; }
   e->plan = Plan();
@@ -1850,6 +1859,7 @@ void rtp_engine_destroy(rtp_engine* e) {
   SYNC_GUARD;
   (void)hipSetDevice(e->cfg.device_id);
   for (auto& c : e->ctx) free_ctx(c);
+  track_free(e);
   if (e->dweights) (void)hipFree(e->dweights);
   if (e->dchmap) (void)hipFree(e->dchmap);
   for (hipEvent_t ev : e->tev) if (ev) (void)hipEventDestroy(ev);

@@ -1,4 +1,4 @@
-// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_calib.cpp) share: the frame slot, the batch context and
+// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_calib.cpp) share: the frame slot, the batch context and
 // rtp_engine itself, the error / lock macros, and the declarations of every helper one of those files defines and another one calls.
 // Internal: only the engine's own files include it (it opens namespace rtp for them); nothing here is part of the library's ABI.
 #pragma once
@@ -39,6 +39,7 @@ size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64
                                unsigned short huff_code[4][256], unsigned char huff_size[4][256]);
 // host_util.cpp
 extern "C" const char* rtp_internal_crops_check(const rtp_crops_config* c, int model_parts);
+extern "C" const char* rtp_internal_track_check(const rtp_track_config* c);
 extern "C" int rtp_internal_yuv_fields(const rtp_yuv_view* v, char* msg, size_t msg_len, long hi[3]);
 extern "C" int rtp_internal_jpeg_geom(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, rtp::JpegGeom* g);
 
@@ -123,6 +124,14 @@ struct CropsOut {
   void free();   // the buffers (engine_crops.cpp); the fence stays
 };
 
+// rtp_set_tracking: the frame's records {id, slot, hits, cost bits} per person and their pinned copy; ev = recorded behind the frame's
+// track kernel: the NEXT frame's kernel waits on it (engine_track.cpp: ORDERING)
+struct TrackOut {
+  int *recs_dev = nullptr, *recs_host = nullptr;
+  hipEvent_t ev = nullptr;
+  void free();   // (engine_track.cpp)
+};
+
 // One frame's post-processing state (a batch context carries batch_frames of them)
 struct Slot {
   hipStream_t stream = nullptr;  // resize -> nms -> connect -> D2H of this frame (slot 0 shares the context's stream)
@@ -168,6 +177,7 @@ struct Slot {
   RenderOut render;   // what leaves the slot besides the joints, by output mode (above)
   MapsOut maps;
   CropsOut crops;
+  TrackOut track;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -263,6 +273,14 @@ struct rtp_engine {
   rtp_crops_config crops_cfg = {};
   std::vector<int> crops_list;
   int crops_direct = 0;
+  // rtp_set_tracking (engine_track.cpp): tracking mode on, its configuration, the device-resident track table (rtp_track_state's
+  // layout) and the event behind the track kernel launched last (nullptr: the next one waits on nothing) with the stream it is on
+  bool track_on = false;
+  rtp_track_config track_cfg = {};
+  TrackTable* track_dev = nullptr;
+  hipEvent_t track_prev = nullptr;
+  hipStream_t track_prev_stream = nullptr;
+  int track_variant = RTP_TRACK_DEFAULT;   // kernels.h RTP_TRACK_*: the assignment's form (rtp_internal_track_variant; tools/bench_track.py times all)
   // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
   JpegBufs jenc;
   unsigned char* jenc_host = nullptr;
@@ -398,6 +416,12 @@ int maps_launch(rtp_engine* e, Ctx& cx, int sj);
 // engine_crops.cpp
 int crops_ensure(rtp_engine* e, Ctx& cx, int nframes);
 int crops_launch(rtp_engine* e, Ctx& cx, int sj);
+
+// engine_track.cpp
+int track_ensure(rtp_engine* e, Ctx& cx, int nframes);
+int track_launch(rtp_engine* e, Ctx& cx, int sj);
+void track_forget_chain(rtp_engine* e);   // the slots' events are gone or complete: the next track kernel waits on nothing
+void track_free(rtp_engine* e);
 
 }  // namespace eng
 }  // namespace rtp

@@ -1,8 +1,11 @@
 // host_util.cpp — the host-only pieces of the path behind the C-ABI: model descriptor tables,
 // default thresholds, process_and_pad_image, the JSON body, the narrow formats of maps mode and the boxes and pixels of
 // crops mode (rtp_crop_people).  No GPU needed.
+#include <algorithm>
+#include <vector>
 #include <charconv>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <sstream>
 #include <string>
@@ -80,7 +83,8 @@ int rtp_process_and_pad_image(float* target, const unsigned char* bgr, int ow, i
 // an ostream insertion: 76 people x 54 numbers (the noise-map worst case) took 1.2 ms per frame through std::ostringstream —
 // one writer thread would have capped an 8-GPU node at ~800 frames/s.  tests/test_ref_golden.py: byte-identical to the
 // reference's own block, edge values included.
-long rtp_format_json(char* buf, size_t buflen, const float* joints, int num_people, int num_parts, float frame_scale) {
+// (recs != nullptr: rtp_format_json_tracked's "id" member in front of every body's "joints")
+static long format_json(char* buf, size_t buflen, const float* joints, int num_people, int num_parts, float frame_scale, const int* recs) {
   if (!buf || (num_people > 0 && !joints) || num_people < 0 || num_parts <= 0) return RTP_EINVAL;
   const double scale = 1.0 / frame_scale;
   char* p = buf;
@@ -95,7 +99,13 @@ long rtp_format_json(char* buf, size_t buflen, const float* joints, int num_peop
   };
   bool ok = lit("{\n\"version\":0.1,\n\"bodies\":[\n");
   for (int ip = 0; ok && ip < num_people; ip++) {
-    ok = lit("{\n\"joints\":[");
+    ok = lit("{\n");
+    if (recs) {
+      char id[32];
+      snprintf(id, sizeof id, "\"id\":%d,", recs[(size_t)ip * RTP_TRACK_REC_INTS]);
+      ok = ok && lit(id);
+    }
+    ok = ok && lit("\"joints\":[");
     for (int ij = 0; ok && ij < num_parts; ij++) {
       const float* j = joints + ((size_t)ip * num_parts + ij) * 3;
       ok = num(scale * j[0]) && lit(",") && num(scale * j[1]) && lit(",") && num((double)j[2]) && (ij == num_parts - 1 || lit(","));
@@ -106,6 +116,12 @@ long rtp_format_json(char* buf, size_t buflen, const float* joints, int num_peop
   if (!ok) return RTP_ERANGE;
   *p = 0;
   return (long)(p - buf);
+}
+long rtp_format_json(char* buf, size_t buflen, const float* joints, int num_people, int num_parts, float frame_scale) {
+  return format_json(buf, buflen, joints, num_people, num_parts, frame_scale, nullptr);
+}
+long rtp_format_json_tracked(char* buf, size_t buflen, const float* joints, int num_people, int num_parts, float frame_scale, const int* recs) {
+  return format_json(buf, buflen, joints, num_people, num_parts, frame_scale, recs);
 }
 
 // The two narrow formats of maps mode (maps_export.hip computes the same bits on the device).  Each float operation is spelled as
@@ -272,6 +288,150 @@ int rtp_crop_people(const unsigned char* display_bgr, int w, int h, const float*
           else out[((size_t)(2 - c) * ch + j) * cw + i] = v;
         }
       }
+  }
+  return n;
+}
+
+}  // extern "C"
+
+// ---- tracking mode: the one definition of its arithmetic (track.hip computes the same integers and float bits on the device) --------
+
+// What is wrong with the configuration, or nullptr.  The engine's switch reports the same text.
+extern "C" const char* rtp_internal_track_check(const rtp_track_config* c) {
+  if (!c) return "NULL rtp_track_config";
+  if (c->struct_size != sizeof(rtp_track_config)) return "rtp_track_config.struct_size is not this library's sizeof(rtp_track_config)";
+  if (!(c->min_score >= 0.f) || std::isinf(c->min_score)) return "min_score must be a finite number >= 0";
+  if (c->min_parts < 1) return "min_parts must be >= 1";
+  if (c->min_common < 1) return "min_common must be >= 1";
+  if (!(c->max_cost > 0.f) || std::isinf(c->max_cost)) return "max_cost must be a finite number > 0";
+  if (c->max_misses < 0) return "max_misses must be >= 0";
+  return nullptr;
+}
+
+extern "C" {
+
+int rtp_track_config_default(rtp_track_config* cfg) {
+  if (!cfg) return RTP_EINVAL;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->struct_size = (unsigned)sizeof *cfg;
+  cfg->min_score = 0.f;
+  cfg->min_parts = 3;
+  cfg->min_common = 2;
+  cfg->max_cost = 0.0625f;
+  cfg->max_misses = 15;
+  return RTP_OK;
+}
+
+int rtp_track_state_init(rtp_track_state* state, int num_parts) {
+  if (!state || num_parts < 1 || num_parts > RTP_MAX_NUM_PARTS) return RTP_EINVAL;
+  memset(state, 0, sizeof *state);
+  state->struct_size = (unsigned)sizeof *state;
+  state->num_parts = num_parts;
+  state->next_id = 1;
+  return RTP_OK;
+}
+
+int rtp_track_update(rtp_track_state* st, const rtp_track_config* cfg, const float* joints, int num_people, int* recs) {
+#pragma clang fp contract(off)
+  if (!st || !recs || rtp_internal_track_check(cfg)) return RTP_EINVAL;
+  if (st->struct_size != sizeof(rtp_track_state) || st->num_parts < 1 || st->num_parts > RTP_MAX_NUM_PARTS) return RTP_EINVAL;
+  const int n = num_people < 0 ? 0 : num_people > RTP_MAX_PEOPLE ? RTP_MAX_PEOPLE : num_people;
+  if (n > 0 && !joints) return RTP_EINVAL;
+  const int P = st->num_parts;
+  auto counts = [&](const float* j) { return j[2] > cfg->min_score && std::isfinite(j[0]) && std::isfinite(j[1]); };
+  // 1. trackable people
+  bool trackable[RTP_MAX_PEOPLE];
+  for (int k = 0; k < n; ++k) {
+    int c = 0;
+    for (int p = 0; p < P; ++p) c += counts(joints + ((size_t)k * P + p) * 3) ? 1 : 0;
+    trackable[k] = c >= cfg->min_parts;
+  }
+  // 2. the candidates, as keys (cost bits, slot, person)
+  struct Cand { uint32_t bits; int t, k; };
+  std::vector<Cand> cand;
+  for (int t = 0; t < RTP_MAX_TRACKS; ++t) {
+    if (!st->id[t]) continue;
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    for (int p = 0; p < P; ++p) {
+      const float* tj = st->joints[t][p];
+      if (!counts(tj)) continue;
+      const float x = tj[0] + 0.0f, y = tj[1] + 0.0f;
+      x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+    }
+    const float w = x1 - x0, h = y1 - y0;
+    const float ww = w * w, hh = h * h;
+    const float wh = ww + hh;
+    const float d = fmaxf(wh, 1.0f);
+    for (int k = 0; k < n; ++k) {
+      if (!trackable[k]) continue;
+      float s = 0.0f;
+      int m = 0;
+      for (int p = 0; p < P; ++p) {
+        const float* pj = joints + ((size_t)k * P + p) * 3;
+        const float* tj = st->joints[t][p];
+        if (!counts(pj) || !counts(tj)) continue;
+        const float dx = pj[0] - tj[0], dy = pj[1] - tj[1];
+        const float a = dx * dx, b = dy * dy;
+        const float c = a + b;
+        s = s + c;
+        ++m;
+      }
+      if (m < cfg->min_common) continue;
+      const float q = s / (float)m;
+      const float cost = q / d;
+      if (!std::isfinite(cost) || !(cost <= cfg->max_cost)) continue;
+      const float cz = cost + 0.0f;
+      Cand c;
+      memcpy(&c.bits, &cz, 4);
+      c.t = t; c.k = k;
+      cand.push_back(c);
+    }
+  }
+  // 3. greedy assignment in key order
+  std::sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.bits != b.bits ? a.bits < b.bits : a.t != b.t ? a.t < b.t : a.k < b.k; });
+  int slot_of[RTP_MAX_PEOPLE], person_of[RTP_MAX_TRACKS];
+  uint32_t cost_of[RTP_MAX_PEOPLE];
+  for (int k = 0; k < RTP_MAX_PEOPLE; ++k) { slot_of[k] = -1; cost_of[k] = 0; }
+  for (int t = 0; t < RTP_MAX_TRACKS; ++t) person_of[t] = -1;
+  for (const Cand& c : cand) {
+    if (person_of[c.t] >= 0 || slot_of[c.k] >= 0) continue;
+    person_of[c.t] = c.k; slot_of[c.k] = c.t; cost_of[c.k] = c.bits;
+  }
+  // 4. matched slots, 5. unmatched live slots
+  for (int t = 0; t < RTP_MAX_TRACKS; ++t) {
+    if (!st->id[t]) continue;
+    if (person_of[t] >= 0) {
+      memcpy(st->joints[t], joints + (size_t)person_of[t] * P * 3, (size_t)P * 3 * sizeof(float));
+      st->hits[t]++;
+      st->misses[t] = 0;
+    } else if (++st->misses[t] > cfg->max_misses) {
+      st->id[t] = st->hits[t] = st->misses[t] = 0;
+      memset(st->joints[t], 0, sizeof st->joints[t]);
+    }
+  }
+  // 6. births: the lowest free slot for each unmatched trackable person, in person order
+  bool born[RTP_MAX_PEOPLE] = {};
+  int free_t = 0;
+  for (int k = 0; k < n; ++k) {
+    if (!trackable[k] || slot_of[k] >= 0) continue;
+    while (free_t < RTP_MAX_TRACKS && st->id[free_t]) ++free_t;
+    if (free_t == RTP_MAX_TRACKS) break;
+    if (st->next_id == 0) st->next_id = 1;
+    st->id[free_t] = (int)st->next_id++;
+    if (st->next_id == 0) st->next_id = 1;
+    st->hits[free_t] = 1;
+    st->misses[free_t] = 0;
+    memcpy(st->joints[free_t], joints + (size_t)k * P * 3, (size_t)P * 3 * sizeof(float));
+    slot_of[k] = free_t;
+    born[k] = true;
+  }
+  st->frames++;   // 7.
+  for (int k = 0; k < n; ++k) {
+    int* r = recs + (size_t)k * RTP_TRACK_REC_INTS;
+    const int t = slot_of[k];
+    if (t < 0) { r[0] = 0; r[1] = -1; r[2] = 0; r[3] = 0; continue; }
+    r[0] = st->id[t]; r[1] = t; r[2] = st->hits[t];
+    r[3] = born[k] ? 0 : (int)cost_of[k];
   }
   return n;
 }

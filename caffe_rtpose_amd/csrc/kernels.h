@@ -398,6 +398,38 @@ struct CropsParams {
 int crops_wide(int crop_w, const void* data, long crop_stride);
 hipError_t launch_crops(const CropsParams& p, hipStream_t stream);
 
+// Tracking mode (track.hip, rtp_set_tracking): the frame's people, read in device memory behind the connect kernels, are associated
+// with the engine's track table; the table is updated and one record {id, slot, hits, cost bits} per person is written.  Integers
+// and float bits are rtp_track_update's (include/rtpose_mi355x.h spells out the arithmetic).  ONE workgroup per launch; launches on
+// one table must be ordered by the caller (the engine chains them with events).  *num_people is read on the device (negative =
+// connect's error code = 0 people).  TrackTable is rtp_track_state's layout (engine_track.cpp asserts it).
+#define RTP_TRACK_SLOTS 128      // RTP_MAX_TRACKS
+#define RTP_TRACK_MAX_PARTS 70   // RTP_MAX_NUM_PARTS
+#define RTP_TRACK_MAX_PEOPLE 96  // RTP_MAX_PEOPLE
+struct TrackTable {
+  unsigned struct_size;
+  int num_parts;
+  unsigned next_id, frames;
+  int id[RTP_TRACK_SLOTS], hits[RTP_TRACK_SLOTS], misses[RTP_TRACK_SLOTS];
+  float joints[RTP_TRACK_SLOTS][RTP_TRACK_MAX_PARTS][3];
+};
+struct TrackParams {
+  const float* joints;       // [max_people][num_parts][3]
+  const int* num_people;
+  TrackTable* table;
+  int* recs;                 // [RTP_TRACK_MAX_PEOPLE][4] records (the first min(max(*num_people, 0), 96) are written)
+  int num_parts, min_parts, min_common, max_misses;
+  float min_score, max_cost;
+  int variant;               // RTP_TRACK_* below: the form of the assignment and the workgroup's size (same records and table in all)
+};
+// The assignment, deterministic on (cost bits, slot, person) keys in both forms:
+//   ARGMIN  a workgroup-wide argmin over the keys per round, the winner's row and column struck out: two barriers per matched person
+//   SORT    the candidates' indices compacted and sorted once in LDS (bitonic, on the keys), then ONE thread walks the list
+// each with a workgroup of 256 or 1024 threads.  profiles/r13_track.txt has all four measured; RTP_TRACK_DEFAULT is the fastest.
+enum { RTP_TRACK_ARGMIN_256 = 0, RTP_TRACK_ARGMIN_1024 = 1, RTP_TRACK_SORT_256 = 2, RTP_TRACK_SORT_1024 = 3, RTP_TRACK_VARIANTS = 4 };
+#define RTP_TRACK_DEFAULT RTP_TRACK_SORT_1024
+hipError_t launch_track(const TrackParams& p, hipStream_t stream);
+
 struct NmsParams {
   const float* src;  // resized map [src_planes][H][W]
   float* peaks;      // [num_parts][max_peaks+1][3]  (in/out)

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <cctype>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +22,7 @@
 #include <fstream>
 #include <future>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <pthread.h>
 #include <sched.h>
@@ -51,6 +53,9 @@ int rtp_peek_maps(rtp_engine* e, uint64_t* tag, void* maps_host, size_t capacity
 // (nor crops mode: --write_crops then writes box files without boxes, as under --dry_engine)
 int rtp_set_crops_output(rtp_engine* e, const rtp_crops_config* cfg) __attribute__((weak));
 int rtp_peek_crops(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_boxes, unsigned char* crops_host, int capacity, int* has_pixels) __attribute__((weak));
+// (nor tracking mode: --track then runs rtp_track_update in the re-orderer, as under --dry_engine)
+int rtp_set_tracking(rtp_engine* e, const rtp_track_config* cfg) __attribute__((weak));
+int rtp_peek_tracks(rtp_engine* e, uint64_t* tag, int* recs_host, int* num_recs, int capacity) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -92,6 +97,12 @@ struct Flags {
   std::string write_crops, crop_size = "128x128", crop_parts = "all";
   double crop_margin = 0.15;
   int max_crops = 16;
+  // --track: stable person ids across frames.  One real GPU worker: the engine's tracking mode (rtp_set_tracking; the association runs
+  // on the GPU in submit order).  --num_gpu N > 1, --dry_engine or --host_preprocess: the re-orderer, which sees the frames in order,
+  // runs rtp_track_update on each frame's joints.  --write_json bodies and --write_crops box records then carry "id".
+  bool track = false;
+  double track_max_cost = 0.0625;
+  int track_max_misses = 15, track_min_parts = 3;
   std::string caffemodel = "model/coco/pose_iter_440000.caffemodel", caffeproto = "model/coco/pose_deploy_linevec.prototxt";
   std::string resolution = "1280x720", net_resolution = "656x368", camera_resolution = "1280x720";
   double start_scale = 1, scale_gap = 0.3;
@@ -123,9 +134,10 @@ int parse_flags(int argc, char** argv, Flags& F) {
       {"net_resolution", &F.net_resolution}, {"camera_resolution", &F.camera_resolution}, {"precision", &F.precision}, {"model", &F.model}, {"devices", &F.devices}};
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
-      {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}, {"max_crops", &F.max_crops}};
-  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display},
+      {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}, {"max_crops", &F.max_crops},
+      {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}};
+  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}, {"track_max_cost", &F.track_max_cost}};
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -188,6 +200,14 @@ void usage() {
          "  The box spans the listed parts (head = nose, eyes and ears; MPI: head and neck), grown by F * its larger side and widened to the\n"
          "  crop's aspect; boxes and crops are computed on the GPU (crops mode of the engine) and equal rtp_crop_people bit for bit.\n"
          "  With --host_preprocess the engine never sees the display image: boxes only.  Under --dry_engine the box files hold no boxes.\n"
+         "  --track [--track_max_cost F (0.0625)] [--track_max_misses N (15)] [--track_min_parts N (3)] follows people across frames: every\n"
+         "  --write_json body gains \"id\":N in front of \"joints\" and every --write_crops box record \"id\":N (0 = not tracked: too few parts,\n"
+         "  or all 128 tracks taken).  A person keeps its id while it is matched to its track: the mean squared displacement of the parts both\n"
+         "  have, over the track's squared diagonal, must be <= F; a track unmatched for more than N frames is dropped.  With ONE real GPU worker\n"
+         "  the association runs on the GPU behind the connect kernels (tracking mode of the engine, frames in submit order).  With --num_gpu N > 1,\n"
+         "  --dry_engine or --host_preprocess the re-orderer, which sees the frames in order, runs the same definition on the host\n"
+         "  (rtp_track_update): the ids are the same.  Frames dropped without --no_frame_drops are simply not seen by the tracker.  Without\n"
+         "  --track every file is what it was.\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
          "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
          "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
@@ -226,6 +246,7 @@ struct Frame {
   std::vector<float> crop_boxes;        // --write_crops: the frame's box records [crop_n][RTP_CROP_BOX_FLOATS] and its crops (HWC BGR; empty
   std::vector<unsigned char> crops;     // for a frame without a display image) (rtp_peek_crops); crop_n < 0: not a --write_crops run
   int crop_n = -1;
+  std::vector<int> track_recs;          // --track: the frame's records [numPeople][RTP_TRACK_REC_INTS] (rtp_peek_tracks, or the re-orderer's rtp_track_update)
   std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
   bool rendered_jpeg = false;
   bool rendered_yuv = false;            // --write_video x.y4m: rendered holds the frame's 4:2:0 planes (rtp_collect_rendered_yuv)
@@ -236,6 +257,9 @@ struct Frame {
   std::string stem;
   std::vector<float> joints;
 };
+
+bool track_on_gpu();
+rtp_track_config track_config();
 
 struct EncodeJob { std::string path; std::vector<unsigned char> bgr; bool jpeg = false; };  // jpeg: bgr already holds the file
 
@@ -612,6 +636,18 @@ void worker(int widx, int device, int* status) {
       }
     }
   }
+  // --track with one real GPU worker: the engine's tracking mode (otherwise the re-orderer tracks on the host)
+  const bool gpu_track = track_on_gpu();
+  if (gpu_track) {
+    const rtp_track_config tc = track_config();
+    if (rtp_set_tracking(e, &tc) != RTP_OK) {
+      fprintf(stderr, "GPU %d: --track: %s\n", device, rtp_last_error(e));
+      *status = 1;
+      G.quit_threads = true;
+      rtp_engine_destroy(e);
+      return;
+    }
+  }
   // --dry_engine: what the engine costs the HOST per frame (the staging copy of rtp_submit_frame, the joints copy of
   // rtp_collect) and when a frame completes (RATE frames/s, at least two frame times after its submit)
   std::vector<unsigned char> dry_staging;
@@ -675,6 +711,14 @@ void worker(int widx, int device, int* status) {
         fr.crops.resize(has_pixels ? (size_t)fr.crop_n * crop_w * crop_h * 3 : 0);
       }
     }
+    int track_n = 0;
+    if (gpu_track) {   // likewise the track records of the oldest frame
+      fr.track_recs.assign((size_t)RTP_MAX_PEOPLE * RTP_TRACK_REC_INTS, 0);
+      if (rtp_peek_tracks(e, &tag, fr.track_recs.data(), &track_n, RTP_MAX_PEOPLE) != RTP_OK) {
+        fprintf(stderr, "GPU %d frame %d: --track: %s\n", device, fr.index, rtp_last_error(e));
+        track_n = 0;
+      }
+    }
     const int rc = dry ? dry_collect(fr, joints.data(), &n)
                    : !want_render ? rtp_collect(e, &tag, joints.data(), &n)
                    : gpu_yuv ? rtp_collect_rendered_yuv(e, &tag, joints.data(), &n, fr.rendered.data(), fr.rendered.size())
@@ -707,6 +751,10 @@ void worker(int widx, int device, int* status) {
       fr.rendered_yuv = true;
     }
     fr.numPeople = n;
+    if (gpu_track) {   // (a frame whose collect failed has no people; one whose peek failed has untracked people)
+      for (int k = track_n; k < n; ++k) { int* r = &fr.track_recs[(size_t)k * RTP_TRACK_REC_INTS]; r[0] = 0; r[1] = -1; r[2] = 0; r[3] = 0; }
+      fr.track_recs.resize((size_t)n * RTP_TRACK_REC_INTS);
+    }
     fr.joints.assign(joints.begin(), joints.begin() + (size_t)n * num_parts * 3);
     fr.gpu_computed_time = wall();
     fr.data.clear();
@@ -777,6 +825,18 @@ void worker(int widx, int device, int* status) {
   if (e) rtp_engine_destroy(e);
 }
 
+// ---- --track ---------------------------------------------------------------------------------------------
+// One real GPU worker tracks on the GPU (the engine sees its frames in submit order); every other arrangement tracks in the re-orderer
+bool track_on_gpu() { return F.track && F.dry_engine <= 0 && !F.host_preprocess && F.num_gpu == 1 && rtp_set_tracking && rtp_peek_tracks; }
+rtp_track_config track_config() {
+  rtp_track_config tc;
+  rtp_track_config_default(&tc);
+  tc.max_cost = (float)F.track_max_cost;
+  tc.max_misses = F.track_max_misses;
+  tc.min_parts = F.track_min_parts;
+  return tc;
+}
+
 // ---- re-orderer (buffer_and_order, rtpose.cpp:1214-1273) ---------------------------------------------
 struct FrameCompare { bool operator()(const Frame& a, const Frame& b) const { return a.index > b.index; } };
 void reorderer(std::atomic<bool>* workers_done) {
@@ -786,7 +846,21 @@ void reorderer(std::atomic<bool>* workers_done) {
     std::lock_guard<std::mutex> l(G.mutex);
     while (!G.dropped_index.empty() && G.dropped_index.top() == frame_waited) { frame_waited++; G.dropped_index.pop(); }
   };
-  auto emit = [&](Frame f) { f.buffer_end_time = wall(); G.output_queue_ordered.push(std::move(f)); };
+  // --track on the host: this thread sees the frames in order, and rtp_track_update is the definition the GPU kernel equals
+  const bool host_track = F.track && !track_on_gpu();
+  const rtp_track_config tc = track_config();
+  std::unique_ptr<rtp_track_state> tstate;
+  auto emit = [&](Frame f) {
+    if (host_track) {
+      if (!tstate) { tstate.reset(new rtp_track_state); rtp_track_state_init(tstate.get(), G.num_parts.load()); }
+      f.track_recs.assign((size_t)std::max(f.numPeople, 1) * RTP_TRACK_REC_INTS, 0);
+      if (rtp_track_update(tstate.get(), &tc, f.joints.data(), f.numPeople, f.track_recs.data()) < 0)
+        for (int k = 0; k < f.numPeople; ++k) f.track_recs[(size_t)k * RTP_TRACK_REC_INTS + 1] = -1;
+      f.track_recs.resize((size_t)f.numPeople * RTP_TRACK_REC_INTS);
+    }
+    f.buffer_end_time = wall();
+    G.output_queue_ordered.push(std::move(f));
+  };
   while (true) {
     Frame fr;
     if (!G.output_queue.try_pop(&fr)) {
@@ -841,7 +915,9 @@ void write_json_file(const Frame& fr, std::vector<char>& buf) {
   char fname[1024];
   if (F.image_dir.empty()) snprintf(fname, sizeof fname, "%s/frame%06d.json", F.write_json.c_str(), fr.video_frame_number);  // :1388
   else snprintf(fname, sizeof fname, "%s/%s.json", F.write_json.c_str(), fr.stem.c_str());                                   // :1390-1393
-  const long n = rtp_format_json(buf.data(), buf.size(), fr.joints.data(), fr.numPeople, G.num_parts.load(), fr.scale);
+  const bool ids = F.track && fr.track_recs.size() == (size_t)fr.numPeople * RTP_TRACK_REC_INTS;
+  const long n = ids ? rtp_format_json_tracked(buf.data(), buf.size(), fr.joints.data(), fr.numPeople, G.num_parts.load(), fr.scale, fr.track_recs.data())
+                     : rtp_format_json(buf.data(), buf.size(), fr.joints.data(), fr.numPeople, G.num_parts.load(), fr.scale);
   if (n >= 0) {
     FILE* f = fopen(fname, "wb");
     if (f) { fwrite(buf.data(), 1, (size_t)n, f); fclose(f); }
@@ -931,7 +1007,9 @@ void writer(std::atomic<bool>* reorder_done) {
         fprintf(f, "{\n\"frame\":%d,\n\"crop_w\":%d,\n\"crop_h\":%d,\n\"boxes\":[", fr.video_frame_number, cw, ch);
         for (int k = 0; k < fr.crop_n; ++k) {
           const float* b = &fr.crop_boxes[(size_t)k * RTP_CROP_BOX_FLOATS];
-          fprintf(f, "%s\n{\"person\":%d,\"left\":%.9g,\"top\":%.9g,\"width\":%.9g,\"height\":%.9g,\"parts\":%d,\"valid\":%d}", k ? "," : "", k, (double)b[0], (double)b[1],
+          fprintf(f, "%s\n{\"person\":%d,", k ? "," : "", k);
+          if (F.track) fprintf(f, "\"id\":%d,", (size_t)k * RTP_TRACK_REC_INTS < fr.track_recs.size() ? fr.track_recs[(size_t)k * RTP_TRACK_REC_INTS] : 0);
+          fprintf(f, "\"left\":%.9g,\"top\":%.9g,\"width\":%.9g,\"height\":%.9g,\"parts\":%d,\"valid\":%d}", (double)b[0], (double)b[1],
                   (double)b[2], (double)b[3], (int)b[4], (int)b[5]);
         }
         fprintf(f, "\n]\n}\n");
@@ -1031,6 +1109,10 @@ int main(int argc, char** argv) {
     if (!d->empty() && !mkdir_p(*d)) { fprintf(stderr, "Could not write to or create directory %s\n", d->c_str()); return 1; }
   if (F.heatmap_channels != "parts" && F.heatmap_channels != "bkg" && F.heatmap_channels != "parts+bkg" && F.heatmap_channels != "pafs" && F.heatmap_channels != "all") {
     fprintf(stderr, "--heatmap_channels must be parts, bkg, parts+bkg, pafs or all\n");
+    return 1;
+  }
+  if (F.track && (!(F.track_max_cost > 0) || !std::isfinite(F.track_max_cost) || F.track_max_misses < 0 || F.track_min_parts < 1)) {
+    fprintf(stderr, "--track: --track_max_cost must be a finite number > 0, --track_max_misses >= 0, --track_min_parts >= 1\n");
     return 1;
   }
   if (!F.write_crops.empty()) {

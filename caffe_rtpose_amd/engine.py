@@ -5,7 +5,7 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -651,6 +651,91 @@ def crop_people(display_bgr, joints, num_parts, crop_w, crop_h, max_crops=MAX_PE
     return boxes, crops
 
 
+MAX_TRACKS = 128
+TRACK_REC_INTS = 4
+
+
+def track_config(min_score=None, min_parts=None, min_common=None, max_cost=None, max_misses=None):
+    """rtp_track_config: rtp_track_config_default's values (min_score 0, min_parts 3, min_common 2, max_cost 0.0625, max_misses 15),
+    each replaced where an argument is given."""
+    cfg = rtp_track_config()
+    lib.rtp_track_config_default(C.byref(cfg))
+    for name, v, conv in (("min_score", min_score, float), ("min_parts", min_parts, int), ("min_common", min_common, int), ("max_cost", max_cost, float),
+                          ("max_misses", max_misses, int)):
+        if v is not None:
+            setattr(cfg, name, conv(v))
+    return cfg
+
+
+class TrackState:
+    """rtp_track_state, the track table as plain data: num_parts, next_id, frames and numpy views id / hits / misses [128] and
+    joints [128][70][3] onto the structure itself (writes through them change it).  == compares every byte's worth: the integers,
+    and the joints bit for bit."""
+
+    def __init__(self, num_parts=18, c=None):
+        if c is None:
+            c = rtp_track_state()
+            if lib.rtp_track_state_init(C.byref(c), int(num_parts)):
+                raise RtpError(RTP_EINVAL, f"rtp_track_state_init: num_parts {num_parts} outside 1 .. 70")
+        self.c = c
+        self.id = np.ctypeslib.as_array(c.id)
+        self.hits = np.ctypeslib.as_array(c.hits)
+        self.misses = np.ctypeslib.as_array(c.misses)
+        self.joints = np.ctypeslib.as_array(c.joints).reshape(MAX_TRACKS, 70, 3)
+
+    num_parts = property(lambda self: self.c.num_parts)
+    next_id = property(lambda self: self.c.next_id, lambda self, v: setattr(self.c, "next_id", int(v)))
+    frames = property(lambda self: self.c.frames, lambda self, v: setattr(self.c, "frames", int(v)))
+
+    def copy(self):
+        c = rtp_track_state()
+        C.memmove(C.byref(c), C.byref(self.c), C.sizeof(c))
+        return TrackState(c=c)
+
+    def tobytes(self):
+        return C.string_at(C.byref(self.c), C.sizeof(self.c))
+
+    def __eq__(self, other):
+        return isinstance(other, TrackState) and self.tobytes() == other.tobytes()
+
+    def live(self):
+        """{slot: id} of the live tracks"""
+        return {int(t): int(self.id[t]) for t in np.nonzero(self.id)[0]}
+
+
+def track_update(state, joints, num_people=None, cfg=None):
+    """rtp_track_update, the host definition of tracking mode: advances `state` (a TrackState) by one frame of joints
+    [people][state.num_parts][3] and returns the records [n][4] int32 {id, slot, hits, cost bits}.  num_people: the frame's count
+    where it is not the array's (above 96 or negative, as the device may hold it); cfg: a track_config() (None = the defaults)."""
+    cfg = cfg if cfg is not None else track_config()
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, state.num_parts, 3)
+    people = j.shape[0] if num_people is None else int(num_people)
+    n = min(max(people, 0), MAX_PEOPLE)
+    if n > j.shape[0]:
+        raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+    recs = np.zeros((max(n, 1), TRACK_REC_INTS), np.int32)
+    rc = lib.rtp_track_update(C.byref(state.c), C.byref(cfg), _f(j) if j.size else None, people, recs.ctypes.data_as(ip))
+    if rc < 0:
+        raise RtpError(rc, "rtp_track_update: an argument is out of range")
+    assert rc == n
+    return recs[:n].copy()
+
+
+def format_json_tracked(joints, num_parts, frame_scale, recs=None):
+    """rtp_format_json_tracked: the JSON body text (bytes) of joints [people][num_parts][3]; recs [people][4] adds "id" members."""
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, int(num_parts), 3)
+    buf = C.create_string_buffer(256 + j.shape[0] * (64 + 48 * int(num_parts)))
+    r = None
+    if recs is not None:
+        r = np.ascontiguousarray(recs, np.int32).reshape(-1, TRACK_REC_INTS)
+        assert r.shape[0] >= j.shape[0]
+    n = lib.rtp_format_json_tracked(buf, len(buf), _f(j) if j.size else None, j.shape[0], int(num_parts), float(frame_scale),
+                                    r.ctypes.data_as(ip) if r is not None else None)
+    if n < 0:
+        raise RtpError(n, "rtp_format_json_tracked")
+    return buf.raw[:n]
+
+
 def _stream_of(obj, stream):
     """(handle or None, torch default stream?) of the stream a device frame is ordered on.  stream: a torch.cuda.Stream, a raw
     hipStream_t as int, or None = torch's current stream of a tensor's device, else the interface's `stream` entry, else NULL."""
@@ -1031,6 +1116,54 @@ class Engine:
         n = C.c_int()
         self._chk(lib.rtp_peek_crops_device(self.h, C.byref(tag), _f(boxes), C.byref(n), info["max_crops"], C.byref(v), st))
         return tag.value, boxes[: n.value].copy()
+
+    # ---- tracking mode
+    def set_tracking(self, cfg=True, **kw):
+        """rtp_set_tracking: every submitted frame's people are associated with the engine's track table; peek_tracks in front of the
+        frame's collect gives the records.  cfg: a track_config(), True (= track_config(**kw)) or None / False (off: the state is
+        discarded).  Off -> on starts from an empty state; a new cfg while the mode is on keeps it."""
+        if cfg is None or cfg is False:
+            self._chk(lib.rtp_set_tracking(self.h, None))
+            return
+        if cfg is True:
+            cfg = track_config(**kw)
+        self._chk(lib.rtp_set_tracking(self.h, C.byref(cfg)))
+
+    def track_reset(self):
+        """rtp_track_reset: an empty table (next_id 1); idle engine."""
+        self._chk(lib.rtp_track_reset(self.h))
+
+    def track_state(self):
+        """rtp_track_get_state: the engine's table as a TrackState; idle engine."""
+        st = TrackState(self.num_parts)
+        self._chk(lib.rtp_track_get_state(self.h, C.byref(st.c)))
+        return st
+
+    def set_track_state(self, state):
+        """rtp_track_set_state: the engine's table becomes a copy of `state` (a TrackState of the engine's num_parts); idle engine."""
+        self._chk(lib.rtp_track_set_state(self.h, C.byref(state.c)))
+
+    def peek_tracks(self, capacity=MAX_PEOPLE):
+        """rtp_peek_tracks: (tag, records [n][4] int32 {id, slot, hits, cost bits}) of the oldest frame in flight, which stays in
+        flight (follow with a collect)."""
+        recs = np.zeros((max(int(capacity), 1), TRACK_REC_INTS), np.int32)
+        tag, n = C.c_uint64(0), C.c_int(0)
+        self._chk(lib.rtp_peek_tracks(self.h, C.byref(tag), recs.ctypes.data_as(ip), C.byref(n), int(capacity)))
+        return tag.value, recs[: n.value].copy()
+
+    def track_from_joints(self, joints, num_people=None):
+        """rtp_track_from_joints: the async path's kernel on joints [people][num_parts][3] (idle engine); the engine's table advances
+        by one frame.  num_people: what the device is told where it is not the array's count (above 96 or negative, which the kernel
+        clamps).  Returns the records [n][4]."""
+        j = np.ascontiguousarray(joints, np.float32).reshape(-1, self.num_parts, 3)
+        people = j.shape[0] if num_people is None else int(num_people)
+        cap = min(max(people, 0), MAX_PEOPLE)
+        if cap > j.shape[0]:
+            raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+        recs = np.zeros((max(cap, 1), TRACK_REC_INTS), np.int32)
+        n = C.c_int(0)
+        self._chk(lib.rtp_track_from_joints(self.h, _f(j) if j.size else None, people, recs.ctypes.data_as(ip), C.byref(n), cap))
+        return recs[: n.value].copy()
 
     def crops_from_joints(self, display_bgr, joints, pixels=True):
         """rtp_crops_from_joints: (boxes, crops) of the current mode for the given display image and joints [people][num_parts][3]

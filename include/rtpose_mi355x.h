@@ -611,7 +611,8 @@ int rtp_decode_jpeg_device(rtp_engine* e, const unsigned char* jpeg_host, size_t
  * scan (or, on the HOST entropy path, the coefficients) crosses PCIe; the decode kernels run in front of the warp and the call does
  * not wait for the GPU.  Header errors are reported by the call (the code of rtp_decode_image); corrupt entropy-coded data found on
  * the device makes the rtp_collect* of this tag release the frame and return RTP_EIO with a message, and the engine stays usable.
- * *w, *h (may be NULL) = the file's size.  Where the device pre-processing cannot run the file is decoded on the host. */
+ * *w, *h (may be NULL) = the file's size.  Where the device pre-processing cannot run the file is decoded on the host.
+ * In tracking mode (rtp_set_tracking) such a frame has advanced the tracker like any other frame, on the people its chain produced. */
 int rtp_submit_frame_jpeg(rtp_engine* e, const unsigned char* jpeg_host, size_t n, uint64_t tag, float* frame_scale, int* w, int* h);
 
 /* ---- maps mode: a frame's part-confidence maps and PAFs from the async path (maps_export.hip) -------------------------- */
@@ -790,6 +791,110 @@ int rtp_peek_crops_device(rtp_engine* e, uint64_t* tag, float* boxes_host, int* 
  * *num_boxes = n. */
 int rtp_crops_from_joints(rtp_engine* e, const unsigned char* display_bgr_host, const float* joints_host, int num_people,
                           float* boxes_host, int* num_boxes, unsigned char* crops_host, int capacity);
+
+/* ---- tracking mode: stable person ids across frames (track.hip) --------------------------------------------------------- */
+
+/* Person k of one frame and person k of the next are unrelated: the connect kernels order people by how the limb assignment
+ * assembled them.  Tracking mode associates every submitted frame's people with a device-resident table of tracks and hands out one
+ * record per person: a stable id, the table slot, the track's age and the match cost.  Off by default, and then nothing about the
+ * engine changes.  On: each frame's post-processing chain gains ONE kernel on the frame's own stream behind the connect kernels.  It
+ * reads num_people and the joints in device memory (no host synchronisation), updates the table and writes the records, which are
+ * copied to pinned memory with the joints.  The table is one per engine and frames update it in SUBMIT order: frame n's kernel
+ * waits on the device for frame n-1's, whichever streams the two frames run on.  Records line up with rtp_collect's joints and
+ * with crops mode's slots by index k.  rtp_track_update is the one definition of the arithmetic; the kernel's integers and float
+ * bits equal it exactly.
+ *
+ * THE UPDATE, everything float32, every operation rounded on its own (no fused multiply-add), in exactly this order.  P = num_parts.
+ * One update takes n = clamp(num_people, 0, RTP_MAX_PEOPLE) people (a negative device num_people is the connect kernels' RTP_ERANGE
+ * flag and counts as 0).  A part (x, y, score) COUNTS when score > min_score and x and y are finite (a NaN score never counts).
+ *  1. Person k is TRACKABLE when its number of counting parts is >= min_parts.
+ *  2. The cost of (live slot t, trackable person k): walk the parts p = 0 .. P-1 in order; where p counts in both,
+ *       dx = px - tx;  dy = py - ty;  a = dx * dx;  b = dy * dy;  c = a + b;  s = s + c;  m++          (s starts at 0.0f)
+ *     m < min_common: the pair is not comparable.  The track's size is taken over ALL counting parts of the track, each x and y
+ *     first taken as x + 0.0f:  x0 = min x, x1 = max x, y0 = min y, y1 = max y,
+ *       w = x1 - x0;  h = y1 - y0;  ww = w * w;  hh = h * h;  d = fmaxf(ww + hh, 1.0f)
+ *       q = s / (float)m;  cost = q / d
+ *     The pair is a CANDIDATE when cost is finite and cost <= max_cost (an overflow to infinity or a NaN fails this).
+ *  3. Greedy assignment: the candidates in ascending order of (bits of cost + 0.0f as uint32, slot t, person k) — cost is >= 0, so
+ *     bit order is value order — are walked once; a candidate is accepted when neither its slot nor its person has been taken.
+ *     (The repeated global minimum: the result is unique, ties included.)
+ *  4. A matched slot's joints become the person's (all P x 3 floats, a bit copy); hits++, misses = 0.
+ *  5. An unmatched live slot: misses++; misses > max_misses: the slot is freed (id, hits, misses 0, joints zeros) and is available
+ *     in step 6 of the same frame.
+ *  6. Births: the unmatched trackable people, in person order, each take the LOWEST free slot with id = next_id++ (0 is skipped at
+ *     the wrap), hits = 1, misses = 0, joints = the person's.  With no free slot the person stays untracked.
+ *  7. frames++.
+ * THE RECORD of person k, RTP_TRACK_REC_INTS int32: {id, slot, hits, cost bits}.  Matched: the track's id, its slot, its hits
+ * after the update, the bits of the match's cost + 0.0f.  Newborn: {id, slot, 1, 0} (told from a zero-cost match by hits == 1).
+ * Untracked (not trackable, or the table is full): {0, -1, 0, 0}.
+ *
+ * The defaults of rtp_track_config_default (min_score 0, min_parts 3, min_common 2, max_cost 0.0625, max_misses 15) are choices,
+ * not measurements: a max_cost of 0.0625 allows a mean squared joint displacement of 1/16 of the track's squared diagonal. */
+#define RTP_MAX_TRACKS 128
+#define RTP_TRACK_REC_INTS 4
+
+typedef struct rtp_track_config {
+  unsigned int struct_size; /* sizeof(rtp_track_config) */
+  float min_score;          /* >= 0: a part COUNTS when score > min_score and x, y are finite (a NaN score never counts) */
+  int min_parts;            /* >= 1: a person with fewer counting parts is not tracked */
+  int min_common;           /* >= 1: parts that must count in BOTH for a (track, person) pair to be comparable */
+  float max_cost;           /* > 0, finite */
+  int max_misses;           /* >= 0: a track unmatched for MORE than this many consecutive frames is dropped */
+} rtp_track_config;
+
+typedef struct rtp_track_state { /* plain data; the device copy has the same layout */
+  unsigned int struct_size;      /* sizeof(rtp_track_state) */
+  int num_parts;                 /* 1 .. RTP_MAX_NUM_PARTS */
+  unsigned int next_id;          /* starts at 1; wraps past 0 to 1 */
+  unsigned int frames;           /* frames seen since the reset */
+  int id[RTP_MAX_TRACKS];        /* 0 = free slot */
+  int hits[RTP_MAX_TRACKS], misses[RTP_MAX_TRACKS];
+  float joints[RTP_MAX_TRACKS][RTP_MAX_NUM_PARTS][3]; /* the joints of the track's last match; zeros in free slots and beyond num_parts */
+} rtp_track_state;
+
+/* Host only (no engine, no GPU).  rtp_track_config_default: the defaults above.  rtp_track_state_init: an empty table for a model
+ * of num_parts parts (next_id 1); RTP_EINVAL for num_parts outside 1 .. RTP_MAX_NUM_PARTS. */
+int rtp_track_config_default(rtp_track_config* cfg);
+int rtp_track_state_init(rtp_track_state* state, int num_parts);
+
+/* Host only: the definition above, one frame.  joints [num_people][state->num_parts][3] as rtp_collect returns them (NULL is
+ * accepted where no person is read); recs receives n records.  Returns n, or RTP_EINVAL with the state untouched: a NULL state, cfg
+ * or recs, NULL joints with people, a wrong struct_size in either structure, a configuration field out of its range, a
+ * state->num_parts outside 1 .. RTP_MAX_NUM_PARTS. */
+int rtp_track_update(rtp_track_state* state, const rtp_track_config* cfg, const float* joints, int num_people, int* recs);
+
+/* Switches tracking mode on, NULL cfg = off (the state is discarded).  Off -> on starts from an empty state (next_id 1); while the
+ * mode is on, a new cfg keeps the state.  Refused, with the engine unchanged: wrong struct_size or a field out of range
+ * (RTP_EINVAL); frames in flight (RTP_EAGAIN).  Only frames that went through rtp_submit* advance the tracker (and
+ * rtp_track_from_joints): the synchronous taps (rtp_forward_debug, rtp_post_from_lowres, the maps and crops taps, calibration,
+ * rtp_profile_steps) never do.  A frame whose collect returns RTP_EIO (rtp_submit_frame_jpeg: a corrupt scan) or RTP_ERANGE has
+ * advanced the tracker like any other frame: the kernel ran on whatever people the chain produced (none, for RTP_ERANGE).
+ * Under the experiments build's RTP_GRAPH_POST=1 the post-processing chains are launched eagerly while the mode is on. */
+int rtp_set_tracking(rtp_engine* e, const rtp_track_config* cfg);
+
+/* Idle engine only (RTP_EAGAIN with frames in flight); RTP_EINVAL while the mode is off.  reset: an empty state (next_id 1).
+ * get / set: the whole table, e.g. to carry the ids over to another engine; set also refuses (RTP_EINVAL) a wrong struct_size and a
+ * num_parts that is not the engine's. */
+int rtp_track_reset(rtp_engine* e);
+int rtp_track_get_state(rtp_engine* e, rtp_track_state* state);
+int rtp_track_set_state(rtp_engine* e, const rtp_track_state* state);
+
+/* The contract of rtp_peek_crops: blocks until the OLDEST frame in flight is finished and hands out its tag, *num_recs = n and n
+ * records of RTP_TRACK_REC_INTS ints into recs_host; capacity = the records recs_host holds.  The frame STAYS in flight; peeking
+ * twice returns the same records.  Refused: mode off, NULL recs_host or num_recs, a negative capacity (RTP_EINVAL); nothing in
+ * flight (RTP_EAGAIN); capacity < n (RTP_ERANGE, *num_recs = n, nothing else written; the frame stays peekable). */
+int rtp_peek_tracks(rtp_engine* e, uint64_t* tag, int* recs_host, int* num_recs, int capacity);
+
+/* Parity tap (idle engine, context 0): the kernel of the async path on caller data, joints_host [num_people][num_parts][3],
+ * of which n = clamp(num_people, 0, RTP_MAX_PEOPLE) people are read; num_people itself goes to the device as it is.  It ADVANCES the
+ * engine's state by one frame; frames submitted next continue from it.  Writes n records, capacity as in rtp_peek_tracks; returns
+ * RTP_OK and *num_recs = n. */
+int rtp_track_from_joints(rtp_engine* e, const float* joints_host, int num_people, int* recs_host, int* num_recs, int capacity);
+
+/* rtp_format_json's text with "id":N, in front of every body's "joints" (N = recs[k * RTP_TRACK_REC_INTS], 0 = untracked).
+ * recs == NULL: byte for byte rtp_format_json's output. */
+long rtp_format_json_tracked(char* buf, size_t buflen, const float* joints, int num_people, int num_parts, float frame_scale,
+                             const int* recs);
 
 #ifdef __cplusplus
 }
