@@ -137,6 +137,37 @@ class rtp_track_state(C.Structure):
     ]
 
 
+class rtp_smooth_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("min_score", C.c_float),
+        ("min_cutoff", C.c_float),
+        ("beta", C.c_float),
+        ("d_cutoff", C.c_float),
+        ("max_hold", C.c_int),
+        ("apply", C.c_uint),
+    ]
+
+
+class rtp_smooth_cell(C.Structure):
+    _fields_ = [
+        ("owner", C.c_int),
+        ("last", C.c_uint),
+        ("pos", C.c_float * 2),
+        ("vel", C.c_float * 2),
+        ("score", C.c_float),
+    ]
+
+
+class rtp_smooth_state(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("num_parts", C.c_int),
+        ("frames", C.c_uint),
+        ("cell", rtp_smooth_cell * 70 * 128),
+    ]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 vp = C.c_void_p
@@ -270,6 +301,15 @@ SIGNATURES = {
     "rtp_peek_tracks": (C.c_int, [vp, C.POINTER(C.c_uint64), ip, ip, C.c_int]),
     "rtp_track_from_joints": (C.c_int, [vp, fp, C.c_int, ip, ip, C.c_int]),
     "rtp_format_json_tracked": (C.c_long, [C.c_char_p, C.c_size_t, fp, C.c_int, C.c_int, C.c_float, ip]),
+    "rtp_smooth_config_default": (C.c_int, [C.POINTER(rtp_smooth_config)]),
+    "rtp_smooth_state_init": (C.c_int, [C.POINTER(rtp_smooth_state), C.c_int]),
+    "rtp_smooth_update": (C.c_int, [C.POINTER(rtp_smooth_state), C.POINTER(rtp_smooth_config), fp, C.c_int, ip, fp, fp, C.POINTER(C.c_ubyte)]),
+    "rtp_set_smoothing": (C.c_int, [vp, C.POINTER(rtp_smooth_config)]),
+    "rtp_smooth_reset": (C.c_int, [vp]),
+    "rtp_smooth_get_state": (C.c_int, [vp, C.POINTER(rtp_smooth_state)]),
+    "rtp_smooth_set_state": (C.c_int, [vp, C.POINTER(rtp_smooth_state)]),
+    "rtp_peek_smoothed": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, fp, C.POINTER(C.c_ubyte), ip, C.c_int]),
+    "rtp_smooth_from_joints": (C.c_int, [vp, fp, C.c_int, ip, fp, fp, C.POINTER(C.c_ubyte), ip, C.c_int]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

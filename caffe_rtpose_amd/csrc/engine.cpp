@@ -605,12 +605,12 @@ int render_buffers(rtp_engine* e, RenderOut& r, bool host) {
   return RTP_OK;
 }
 // render() of rtpose.cpp:270-299 on the slot's stream: `src` -> render.dev, the pose overlay of the slot's joints (part_to_show 0;
-// renderFunctions.cu) or a --part_to_show view of its net-resolution maps
-int render_launch(rtp_engine* e, Slot& sl, const unsigned char* src, int part_to_show, int googly) {
+// renderFunctions.cu; poses: the joints to draw where they are not the slot's) or a --part_to_show view of its net-resolution maps
+int render_launch(rtp_engine* e, Slot& sl, const unsigned char* src, int part_to_show, int googly, const float* poses = nullptr) {
   if (part_to_show == 0) {
     RenderParams rp;
     rp.src = src; rp.dst = sl.render.dev; rp.w = e->cfg.disp_w; rp.h = e->cfg.disp_h;
-    rp.poses = sl.joints; rp.num_people = sl.num_people; rp.tab = sl.render.tab;
+    rp.poses = poses ? poses : sl.joints; rp.num_people = sl.num_people; rp.tab = sl.render.tab;
     rp.model = e->plan.model; rp.googly = googly; rp.max_people = RTP_MAX_PEOPLE;
     HIPCHK(e, launch_render(rp, sl.stream));
   } else {
@@ -644,6 +644,7 @@ int frame_outputs_ensure(rtp_engine* e, Ctx& cx, int nframes) {
   if (e->maps_on && (rc = maps_ensure(e, cx, nframes))) return rc;
   if (e->crops_on && (rc = crops_ensure(e, cx, nframes))) return rc;
   if (e->track_on && (rc = track_ensure(e, cx, nframes))) return rc;
+  if (e->smooth_on && (rc = smooth_ensure(e, cx, nframes))) return rc;
   return RTP_OK;
 }
 
@@ -653,9 +654,14 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
   int rc;
   Slot& sl = cx.slot[j];
   RenderOut& r = sl.render;
-  if (e->cfg.render && sl.has_disp) {
+  // Smoothing mode (engine_smooth.cpp) runs behind the tracker, on the frames the tracker runs on.  With RTP_SMOOTH_RENDER / RTP_SMOOTH_CROPS
+  // the pose overlay / crops mode's kernel move behind the smooth kernel and read its joints_s; otherwise every stage is where it was.
+  const bool smooth = e->smooth_on && e->track_on && sl.busy;
+  const bool late_render = smooth && (e->smooth_cfg.apply & RTP_SMOOTH_RENDER) && e->cfg.render == 1;
+  const bool late_crops = smooth && (e->smooth_cfg.apply & RTP_SMOOTH_CROPS) && e->crops_on;
+  auto render_stage = [&](const float* poses) -> int {
     if (e->cfg.render > 1 && !materialized && (rc = run_resize(e, cx, j))) return rc;
-    if ((rc = render_launch(e, sl, sl.disp_cur, e->cfg.render - 1, 0))) return rc;
+    if ((rc = render_launch(e, sl, sl.disp_cur, e->cfg.render - 1, 0, poses))) return rc;
     if (e->yuv_mode) {  // rtp_set_render_yuv: only the planes cross PCIe
       if ((rc = yuv_out_launch(e, cx, j))) return rc;
     } else if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
@@ -664,14 +670,20 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
     } else {
       HIPCHK(e, hipMemcpyAsync(r.host, r.dev, (size_t)e->cfg.disp_w * e->cfg.disp_h * 3, hipMemcpyDeviceToHost, sl.stream));
     }
-  }
+    return RTP_OK;
+  };
+  const bool render = e->cfg.render && sl.has_disp;
+  if (render && !late_render && (rc = render_stage(nullptr))) return rc;
   if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // the frame's maps -> its pinned buffer (engine_maps.cpp)
-  if (e->crops_on && (rc = crops_launch(e, cx, j))) return rc;   // the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
+  if (e->crops_on && !late_crops && (rc = crops_launch(e, cx, j))) return rc;   // the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
   // the frame's people against the engine's track table (engine_track.cpp).  Only a frame in flight (rtp_submit*) advances the tracker:
   // the synchronous taps, calibration and the profiling passes run this chain on an idle engine, whose slots are not busy.  The kernels
   // of consecutive frames are chained in LAUNCH order, which is submit order: batches are launched in the order they were filled and
   // launch_batch_body walks a batch's slots in slot order.
-  if (e->track_on && sl.busy && (rc = track_launch(e, cx, j))) return rc;
+  if (e->track_on && sl.busy && (rc = track_launch(e, cx, j, smooth))) return rc;
+  if (smooth && (rc = smooth_launch(e, cx, j))) return rc;   // the frame's people through the filter table, and the chain's event
+  if (render && late_render && (rc = render_stage(sl.smooth.joints_dev))) return rc;
+  if (late_crops && (rc = crops_launch(e, cx, j, sl.smooth.joints_dev))) return rc;
   return RTP_OK;
 }
 
@@ -1110,6 +1122,7 @@ void free_ctx(Ctx& cx) {
     sl.maps.free();
     sl.crops.free();
     sl.track.free();
+    sl.smooth.free();
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
     for (int i = 0; i < 5; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
@@ -1860,6 +1873,7 @@ void rtp_engine_destroy(rtp_engine* e) {
   (void)hipSetDevice(e->cfg.device_id);
   for (auto& c : e->ctx) free_ctx(c);
   track_free(e);
+  smooth_free(e);
   if (e->dweights) (void)hipFree(e->dweights);
   if (e->dchmap) (void)hipFree(e->dchmap);
   for (hipEvent_t ev : e->tev) if (ev) (void)hipEventDestroy(ev);

@@ -11,14 +11,14 @@ namespace {
 size_t crop_bytes(const rtp_engine* e) { return (size_t)e->crops_cfg.crop_w * e->crops_cfg.crop_h * 3; }
 size_t boxes_bytes(const rtp_engine* e) { return (size_t)e->crops_cfg.max_crops * RTP_CROP_BOX_FLOATS * sizeof(float); }
 
-// frame sj's boxes -> boxes (or nullptr), its crops -> dst (or nullptr: boxes only) on `stream`
-int crops_enqueue(rtp_engine* e, Ctx& cx, int sj, float* boxes, unsigned char* dst, long crop_stride, hipStream_t stream) {
+// frame sj's boxes -> boxes (or nullptr), its crops -> dst (or nullptr: boxes only) on `stream`, from the joints `poses`
+int crops_enqueue(rtp_engine* e, Ctx& cx, int sj, const float* poses, float* boxes, unsigned char* dst, long crop_stride, hipStream_t stream) {
   Slot& sl = cx.slot[sj];
   const rtp_crops_config& c = e->crops_cfg;
   CropsParams p;
   memset(&p, 0, sizeof p);
   p.src = dst ? sl.disp_cur : nullptr; p.w = e->cfg.disp_w; p.h = e->cfg.disp_h;
-  p.joints = sl.joints; p.num_people = sl.num_people;
+  p.joints = poses; p.num_people = sl.num_people;
   p.boxes = boxes; p.dst = p.src ? dst : nullptr; p.crop_stride = crop_stride;
   p.num_parts = e->plan.num_parts; p.nlist = (int)e->crops_list.size(); p.min_parts = c.min_parts;
   p.crop_w = c.crop_w; p.crop_h = c.crop_h; p.max_crops = c.max_crops; p.layout = c.layout;
@@ -98,11 +98,12 @@ int crops_ensure(rtp_engine* e, Ctx& cx, int nframes) {
 
 // frame_outputs_launch: frame sj's boxes and crops -> the slot's buffers -> pinned memory, on the frame's own stream behind the connect
 // kernels and in front of the frame's last event.  A frame without a display image gets boxes only.
-int crops_launch(rtp_engine* e, Ctx& cx, int sj) {
+int crops_launch(rtp_engine* e, Ctx& cx, int sj, const float* poses) {
   Slot& sl = cx.slot[sj];
   sl.crops.pixels = sl.has_disp && sl.disp_cur;
+  sl.crops.poses = poses ? poses : sl.joints;
   int rc;
-  if ((rc = crops_enqueue(e, cx, sj, sl.crops.boxes_dev, sl.crops.pixels ? sl.crops.dst : nullptr, (long)crop_bytes(e), sl.stream))) return rc;
+  if ((rc = crops_enqueue(e, cx, sj, sl.crops.poses, sl.crops.boxes_dev, sl.crops.pixels ? sl.crops.dst : nullptr, (long)crop_bytes(e), sl.stream))) return rc;
   HIPCHK(e, hipMemcpyAsync(sl.crops.boxes_host, sl.crops.boxes_dev, boxes_bytes(e), hipMemcpyDeviceToHost, sl.stream));
   if (sl.crops.pixels && !e->crops_direct)
     HIPCHK(e, hipMemcpyAsync(sl.crops.host, sl.crops.dev, crop_bytes(e) * e->crops_cfg.max_crops, hipMemcpyDeviceToHost, sl.stream));
@@ -166,14 +167,14 @@ extern "C" int rtp_internal_crops_time(rtp_engine* e, const unsigned char* displ
   hipEvent_t ev[2];
   HIPCHK(e, hipEventCreate(&ev[0]));
   HIPCHK(e, hipEventCreate(&ev[1]));
-  for (int i = 0; i < 3 && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.crops.boxes_dev, sl.crops.dst, (long)crop_bytes(e), sl.stream);   // warm-up
+  for (int i = 0; i < 3 && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.joints, sl.crops.boxes_dev, sl.crops.dst, (long)crop_bytes(e), sl.stream);   // warm-up
   // a wave that waits 4 ms holds the stream while the train is enqueued, so that the event pair brackets device work only
   unsigned long long* hold = nullptr;
   hipError_t s = hipMalloc((void**)&hold, 2 * sizeof(unsigned long long));
   if (s == hipSuccess) s = hipStreamSynchronize(sl.stream);
   if (s == hipSuccess) s = launch_queue_wait(400000, hold, sl.stream);
   if (s == hipSuccess) s = hipEventRecord(ev[0], sl.stream);
-  for (int i = 0; i < launches && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.crops.boxes_dev, sl.crops.dst, (long)crop_bytes(e), sl.stream);
+  for (int i = 0; i < launches && !rc; ++i) rc = crops_enqueue(e, cx, 0, sl.joints, sl.crops.boxes_dev, sl.crops.dst, (long)crop_bytes(e), sl.stream);
   if (s == hipSuccess) s = hipEventRecord(ev[1], sl.stream);
   if (s == hipSuccess) s = hipEventSynchronize(ev[1]);
   float ms = 0.f;
@@ -248,7 +249,7 @@ int rtp_peek_crops(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_box
   return RTP_OK;
 }
 
-// The kernel runs again, from the frame's display image and joints (complete, and untouched until the slot's next frame is staged)
+// The kernel runs again, from the frame's display image and the joints its chain cropped from (complete, and untouched until the slot's next frame is staged)
 // into the caller's view, on the caller's stream (NULL: on the frame's own stream, waited for here).
 int rtp_peek_crops_device(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_boxes, int capacity, const rtp_crops_view* out_dev, void* stream) {
   static const char* fn = "rtp_peek_crops_device";
@@ -267,7 +268,7 @@ int rtp_peek_crops_device(rtp_engine* e, uint64_t* tag, float* boxes_host, int* 
   if (!sl.crops.pixels) return fail(e, RTP_EINVAL, "%s: the frame has no display image (it was submitted as a net input): rtp_peek_crops gives its boxes", fn);
   if ((rc = frame_boxes(e, fn, sl, capacity, num_boxes))) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : sl.stream;
-  if ((rc = crops_enqueue(e, cx, sj, nullptr, (unsigned char*)out_dev->data, out_dev->crop_stride, st))) return rc;
+  if ((rc = crops_enqueue(e, cx, sj, sl.crops.poses ? sl.crops.poses : sl.joints, nullptr, (unsigned char*)out_dev->data, out_dev->crop_stride, st))) return rc;
   if ((rc = fence_arm(e, sl.crops.fence, st, !stream))) return rc;
   memcpy(boxes_host, sl.crops.boxes_host, (size_t)*num_boxes * RTP_CROP_BOX_FLOATS * sizeof(float));
   if (tag) *tag = sl.tag;

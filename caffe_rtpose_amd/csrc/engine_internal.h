@@ -1,4 +1,4 @@
-// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_calib.cpp) share: the frame slot, the batch context and
+// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_smooth.cpp, engine_calib.cpp) share: the frame slot, the batch context and
 // rtp_engine itself, the error / lock macros, and the declarations of every helper one of those files defines and another one calls.
 // Internal: only the engine's own files include it (it opens namespace rtp for them); nothing here is part of the library's ABI.
 #pragma once
@@ -40,6 +40,7 @@ size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64
 // host_util.cpp
 extern "C" const char* rtp_internal_crops_check(const rtp_crops_config* c, int model_parts);
 extern "C" const char* rtp_internal_track_check(const rtp_track_config* c);
+extern "C" const char* rtp_internal_smooth_check(const rtp_smooth_config* c);
 extern "C" int rtp_internal_yuv_fields(const rtp_yuv_view* v, char* msg, size_t msg_len, long hi[3]);
 extern "C" int rtp_internal_jpeg_geom(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, rtp::JpegGeom* g);
 
@@ -120,6 +121,7 @@ struct CropsOut {
   float *boxes_dev = nullptr, *boxes_host = nullptr;
   unsigned char *dev = nullptr, *host = nullptr, *dst = nullptr;
   bool pixels = false;
+  const float* poses = nullptr;   // the joints the chain's kernel took this frame's boxes and crops from: the slot's, or smooth.joints_dev (RTP_SMOOTH_CROPS)
   ExportFence fence;
   void free();   // the buffers (engine_crops.cpp); the fence stays
 };
@@ -130,6 +132,14 @@ struct TrackOut {
   int *recs_dev = nullptr, *recs_host = nullptr;
   hipEvent_t ev = nullptr;
   void free();   // (engine_track.cpp)
+};
+
+// rtp_set_smoothing: the frame's filtered joints [96][P][3], velocities [96][P][2] and flags [96][P], and their pinned copy, one block
+// in that order
+struct SmoothOut {
+  float *joints_dev = nullptr, *vel_dev = nullptr;
+  unsigned char *flags_dev = nullptr, *host = nullptr;
+  void free();   // (engine_smooth.cpp)
 };
 
 // One frame's post-processing state (a batch context carries batch_frames of them)
@@ -178,6 +188,7 @@ struct Slot {
   MapsOut maps;
   CropsOut crops;
   TrackOut track;
+  SmoothOut smooth;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -280,6 +291,12 @@ struct rtp_engine {
   TrackTable* track_dev = nullptr;
   hipEvent_t track_prev = nullptr;
   hipStream_t track_prev_stream = nullptr;
+  // rtp_set_smoothing (engine_smooth.cpp): smoothing mode on (only while track_on), its configuration and the device-resident filter
+  // table (rtp_smooth_state's layout); its kernels are ordered by the tracker's chain of events
+  bool smooth_on = false;
+  rtp_smooth_config smooth_cfg = {};
+  SmoothTable* smooth_dev = nullptr;
+  int smooth_variant = RTP_SMOOTH_DEFAULT;   // kernels.h RTP_SMOOTH_*: the workgroup's size (rtp_internal_smooth_variant; tools/bench_smooth.py times both)
   int track_variant = RTP_TRACK_DEFAULT;   // kernels.h RTP_TRACK_*: the assignment's form (rtp_internal_track_variant; tools/bench_track.py times all)
   // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
   JpegBufs jenc;
@@ -415,13 +432,18 @@ int maps_launch(rtp_engine* e, Ctx& cx, int sj);
 
 // engine_crops.cpp
 int crops_ensure(rtp_engine* e, Ctx& cx, int nframes);
-int crops_launch(rtp_engine* e, Ctx& cx, int sj);
+int crops_launch(rtp_engine* e, Ctx& cx, int sj, const float* poses = nullptr);   // poses: the joints to crop from (nullptr: the slot's)
 
 // engine_track.cpp
 int track_ensure(rtp_engine* e, Ctx& cx, int nframes);
-int track_launch(rtp_engine* e, Ctx& cx, int sj);
+int track_launch(rtp_engine* e, Ctx& cx, int sj, bool smooth_follows = false);   // smooth_follows: smooth_launch records the chain's event
 void track_forget_chain(rtp_engine* e);   // the slots' events are gone or complete: the next track kernel waits on nothing
 void track_free(rtp_engine* e);
+
+// engine_smooth.cpp
+int smooth_ensure(rtp_engine* e, Ctx& cx, int nframes);
+int smooth_launch(rtp_engine* e, Ctx& cx, int sj);   // behind track_launch(.., true) on the same stream
+void smooth_free(rtp_engine* e);
 
 }  // namespace eng
 }  // namespace rtp

@@ -8,6 +8,10 @@
 // launch_batch_body walks a batch's slots in slot order, so LAUNCH order is SUBMIT order, and the chain of events built at launch
 // time is the chain of frames.  Whoever changes either order has to keep this one.  The first frame after a reset, and after every
 // entry that synchronises with the device on an idle engine, waits on nothing.
+// Smoothing mode (engine_smooth.cpp) has a table of its own with the same rule.  While it is on, a frame's smooth kernel follows its
+// track kernel on the same stream, and the event (track_prev) is recorded behind the SMOOTH kernel instead: frame n's track kernel
+// then waits for both of frame n-1's kernels, and this one chain of events orders both tables.  With smoothing off the event is
+// recorded behind the track kernel.
 #include "engine_internal.h"
 
 static_assert(sizeof(TrackTable) == sizeof(rtp_track_state), "TrackTable is rtp_track_state's layout");
@@ -96,14 +100,16 @@ int track_ensure(rtp_engine* e, Ctx& cx, int nframes) {
 
 // frame_outputs_launch: frame sj's association on the frame's own stream behind the connect kernels, behind the previous frame's
 // association wherever that ran (ORDERING above), and its records -> pinned memory in front of the frame's last event
-int track_launch(rtp_engine* e, Ctx& cx, int sj) {
+int track_launch(rtp_engine* e, Ctx& cx, int sj, bool smooth_follows) {
   Slot& sl = cx.slot[sj];
   int rc;
   if (e->track_prev && e->track_prev_stream != sl.stream) HIPCHK(e, hipStreamWaitEvent(sl.stream, e->track_prev, 0));
   if ((rc = track_enqueue(e, cx, sj, sl.stream))) return rc;
-  HIPCHK(e, hipEventRecord(sl.track.ev, sl.stream));
-  e->track_prev = sl.track.ev;
-  e->track_prev_stream = sl.stream;
+  if (!smooth_follows) {   // (otherwise smooth_launch records it, behind its kernel)
+    HIPCHK(e, hipEventRecord(sl.track.ev, sl.stream));
+    e->track_prev = sl.track.ev;
+    e->track_prev_stream = sl.stream;
+  }
   HIPCHK(e, hipMemcpyAsync(sl.track.recs_host, sl.track.recs_dev, kRecBytes, hipMemcpyDeviceToHost, sl.stream));
   return RTP_OK;
 }
@@ -181,6 +187,7 @@ int rtp_set_tracking(rtp_engine* e, const rtp_track_config* cfg) {
     if (bad) return fail(e, RTP_EINVAL, "%s: %s (min_score %g, min_parts %d, min_common %d, max_cost %g, max_misses %d)", fn, bad, (double)cfg->min_score, cfg->min_parts,
                          cfg->min_common, (double)cfg->max_cost, cfg->max_misses);
   }
+  if (!cfg && e->smooth_on) return fail(e, RTP_EINVAL, "%s: smoothing mode is on and needs the tracker: rtp_set_smoothing(e, NULL) first", fn);
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "%s: %zu frames in flight (collect them first)", fn, e->fifo.size());
   if (!cfg && !e->track_on) return RTP_OK;
   if (e->ctx.empty()) return fail(e, RTP_EINVAL, "%s: the engine has no plan", fn);

@@ -1,6 +1,6 @@
 // host_util.cpp — the host-only pieces of the path behind the C-ABI: model descriptor tables,
 // default thresholds, process_and_pad_image, the JSON body, the narrow formats of maps mode and the boxes and pixels of
-// crops mode (rtp_crop_people).  No GPU needed.
+// crops mode (rtp_crop_people), tracking mode (rtp_track_update) and smoothing mode (rtp_smooth_update).  No GPU needed.
 #include <algorithm>
 #include <vector>
 #include <charconv>
@@ -432,6 +432,143 @@ int rtp_track_update(rtp_track_state* st, const rtp_track_config* cfg, const flo
     if (t < 0) { r[0] = 0; r[1] = -1; r[2] = 0; r[3] = 0; continue; }
     r[0] = st->id[t]; r[1] = t; r[2] = st->hits[t];
     r[3] = born[k] ? 0 : (int)cost_of[k];
+  }
+  return n;
+}
+
+}  // extern "C"
+
+// ---- smoothing mode: the one definition of its arithmetic (smooth.hip computes the same float bits and bytes on the device) ---------
+
+// What is wrong with the configuration, or nullptr.  The engine's switch reports the same text.
+extern "C" const char* rtp_internal_smooth_check(const rtp_smooth_config* c) {
+  if (!c) return "NULL rtp_smooth_config";
+  if (c->struct_size != sizeof(rtp_smooth_config)) return "rtp_smooth_config.struct_size is not this library's sizeof(rtp_smooth_config)";
+  if (!(c->min_score >= 0.f) || std::isinf(c->min_score)) return "min_score must be a finite number >= 0";
+  if (!(c->min_cutoff > 0.f) || std::isinf(c->min_cutoff)) return "min_cutoff must be a finite number > 0";
+  if (!(c->beta >= 0.f) || std::isinf(c->beta)) return "beta must be a finite number >= 0";
+  if (!(c->d_cutoff > 0.f) || std::isinf(c->d_cutoff)) return "d_cutoff must be a finite number > 0";
+  if (c->max_hold < 0 || c->max_hold > RTP_SMOOTH_MAX_HOLD) return "max_hold must be 0 .. 1000";
+  if (c->apply & ~(unsigned)(RTP_SMOOTH_RENDER | RTP_SMOOTH_CROPS)) return "apply must be a mask of RTP_SMOOTH_RENDER and RTP_SMOOTH_CROPS";
+  return nullptr;
+}
+
+extern "C" {
+
+int rtp_smooth_config_default(rtp_smooth_config* cfg) {
+  if (!cfg) return RTP_EINVAL;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->struct_size = (unsigned)sizeof *cfg;
+  cfg->min_score = 0.f;
+  cfg->min_cutoff = 1.0f / 30.0f;
+  cfg->beta = 0.01f;
+  cfg->d_cutoff = 1.0f / 30.0f;
+  cfg->max_hold = 5;
+  cfg->apply = 0;
+  return RTP_OK;
+}
+
+int rtp_smooth_state_init(rtp_smooth_state* state, int num_parts) {
+  if (!state || num_parts < 1 || num_parts > RTP_MAX_NUM_PARTS) return RTP_EINVAL;
+  memset(state, 0, sizeof *state);
+  state->struct_size = (unsigned)sizeof *state;
+  state->num_parts = num_parts;
+  return RTP_OK;
+}
+
+int rtp_smooth_update(rtp_smooth_state* st, const rtp_smooth_config* cfg, const float* joints, int num_people, const int* recs, float* joints_s,
+                      float* vel, unsigned char* flags) {
+#pragma clang fp contract(off)
+  if (!st || !joints_s || rtp_internal_smooth_check(cfg)) return RTP_EINVAL;
+  if (st->struct_size != sizeof(rtp_smooth_state) || st->num_parts < 1 || st->num_parts > RTP_MAX_NUM_PARTS) return RTP_EINVAL;
+  const int n = num_people < 0 ? 0 : num_people > RTP_MAX_PEOPLE ? RTP_MAX_PEOPLE : num_people;
+  if (n > 0 && (!joints || !recs)) return RTP_EINVAL;
+  bool taken[RTP_MAX_TRACKS] = {};
+  for (int k = 0; k < n; ++k) {
+    const int* r = recs + (size_t)k * RTP_TRACK_REC_INTS;
+    if (r[0] == 0) continue;
+    if (r[1] < 0 || r[1] >= RTP_MAX_TRACKS || taken[r[1]]) return RTP_EINVAL;
+    taken[r[1]] = true;
+  }
+  const int P = st->num_parts;
+  const float TWO_PI = 6.2831855f;
+  const unsigned max_hold = (unsigned)cfg->max_hold;
+  // 1.
+  st->frames++;
+  if (st->frames == 0) st->frames = 1;
+  const unsigned now = st->frames;
+  for (int k = 0; k < n; ++k) {
+    const int id = recs[(size_t)k * RTP_TRACK_REC_INTS], t = recs[(size_t)k * RTP_TRACK_REC_INTS + 1];
+    for (int p = 0; p < P; ++p) {
+      const size_t i = (size_t)k * P + p;
+      const float* j = joints + i * 3;
+      const float x = j[0], y = j[1], score = j[2];
+      const bool counts = score > cfg->min_score && std::isfinite(x) && std::isfinite(y);
+      float o[3], ov[2] = {0.0f, 0.0f};
+      unsigned char flag = RTP_SMOOTH_FLAG_NONE;
+      memcpy(o, j, sizeof o);
+      if (id == 0) {   // 2.
+        flag = counts ? RTP_SMOOTH_FLAG_START : RTP_SMOOTH_FLAG_NONE;
+      } else {         // 3.
+        rtp_smooth_cell& c = st->cell[t][p];
+        const bool live = c.owner == id && c.last != 0;
+        const unsigned g = now - c.last;
+        bool start = counts && (!live || g - 1u > max_hold);
+        if (counts && !start) {
+          const float dt = (float)g;
+          const float v2[2] = {x, y};
+          float nh[2], ne[2];
+          for (int a2 = 0; a2 < 2; ++a2) {
+            const float v = v2[a2], vh = c.pos[a2], dvh = c.vel[a2];
+            const float d = v - vh;
+            const float dv = d / dt;
+            float rd = TWO_PI * cfg->d_cutoff;
+            rd = rd * dt;
+            const float rd1 = rd + 1.0f;
+            const float ad = rd / rd1;
+            const float t1 = ad * dv;
+            const float ad1 = 1.0f - ad;
+            const float t2 = ad1 * dvh;
+            const float e = t1 + t2;
+            float fc = cfg->beta * fabsf(e);
+            fc = cfg->min_cutoff + fc;
+            float r = TWO_PI * fc;
+            r = r * dt;
+            const float r1 = r + 1.0f;
+            const float a = r / r1;
+            const float u1 = a * v;
+            const float a1 = 1.0f - a;
+            const float u2 = a1 * vh;
+            nh[a2] = u1 + u2;
+            ne[a2] = e;
+          }
+          if (std::isfinite(nh[0]) && std::isfinite(nh[1]) && std::isfinite(ne[0]) && std::isfinite(ne[1])) {
+            c.pos[0] = nh[0]; c.pos[1] = nh[1]; c.vel[0] = ne[0]; c.vel[1] = ne[1]; c.score = score; c.last = now;
+            o[0] = nh[0]; o[1] = nh[1];
+            ov[0] = ne[0]; ov[1] = ne[1];
+            flag = RTP_SMOOTH_FLAG_FILTER;
+          } else {
+            start = true;
+          }
+        }
+        if (start) {
+          c.owner = id; c.last = now; c.pos[0] = x; c.pos[1] = y; c.vel[0] = 0.0f; c.vel[1] = 0.0f; c.score = score;
+          flag = RTP_SMOOTH_FLAG_START;
+        } else if (!counts) {
+          if (live && g <= max_hold) {
+            memcpy(o, c.pos, 2 * sizeof(float));
+            memcpy(o + 2, &c.score, sizeof(float));
+            memcpy(ov, c.vel, sizeof ov);
+            flag = RTP_SMOOTH_FLAG_HELD;
+          } else {
+            flag = RTP_SMOOTH_FLAG_NONE;
+          }
+        }
+      }
+      memcpy(joints_s + i * 3, o, sizeof o);
+      if (vel) memcpy(vel + i * 2, ov, sizeof ov);
+      if (flags) flags[i] = flag;
+    }
   }
   return n;
 }

@@ -430,6 +430,43 @@ enum { RTP_TRACK_ARGMIN_256 = 0, RTP_TRACK_ARGMIN_1024 = 1, RTP_TRACK_SORT_256 =
 #define RTP_TRACK_DEFAULT RTP_TRACK_SORT_1024
 hipError_t launch_track(const TrackParams& p, hipStream_t stream);
 
+// Smoothing mode (smooth.hip, rtp_set_smoothing): the frame's people, read in device memory behind the track kernel with their
+// records, go through a per-(track slot, part) One-Euro filter; the filter table is updated and joints_s, vel and flags are written.
+// Float bits and bytes are rtp_smooth_update's (include/rtpose_mi355x.h spells out the arithmetic).  ONE workgroup per launch that
+// loops over the n * P <= 6720 independent (person, part) items; the one shared value is the table's `frames`, which every thread
+// reads before a barrier and one thread writes behind it.  Launches on one table must be ordered by the caller (the engine chains
+// them with events).  SmoothTable is rtp_smooth_state's layout (engine_smooth.cpp asserts it).
+struct SmoothCell {
+  int owner;
+  unsigned last;
+  float pos[2], vel[2];
+  float score;
+};
+struct SmoothTable {
+  unsigned struct_size;
+  int num_parts;
+  unsigned frames;
+  SmoothCell cell[RTP_TRACK_SLOTS][RTP_TRACK_MAX_PARTS];
+};
+struct SmoothParams {
+  const float* joints;       // [max_people][num_parts][3]
+  const int* num_people;
+  const int* recs;           // [RTP_TRACK_MAX_PEOPLE][4] the frame's track records
+  SmoothTable* table;
+  float* joints_s;           // [RTP_TRACK_MAX_PEOPLE][num_parts][3]   (the first n people of each are written)
+  float* vel;                // [RTP_TRACK_MAX_PEOPLE][num_parts][2]
+  unsigned char* flags;      // [RTP_TRACK_MAX_PEOPLE][num_parts]
+  int num_parts, max_hold;
+  float min_score, min_cutoff, beta, d_cutoff;
+  int variant;               // RTP_SMOOTH_* below: the workgroup's size (same outputs and table in both)
+};
+// Both sizes are built and measured (profiles/r14_smooth.txt, tools/bench_smooth.py): a launch's period for 1 / 8 / 96 tracked people
+// is 2.1 / 2.3 / 7.2 us with 256 threads and 2.2 / 2.3 / 3.8 us with 1024.  1024 is the default: twice as fast on a full frame, within
+// 0.1 us on a small one.
+enum { RTP_SMOOTH_256 = 0, RTP_SMOOTH_1024 = 1, RTP_SMOOTH_VARIANTS = 2 };
+#define RTP_SMOOTH_DEFAULT RTP_SMOOTH_1024
+hipError_t launch_smooth(const SmoothParams& p, hipStream_t stream);
+
 struct NmsParams {
   const float* src;  // resized map [src_planes][H][W]
   float* peaks;      // [num_parts][max_peaks+1][3]  (in/out)

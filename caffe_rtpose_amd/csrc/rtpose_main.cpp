@@ -56,6 +56,9 @@ int rtp_peek_crops(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_box
 // (nor tracking mode: --track then runs rtp_track_update in the re-orderer, as under --dry_engine)
 int rtp_set_tracking(rtp_engine* e, const rtp_track_config* cfg) __attribute__((weak));
 int rtp_peek_tracks(rtp_engine* e, uint64_t* tag, int* recs_host, int* num_recs, int capacity) __attribute__((weak));
+// (nor smoothing mode: --smooth then runs rtp_smooth_update in the re-orderer, as under --dry_engine)
+int rtp_set_smoothing(rtp_engine* e, const rtp_smooth_config* cfg) __attribute__((weak));
+int rtp_peek_smoothed(rtp_engine* e, uint64_t* tag, float* joints_s_host, float* vel_host, unsigned char* flags_host, int* num_people, int capacity) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -103,6 +106,12 @@ struct Flags {
   bool track = false;
   double track_max_cost = 0.0625;
   int track_max_misses = 15, track_min_parts = 3;
+  // --smooth (needs --track): every tracked person's parts through the One-Euro filter, parts that drop out held for --smooth_max_hold
+  // frames.  One real GPU worker: the engine's smoothing mode with both apply flags (the filter runs on the GPU behind the track kernel;
+  // rendered frames and crops show the smoothed people).  Otherwise the re-orderer runs rtp_smooth_update behind rtp_track_update.
+  bool smooth = false;
+  double smooth_min_cutoff = 1.0 / 30.0, smooth_beta = 0.01, smooth_d_cutoff = 1.0 / 30.0;
+  int smooth_max_hold = 5;
   std::string caffemodel = "model/coco/pose_iter_440000.caffemodel", caffeproto = "model/coco/pose_deploy_linevec.prototxt";
   std::string resolution = "1280x720", net_resolution = "656x368", camera_resolution = "1280x720";
   double start_scale = 1, scale_gap = 0.3;
@@ -135,9 +144,10 @@ int parse_flags(int argc, char** argv, Flags& F) {
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
       {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}, {"max_crops", &F.max_crops},
-      {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}};
-  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}, {"track_max_cost", &F.track_max_cost}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track},
+      {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}, {"smooth_max_hold", &F.smooth_max_hold}};
+  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}, {"track_max_cost", &F.track_max_cost},
+      {"smooth_min_cutoff", &F.smooth_min_cutoff}, {"smooth_beta", &F.smooth_beta}, {"smooth_d_cutoff", &F.smooth_d_cutoff}};
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track}, {"smooth", &F.smooth},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -208,6 +218,13 @@ void usage() {
          "  --dry_engine or --host_preprocess the re-orderer, which sees the frames in order, runs the same definition on the host\n"
          "  (rtp_track_update): the ids are the same.  Frames dropped without --no_frame_drops are simply not seen by the tracker.  Without\n"
          "  --track every file is what it was.\n"
+         "  --smooth [--smooth_min_cutoff F (1/30)] [--smooth_beta F (0.01)] [--smooth_d_cutoff F (1/30)] [--smooth_max_hold N (5)] (needs --track)\n"
+         "  filters every tracked person's parts over time (One-Euro filter, cutoffs in cycles per frame, beta per pixel) and holds a part that\n"
+         "  dropped out at its last filtered value for up to N frames: the --write_json bodies then hold the smoothed joints.  With ONE real GPU\n"
+         "  worker the filter runs on the GPU behind the track kernel (smoothing mode of the engine, both apply flags), and --write_crops,\n"
+         "  --write_frames and --write_video show the smoothed people.  With --num_gpu N > 1, --dry_engine or --host_preprocess the re-orderer\n"
+         "  runs the same definition on the host (rtp_smooth_update behind rtp_track_update): the JSON files are the same, frames and crops\n"
+         "  are drawn from the raw joints.  Without --smooth every file is what it was.\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
          "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
          "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
@@ -246,6 +263,7 @@ struct Frame {
   std::vector<float> crop_boxes;        // --write_crops: the frame's box records [crop_n][RTP_CROP_BOX_FLOATS] and its crops (HWC BGR; empty
   std::vector<unsigned char> crops;     // for a frame without a display image) (rtp_peek_crops); crop_n < 0: not a --write_crops run
   int crop_n = -1;
+  std::vector<float> joints_s;          // --smooth: the frame's smoothed joints [numPeople][num_parts][3] (rtp_peek_smoothed, or the re-orderer's rtp_smooth_update)
   std::vector<int> track_recs;          // --track: the frame's records [numPeople][RTP_TRACK_REC_INTS] (rtp_peek_tracks, or the re-orderer's rtp_track_update)
   std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
   bool rendered_jpeg = false;
@@ -260,6 +278,8 @@ struct Frame {
 
 bool track_on_gpu();
 rtp_track_config track_config();
+bool smooth_on_gpu();
+rtp_smooth_config smooth_config();
 
 struct EncodeJob { std::string path; std::vector<unsigned char> bgr; bool jpeg = false; };  // jpeg: bgr already holds the file
 
@@ -648,6 +668,18 @@ void worker(int widx, int device, int* status) {
       return;
     }
   }
+  // --smooth likewise: the engine's smoothing mode, applied to the rendered frames and the crops
+  const bool gpu_smooth = smooth_on_gpu();
+  if (gpu_smooth) {
+    const rtp_smooth_config sc = smooth_config();
+    if (rtp_set_smoothing(e, &sc) != RTP_OK) {
+      fprintf(stderr, "GPU %d: --smooth: %s\n", device, rtp_last_error(e));
+      *status = 1;
+      G.quit_threads = true;
+      rtp_engine_destroy(e);
+      return;
+    }
+  }
   // --dry_engine: what the engine costs the HOST per frame (the staging copy of rtp_submit_frame, the joints copy of
   // rtp_collect) and when a frame completes (RATE frames/s, at least two frame times after its submit)
   std::vector<unsigned char> dry_staging;
@@ -719,6 +751,14 @@ void worker(int widx, int device, int* status) {
         track_n = 0;
       }
     }
+    int smooth_n = -1;
+    if (gpu_smooth) {   // and its smoothed joints
+      fr.joints_s.assign((size_t)RTP_MAX_PEOPLE * num_parts * 3, 0.f);
+      if (rtp_peek_smoothed(e, &tag, fr.joints_s.data(), nullptr, nullptr, &smooth_n, RTP_MAX_PEOPLE) != RTP_OK) {
+        fprintf(stderr, "GPU %d frame %d: --smooth: %s\n", device, fr.index, rtp_last_error(e));
+        smooth_n = -1;
+      }
+    }
     const int rc = dry ? dry_collect(fr, joints.data(), &n)
                    : !want_render ? rtp_collect(e, &tag, joints.data(), &n)
                    : gpu_yuv ? rtp_collect_rendered_yuv(e, &tag, joints.data(), &n, fr.rendered.data(), fr.rendered.size())
@@ -756,6 +796,10 @@ void worker(int widx, int device, int* status) {
       fr.track_recs.resize((size_t)n * RTP_TRACK_REC_INTS);
     }
     fr.joints.assign(joints.begin(), joints.begin() + (size_t)n * num_parts * 3);
+    if (gpu_smooth) {   // (a frame whose peek failed keeps its raw joints)
+      if (smooth_n == n) fr.joints_s.resize((size_t)n * num_parts * 3);
+      else fr.joints_s = fr.joints;
+    }
     fr.gpu_computed_time = wall();
     fr.data.clear();
     fr.data.shrink_to_fit();
@@ -837,6 +881,19 @@ rtp_track_config track_config() {
   return tc;
 }
 
+// --smooth: on the GPU where the tracker is; otherwise in the re-orderer, behind its rtp_track_update
+bool smooth_on_gpu() { return F.smooth && track_on_gpu() && rtp_set_smoothing && rtp_peek_smoothed; }
+rtp_smooth_config smooth_config() {
+  rtp_smooth_config sc;
+  rtp_smooth_config_default(&sc);
+  sc.min_cutoff = (float)F.smooth_min_cutoff;
+  sc.beta = (float)F.smooth_beta;
+  sc.d_cutoff = (float)F.smooth_d_cutoff;
+  sc.max_hold = F.smooth_max_hold;
+  sc.apply = RTP_SMOOTH_RENDER | RTP_SMOOTH_CROPS;
+  return sc;
+}
+
 // ---- re-orderer (buffer_and_order, rtpose.cpp:1214-1273) ---------------------------------------------
 struct FrameCompare { bool operator()(const Frame& a, const Frame& b) const { return a.index > b.index; } };
 void reorderer(std::atomic<bool>* workers_done) {
@@ -850,6 +907,10 @@ void reorderer(std::atomic<bool>* workers_done) {
   const bool host_track = F.track && !track_on_gpu();
   const rtp_track_config tc = track_config();
   std::unique_ptr<rtp_track_state> tstate;
+  // --smooth on the host: behind the tracker, on the records the frame carries by then (the re-orderer's or the GPU's)
+  const bool host_smooth = F.smooth && F.track && !smooth_on_gpu();
+  const rtp_smooth_config sc = smooth_config();
+  std::unique_ptr<rtp_smooth_state> sstate;
   auto emit = [&](Frame f) {
     if (host_track) {
       if (!tstate) { tstate.reset(new rtp_track_state); rtp_track_state_init(tstate.get(), G.num_parts.load()); }
@@ -857,6 +918,12 @@ void reorderer(std::atomic<bool>* workers_done) {
       if (rtp_track_update(tstate.get(), &tc, f.joints.data(), f.numPeople, f.track_recs.data()) < 0)
         for (int k = 0; k < f.numPeople; ++k) f.track_recs[(size_t)k * RTP_TRACK_REC_INTS + 1] = -1;
       f.track_recs.resize((size_t)f.numPeople * RTP_TRACK_REC_INTS);
+    }
+    if (host_smooth && f.track_recs.size() == (size_t)f.numPeople * RTP_TRACK_REC_INTS) {
+      if (!sstate) { sstate.reset(new rtp_smooth_state); rtp_smooth_state_init(sstate.get(), G.num_parts.load()); }
+      f.joints_s.assign(std::max(f.joints.size(), (size_t)1), 0.f);
+      if (rtp_smooth_update(sstate.get(), &sc, f.joints.data(), f.numPeople, f.track_recs.data(), f.joints_s.data(), nullptr, nullptr) < 0) f.joints_s = f.joints;
+      f.joints_s.resize(f.joints.size());
     }
     f.buffer_end_time = wall();
     G.output_queue_ordered.push(std::move(f));
@@ -916,8 +983,9 @@ void write_json_file(const Frame& fr, std::vector<char>& buf) {
   if (F.image_dir.empty()) snprintf(fname, sizeof fname, "%s/frame%06d.json", F.write_json.c_str(), fr.video_frame_number);  // :1388
   else snprintf(fname, sizeof fname, "%s/%s.json", F.write_json.c_str(), fr.stem.c_str());                                   // :1390-1393
   const bool ids = F.track && fr.track_recs.size() == (size_t)fr.numPeople * RTP_TRACK_REC_INTS;
-  const long n = ids ? rtp_format_json_tracked(buf.data(), buf.size(), fr.joints.data(), fr.numPeople, G.num_parts.load(), fr.scale, fr.track_recs.data())
-                     : rtp_format_json(buf.data(), buf.size(), fr.joints.data(), fr.numPeople, G.num_parts.load(), fr.scale);
+  const float* joints = F.smooth && fr.joints_s.size() == fr.joints.size() ? fr.joints_s.data() : fr.joints.data();   // --smooth: the smoothed people
+  const long n = ids ? rtp_format_json_tracked(buf.data(), buf.size(), joints, fr.numPeople, G.num_parts.load(), fr.scale, fr.track_recs.data())
+                     : rtp_format_json(buf.data(), buf.size(), joints, fr.numPeople, G.num_parts.load(), fr.scale);
   if (n >= 0) {
     FILE* f = fopen(fname, "wb");
     if (f) { fwrite(buf.data(), 1, (size_t)n, f); fclose(f); }
@@ -1113,6 +1181,16 @@ int main(int argc, char** argv) {
   }
   if (F.track && (!(F.track_max_cost > 0) || !std::isfinite(F.track_max_cost) || F.track_max_misses < 0 || F.track_min_parts < 1)) {
     fprintf(stderr, "--track: --track_max_cost must be a finite number > 0, --track_max_misses >= 0, --track_min_parts >= 1\n");
+    return 1;
+  }
+  if (F.smooth && !F.track) {
+    fprintf(stderr, "--smooth needs --track (the filter follows tracked people)\n");
+    usage();
+    return 1;
+  }
+  if (F.smooth && (!(F.smooth_min_cutoff > 0) || !std::isfinite(F.smooth_min_cutoff) || !(F.smooth_beta >= 0) || !std::isfinite(F.smooth_beta) || !(F.smooth_d_cutoff > 0) ||
+                   !std::isfinite(F.smooth_d_cutoff) || F.smooth_max_hold < 0 || F.smooth_max_hold > RTP_SMOOTH_MAX_HOLD)) {
+    fprintf(stderr, "--smooth: --smooth_min_cutoff and --smooth_d_cutoff must be finite numbers > 0, --smooth_beta a finite number >= 0, --smooth_max_hold 0 .. %d\n", RTP_SMOOTH_MAX_HOLD);
     return 1;
   }
   if (!F.write_crops.empty()) {

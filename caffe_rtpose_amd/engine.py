@@ -5,7 +5,7 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, rtp_smooth_config, rtp_smooth_state, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -736,6 +736,73 @@ def format_json_tracked(joints, num_parts, frame_scale, recs=None):
     return buf.raw[:n]
 
 
+SMOOTH_RENDER, SMOOTH_CROPS = 1, 2
+_SMOOTH_CELL = np.dtype([("owner", np.int32), ("last", np.uint32), ("pos", np.float32, 2), ("vel", np.float32, 2), ("score", np.float32)])
+
+
+def smooth_config(min_score=None, min_cutoff=None, beta=None, d_cutoff=None, max_hold=None, apply=None):
+    """rtp_smooth_config: rtp_smooth_config_default's values (min_score 0, min_cutoff and d_cutoff 1/30 cycles per frame, beta 0.01,
+    max_hold 5, apply 0), each replaced where an argument is given.  apply: a mask of SMOOTH_RENDER and SMOOTH_CROPS."""
+    cfg = rtp_smooth_config()
+    lib.rtp_smooth_config_default(C.byref(cfg))
+    for name, v, conv in (("min_score", min_score, float), ("min_cutoff", min_cutoff, float), ("beta", beta, float), ("d_cutoff", d_cutoff, float),
+                          ("max_hold", max_hold, int), ("apply", apply, int)):
+        if v is not None:
+            setattr(cfg, name, conv(v))
+    return cfg
+
+
+class SmoothState:
+    """rtp_smooth_state, the filter table as plain data: num_parts, frames and `cell`, a numpy structured view [128][70] with the fields
+    owner, last, pos [2], vel [2] and score onto the structure itself (writes through it change it).  == compares every byte."""
+
+    def __init__(self, num_parts=18, c=None):
+        if c is None:
+            c = rtp_smooth_state()
+            if lib.rtp_smooth_state_init(C.byref(c), int(num_parts)):
+                raise RtpError(RTP_EINVAL, f"rtp_smooth_state_init: num_parts {num_parts} outside 1 .. 70")
+        self.c = c
+        self.cell = np.frombuffer(c, dtype=_SMOOTH_CELL, count=MAX_TRACKS * 70, offset=rtp_smooth_state.cell.offset).reshape(MAX_TRACKS, 70)   # (holds a reference to c)
+
+    num_parts = property(lambda self: self.c.num_parts)
+    frames = property(lambda self: self.c.frames, lambda self, v: setattr(self.c, "frames", int(v)))
+
+    def copy(self):
+        c = rtp_smooth_state()
+        C.memmove(C.byref(c), C.byref(self.c), C.sizeof(c))
+        return SmoothState(c=c)
+
+    def tobytes(self):
+        return C.string_at(C.byref(self.c), C.sizeof(self.c))
+
+    def __eq__(self, other):
+        return isinstance(other, SmoothState) and self.tobytes() == other.tobytes()
+
+
+def smooth_update(state, joints, num_people=None, recs=None, cfg=None):
+    """rtp_smooth_update, the host definition of smoothing mode: advances `state` (a SmoothState) by one frame of joints
+    [people][state.num_parts][3] with their track records [n][4] (track_update's) and returns (joints_s [n][P][3] float32,
+    vel [n][P][2] float32, flags [n][P] uint8).  num_people: the frame's count where it is not the array's (above 96 or negative, as
+    the device may hold it); cfg: a smooth_config() (None = the defaults)."""
+    cfg = cfg if cfg is not None else smooth_config()
+    P = state.num_parts
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, P, 3)
+    people = j.shape[0] if num_people is None else int(num_people)
+    n = min(max(people, 0), MAX_PEOPLE)
+    if n > j.shape[0]:
+        raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+    r = np.ascontiguousarray(recs if recs is not None else np.zeros((0, TRACK_REC_INTS)), np.int32).reshape(-1, TRACK_REC_INTS)
+    if n > r.shape[0]:
+        raise ValueError(f"{n} people, {r.shape[0]} records")
+    js, vel, flags = np.zeros((max(n, 1), P, 3), np.float32), np.zeros((max(n, 1), P, 2), np.float32), np.zeros((max(n, 1), P), np.uint8)
+    rc = lib.rtp_smooth_update(C.byref(state.c), C.byref(cfg), _f(j) if j.size else None, people, r.ctypes.data_as(ip) if r.size else None, _f(js), _f(vel),
+                               flags.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    if rc < 0:
+        raise RtpError(rc, "rtp_smooth_update: an argument is out of range")
+    assert rc == n
+    return js[:n].copy(), vel[:n].copy(), flags[:n].copy()
+
+
 def _stream_of(obj, stream):
     """(handle or None, torch default stream?) of the stream a device frame is ordered on.  stream: a torch.cuda.Stream, a raw
     hipStream_t as int, or None = torch's current stream of a tensor's device, else the interface's `stream` entry, else NULL."""
@@ -1164,6 +1231,59 @@ class Engine:
         n = C.c_int(0)
         self._chk(lib.rtp_track_from_joints(self.h, _f(j) if j.size else None, people, recs.ctypes.data_as(ip), C.byref(n), cap))
         return recs[: n.value].copy()
+
+    # ---- smoothing mode
+    def set_smoothing(self, cfg=True, **kw):
+        """rtp_set_smoothing (tracking mode must be on): every submitted frame's tracked people go through the engine's filter table;
+        peek_smoothed in front of the frame's collect gives the result.  cfg: a smooth_config(), True (= smooth_config(**kw)) or None /
+        False (off: the state is discarded).  Off -> on starts from an empty state; a new cfg while the mode is on keeps it."""
+        if cfg is None or cfg is False:
+            self._chk(lib.rtp_set_smoothing(self.h, None))
+            return
+        if cfg is True:
+            cfg = smooth_config(**kw)
+        self._chk(lib.rtp_set_smoothing(self.h, C.byref(cfg)))
+
+    def smooth_reset(self):
+        """rtp_smooth_reset: an empty filter table; idle engine."""
+        self._chk(lib.rtp_smooth_reset(self.h))
+
+    def smooth_state(self):
+        """rtp_smooth_get_state: the engine's filter table as a SmoothState; idle engine."""
+        st = SmoothState(self.num_parts)
+        self._chk(lib.rtp_smooth_get_state(self.h, C.byref(st.c)))
+        return st
+
+    def set_smooth_state(self, state):
+        """rtp_smooth_set_state: the engine's filter table becomes a copy of `state` (a SmoothState of the engine's num_parts); idle engine."""
+        self._chk(lib.rtp_smooth_set_state(self.h, C.byref(state.c)))
+
+    def peek_smoothed(self, capacity=MAX_PEOPLE):
+        """rtp_peek_smoothed: (tag, joints_s [n][P][3], vel [n][P][2], flags [n][P] uint8) of the oldest frame in flight, which stays in
+        flight (follow with a collect)."""
+        P, cap = self.num_parts, max(int(capacity), 1)
+        js, vel, flags = np.zeros((cap, P, 3), np.float32), np.zeros((cap, P, 2), np.float32), np.zeros((cap, P), np.uint8)
+        tag, n = C.c_uint64(0), C.c_int(0)
+        self._chk(lib.rtp_peek_smoothed(self.h, C.byref(tag), _f(js), _f(vel), flags.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(n), int(capacity)))
+        return tag.value, js[: n.value].copy(), vel[: n.value].copy(), flags[: n.value].copy()
+
+    def smooth_from_joints(self, joints, num_people=None):
+        """rtp_smooth_from_joints: the async path's track and smooth kernels on joints [people][num_parts][3] (idle engine); both of the
+        engine's tables advance by one frame.  num_people: what the device is told where it is not the array's count.  Returns
+        (records [n][4], joints_s, vel, flags)."""
+        P = self.num_parts
+        j = np.ascontiguousarray(joints, np.float32).reshape(-1, P, 3)
+        people = j.shape[0] if num_people is None else int(num_people)
+        cap = min(max(people, 0), MAX_PEOPLE)
+        if cap > j.shape[0]:
+            raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+        m = max(cap, 1)
+        recs = np.zeros((m, TRACK_REC_INTS), np.int32)
+        js, vel, flags = np.zeros((m, P, 3), np.float32), np.zeros((m, P, 2), np.float32), np.zeros((m, P), np.uint8)
+        n = C.c_int(0)
+        self._chk(lib.rtp_smooth_from_joints(self.h, _f(j) if j.size else None, people, recs.ctypes.data_as(ip), _f(js), _f(vel),
+                                             flags.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(n), cap))
+        return recs[: n.value].copy(), js[: n.value].copy(), vel[: n.value].copy(), flags[: n.value].copy()
 
     def crops_from_joints(self, display_bgr, joints, pixels=True):
         """rtp_crops_from_joints: (boxes, crops) of the current mode for the given display image and joints [people][num_parts][3]

@@ -896,6 +896,129 @@ int rtp_track_from_joints(rtp_engine* e, const float* joints_host, int num_peopl
 long rtp_format_json_tracked(char* buf, size_t buflen, const float* joints, int num_people, int num_parts, float frame_scale,
                              const int* recs);
 
+/* ---- smoothing mode: tracked people filtered over time, per joint (smooth.hip) ------------------------------------------ */
+
+/* The joints of rtp_collect are per-frame NMS peaks: on a still person they jitter by a fraction of a pixel to a few pixels, and a
+ * part whose peak falls under the threshold for a frame or two vanishes and comes back.  Smoothing mode, off by default and usable
+ * only while tracking mode is on, filters every tracked person's parts over time with the One-Euro filter (Casiez, Roussel and
+ * Vogel, CHI 2012; time is counted in frames) and holds a part that dropped out for up to max_hold frames.  Each submitted frame's
+ * chain gains ONE more kernel behind the track kernel on the frame's own stream.  It reads num_people, the joints and the frame's
+ * track records in device memory (no host synchronisation), updates a device-resident filter table, one cell per (track slot,
+ * part), and writes three arrays per frame, which are copied to pinned memory in front of the frame's last event:
+ *   joints_s [n][P][3] float32   the filtered (x, y, score);   vel [n][P][2] float32   the filtered velocity in pixels per frame;
+ *   flags [n][P] uint8           RTP_SMOOTH_FLAG_*: what happened to the part.
+ * rtp_collect's joints stay the raw ones, always.  The table is one per engine and is updated in submit order, like the track table:
+ * the event the next frame's chain waits on is recorded behind the smooth kernel.  rtp_smooth_update is the one definition of the
+ * arithmetic; the kernel's float bits and bytes equal it exactly.
+ *
+ * THE UPDATE, everything float32, every operation rounded on its own (no fused multiply-add), in exactly this order; `/` is the
+ * correctly rounded division.  TWO_PI = 6.2831855f (bits 0x40C90FDB).  P = num_parts.  One update takes
+ * n = clamp(num_people, 0, RTP_MAX_PEOPLE) people with their n track records (rtp_track_update's, or rtp_peek_tracks').
+ *  1. frames++ (0 is skipped at the wrap, as next_id is); now = frames.  Gaps are now - last in uint32 arithmetic.
+ *  2. Person k whose record has id == 0 is untracked: joints_s is a bit copy of the person's triples, vel is 0, a part's flag is
+ *     1 where it COUNTS and 0 otherwise.  A part counts under tracking's rule: score > min_score and x, y finite (a NaN score never
+ *     counts).  No cell is touched.
+ *  3. Person k with id != 0 and slot t is handled part by part, independently.  The cell C = (t, p) is LIVE when C.owner == id and
+ *     C.last != 0.  g = now - C.last.
+ *     - The part counts, and C is not live or g - 1 > max_hold: START.  C.owner = id, C.last = now, C.pos = (x, y), C.vel = (0, 0),
+ *       C.score = score.  Output (x, y, score), vel 0, flag 1.
+ *     - The part counts otherwise: FILTER.  dt = (float)g; per coordinate v (x, then y), with vh = C.pos[i], dvh = C.vel[i]:
+ *         d = v - vh;  dv = d / dt
+ *         rd = TWO_PI * d_cutoff;  rd = rd * dt;  ad = rd / (rd + 1.0f)
+ *         t1 = ad * dv;  t2 = (1.0f - ad) * dvh;  e = t1 + t2
+ *         fc = beta * fabsf(e);  fc = min_cutoff + fc
+ *         r = TWO_PI * fc;  r = r * dt;  a = r / (r + 1.0f)
+ *         u1 = a * v;  u2 = (1.0f - a) * vh;  vh' = u1 + u2
+ *       If any of the four results (vh' and e, for x and y) is not finite, the part is STARTed instead.  Otherwise
+ *       C.pos = (xh', yh'), C.vel = (ex, ey), C.score = score, C.last = now.  Output (xh', yh', score), vel (ex, ey), flag 2.
+ *     - The part does not count, C is live and g <= max_hold: HELD.  Output (C.pos, C.score) and C.vel as bit copies, flag 3.  The
+ *       cell is unchanged.
+ *     - The part does not count otherwise: output the person's triple as a bit copy, vel 0, flag 0.  The cell is unchanged.
+ *     The boundary is consistent: a part held for max_hold frames and measured in the next one continues its filter with
+ *     dt = max_hold + 1.
+ * A reborn slot carries a new id, so its old cells are not live: nothing has to be cleared when a track dies.  Cells beyond
+ * num_parts are never touched.
+ *
+ * The defaults of rtp_smooth_config_default (min_score 0, min_cutoff and d_cutoff 1/30 cycles per frame = 1 Hz at 30 frames/s,
+ * beta 0.01 per pixel, max_hold 5, apply 0) are choices, not measurements. */
+#define RTP_SMOOTH_RENDER 1 /* apply: the rendered frame draws joints_s (held parts included: no flicker) */
+#define RTP_SMOOTH_CROPS 2  /* apply: crops mode takes its boxes and crops from joints_s */
+#define RTP_SMOOTH_FLAG_NONE 0
+#define RTP_SMOOTH_FLAG_START 1 /* also: a counting part of an untracked person */
+#define RTP_SMOOTH_FLAG_FILTER 2
+#define RTP_SMOOTH_FLAG_HELD 3
+#define RTP_SMOOTH_MAX_HOLD 1000
+
+typedef struct rtp_smooth_config {
+  unsigned int struct_size; /* sizeof(rtp_smooth_config) */
+  float min_score;          /* >= 0, finite: a part COUNTS when score > min_score and x, y are finite */
+  float min_cutoff;         /* > 0, finite: the cutoff at rest, cycles per frame */
+  float beta;               /* >= 0, finite: how fast the cutoff opens with speed, 1 / pixel */
+  float d_cutoff;           /* > 0, finite: the cutoff of the velocity's own filter, cycles per frame */
+  int max_hold;             /* 0 .. RTP_SMOOTH_MAX_HOLD: frames a part that does not count is held at its last filtered value */
+  unsigned int apply;       /* bit mask of RTP_SMOOTH_RENDER and RTP_SMOOTH_CROPS (the engine's mode only; rtp_smooth_update ignores it) */
+} rtp_smooth_config;
+
+typedef struct rtp_smooth_cell {
+  int owner;         /* a track id, 0 = none */
+  unsigned int last; /* the value of frames at the part's last measurement, 0 = no filter */
+  float pos[2], vel[2];
+  float score;
+} rtp_smooth_cell;
+
+typedef struct rtp_smooth_state { /* plain data; the device copy has the same layout */
+  unsigned int struct_size;       /* sizeof(rtp_smooth_state) */
+  int num_parts;                  /* 1 .. RTP_MAX_NUM_PARTS */
+  unsigned int frames;            /* updates since the reset; wraps past 0 to 1 */
+  rtp_smooth_cell cell[RTP_MAX_TRACKS][RTP_MAX_NUM_PARTS];
+} rtp_smooth_state;
+
+/* Host only (no engine, no GPU).  rtp_smooth_config_default: the defaults above.  rtp_smooth_state_init: an empty table for a model
+ * of num_parts parts; RTP_EINVAL for num_parts outside 1 .. RTP_MAX_NUM_PARTS. */
+int rtp_smooth_config_default(rtp_smooth_config* cfg);
+int rtp_smooth_state_init(rtp_smooth_state* state, int num_parts);
+
+/* Host only: the definition above, one frame.  joints [num_people][state->num_parts][3] as rtp_collect returns them and recs
+ * [n][RTP_TRACK_REC_INTS] (NULL is accepted for either where no person is read); joints_s [n][P][3], vel [n][P][2] and flags [n][P]
+ * receive the outputs; vel and flags may be NULL.  Returns n, or RTP_EINVAL with the state untouched: a NULL state, cfg or joints_s,
+ * NULL joints or recs with people, a wrong struct_size in either structure, a configuration field out of its range, a
+ * state->num_parts outside 1 .. RTP_MAX_NUM_PARTS, a record with id != 0 whose slot is outside 0 .. RTP_MAX_TRACKS - 1, two records
+ * with id != 0 that name the same slot. */
+int rtp_smooth_update(rtp_smooth_state* state, const rtp_smooth_config* cfg, const float* joints, int num_people, const int* recs,
+                      float* joints_s, float* vel, unsigned char* flags);
+
+/* Switches smoothing mode on, NULL cfg = off (the state is discarded).  Off -> on starts from an empty state; while the mode is on,
+ * a new cfg keeps the state.  Refused, with the engine unchanged: tracking mode off, a wrong struct_size or a field out of range
+ * (RTP_EINVAL); frames in flight (RTP_EAGAIN).  While smoothing is on rtp_set_tracking(e, NULL) is refused with RTP_EINVAL: switch
+ * smoothing off first.  rtp_track_reset and rtp_track_set_state leave the smoothing state alone: ids stay unique, so stale cells are
+ * simply not live.  Only frames that went through rtp_submit* advance the filter (and rtp_smooth_from_joints); the synchronous taps,
+ * calibration and rtp_profile_steps never do, and they render and crop from the raw joints.
+ * apply: with RTP_SMOOTH_RENDER the render stage of a submitted frame (cfg.render = 1) runs behind the smooth kernel and draws
+ * joints_s; with RTP_SMOOTH_CROPS crops mode's kernel does and takes boxes and crops from joints_s.  Held parts carry their last
+ * score, so the renderer draws them and the boxes span them.  Record k stays person k.  With apply == 0 the stages run where they
+ * run without the mode. */
+int rtp_set_smoothing(rtp_engine* e, const rtp_smooth_config* cfg);
+
+/* Idle engine only (RTP_EAGAIN with frames in flight); RTP_EINVAL while the mode is off.  reset: an empty state.  get / set: the whole
+ * table; set also refuses (RTP_EINVAL) a wrong struct_size and a num_parts that is not the engine's. */
+int rtp_smooth_reset(rtp_engine* e);
+int rtp_smooth_get_state(rtp_engine* e, rtp_smooth_state* state);
+int rtp_smooth_set_state(rtp_engine* e, const rtp_smooth_state* state);
+
+/* The contract of rtp_peek_tracks: blocks until the OLDEST frame in flight is finished and hands out its tag, *num_people = n and the
+ * three arrays of n people; capacity = the people each array holds; vel_host and flags_host may be NULL.  The frame STAYS in flight;
+ * peeking twice returns the same data.  Refused: mode off, NULL joints_s_host or num_people, a negative capacity (RTP_EINVAL);
+ * nothing in flight (RTP_EAGAIN); capacity < n (RTP_ERANGE, *num_people = n, nothing else written; the frame stays peekable). */
+int rtp_peek_smoothed(rtp_engine* e, uint64_t* tag, float* joints_s_host, float* vel_host, unsigned char* flags_host, int* num_people,
+                      int capacity);
+
+/* Parity tap (idle engine, context 0): the track kernel and then the smooth kernel of the async path on caller data, joints_host
+ * [num_people][num_parts][3], of which n = clamp(num_people, 0, RTP_MAX_PEOPLE) people are read; num_people itself goes to the
+ * device as it is.  It ADVANCES both states by one frame.  Writes n records (recs_host may be NULL) and the three arrays of n people
+ * (vel_host and flags_host may be NULL), capacity as in rtp_peek_smoothed; returns RTP_OK and *num_out = n. */
+int rtp_smooth_from_joints(rtp_engine* e, const float* joints_host, int num_people, int* recs_host, float* joints_s_host,
+                           float* vel_host, unsigned char* flags_host, int* num_out, int capacity);
+
 #ifdef __cplusplus
 }
 #endif
