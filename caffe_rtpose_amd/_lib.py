@@ -168,6 +168,38 @@ class rtp_smooth_state(C.Structure):
     ]
 
 
+class rtp_overlay_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("what", C.c_uint),
+        ("min_score", C.c_float),
+        ("box_margin", C.c_int),
+        ("line_width", C.c_int),
+        ("label_scale", C.c_int),
+        ("trail_len", C.c_int),
+        ("trail_radius", C.c_int),
+        ("alpha", C.c_int),
+    ]
+
+
+class rtp_trail_slot(C.Structure):
+    _fields_ = [
+        ("owner", C.c_int),
+        ("count", C.c_int),
+        ("head", C.c_int),
+        ("pts", C.c_int * 2 * 32),
+    ]
+
+
+class rtp_trail_state(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("num_parts", C.c_int),
+        ("frames", C.c_uint),
+        ("slot", rtp_trail_slot * 128),
+    ]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 vp = C.c_void_p
@@ -310,6 +342,16 @@ SIGNATURES = {
     "rtp_smooth_set_state": (C.c_int, [vp, C.POINTER(rtp_smooth_state)]),
     "rtp_peek_smoothed": (C.c_int, [vp, C.POINTER(C.c_uint64), fp, fp, C.POINTER(C.c_ubyte), ip, C.c_int]),
     "rtp_smooth_from_joints": (C.c_int, [vp, fp, C.c_int, ip, fp, fp, C.POINTER(C.c_ubyte), ip, C.c_int]),
+    "rtp_overlay_config_default": (C.c_int, [C.POINTER(rtp_overlay_config)]),
+    "rtp_trail_state_init": (C.c_int, [C.POINTER(rtp_trail_state), C.c_int]),
+    "rtp_overlay_update": (C.c_int, [C.POINTER(rtp_trail_state), C.POINTER(rtp_overlay_config), fp, C.c_int, ip, ip, ip, C.c_int]),
+    "rtp_overlay_draw": (C.c_int, [ip, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_long]),
+    "rtp_set_track_overlay": (C.c_int, [vp, C.POINTER(rtp_overlay_config)]),
+    "rtp_overlay_reset": (C.c_int, [vp]),
+    "rtp_overlay_get_state": (C.c_int, [vp, C.POINTER(rtp_trail_state)]),
+    "rtp_overlay_set_state": (C.c_int, [vp, C.POINTER(rtp_trail_state)]),
+    "rtp_peek_overlay_items": (C.c_int, [vp, C.POINTER(C.c_uint64), ip, ip, C.c_int]),
+    "rtp_overlay_from_joints": (C.c_int, [vp, fp, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int, ip, ip, ip, C.c_int]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -645,6 +645,7 @@ int frame_outputs_ensure(rtp_engine* e, Ctx& cx, int nframes) {
   if (e->crops_on && (rc = crops_ensure(e, cx, nframes))) return rc;
   if (e->track_on && (rc = track_ensure(e, cx, nframes))) return rc;
   if (e->smooth_on && (rc = smooth_ensure(e, cx, nframes))) return rc;
+  if (e->overlay_on && (rc = overlay_ensure(e, cx, nframes))) return rc;
   return RTP_OK;
 }
 
@@ -659,9 +660,15 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
   const bool smooth = e->smooth_on && e->track_on && sl.busy;
   const bool late_render = smooth && (e->smooth_cfg.apply & RTP_SMOOTH_RENDER) && e->cfg.render == 1;
   const bool late_crops = smooth && (e->smooth_cfg.apply & RTP_SMOOTH_CROPS) && e->crops_on;
-  auto render_stage = [&](const float* poses) -> int {
+  // Overlay mode (engine_overlay.cpp) likewise.  Its update kernel is the last of the frame's table kernels; its draw kernel works in place on
+  // the rendered image, so the stage's EXPORT part (YUV, JPEG or the copy to the host) moves behind it while the DRAW part (the pose overlay
+  // or a --part_to_show view) stays where it is.  With the mode off the launches are, one for one and in order, what they were.
+  const bool overlay = e->overlay_on && e->track_on && sl.busy;
+  auto render_draw = [&](const float* poses) -> int {
     if (e->cfg.render > 1 && !materialized && (rc = run_resize(e, cx, j))) return rc;
-    if ((rc = render_launch(e, sl, sl.disp_cur, e->cfg.render - 1, 0, poses))) return rc;
+    return render_launch(e, sl, sl.disp_cur, e->cfg.render - 1, 0, poses);
+  };
+  auto render_export = [&]() -> int {
     if (e->yuv_mode) {  // rtp_set_render_yuv: only the planes cross PCIe
       if ((rc = yuv_out_launch(e, cx, j))) return rc;
     } else if (e->jpeg_quality) {  // rtp_set_render_jpeg: only the file crosses PCIe, written into the pinned buffer by the encoder itself
@@ -673,16 +680,20 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
     return RTP_OK;
   };
   const bool render = e->cfg.render && sl.has_disp;
-  if (render && !late_render && (rc = render_stage(nullptr))) return rc;
+  if (render && !late_render && ((rc = render_draw(nullptr)) || (!overlay && (rc = render_export())))) return rc;
   if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // the frame's maps -> its pinned buffer (engine_maps.cpp)
   if (e->crops_on && !late_crops && (rc = crops_launch(e, cx, j))) return rc;   // the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
   // the frame's people against the engine's track table (engine_track.cpp).  Only a frame in flight (rtp_submit*) advances the tracker:
   // the synchronous taps, calibration and the profiling passes run this chain on an idle engine, whose slots are not busy.  The kernels
   // of consecutive frames are chained in LAUNCH order, which is submit order: batches are launched in the order they were filled and
   // launch_batch_body walks a batch's slots in slot order.
-  if (e->track_on && sl.busy && (rc = track_launch(e, cx, j, smooth))) return rc;
-  if (smooth && (rc = smooth_launch(e, cx, j))) return rc;   // the frame's people through the filter table, and the chain's event
-  if (render && late_render && (rc = render_stage(sl.smooth.joints_dev))) return rc;
+  if (e->track_on && sl.busy && (rc = track_launch(e, cx, j, smooth || overlay))) return rc;
+  if (smooth && (rc = smooth_launch(e, cx, j, overlay))) return rc;   // the frame's people through the filter table, and the chain's event
+  // the frame's draw list and the trail table, from the people the frame is rendered with, and the chain's event
+  if (overlay && (rc = overlay_update_launch(e, cx, j, late_render ? sl.smooth.joints_dev : sl.joints))) return rc;
+  if (render && late_render && (rc = render_draw(sl.smooth.joints_dev))) return rc;
+  if (render && overlay && (rc = overlay_draw_launch(e, cx, j))) return rc;
+  if (render && (late_render || overlay) && (rc = render_export())) return rc;
   if (late_crops && (rc = crops_launch(e, cx, j, sl.smooth.joints_dev))) return rc;
   return RTP_OK;
 }
@@ -1123,6 +1134,7 @@ void free_ctx(Ctx& cx) {
     sl.crops.free();
     sl.track.free();
     sl.smooth.free();
+    sl.overlay.free();
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
     for (int i = 0; i < 5; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
@@ -1874,6 +1886,7 @@ void rtp_engine_destroy(rtp_engine* e) {
   for (auto& c : e->ctx) free_ctx(c);
   track_free(e);
   smooth_free(e);
+  overlay_free(e);
   if (e->dweights) (void)hipFree(e->dweights);
   if (e->dchmap) (void)hipFree(e->dchmap);
   for (hipEvent_t ev : e->tev) if (ev) (void)hipEventDestroy(ev);

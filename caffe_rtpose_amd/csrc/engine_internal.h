@@ -1,4 +1,4 @@
-// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_smooth.cpp, engine_calib.cpp) share: the frame slot, the batch context and
+// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_smooth.cpp, engine_overlay.cpp, engine_calib.cpp) share: the frame slot, the batch context and
 // rtp_engine itself, the error / lock macros, and the declarations of every helper one of those files defines and another one calls.
 // Internal: only the engine's own files include it (it opens namespace rtp for them); nothing here is part of the library's ABI.
 #pragma once
@@ -41,6 +41,8 @@ size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64
 extern "C" const char* rtp_internal_crops_check(const rtp_crops_config* c, int model_parts);
 extern "C" const char* rtp_internal_track_check(const rtp_track_config* c);
 extern "C" const char* rtp_internal_smooth_check(const rtp_smooth_config* c);
+extern "C" const char* rtp_internal_overlay_check(const rtp_overlay_config* c);
+extern "C" const char* rtp_internal_trail_check(const rtp_trail_state* st);
 extern "C" int rtp_internal_yuv_fields(const rtp_yuv_view* v, char* msg, size_t msg_len, long hi[3]);
 extern "C" int rtp_internal_jpeg_geom(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, rtp::JpegGeom* g);
 
@@ -142,6 +144,13 @@ struct SmoothOut {
   void free();   // (engine_smooth.cpp)
 };
 
+// rtp_set_track_overlay: the frame's draw list and, behind it, its length — [RTP_OVERLAY_MAX_ITEMS][RTP_OVERLAY_ITEM_INTS] ints and one
+// more — and their pinned copy
+struct OverlayOut {
+  int *dev = nullptr, *host = nullptr;
+  void free();   // (engine_overlay.cpp)
+};
+
 // One frame's post-processing state (a batch context carries batch_frames of them)
 struct Slot {
   hipStream_t stream = nullptr;  // resize -> nms -> connect -> D2H of this frame (slot 0 shares the context's stream)
@@ -189,6 +198,7 @@ struct Slot {
   CropsOut crops;
   TrackOut track;
   SmoothOut smooth;
+  OverlayOut overlay;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -297,6 +307,11 @@ struct rtp_engine {
   rtp_smooth_config smooth_cfg = {};
   SmoothTable* smooth_dev = nullptr;
   int smooth_variant = RTP_SMOOTH_DEFAULT;   // kernels.h RTP_SMOOTH_*: the workgroup's size (rtp_internal_smooth_variant; tools/bench_smooth.py times both)
+  // rtp_set_track_overlay (engine_overlay.cpp): overlay mode on (only while track_on and cfg.render), its configuration and the
+  // device-resident trail table (rtp_trail_state's layout); its update kernels are ordered by the tracker's chain of events
+  bool overlay_on = false;
+  rtp_overlay_config overlay_cfg = {};
+  TrailTable* overlay_dev = nullptr;
   int track_variant = RTP_TRACK_DEFAULT;   // kernels.h RTP_TRACK_*: the assignment's form (rtp_internal_track_variant; tools/bench_track.py times all)
   // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
   JpegBufs jenc;
@@ -436,14 +451,21 @@ int crops_launch(rtp_engine* e, Ctx& cx, int sj, const float* poses = nullptr); 
 
 // engine_track.cpp
 int track_ensure(rtp_engine* e, Ctx& cx, int nframes);
-int track_launch(rtp_engine* e, Ctx& cx, int sj, bool smooth_follows = false);   // smooth_follows: smooth_launch records the chain's event
+// table_kernel_follows: a later kernel of the frame's ordered chain (smooth_launch, overlay_update_launch) records the chain's event
+int track_launch(rtp_engine* e, Ctx& cx, int sj, bool table_kernel_follows = false);
 void track_forget_chain(rtp_engine* e);   // the slots' events are gone or complete: the next track kernel waits on nothing
 void track_free(rtp_engine* e);
 
 // engine_smooth.cpp
 int smooth_ensure(rtp_engine* e, Ctx& cx, int nframes);
-int smooth_launch(rtp_engine* e, Ctx& cx, int sj);   // behind track_launch(.., true) on the same stream
+int smooth_launch(rtp_engine* e, Ctx& cx, int sj, bool table_kernel_follows = false);   // behind track_launch(.., true) on the same stream
 void smooth_free(rtp_engine* e);
+
+// engine_overlay.cpp
+int overlay_ensure(rtp_engine* e, Ctx& cx, int nframes);
+int overlay_update_launch(rtp_engine* e, Ctx& cx, int sj, const float* poses);   // behind track_launch / smooth_launch(.., true) on the same stream: the chain's event
+int overlay_draw_launch(rtp_engine* e, Ctx& cx, int sj);   // the frame's list into its rendered image, in place
+void overlay_free(rtp_engine* e);
 
 }  // namespace eng
 }  // namespace rtp

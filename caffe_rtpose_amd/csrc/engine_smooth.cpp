@@ -96,13 +96,15 @@ int smooth_ensure(rtp_engine* e, Ctx& cx, int nframes) {
 
 // frame_outputs_launch: frame sj's filter step on the frame's own stream behind its track kernel (track_launch with smooth_follows),
 // the event the next frame's chain waits on behind it, and the three arrays -> pinned memory in front of the frame's last event
-int smooth_launch(rtp_engine* e, Ctx& cx, int sj) {
+int smooth_launch(rtp_engine* e, Ctx& cx, int sj, bool table_kernel_follows) {
   Slot& sl = cx.slot[sj];
   int rc;
   if ((rc = smooth_enqueue(e, cx, sj, sl.stream))) return rc;
-  HIPCHK(e, hipEventRecord(sl.track.ev, sl.stream));
-  e->track_prev = sl.track.ev;
-  e->track_prev_stream = sl.stream;
+  if (!table_kernel_follows) {   // (otherwise overlay_update_launch records it, behind its kernel)
+    HIPCHK(e, hipEventRecord(sl.track.ev, sl.stream));
+    e->track_prev = sl.track.ev;
+    e->track_prev_stream = sl.stream;
+  }
   const size_t n = items(e);
   unsigned char* h = sl.smooth.host;
   HIPCHK(e, hipMemcpyAsync(h, sl.smooth.joints_dev, n * 3 * sizeof(float), hipMemcpyDeviceToHost, sl.stream));

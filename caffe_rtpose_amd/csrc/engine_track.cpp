@@ -11,7 +11,8 @@
 // Smoothing mode (engine_smooth.cpp) has a table of its own with the same rule.  While it is on, a frame's smooth kernel follows its
 // track kernel on the same stream, and the event (track_prev) is recorded behind the SMOOTH kernel instead: frame n's track kernel
 // then waits for both of frame n-1's kernels, and this one chain of events orders both tables.  With smoothing off the event is
-// recorded behind the track kernel.
+// recorded behind the track kernel.  Overlay mode (engine_overlay.cpp) adds a third table and a third kernel by the same rule: the
+// event is recorded behind the LAST table kernel of the frame's chain (track -> smooth where on -> overlay_update where on).
 #include "engine_internal.h"
 
 static_assert(sizeof(TrackTable) == sizeof(rtp_track_state), "TrackTable is rtp_track_state's layout");
@@ -100,12 +101,12 @@ int track_ensure(rtp_engine* e, Ctx& cx, int nframes) {
 
 // frame_outputs_launch: frame sj's association on the frame's own stream behind the connect kernels, behind the previous frame's
 // association wherever that ran (ORDERING above), and its records -> pinned memory in front of the frame's last event
-int track_launch(rtp_engine* e, Ctx& cx, int sj, bool smooth_follows) {
+int track_launch(rtp_engine* e, Ctx& cx, int sj, bool table_kernel_follows) {
   Slot& sl = cx.slot[sj];
   int rc;
   if (e->track_prev && e->track_prev_stream != sl.stream) HIPCHK(e, hipStreamWaitEvent(sl.stream, e->track_prev, 0));
   if ((rc = track_enqueue(e, cx, sj, sl.stream))) return rc;
-  if (!smooth_follows) {   // (otherwise smooth_launch records it, behind its kernel)
+  if (!table_kernel_follows) {   // (otherwise the last table kernel of the frame's chain records it, behind itself: smooth_launch, overlay_update_launch)
     HIPCHK(e, hipEventRecord(sl.track.ev, sl.stream));
     e->track_prev = sl.track.ev;
     e->track_prev_stream = sl.stream;
@@ -188,6 +189,7 @@ int rtp_set_tracking(rtp_engine* e, const rtp_track_config* cfg) {
                          cfg->min_common, (double)cfg->max_cost, cfg->max_misses);
   }
   if (!cfg && e->smooth_on) return fail(e, RTP_EINVAL, "%s: smoothing mode is on and needs the tracker: rtp_set_smoothing(e, NULL) first", fn);
+  if (!cfg && e->overlay_on) return fail(e, RTP_EINVAL, "%s: overlay mode is on and needs the tracker: rtp_set_track_overlay(e, NULL) first", fn);
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "%s: %zu frames in flight (collect them first)", fn, e->fifo.size());
   if (!cfg && !e->track_on) return RTP_OK;
   if (e->ctx.empty()) return fail(e, RTP_EINVAL, "%s: the engine has no plan", fn);

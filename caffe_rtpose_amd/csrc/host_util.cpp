@@ -1,6 +1,7 @@
 // host_util.cpp — the host-only pieces of the path behind the C-ABI: model descriptor tables,
 // default thresholds, process_and_pad_image, the JSON body, the narrow formats of maps mode and the boxes and pixels of
-// crops mode (rtp_crop_people), tracking mode (rtp_track_update) and smoothing mode (rtp_smooth_update).  No GPU needed.
+// crops mode (rtp_crop_people), tracking mode (rtp_track_update), smoothing mode (rtp_smooth_update) and overlay mode
+// (rtp_overlay_update, rtp_overlay_draw).  No GPU needed.
 #include <algorithm>
 #include <vector>
 #include <charconv>
@@ -571,6 +572,226 @@ int rtp_smooth_update(rtp_smooth_state* st, const rtp_smooth_config* cfg, const 
     }
   }
   return n;
+}
+
+}  // extern "C"
+
+// ---- overlay mode: the one definition of its draw list and its pixels (overlay.hip computes the same integers and bytes on the device)
+
+// What is wrong with the configuration, or nullptr.  The engine's switch reports the same text.
+extern "C" const char* rtp_internal_overlay_check(const rtp_overlay_config* c) {
+  if (!c) return "NULL rtp_overlay_config";
+  if (c->struct_size != sizeof(rtp_overlay_config)) return "rtp_overlay_config.struct_size is not this library's sizeof(rtp_overlay_config)";
+  if (c->what == 0 || (c->what & ~(unsigned)(RTP_OVERLAY_BOX | RTP_OVERLAY_LABEL | RTP_OVERLAY_TRAIL))) return "what must be a non-empty mask of RTP_OVERLAY_BOX, RTP_OVERLAY_LABEL and RTP_OVERLAY_TRAIL";
+  if (!(c->min_score >= 0.f) || std::isinf(c->min_score)) return "min_score must be a finite number >= 0";
+  if (c->box_margin < 0 || c->box_margin > RTP_OVERLAY_MAX_MARGIN) return "box_margin must be 0 .. 1024";
+  if (c->line_width < 1 || c->line_width > 16) return "line_width must be 1 .. 16";
+  if (c->label_scale < 1 || c->label_scale > 8) return "label_scale must be 1 .. 8";
+  if (c->trail_len < 0 || c->trail_len > RTP_TRAIL_MAX) return "trail_len must be 0 .. 32";
+  if (c->trail_radius < 0 || c->trail_radius > 16) return "trail_radius must be 0 .. 16";
+  if (c->alpha < 0 || c->alpha > 256) return "alpha must be 0 .. 256";
+  return nullptr;
+}
+
+// What is wrong with the trail table (but its num_parts), or nullptr
+extern "C" const char* rtp_internal_trail_check(const rtp_trail_state* st) {
+  if (!st) return "NULL rtp_trail_state";
+  if (st->struct_size != sizeof(rtp_trail_state)) return "rtp_trail_state.struct_size is not this library's sizeof(rtp_trail_state)";
+  for (int t = 0; t < RTP_MAX_TRACKS; ++t)
+    if (st->slot[t].count < 0 || st->slot[t].count > RTP_TRAIL_MAX || st->slot[t].head < 0 || st->slot[t].head >= RTP_TRAIL_MAX) return "a ring's count must be 0 .. 32 and its head 0 .. 31";
+  return nullptr;
+}
+
+namespace {
+
+const int kOverlayPalette[16] = RTP_OVERLAY_PALETTE;
+const unsigned char kOverlayFont[10][7] = RTP_OVERLAY_FONT;
+
+int overlay_round(float v) {
+#pragma clang fp contract(off)
+  v = v < -32767.0f ? -32767.0f : v > 32767.0f ? 32767.0f : v;
+  return (int)floorf(v + 0.5f);
+}
+
+// steps 1 and 2 for one person: false = no counting part; box = {x0, y0, x1, y1} with the margin
+bool overlay_box(const float* j, int P, float min_score, int margin, int box[4]) {
+  float fx0 = 0.f, fx1 = 0.f, fy0 = 0.f, fy1 = 0.f;
+  bool any = false;
+  for (int p = 0; p < P; ++p) {
+    const float x = j[3 * p], y = j[3 * p + 1], s = j[3 * p + 2];
+    if (!(s > min_score) || !std::isfinite(x) || !std::isfinite(y)) continue;
+    if (!any) { fx0 = fx1 = x; fy0 = fy1 = y; any = true; continue; }
+    if (x < fx0) fx0 = x;
+    if (x > fx1) fx1 = x;
+    if (y < fy0) fy0 = y;
+    if (y > fy1) fy1 = y;
+  }
+  if (!any) return false;
+  box[0] = overlay_round(fx0) - margin; box[1] = overlay_round(fy0) - margin;
+  box[2] = overlay_round(fx1) + margin; box[3] = overlay_round(fy1) + margin;
+  return true;
+}
+
+int overlay_digits(unsigned v) {
+  int d = 1;
+  while (v >= 10u) { v /= 10u; ++d; }
+  return d;
+}
+
+int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// 0: the item does not cover (px, py); 1: with its colour; 2: with the text colour.  `it` has been clamped (rtp_overlay_draw).
+int overlay_covers(const int* it, const int* digit, int ndig, int px, int py) {
+  const int x0 = it[1], y0 = it[2], x1 = it[3], y1 = it[4], size = it[5];
+  switch (it[0]) {
+    case RTP_OVERLAY_KIND_RECT:
+      if (px < x0 || px > x1 || py < y0 || py > y1) return 0;
+      return px - x0 < size || x1 - px < size || py - y0 < size || y1 - py < size;
+    case RTP_OVERLAY_KIND_CAPSULE: {
+      const long long dx = (long long)x1 - x0, dy = (long long)y1 - y0, ux = (long long)px - x0, uy = (long long)py - y0, r2 = (long long)size * size;
+      const long long L = dx * dx + dy * dy, t = ux * dx + uy * dy;
+      if (L == 0 || t < 0) return ux * ux + uy * uy <= r2;
+      if (t > L) { const long long vx = (long long)px - x1, vy = (long long)py - y1; return vx * vx + vy * vy <= r2; }
+      long long cross = ux * dy - uy * dx;
+      if (cross < 0) cross = -cross;
+      if (cross > (1LL << 31)) cross = 1LL << 31;
+      return cross * cross <= r2 * L;
+    }
+    case RTP_OVERLAY_KIND_LABEL: {
+      if (px < x0 || px > x1 || py < y0 || py > y1) return 0;
+      const int u = (px - x0) / size, v = (py - y0) / size;
+      if (v < 1 || v > 7 || u < 1) return 1;
+      const int c = (u - 1) % 6, i = (u - 1) / 6;
+      if (c >= 5 || i >= ndig) return 1;
+      return (kOverlayFont[digit[i]][v - 1] >> (4 - c)) & 1 ? 2 : 1;
+    }
+    default: return 0;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtp_overlay_config_default(rtp_overlay_config* cfg) {
+  if (!cfg) return RTP_EINVAL;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->struct_size = (unsigned)sizeof *cfg;
+  cfg->what = RTP_OVERLAY_BOX | RTP_OVERLAY_LABEL | RTP_OVERLAY_TRAIL;
+  cfg->min_score = 0.f;
+  cfg->box_margin = 4;
+  cfg->line_width = 2;
+  cfg->label_scale = 1;
+  cfg->trail_len = 16;
+  cfg->trail_radius = 1;
+  cfg->alpha = 192;
+  return RTP_OK;
+}
+
+int rtp_trail_state_init(rtp_trail_state* state, int num_parts) {
+  if (!state || num_parts < 1 || num_parts > RTP_MAX_NUM_PARTS) return RTP_EINVAL;
+  memset(state, 0, sizeof *state);
+  state->struct_size = (unsigned)sizeof *state;
+  state->num_parts = num_parts;
+  return RTP_OK;
+}
+
+int rtp_overlay_update(rtp_trail_state* st, const rtp_overlay_config* cfg, const float* joints, int num_people, const int* recs, int* items, int* num_items,
+                       int capacity) {
+  if (!items || !num_items || capacity < 0 || rtp_internal_overlay_check(cfg) || rtp_internal_trail_check(st)) return RTP_EINVAL;
+  if (st->num_parts < 1 || st->num_parts > RTP_MAX_NUM_PARTS) return RTP_EINVAL;
+  const int n = num_people < 0 ? 0 : num_people > RTP_MAX_PEOPLE ? RTP_MAX_PEOPLE : num_people;
+  if (n > 0 && (!joints || !recs)) return RTP_EINVAL;
+  const int P = st->num_parts, L = cfg->trail_len;
+  bool taken[RTP_MAX_TRACKS] = {};
+  int box[RTP_MAX_PEOPLE][4];
+  bool draws[RTP_MAX_PEOPLE];
+  int total = 0;
+  // the frame's count first: a refused call leaves the state untouched
+  for (int k = 0; k < n; ++k) {
+    const int id = recs[(size_t)k * RTP_TRACK_REC_INTS], t = recs[(size_t)k * RTP_TRACK_REC_INTS + 1];
+    draws[k] = false;
+    if (id == 0) continue;
+    if (t < 0 || t >= RTP_MAX_TRACKS || taken[t]) return RTP_EINVAL;
+    taken[t] = true;
+    draws[k] = overlay_box(joints + (size_t)k * P * 3, P, cfg->min_score, cfg->box_margin, box[k]);
+    if (!draws[k]) continue;
+    const int count = std::min((st->slot[t].owner == id ? st->slot[t].count : 0) + 1, L);
+    total += ((cfg->what & RTP_OVERLAY_TRAIL) ? std::max(count - 1, 0) : 0) + ((cfg->what & RTP_OVERLAY_BOX) ? 1 : 0) + ((cfg->what & RTP_OVERLAY_LABEL) ? 1 : 0);
+  }
+  *num_items = total;
+  if (total > capacity) return RTP_ERANGE;
+  st->frames++;
+  if (st->frames == 0) st->frames = 1;
+  int* it = items;
+  for (int k = 0; k < n; ++k) {
+    if (!draws[k]) continue;
+    const int id = recs[(size_t)k * RTP_TRACK_REC_INTS];
+    rtp_trail_slot& S = st->slot[recs[(size_t)k * RTP_TRACK_REC_INTS + 1]];
+    const int* b = box[k];
+    if (S.owner != id) { S.owner = id; S.count = 0; S.head = 0; }
+    S.pts[S.head][0] = (b[0] + b[2]) >> 1;
+    S.pts[S.head][1] = (b[1] + b[3]) >> 1;
+    S.head = (S.head + 1) % RTP_TRAIL_MAX;
+    S.count = std::min(S.count + 1, L);
+    const int colour = kOverlayPalette[id & 15];
+    if (cfg->what & RTP_OVERLAY_TRAIL) {
+      const int m = std::max(S.count - 1, 0);
+      for (int j = 0; j < m; ++j, it += RTP_OVERLAY_ITEM_INTS) {
+        const int* a = S.pts[(S.head - S.count + j + RTP_TRAIL_MAX) % RTP_TRAIL_MAX];
+        const int* c = S.pts[(S.head - S.count + j + 1 + RTP_TRAIL_MAX) % RTP_TRAIL_MAX];
+        const int item[RTP_OVERLAY_ITEM_INTS] = {RTP_OVERLAY_KIND_CAPSULE, a[0], a[1], c[0], c[1], cfg->trail_radius, colour, cfg->alpha * (j + 1) / m, 0};
+        memcpy(it, item, sizeof item);
+      }
+    }
+    if (cfg->what & RTP_OVERLAY_BOX) {
+      const int item[RTP_OVERLAY_ITEM_INTS] = {RTP_OVERLAY_KIND_RECT, b[0], b[1], b[2], b[3], cfg->line_width, colour, cfg->alpha, 0};
+      memcpy(it, item, sizeof item);
+      it += RTP_OVERLAY_ITEM_INTS;
+    }
+    if (cfg->what & RTP_OVERLAY_LABEL) {
+      const int lw = (6 * overlay_digits((unsigned)id) + 1) * cfg->label_scale, lh = 9 * cfg->label_scale;
+      const int ly = b[1] - lh < 0 ? b[1] : b[1] - lh;
+      const int item[RTP_OVERLAY_ITEM_INTS] = {RTP_OVERLAY_KIND_LABEL, b[0], ly, b[0] + lw - 1, ly + lh - 1, cfg->label_scale, colour, cfg->alpha, id};
+      memcpy(it, item, sizeof item);
+      it += RTP_OVERLAY_ITEM_INTS;
+    }
+  }
+  return RTP_OK;
+}
+
+int rtp_overlay_draw(const int* items, int num_items, unsigned char* image_bgr, int w, int h, long stride) {
+  if (!image_bgr || num_items < 0 || (num_items > 0 && !items) || w < 1 || h < 1 || stride < 3L * w) return RTP_EINVAL;
+  for (int i = 0; i < num_items; ++i) {
+    int it[RTP_OVERLAY_ITEM_INTS];
+    memcpy(it, items + (size_t)i * RTP_OVERLAY_ITEM_INTS, sizeof it);
+    const int kind = it[0];
+    if (kind != RTP_OVERLAY_KIND_CAPSULE && kind != RTP_OVERLAY_KIND_RECT && kind != RTP_OVERLAY_KIND_LABEL) continue;
+    for (int q = 1; q <= 4; ++q) it[q] = clampi(it[q], -65535, 65535);
+    it[5] = kind == RTP_OVERLAY_KIND_LABEL ? clampi(it[5], 1, 8) : clampi(it[5], 0, 16);
+    const int a = clampi(it[7], 0, 256);
+    // the item's bounding box, clipped to the image
+    const int grow = kind == RTP_OVERLAY_KIND_CAPSULE ? it[5] : 0;
+    const int bx0 = std::max(std::min(it[1], it[3]) - grow, 0), bx1 = std::min(std::max(it[1], it[3]) + grow, w - 1);
+    const int by0 = std::max(std::min(it[2], it[4]) - grow, 0), by1 = std::min(std::max(it[2], it[4]) + grow, h - 1);
+    int digit[10] = {}, ndig = 0;
+    if (kind == RTP_OVERLAY_KIND_LABEL) {
+      unsigned v = (unsigned)it[8];
+      ndig = overlay_digits(v);
+      for (int d = ndig - 1; d >= 0; --d, v /= 10u) digit[d] = (int)(v % 10u);
+    }
+    const int cb = it[6] & 255, cg = (it[6] >> 8) & 255, cr = (it[6] >> 16) & 255;
+    const int text = ((29 * cb + 150 * cg + 77 * cr) >> 8) >= 128 ? 0 : 255;
+    for (int py = by0; py <= by1; ++py)
+      for (int px = bx0; px <= bx1; ++px) {
+        const int c = overlay_covers(it, digit, ndig, px, py);
+        if (!c) continue;
+        unsigned char* p = image_bgr + (size_t)py * stride + (size_t)px * 3;
+        const int col[3] = {c == 2 ? text : cb, c == 2 ? text : cg, c == 2 ? text : cr};
+        for (int ch = 0; ch < 3; ++ch) p[ch] = (unsigned char)((p[ch] * (256 - a) + col[ch] * a + 128) >> 8);
+      }
+  }
+  return RTP_OK;
 }
 
 }  // extern "C"

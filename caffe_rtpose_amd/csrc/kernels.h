@@ -467,6 +467,57 @@ enum { RTP_SMOOTH_256 = 0, RTP_SMOOTH_1024 = 1, RTP_SMOOTH_VARIANTS = 2 };
 #define RTP_SMOOTH_DEFAULT RTP_SMOOTH_1024
 hipError_t launch_smooth(const SmoothParams& p, hipStream_t stream);
 
+// Overlay mode (overlay.hip, rtp_set_track_overlay): two kernels.  Integers and bytes are rtp_overlay_update's and rtp_overlay_draw's
+// (include/rtpose_mi355x.h spells out both).
+// overlay_update: ONE workgroup per launch, behind the frame's track (and smooth) kernel.  The frame's people, read in device memory
+// with their records, advance the trail table, one ring per track slot, and the frame's draw list is written: a prefix sum over the
+// people's item counts gives every person its place, so the list is in person order.  Launches on one table must be ordered by the
+// caller (the engine chains them with events).  TrailTable is rtp_trail_state's layout (engine_overlay.cpp asserts it).
+#define RTP_OVL_TRAIL_MAX 32                                          // RTP_TRAIL_MAX
+#define RTP_OVL_ITEM_INTS 9                                           // RTP_OVERLAY_ITEM_INTS
+#define RTP_OVL_MAX_ITEMS (RTP_TRACK_MAX_PEOPLE * (RTP_OVL_TRAIL_MAX + 1))   // RTP_OVERLAY_MAX_ITEMS
+struct TrailSlot {
+  int owner, count, head;
+  int pts[RTP_OVL_TRAIL_MAX][2];
+};
+struct TrailTable {
+  unsigned struct_size;
+  int num_parts;
+  unsigned frames;
+  TrailSlot slot[RTP_TRACK_SLOTS];
+};
+struct OverlayUpdateParams {
+  const float* joints;       // [max_people][num_parts][3]
+  const int* num_people;
+  const int* recs;           // [RTP_TRACK_MAX_PEOPLE][4] the frame's track records
+  TrailTable* table;
+  int* items;                // [RTP_OVL_MAX_ITEMS][RTP_OVL_ITEM_INTS]   (the first *num_items are written)
+  int* num_items;
+  int num_parts;
+  unsigned what;
+  float min_score;
+  int box_margin, line_width, label_scale, trail_len, trail_radius, alpha;
+  int palette[16];           // RTP_OVERLAY_PALETTE
+};
+hipError_t launch_overlay_update(const OverlayUpdateParams& p, hipStream_t stream);
+// overlay_draw: the draw list in place into a BGR image, one workgroup of 256 threads per tile of RTP_OVL_TILE_W x RTP_OVL_TILE_H
+// pixels (two rows per thread).  The workgroup walks the list 256 items at a time: every thread tests one item's bounding box against
+// the tile, a wave ballot and a prefix count over the four waves compact the hits IN ITEM ORDER into an LDS list, and whenever the
+// next 256 candidates might not fit any more (and at the end) every thread blends its pixels through the list in order.  A tile that
+// no item touches loads and stores no pixel.  Reads only *num_items, the items and the image: no table, so it needs no ordering
+// against other frames.
+#define RTP_OVL_TILE_W 32
+#define RTP_OVL_TILE_H 16
+struct OverlayDrawParams {
+  const int* items;
+  const int* num_items;      // clamped to 0 .. RTP_OVL_MAX_ITEMS
+  unsigned char* image;      // BGR, in place
+  int w, h;
+  long stride;
+  unsigned char font[10][7]; // RTP_OVERLAY_FONT
+};
+hipError_t launch_overlay_draw(const OverlayDrawParams& p, hipStream_t stream);
+
 struct NmsParams {
   const float* src;  // resized map [src_planes][H][W]
   float* peaks;      // [num_parts][max_peaks+1][3]  (in/out)

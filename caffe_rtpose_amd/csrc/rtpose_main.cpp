@@ -59,6 +59,8 @@ int rtp_peek_tracks(rtp_engine* e, uint64_t* tag, int* recs_host, int* num_recs,
 // (nor smoothing mode: --smooth then runs rtp_smooth_update in the re-orderer, as under --dry_engine)
 int rtp_set_smoothing(rtp_engine* e, const rtp_smooth_config* cfg) __attribute__((weak));
 int rtp_peek_smoothed(rtp_engine* e, uint64_t* tag, float* joints_s_host, float* vel_host, unsigned char* flags_host, int* num_people, int capacity) __attribute__((weak));
+// (nor overlay mode: --draw_tracks then runs rtp_overlay_update and rtp_overlay_draw in the re-orderer, as with --host_draw)
+int rtp_set_track_overlay(rtp_engine* e, const rtp_overlay_config* cfg) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -112,6 +114,12 @@ struct Flags {
   bool smooth = false;
   double smooth_min_cutoff = 1.0 / 30.0, smooth_beta = 0.01, smooth_d_cutoff = 1.0 / 30.0;
   int smooth_max_hold = 5;
+  // --draw_tracks (needs --track and --write_frames or --write_video): a box, an id label and a fading trail per tracked person in the
+  // rendered frames.  One real GPU worker: the engine's overlay mode (drawn on the GPU before the frame is encoded or converted there).
+  // Otherwise, or with --host_draw: the re-orderer draws with rtp_overlay_update + rtp_overlay_draw on the raw rendered frame.
+  bool draw_tracks = false, host_draw = false;
+  std::string draw_what = "box,label,trail";
+  int trail_len = 16, label_scale = 1, draw_alpha = 192;
   std::string caffemodel = "model/coco/pose_iter_440000.caffemodel", caffeproto = "model/coco/pose_deploy_linevec.prototxt";
   std::string resolution = "1280x720", net_resolution = "656x368", camera_resolution = "1280x720";
   double start_scale = 1, scale_gap = 0.3;
@@ -138,16 +146,17 @@ struct Flags {
 
 int parse_flags(int argc, char** argv, Flags& F) {
   std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video}, {"write_video", &F.write_video}, {"write_heatmaps", &F.write_heatmaps}, {"heatmap_channels", &F.heatmap_channels},
-      {"write_crops", &F.write_crops}, {"crop_size", &F.crop_size}, {"crop_parts", &F.crop_parts},
+      {"write_crops", &F.write_crops}, {"crop_size", &F.crop_size}, {"crop_parts", &F.crop_parts}, {"draw_what", &F.draw_what},
       {"image_dir", &F.image_dir}, {"caffemodel", &F.caffemodel}, {"caffeproto", &F.caffeproto}, {"resolution", &F.resolution},
       {"net_resolution", &F.net_resolution}, {"camera_resolution", &F.camera_resolution}, {"precision", &F.precision}, {"model", &F.model}, {"devices", &F.devices}};
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
       {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}, {"max_crops", &F.max_crops},
-      {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}, {"smooth_max_hold", &F.smooth_max_hold}};
+      {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}, {"smooth_max_hold", &F.smooth_max_hold},
+      {"trail_len", &F.trail_len}, {"label_scale", &F.label_scale}, {"draw_alpha", &F.draw_alpha}};
   std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}, {"track_max_cost", &F.track_max_cost},
       {"smooth_min_cutoff", &F.smooth_min_cutoff}, {"smooth_beta", &F.smooth_beta}, {"smooth_d_cutoff", &F.smooth_d_cutoff}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track}, {"smooth", &F.smooth},
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track}, {"smooth", &F.smooth}, {"draw_tracks", &F.draw_tracks}, {"host_draw", &F.host_draw},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -225,6 +234,13 @@ void usage() {
          "  --write_frames and --write_video show the smoothed people.  With --num_gpu N > 1, --dry_engine or --host_preprocess the re-orderer\n"
          "  runs the same definition on the host (rtp_smooth_update behind rtp_track_update): the JSON files are the same, frames and crops\n"
          "  are drawn from the raw joints.  Without --smooth every file is what it was.\n"
+         "  --draw_tracks [--draw_what box,label,trail] [--trail_len N (16)] [--label_scale N (1)] [--draw_alpha N (192, of 256)] [--host_draw]\n"
+         "  (needs --track and --write_frames or --write_video) draws every tracked person's box, id and a fading trail of its last N positions\n"
+         "  into the rendered frames, in a colour derived from the id.  With ONE real GPU worker the drawing runs on the GPU behind the track\n"
+         "  kernel (overlay mode of the engine), and the GPU's JPEG encoder / YUV conversion stay in use.  With --num_gpu N > 1 or --dry_engine\n"
+         "  the ids exist only in the re-orderer, which then draws on the raw rendered frame with the same definition (rtp_overlay_update +\n"
+         "  rtp_overlay_draw: the same pixels), and the host encoders write the files, as with --host_jpeg / --host_video.  --host_draw asks\n"
+         "  for that path with one GPU worker too: it is there to compare the two paths (the tests do), nothing is gained by it otherwise.  (--host_preprocess renders no frames at all.)  Without --draw_tracks every file is what it was.\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
          "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
          "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
@@ -280,6 +296,8 @@ bool track_on_gpu();
 rtp_track_config track_config();
 bool smooth_on_gpu();
 rtp_smooth_config smooth_config();
+bool overlay_on_gpu();
+rtp_overlay_config overlay_config();
 
 struct EncodeJob { std::string path; std::vector<unsigned char> bgr; bool jpeg = false; };  // jpeg: bgr already holds the file
 
@@ -543,9 +561,11 @@ void worker(int widx, int device, int* status) {
   }
   // --write_frames: the files are encoded on the GPU (quality 98, rtpose.cpp:1367-1381) unless --host_jpeg; --dry_engine has no GPU
   // --write_video x.mjpeg takes the same files (main() refuses the combinations in which one output wants the GPU's and the other the host's)
-  const bool gpu_jpeg = !dry && ((!F.write_frames.empty() && !F.host_jpeg) || (G.video_kind == RTP_VIDEO_MJPEG && !F.host_video));
+  // --draw_tracks in the re-orderer: it needs the raw frames, and the host encoders write the files
+  const bool host_draw = F.draw_tracks && !overlay_on_gpu();
+  const bool gpu_jpeg = !dry && !host_draw && ((!F.write_frames.empty() && !F.host_jpeg) || (G.video_kind == RTP_VIDEO_MJPEG && !F.host_video));
   // --write_video x.y4m: the renderer's YUV mode unless --host_video
-  const bool gpu_yuv = !dry && G.video_kind == RTP_VIDEO_Y4M && !F.host_video;
+  const bool gpu_yuv = !dry && !host_draw && G.video_kind == RTP_VIDEO_Y4M && !F.host_video;
   if (gpu_yuv) {
     const char* err = !rtp_set_render_yuv || !rtp_collect_rendered_yuv ? "this binary was linked without the engine's YUV output"
                       : rtp_set_render_yuv(e, 420) != RTP_OK            ? rtp_last_error(e) : nullptr;
@@ -560,7 +580,7 @@ void worker(int widx, int device, int* status) {
   if (!F.write_video.empty() && widx == 0)
     fprintf(stderr, "--write_video: frames %s\n", gpu_yuv ? "converted to YUV 4:2:0 on the GPU (rtp_collect_rendered_yuv)"
                                                   : gpu_jpeg ? "encoded on the GPU (rtp_collect_rendered_jpeg)"
-                                                             : "converted / encoded on the host (--host_video)");
+                                                             : "converted / encoded on the host (--host_video, or --draw_tracks in the re-orderer)");
   std::vector<unsigned char> jpeg_buf(gpu_jpeg ? rtp_jpeg_max_bytes(DISP_W, DISP_H) : 0);
   if (gpu_jpeg) {
     const char* err = !rtp_set_render_jpeg || !rtp_collect_rendered_jpeg ? "this binary was linked without the engine's GPU JPEG encoder"
@@ -674,6 +694,17 @@ void worker(int widx, int device, int* status) {
     const rtp_smooth_config sc = smooth_config();
     if (rtp_set_smoothing(e, &sc) != RTP_OK) {
       fprintf(stderr, "GPU %d: --smooth: %s\n", device, rtp_last_error(e));
+      *status = 1;
+      G.quit_threads = true;
+      rtp_engine_destroy(e);
+      return;
+    }
+  }
+  // --draw_tracks likewise: the engine's overlay mode, drawn into the rendered frame before it is encoded or converted
+  if (overlay_on_gpu()) {
+    const rtp_overlay_config oc = overlay_config();
+    if (rtp_set_track_overlay(e, &oc) != RTP_OK) {
+      fprintf(stderr, "GPU %d: --draw_tracks: %s\n", device, rtp_last_error(e));
       *status = 1;
       G.quit_threads = true;
       rtp_engine_destroy(e);
@@ -894,6 +925,24 @@ rtp_smooth_config smooth_config() {
   return sc;
 }
 
+// --draw_tracks: on the GPU where the tracker is, unless --host_draw; otherwise in the re-orderer, behind its rtp_track_update
+bool overlay_on_gpu() { return F.draw_tracks && !F.host_draw && track_on_gpu() && rtp_set_track_overlay; }
+rtp_overlay_config overlay_config() {
+  rtp_overlay_config oc;
+  rtp_overlay_config_default(&oc);
+  oc.what = 0;
+  for (size_t a = 0; a <= F.draw_what.size();) {
+    const size_t b = std::min(F.draw_what.find(',', a), F.draw_what.size());
+    const std::string w = F.draw_what.substr(a, b - a);
+    oc.what |= w == "box" ? RTP_OVERLAY_BOX : w == "label" ? RTP_OVERLAY_LABEL : w == "trail" ? RTP_OVERLAY_TRAIL : 8u;   // (8: refused by main())
+    a = b + 1;
+  }
+  oc.trail_len = F.trail_len;
+  oc.label_scale = F.label_scale;
+  oc.alpha = F.draw_alpha;
+  return oc;
+}
+
 // ---- re-orderer (buffer_and_order, rtpose.cpp:1214-1273) ---------------------------------------------
 struct FrameCompare { bool operator()(const Frame& a, const Frame& b) const { return a.index > b.index; } };
 void reorderer(std::atomic<bool>* workers_done) {
@@ -911,6 +960,12 @@ void reorderer(std::atomic<bool>* workers_done) {
   const bool host_smooth = F.smooth && F.track && !smooth_on_gpu();
   const rtp_smooth_config sc = smooth_config();
   std::unique_ptr<rtp_smooth_state> sstate;
+  // --draw_tracks on the host: on the raw rendered frame, from the records the frame carries by then and the joints the frame was rendered
+  // from: the raw ones, or, where the engine smooths (--smooth with one GPU worker: RTP_SMOOTH_RENDER), the smoothed ones it handed out
+  const bool host_draw = F.draw_tracks && !overlay_on_gpu();
+  const rtp_overlay_config oc = overlay_config();
+  std::unique_ptr<rtp_trail_state> ostate;
+  std::vector<int> draw_items(host_draw ? (size_t)RTP_OVERLAY_MAX_ITEMS * RTP_OVERLAY_ITEM_INTS : 0);
   auto emit = [&](Frame f) {
     if (host_track) {
       if (!tstate) { tstate.reset(new rtp_track_state); rtp_track_state_init(tstate.get(), G.num_parts.load()); }
@@ -924,6 +979,14 @@ void reorderer(std::atomic<bool>* workers_done) {
       f.joints_s.assign(std::max(f.joints.size(), (size_t)1), 0.f);
       if (rtp_smooth_update(sstate.get(), &sc, f.joints.data(), f.numPeople, f.track_recs.data(), f.joints_s.data(), nullptr, nullptr) < 0) f.joints_s = f.joints;
       f.joints_s.resize(f.joints.size());
+    }
+    if (host_draw && f.track_recs.size() == (size_t)f.numPeople * RTP_TRACK_REC_INTS) {
+      if (!ostate) { ostate.reset(new rtp_trail_state); rtp_trail_state_init(ostate.get(), G.num_parts.load()); }
+      int m = 0;
+      const bool raw = !f.rendered_jpeg && !f.rendered_yuv && f.rendered.size() == (size_t)DISP_W * DISP_H * 3;
+      const float* poses = smooth_on_gpu() && f.joints_s.size() == f.joints.size() ? f.joints_s.data() : f.joints.data();
+      if (rtp_overlay_update(ostate.get(), &oc, poses, f.numPeople, f.track_recs.data(), draw_items.data(), &m, RTP_OVERLAY_MAX_ITEMS) == RTP_OK && raw)
+        rtp_overlay_draw(draw_items.data(), m, f.rendered.data(), DISP_W, DISP_H, 3L * DISP_W);
     }
     f.buffer_end_time = wall();
     G.output_queue_ordered.push(std::move(f));
@@ -1193,6 +1256,18 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--smooth: --smooth_min_cutoff and --smooth_d_cutoff must be finite numbers > 0, --smooth_beta a finite number >= 0, --smooth_max_hold 0 .. %d\n", RTP_SMOOTH_MAX_HOLD);
     return 1;
   }
+  if ((F.draw_tracks || F.host_draw) && (!F.track || !F.draw_tracks || (F.write_frames.empty() && F.write_video.empty()))) {
+    fprintf(stderr, "--draw_tracks needs --track and --write_frames or --write_video (it draws tracked people into the rendered frames); --host_draw needs --draw_tracks\n");
+    usage();
+    return 1;
+  }
+  if (F.draw_tracks) {
+    const rtp_overlay_config oc = overlay_config();
+    if (oc.what == 0 || (oc.what & 8u) || oc.trail_len < 0 || oc.trail_len > RTP_TRAIL_MAX || oc.label_scale < 1 || oc.label_scale > 8 || oc.alpha < 0 || oc.alpha > 256) {
+      fprintf(stderr, "--draw_tracks: --draw_what is a comma-separated list of box, label and trail, --trail_len 0 .. %d, --label_scale 1 .. 8, --draw_alpha 0 .. 256\n", RTP_TRAIL_MAX);
+      return 1;
+    }
+  }
   if (!F.write_crops.empty()) {
     int cw = 0, ch = 0;
     char tail = 0;
@@ -1242,7 +1317,7 @@ int main(int argc, char** argv) {
                       "write an .mjpeg video next to the frames, or run twice\n", F.write_video.c_str());
       return 1;
     }
-    if (G.video_kind == RTP_VIDEO_MJPEG && !F.write_frames.empty() && !(F.dry_engine > 0) && F.host_jpeg != F.host_video) {
+    if (G.video_kind == RTP_VIDEO_MJPEG && !F.write_frames.empty() && !(F.dry_engine > 0) && F.host_jpeg != F.host_video && !(F.draw_tracks && !overlay_on_gpu())) {
       fprintf(stderr, "--write_frames with --write_video x.mjpeg: both take the same files, so give --host_jpeg and --host_video together or neither\n");
       return 1;
     }

@@ -5,7 +5,7 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, rtp_smooth_config, rtp_smooth_state, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, rtp_smooth_config, rtp_smooth_state, rtp_overlay_config, rtp_trail_state, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -803,6 +803,96 @@ def smooth_update(state, joints, num_people=None, recs=None, cfg=None):
     return js[:n].copy(), vel[:n].copy(), flags[:n].copy()
 
 
+OVERLAY_BOX, OVERLAY_LABEL, OVERLAY_TRAIL = 1, 2, 4
+OVERLAY_KIND_CAPSULE, OVERLAY_KIND_RECT, OVERLAY_KIND_LABEL = 1, 2, 3
+TRAIL_MAX, OVERLAY_ITEM_INTS = 32, 9
+OVERLAY_MAX_ITEMS = MAX_PEOPLE * (TRAIL_MAX + 1)
+# RTP_OVERLAY_PALETTE (packed b | g << 8 | r << 16) and RTP_OVERLAY_FONT (seven row bytes per digit, bit 4 = the leftmost column)
+OVERLAY_PALETTE = (0x3C14DC, 0x32CD32, 0xFF901E, 0x00D7FF, 0xD355BA, 0xD1CE00, 0x008CFF, 0x9314FF, 0x578B2E, 0xE16941, 0x20A5DA, 0xCC3299, 0xAAB220, 0x2D52A0,
+                   0x7FFF00, 0xB469FF)
+OVERLAY_FONT = ((0x0E, 0x11, 0x13, 0x15, 0x19, 0x11, 0x0E), (0x04, 0x0C, 0x04, 0x04, 0x04, 0x04, 0x0E), (0x0E, 0x11, 0x01, 0x02, 0x04, 0x08, 0x1F),
+                (0x1E, 0x01, 0x01, 0x0E, 0x01, 0x01, 0x1E), (0x02, 0x06, 0x0A, 0x12, 0x1F, 0x02, 0x02), (0x1F, 0x10, 0x1E, 0x01, 0x01, 0x11, 0x0E),
+                (0x06, 0x08, 0x10, 0x1E, 0x11, 0x11, 0x0E), (0x1F, 0x01, 0x02, 0x04, 0x08, 0x08, 0x08), (0x0E, 0x11, 0x11, 0x0E, 0x11, 0x11, 0x0E),
+                (0x0E, 0x11, 0x11, 0x0F, 0x01, 0x02, 0x0C))
+_TRAIL_SLOT = np.dtype([("owner", np.int32), ("count", np.int32), ("head", np.int32), ("pts", np.int32, (TRAIL_MAX, 2))])
+
+
+def overlay_config(what=None, min_score=None, box_margin=None, line_width=None, label_scale=None, trail_len=None, trail_radius=None, alpha=None):
+    """rtp_overlay_config: rtp_overlay_config_default's values (everything drawn, min_score 0, box_margin 4, line_width 2, label_scale 1,
+    trail_len 16, trail_radius 1, alpha 192), each replaced where an argument is given.  what: a mask of OVERLAY_BOX, OVERLAY_LABEL and
+    OVERLAY_TRAIL."""
+    cfg = rtp_overlay_config()
+    lib.rtp_overlay_config_default(C.byref(cfg))
+    for name, v, conv in (("what", what, int), ("min_score", min_score, float), ("box_margin", box_margin, int), ("line_width", line_width, int),
+                          ("label_scale", label_scale, int), ("trail_len", trail_len, int), ("trail_radius", trail_radius, int), ("alpha", alpha, int)):
+        if v is not None:
+            setattr(cfg, name, conv(v))
+    return cfg
+
+
+class TrailState:
+    """rtp_trail_state, the trail table as plain data: num_parts, frames and `slot`, a numpy structured view [128] with the fields owner,
+    count, head and pts [32][2] onto the structure itself (writes through it change it).  == compares every byte."""
+
+    def __init__(self, num_parts=18, c=None):
+        if c is None:
+            c = rtp_trail_state()
+            if lib.rtp_trail_state_init(C.byref(c), int(num_parts)):
+                raise RtpError(RTP_EINVAL, f"rtp_trail_state_init: num_parts {num_parts} outside 1 .. 70")
+        self.c = c
+        self.slot = np.frombuffer(c, dtype=_TRAIL_SLOT, count=MAX_TRACKS, offset=rtp_trail_state.slot.offset)   # (holds a reference to c)
+
+    num_parts = property(lambda self: self.c.num_parts)
+    frames = property(lambda self: self.c.frames, lambda self, v: setattr(self.c, "frames", int(v)))
+
+    def copy(self):
+        c = rtp_trail_state()
+        C.memmove(C.byref(c), C.byref(self.c), C.sizeof(c))
+        return TrailState(c=c)
+
+    def tobytes(self):
+        return C.string_at(C.byref(self.c), C.sizeof(self.c))
+
+    def __eq__(self, other):
+        return isinstance(other, TrailState) and self.tobytes() == other.tobytes()
+
+
+def overlay_update(state, joints, num_people=None, recs=None, cfg=None, capacity=OVERLAY_MAX_ITEMS):
+    """rtp_overlay_update, the host definition of overlay mode's draw list: advances `state` (a TrailState) by one frame of joints
+    [people][state.num_parts][3] with their track records [n][4] and returns the frame's items [m][9] int32.  num_people: the frame's
+    count where it is not the array's; cfg: an overlay_config() (None = the defaults)."""
+    cfg = cfg if cfg is not None else overlay_config()
+    P = state.num_parts
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, P, 3)
+    people = j.shape[0] if num_people is None else int(num_people)
+    n = min(max(people, 0), MAX_PEOPLE)
+    if n > j.shape[0]:
+        raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+    r = np.ascontiguousarray(recs if recs is not None else np.zeros((0, TRACK_REC_INTS)), np.int32).reshape(-1, TRACK_REC_INTS)
+    if n > r.shape[0]:
+        raise ValueError(f"{n} people, {r.shape[0]} records")
+    items = np.zeros((max(int(capacity), 1), OVERLAY_ITEM_INTS), np.int32)
+    m = C.c_int(0)
+    rc = lib.rtp_overlay_update(C.byref(state.c), C.byref(cfg), _f(j) if j.size else None, people, r.ctypes.data_as(ip) if r.size else None, items.ctypes.data_as(ip),
+                                C.byref(m), int(capacity))
+    if rc < 0:
+        raise RtpError(rc, f"rtp_overlay_update: {'the frame has %d items' % m.value if rc == RTP_ERANGE else 'an argument is out of range'}")
+    return items[: m.value].copy()
+
+
+def overlay_draw(items, image, num_items=None):
+    """rtp_overlay_draw, the host definition of overlay mode's pixels: draws items [m][9] int32 in order into `image`, a uint8 array
+    [h][w][3] (BGR) whose rows may be strided, IN PLACE; returns it."""
+    it = np.ascontiguousarray(items, np.int32).reshape(-1, OVERLAY_ITEM_INTS)
+    m = it.shape[0] if num_items is None else int(num_items)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.strides[2] != 1 or image.strides[1] != 3 or not image.flags.writeable:
+        raise ValueError("image: a writeable uint8 array [h][w][3] with dense rows")
+    rc = lib.rtp_overlay_draw(it.ctypes.data_as(ip) if it.size else None, m, image.ctypes.data_as(C.POINTER(C.c_ubyte)), image.shape[1], image.shape[0], image.strides[0])
+    if rc < 0:
+        raise RtpError(rc, "rtp_overlay_draw: an argument is out of range")
+    return image
+
+
 def _stream_of(obj, stream):
     """(handle or None, torch default stream?) of the stream a device frame is ordered on.  stream: a torch.cuda.Stream, a raw
     hipStream_t as int, or None = torch's current stream of a tensor's device, else the interface's `stream` entry, else NULL."""
@@ -1284,6 +1374,59 @@ class Engine:
         self._chk(lib.rtp_smooth_from_joints(self.h, _f(j) if j.size else None, people, recs.ctypes.data_as(ip), _f(js), _f(vel),
                                              flags.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(n), cap))
         return recs[: n.value].copy(), js[: n.value].copy(), vel[: n.value].copy(), flags[: n.value].copy()
+
+    # ---- overlay mode
+    def set_track_overlay(self, cfg=True, **kw):
+        """rtp_set_track_overlay (tracking mode must be on, Config.render >= 1): every submitted frame's rendered image gets a box, an id
+        label and a fading trail per tracked person before it is exported; peek_overlay_items in front of the frame's collect gives the
+        draw list.  cfg: an overlay_config(), True (= overlay_config(**kw)) or None / False (off: the trail table is discarded).  Off -> on
+        starts from an empty table; a new cfg while the mode is on keeps it."""
+        if cfg is None or cfg is False:
+            self._chk(lib.rtp_set_track_overlay(self.h, None))
+            return
+        if cfg is True:
+            cfg = overlay_config(**kw)
+        self._chk(lib.rtp_set_track_overlay(self.h, C.byref(cfg)))
+
+    def overlay_reset(self):
+        """rtp_overlay_reset: an empty trail table; idle engine."""
+        self._chk(lib.rtp_overlay_reset(self.h))
+
+    def overlay_state(self):
+        """rtp_overlay_get_state: the engine's trail table as a TrailState; idle engine."""
+        st = TrailState(self.num_parts)
+        self._chk(lib.rtp_overlay_get_state(self.h, C.byref(st.c)))
+        return st
+
+    def set_overlay_state(self, state):
+        """rtp_overlay_set_state: the engine's trail table becomes a copy of `state` (a TrailState of the engine's num_parts); idle engine."""
+        self._chk(lib.rtp_overlay_set_state(self.h, C.byref(state.c)))
+
+    def peek_overlay_items(self, capacity=OVERLAY_MAX_ITEMS):
+        """rtp_peek_overlay_items: (tag, items [m][9] int32) of the oldest frame in flight, which stays in flight (follow with a collect)."""
+        items = np.zeros((max(int(capacity), 1), OVERLAY_ITEM_INTS), np.int32)
+        tag, m = C.c_uint64(0), C.c_int(0)
+        self._chk(lib.rtp_peek_overlay_items(self.h, C.byref(tag), items.ctypes.data_as(ip), C.byref(m), int(capacity)))
+        return tag.value, items[: m.value].copy()
+
+    def overlay_from_joints(self, joints, num_people=None, image=None, capacity=OVERLAY_MAX_ITEMS):
+        """rtp_overlay_from_joints: the async path's track, overlay_update and overlay_draw kernels on joints [people][num_parts][3] (idle
+        engine); the track table and the trail table advance by one frame.  image: a uint8 array [h][w][3] up to the display size, or
+        None (no drawing).  Returns (records [n][4], items [m][9], the image with the drawing or None)."""
+        P = self.num_parts
+        j = np.ascontiguousarray(joints, np.float32).reshape(-1, P, 3)
+        people = j.shape[0] if num_people is None else int(num_people)
+        n = min(max(people, 0), MAX_PEOPLE)
+        if n > j.shape[0]:
+            raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+        recs = np.zeros((max(n, 1), TRACK_REC_INTS), np.int32)
+        items = np.zeros((max(int(capacity), 1), OVERLAY_ITEM_INTS), np.int32)
+        img = None if image is None else np.ascontiguousarray(image, np.uint8).copy()
+        h, w = (0, 0) if img is None else img.shape[:2]
+        m = C.c_int(0)
+        self._chk(lib.rtp_overlay_from_joints(self.h, _f(j) if j.size else None, people, None if img is None else img.ctypes.data_as(C.POINTER(C.c_ubyte)), w, h,
+                                              recs.ctypes.data_as(ip), items.ctypes.data_as(ip), C.byref(m), int(capacity)))
+        return recs[:n].copy(), items[: m.value].copy(), img
 
     def crops_from_joints(self, display_bgr, joints, pixels=True):
         """rtp_crops_from_joints: (boxes, crops) of the current mode for the given display image and joints [people][num_parts][3]

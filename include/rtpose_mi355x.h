@@ -1019,6 +1019,158 @@ int rtp_peek_smoothed(rtp_engine* e, uint64_t* tag, float* joints_s_host, float*
 int rtp_smooth_from_joints(rtp_engine* e, const float* joints_host, int num_people, int* recs_host, float* joints_s_host,
                            float* vel_host, unsigned char* flags_host, int* num_out, int capacity);
 
+/* ---- overlay mode: tracked people drawn into the rendered frame: boxes, ids, trails (overlay.hip) -------------------------- */
+
+/* The rendered frame (rtp_collect_rendered*, JPEG and YUV mode) shows anonymous skeletons.  Overlay mode, off by default and usable
+ * only while tracking mode is on and rtp_config.render >= 1, draws for every tracked person of a submitted frame a box, an id label
+ * in a built-in bitmap font and a fading trail of the track's recent positions, all in a colour derived from the id, BEFORE the
+ * image is exported: the raw host copy, rtp_collect_rendered_device, JPEG mode and YUV mode all carry the drawing.  Each submitted
+ * frame's chain gains two kernels.  overlay_update runs as one workgroup behind the track kernel (and the smooth kernel where that
+ * mode is on): it reads num_people, the joints and the frame's records in device memory, advances a device-resident trail table,
+ * one ring of anchor points per track slot, in submit order (the tracker's chain of events, recorded behind this kernel), and
+ * writes the frame's DRAW LIST.  overlay_draw then draws the list, in item order, in place into the slot's rendered image.
+ * rtp_overlay_update and rtp_overlay_draw are the one definition of both; the kernels' integers and bytes equal them exactly.
+ *
+ * THE UPDATE.  One update takes n = clamp(num_people, 0, RTP_MAX_PEOPLE) people with their n track records.  frames++ (0 is skipped
+ * at the wrap).  Then, per person k in person order:
+ *  1. A record with id == 0 produces nothing and touches nothing.  A part COUNTS under tracking's rule: score > min_score and x, y
+ *     finite.  A person without a counting part produces nothing and touches nothing.
+ *  2. Over the counting parts, in float32 comparisons: fx0 = min x, fx1 = max x, fy0 = min y, fy1 = max y.  Each is rounded ONCE:
+ *       q(v) = (int)floorf(clampf(v, -32767.0f, 32767.0f) + 0.5f)          (round half up; the sum is one float32 addition)
+ *     Everything from here on is integer arithmetic.  The box is x0 = q(fx0) - box_margin, y0 = q(fy0) - box_margin,
+ *     x1 = q(fx1) + box_margin, y1 = q(fy1) + box_margin, corners inclusive.  The ANCHOR is (floor((x0 + x1) / 2), floor((y0 + y1) / 2)).
+ *  3. The trail ring S of the record's slot: where S.owner != id the ring is emptied and re-owned (owner = id, count = 0, head = 0;
+ *     the points stay as they are: nothing is cleared when a track dies, a reborn slot carries a new id).  The anchor is pushed:
+ *     pts[head] = anchor, head = (head + 1) % RTP_TRAIL_MAX, count = min(count + 1, trail_len).  The kept points are the last `count`
+ *     pushed ones; the oldest is pts[(head - count) mod RTP_TRAIL_MAX].  (trail_len 0 keeps none, a smaller trail_len forgets the oldest.)
+ *  4. The person's items, in this order: with RTP_OVERLAY_TRAIL the m = max(count - 1, 0) capsules between consecutive kept points,
+ *     oldest pair first; with RTP_OVERLAY_BOX the box; with RTP_OVERLAY_LABEL the label.
+ * AN ITEM is RTP_OVERLAY_ITEM_INTS int32: {kind, x0, y0, x1, y1, size, colour, alpha, value}.  colour = RTP_OVERLAY_PALETTE[id & 15],
+ * packed b | g << 8 | r << 16.
+ *   capsule j of m: {RTP_OVERLAY_KIND_CAPSULE, ax, ay, bx, by, trail_radius, colour, alpha * (j + 1) / m (integer division), 0}
+ *   box:            {RTP_OVERLAY_KIND_RECT, x0, y0, x1, y1, line_width, colour, alpha, 0}
+ *   label:          {RTP_OVERLAY_KIND_LABEL, lx, ly, lx + LW - 1, ly + LH - 1, label_scale, colour, alpha, id}
+ *     D = the number of decimal digits of the id taken as uint32 (1 .. 10); LW = (6 * D + 1) * label_scale, LH = 9 * label_scale.
+ *     lx = x0; ly = y0 - LH: the label sits above the box's top-left corner; where ly < 0 (it would leave the image's top)
+ *     ly = y0: inside the box.
+ *
+ * THE DRAWING walks the items in order; the blends do not commute, so the order matters.  A pixel (px, py) that an item COVERS becomes,
+ * per channel c of the item's colour (the label: see below), (src * (256 - alpha) + c * alpha + 128) >> 8.  Pixels outside the image
+ * are skipped, whatever the item's coordinates.
+ *   RECT covers x0 <= px <= x1, y0 <= py <= y1 with px - x0 < size or x1 - px < size or py - y0 < size or y1 - py < size: an outline
+ *     of `size` pixels that grows inwards (a size beyond half the box fills it).
+ *   CAPSULE, a = (x0, y0), b = (x1, y1), d = b - a, r = size, in exact integer arithmetic (int64, no float): t = (p - a) . d,
+ *     L = d . d.  L == 0 or t < 0: |p - a|^2 <= r^2.  t > L: |p - b|^2 <= r^2.  Otherwise cross = (px - ax) * dy - (py - ay) * dx and
+ *     cross^2 <= r^2 * L (r^2 * L < 2^44: an implementation may clamp |cross| to 2^31 before squaring).
+ *   LABEL covers its whole rectangle.  With s = size, u = (px - x0) / s, v = (py - y0) / s: the pixel belongs to a digit when
+ *     1 <= v <= 7, u >= 1, c = (u - 1) % 6 < 5, i = (u - 1) / 6 < D, and bit (4 - c) of RTP_OVERLAY_FONT[digit i][v - 1] is set, digit 0
+ *     being the most significant one of `value` as uint32.  A digit's pixel takes the text colour, every other one the item's
+ *     colour.  The text colour is black (0, 0, 0) where (29 * b + 150 * g + 77 * r) >> 8 >= 128 for the item's colour, white
+ *     (255, 255, 255) otherwise.  One blend per pixel.
+ *   Any other kind covers nothing.
+ *
+ * The font (5 x 7, seven row bytes per digit, bit 4 = the leftmost column) and the palette were written for this project.  The
+ * defaults of rtp_overlay_config_default (everything drawn, min_score 0, box_margin 4, line_width 2, label_scale 1, trail_len 16,
+ * trail_radius 1, alpha 192) are choices, not measurements. */
+#define RTP_OVERLAY_BOX 1
+#define RTP_OVERLAY_LABEL 2
+#define RTP_OVERLAY_TRAIL 4
+#define RTP_OVERLAY_KIND_CAPSULE 1
+#define RTP_OVERLAY_KIND_RECT 2
+#define RTP_OVERLAY_KIND_LABEL 3
+#define RTP_TRAIL_MAX 32
+#define RTP_OVERLAY_ITEM_INTS 9
+#define RTP_OVERLAY_MAX_ITEMS (RTP_MAX_PEOPLE * (RTP_TRAIL_MAX + 1))
+#define RTP_OVERLAY_MAX_MARGIN 1024
+/* packed b | g << 8 | r << 16 */
+#define RTP_OVERLAY_PALETTE \
+  { 0x3C14DC, 0x32CD32, 0xFF901E, 0x00D7FF, 0xD355BA, 0xD1CE00, 0x008CFF, 0x9314FF, 0x578B2E, 0xE16941, 0x20A5DA, 0xCC3299, 0xAAB220, 0x2D52A0, \
+    0x7FFF00, 0xB469FF }
+#define RTP_OVERLAY_FONT \
+  { {0x0E, 0x11, 0x13, 0x15, 0x19, 0x11, 0x0E}, {0x04, 0x0C, 0x04, 0x04, 0x04, 0x04, 0x0E}, {0x0E, 0x11, 0x01, 0x02, 0x04, 0x08, 0x1F}, \
+    {0x1E, 0x01, 0x01, 0x0E, 0x01, 0x01, 0x1E}, {0x02, 0x06, 0x0A, 0x12, 0x1F, 0x02, 0x02}, {0x1F, 0x10, 0x1E, 0x01, 0x01, 0x11, 0x0E}, \
+    {0x06, 0x08, 0x10, 0x1E, 0x11, 0x11, 0x0E}, {0x1F, 0x01, 0x02, 0x04, 0x08, 0x08, 0x08}, {0x0E, 0x11, 0x11, 0x0E, 0x11, 0x11, 0x0E}, \
+    {0x0E, 0x11, 0x11, 0x0F, 0x01, 0x02, 0x0C} }
+
+typedef struct rtp_overlay_config {
+  unsigned int struct_size; /* sizeof(rtp_overlay_config) */
+  unsigned int what;        /* a non-empty mask of RTP_OVERLAY_BOX | RTP_OVERLAY_LABEL | RTP_OVERLAY_TRAIL */
+  float min_score;          /* >= 0, finite: a part COUNTS when score > min_score and x, y are finite */
+  int box_margin;           /* 0 .. RTP_OVERLAY_MAX_MARGIN pixels around the counting parts */
+  int line_width;           /* 1 .. 16 */
+  int label_scale;          /* 1 .. 8: pixels per font pixel */
+  int trail_len;            /* 0 .. RTP_TRAIL_MAX points kept per track */
+  int trail_radius;         /* 0 .. 16 */
+  int alpha;                /* 0 .. 256 */
+} rtp_overlay_config;
+
+typedef struct rtp_trail_slot {
+  int owner; /* a track id, 0 = none */
+  int count; /* kept points, 0 .. RTP_TRAIL_MAX */
+  int head;  /* where the next point goes, 0 .. RTP_TRAIL_MAX - 1 */
+  int pts[RTP_TRAIL_MAX][2];
+} rtp_trail_slot;
+
+typedef struct rtp_trail_state { /* plain data; the device copy has the same layout */
+  unsigned int struct_size;      /* sizeof(rtp_trail_state) */
+  int num_parts;                 /* 1 .. RTP_MAX_NUM_PARTS */
+  unsigned int frames;           /* updates since the reset; wraps past 0 to 1 */
+  rtp_trail_slot slot[RTP_MAX_TRACKS];
+} rtp_trail_state;
+
+/* Host only (no engine, no GPU).  rtp_overlay_config_default: the defaults above.  rtp_trail_state_init: an empty table for a model
+ * of num_parts parts; RTP_EINVAL for num_parts outside 1 .. RTP_MAX_NUM_PARTS. */
+int rtp_overlay_config_default(rtp_overlay_config* cfg);
+int rtp_trail_state_init(rtp_trail_state* state, int num_parts);
+
+/* Host only: THE UPDATE above, one frame.  joints [num_people][state->num_parts][3] and recs [n][RTP_TRACK_REC_INTS] (NULL is
+ * accepted for either where no person is read); items receives *num_items items of RTP_OVERLAY_ITEM_INTS ints, capacity = the items
+ * it holds (RTP_OVERLAY_MAX_ITEMS always suffices).  Returns RTP_OK; RTP_ERANGE with *num_items = the frame's count and the state
+ * untouched where capacity is smaller; RTP_EINVAL with the state untouched: a NULL state, cfg, items or num_items, a negative
+ * capacity, NULL joints or recs with people, a wrong struct_size in either structure, a configuration field out of its range, a
+ * state->num_parts outside 1 .. RTP_MAX_NUM_PARTS, a ring whose count or head is out of its range, a record with id != 0 whose slot
+ * is outside 0 .. RTP_MAX_TRACKS - 1, two records with id != 0 that name the same slot. */
+int rtp_overlay_update(rtp_trail_state* state, const rtp_overlay_config* cfg, const float* joints, int num_people, const int* recs,
+                       int* items, int* num_items, int capacity);
+
+/* Host only: THE DRAWING above onto image_bgr, h rows of w BGR pixels, `stride` bytes from row to row (>= 3 * w).  num_items 0
+ * leaves the image untouched.  RTP_EINVAL: a NULL image, NULL items with num_items > 0, a negative num_items, w or h < 1, a stride
+ * below 3 * w.  An item's alpha is taken as clamp(alpha, 0, 256) and its size as clamp(size, 0, 16) (a label's: 1 .. 8); rectangle
+ * and label corners and capsule end points are taken as clamp(v, -65535, 65535). */
+int rtp_overlay_draw(const int* items, int num_items, unsigned char* image_bgr, int w, int h, long stride);
+
+/* Switches overlay mode on, NULL cfg = off (the trail table is discarded).  Off -> on starts from an empty table; while the mode is
+ * on, a new cfg keeps it.  Refused, with the engine unchanged: tracking mode off, rtp_config.render == 0, a wrong struct_size or a
+ * field out of range (RTP_EINVAL); frames in flight (RTP_EAGAIN).  While the overlay is on rtp_set_tracking(e, NULL) is refused with
+ * RTP_EINVAL.  Only frames that went through rtp_submit* advance the trail table (and rtp_overlay_from_joints); the synchronous taps
+ * never do, and their rendered images carry no drawing.  With smoothing mode's RTP_SMOOTH_RENDER the overlay takes the smoothed
+ * joints, held parts included, so that box and skeleton agree; otherwise the raw ones.  A frame submitted without a display image
+ * (rtp_submit) advances the table and has a draw list, but nothing is drawn.  With the mode off the engine launches what it
+ * launched before the mode existed. */
+int rtp_set_track_overlay(rtp_engine* e, const rtp_overlay_config* cfg);
+
+/* Idle engine only (RTP_EAGAIN with frames in flight); RTP_EINVAL while the mode is off.  reset: an empty table.  get / set: the whole
+ * table; set also refuses (RTP_EINVAL) a wrong struct_size, a num_parts that is not the engine's and a ring whose count or head is
+ * out of its range. */
+int rtp_overlay_reset(rtp_engine* e);
+int rtp_overlay_get_state(rtp_engine* e, rtp_trail_state* state);
+int rtp_overlay_set_state(rtp_engine* e, const rtp_trail_state* state);
+
+/* The contract of rtp_peek_tracks: blocks until the OLDEST frame in flight is finished and hands out its tag, *num_items and that
+ * many items; capacity = the items items_host holds.  The frame STAYS in flight.  Refused: mode off, NULL items_host or num_items, a
+ * negative capacity (RTP_EINVAL); nothing in flight (RTP_EAGAIN); capacity < *num_items (RTP_ERANGE, *num_items set, nothing else
+ * written; the frame stays peekable). */
+int rtp_peek_overlay_items(rtp_engine* e, uint64_t* tag, int* items_host, int* num_items, int capacity);
+
+/* Parity tap (idle engine, context 0): the track, overlay_update and overlay_draw kernels of the async path on caller data.  joints_host
+ * [num_people][num_parts][3], of which n = clamp(num_people, 0, RTP_MAX_PEOPLE) people are read; num_people itself goes to the device
+ * as it is.  image_host_in_out: a dense w x h BGR image (1 <= w <= cfg.disp_w, 1 <= h <= cfg.disp_h; no display frame is needed) that
+ * comes back with the drawing, or NULL (w and h ignored: no drawing).  It ADVANCES the track table and the trail table by one
+ * frame.  Writes n records (recs_out may be NULL; room for n <= RTP_MAX_PEOPLE records) and *num_items items, capacity as in
+ * rtp_peek_overlay_items. */
+int rtp_overlay_from_joints(rtp_engine* e, const float* joints_host, int num_people, unsigned char* image_host_in_out, int w, int h,
+                            int* recs_out, int* items_out, int* num_items, int capacity);
+
 #ifdef __cplusplus
 }
 #endif
