@@ -7,9 +7,17 @@
 //         what cv::imread and PIL both run —: dequantise, jidctint.c `jpeg_idct_islow`
 //         (CONST_BITS 13, PASS1_BITS 2), jdsample.c fancy ("triangle") up-sampling h2v1 / h2v2 /
 //         h1v2 when the down-sampled width > 2 (else replication), jdcolor.c YCbCr->RGB tables
-//         (SCALEBITS 16).  PINNED bit-for-bit against PIL's (libjpeg-turbo) decode of the fixtures in
-//         tests/golden/codecs (tools/make_codec_fixtures.py).  Arithmetic-coded / lossless / 12-bit /
-//         CMYK files are rejected with a message.
+//         (SCALEBITS 16); every other integral ratio (x3, x4, ...) is replicated (int_upsample).  The
+//         colour model is decided in jdapimin.c's order: JFIF seen -> YCbCr, else the Adobe
+//         transform (0 = RGB), else the component ids ('R' 'G' 'B' = RGB).  A component keeps the
+//         quantiser its table slot held at its first scan (jdinput.c latch_quant_tables).
+//         PINNED bit-for-bit against PIL's (libjpeg-turbo) decode of the fixtures in
+//         tests/golden/codecs (Pillow's own baseline / progressive files) and tests/golden/codecs/layouts
+//         (sampling factors up to 10 blocks per MCU, one scan per component, restart interval 1, fill
+//         bytes, SOF1, tables under id 3, 16-bit and redefined quantisers, JFIF / Adobe / id colour
+//         models), both made by tools/make_codec_fixtures.py.  UNPINNED: IDCT output beyond +-380 around
+//         the level shift (libjpeg's range-limit table wraps there, and its SIMD and C IDCTs differ).
+//         Arithmetic-coded / lossless / 12-bit / CMYK files are rejected with a message.
 //   PNG   all colour types and bit depths, Adam7, through zlib's inflate (the one library
 //         dependency; libz ships with the ROCm image); alpha stripped, 16 bit -> high byte,
 //         low-bit grey expanded — libpng's transforms under cv::IMREAD_COLOR.  Lossless: pinned
@@ -194,6 +202,8 @@ struct JComp {
   int bw = 0, bh = 0;          // blocks per row / column (padded to whole MCUs)
   int dw = 0, dh = 0;          // down-sampled size in samples (ceil)
   int pred = 0;
+  bool qlatched = false;
+  uint16_t q[64];                    // the quantiser (zig-zag order) latched when the component first appeared in a scan
   std::vector<short> coef;           // bw*bh blocks of 64 coefficients (natural order, not dequantised)
   std::vector<unsigned char> plane;  // bw*8 x bh*8
 };
@@ -281,9 +291,34 @@ struct JpegFile {
   std::vector<JComp> comps;
   int W = 0, H = 0, restart = 0;
   int adobe_transform = -1;
+  bool jfif = false;
   bool have_sof = false, progressive = false, geometry_done = false;
   int hmax = 1, vmax = 1, mcux = 0, mcuy = 0, scans_done = 0;
 };
+
+// jdapimin.c default_decompress_parms for three components: JFIF seen -> YCbCr; else an Adobe marker decides (transform 0 = RGB,
+// anything else YCbCr); else the component ids 'R' 'G' 'B' mean RGB and everything else YCbCr
+bool jpeg_is_rgb(const JpegFile& J) {
+  if (J.comps.size() != 3 || J.jfif) return false;
+  if (J.adobe_transform >= 0) return J.adobe_transform == 0;
+  return J.comps[0].id == 'R' && J.comps[1].id == 'G' && J.comps[2].id == 'B';
+}
+
+// jdinput.c latch_quant_tables: a component keeps the table its slot held when it first appeared in a scan
+void latch_quant(const JpegFile& J, JComp* c) {
+  if (c->qlatched || !J.qset[c->tq]) return;
+  memcpy(c->q, J.qt[c->tq], sizeof c->q);
+  c->qlatched = true;
+}
+// before reconstruction: a component no scan latched (it appeared in none, or its table came behind its scan, which libjpeg
+// refuses) takes what its slot holds now
+int latch_remaining(JpegFile* J) {
+  for (auto& c : J->comps) {
+    latch_quant(*J, &c);
+    if (!c.qlatched) return cfail(RTP_EIO, "JPEG: missing quantisation table");
+  }
+  return RTP_OK;
+}
 
 // A request to leave the entropy decoding of the (one) scan to the device: set by jpeg_coefficients when the file qualifies
 struct ScanRequest {
@@ -304,6 +339,7 @@ int jpeg_coefficients(const unsigned char* d, size_t n, JpegFile* J, bool size_o
   auto& hac = J->hac;
   std::vector<JComp>& comps = J->comps;
   int &W = J->W, &H = J->H, &restart = J->restart, &adobe_transform = J->adobe_transform;
+  bool& jfif = J->jfif;
   bool &have_sof = J->have_sof, &progressive = J->progressive, &geometry_done = J->geometry_done;
   int &hmax = J->hmax, &vmax = J->vmax, &mcux = J->mcux, &mcuy = J->mcuy, &scans_done = J->scans_done;
   size_t pos = 2;
@@ -370,8 +406,10 @@ int jpeg_coefficients(const unsigned char* d, size_t n, JpegFile* J, bool size_o
     } else if (m == 0xDD) {
       if (sl < 2) return cfail(RTP_EIO, "JPEG: truncated DRI");
       restart = u16(pos + 2);
+    } else if (m == 0xE0 && sl >= 14 && !memcmp(s, "JFIF\0", 5)) {  // (the colour model is settled at the first scan)
+      if (!scans_done) jfif = true;
     } else if (m == 0xEE && sl >= 12 && !memcmp(s, "Adobe", 5)) {
-      adobe_transform = s[11];
+      if (!scans_done) adobe_transform = s[11];
     } else if (m == 0xDA) {  // SOS: one scan into the coefficient buffers
       if (!have_sof) return cfail(RTP_EIO, "JPEG: SOS before SOF");
       const int ns = sl >= 1 ? s[0] : 0;
@@ -406,6 +444,7 @@ int jpeg_coefficients(const unsigned char* d, size_t n, JpegFile* J, bool size_o
         }
         geometry_done = true;
       }
+      for (int i = 0; i < ns; ++i) latch_quant(*J, sc[i]);
       if (rq && scans_done == 0 && plan_scan(d, n, pos, *J, sc, ns, rq)) { rq->taken = true; return RTP_OK; }
       for (int i = 0; i < ns; ++i) sc[i]->pred = 0;
       BitReader br;
@@ -551,19 +590,18 @@ int jpeg_coefficients(const unsigned char* d, size_t n, JpegFile* J, bool size_o
 // coefficients -> pixels (BGR HWC).  out may be NULL: everything but the up-sampling and colour stage runs (the size query of a
 // file whose SOF came after its scans never got here before either).
 int jpeg_reconstruct(JpegFile* J, unsigned char* out, size_t cap, int* ow_, int* oh_) {
-  auto& qt = J->qt;
-  auto& qset = J->qset;
   std::vector<JComp>& comps = J->comps;
-  const int W = J->W, H = J->H, adobe_transform = J->adobe_transform, hmax = J->hmax, vmax = J->vmax;
+  const int W = J->W, H = J->H, hmax = J->hmax, vmax = J->vmax;
+  const int lrc = latch_remaining(J);
+  if (lrc) return lrc;
   // ---- coefficients -> samples: dequantise + IDCT of every block ----
   for (auto& c : comps) {
-    if (!qset[c.tq]) return cfail(RTP_EIO, "JPEG: missing quantisation table");
     c.plane.assign((size_t)c.bw * 8 * c.bh * 8, 0);
     int coef[64];
     for (int by = 0; by < c.bh; ++by)
       for (int bx = 0; bx < c.bw; ++bx) {
         const short* blk = c.coef.data() + ((size_t)by * c.bw + bx) * 64;
-        for (int k = 0; k < 64; ++k) coef[kZigzag[k]] = blk[kZigzag[k]] * qt[c.tq][k];
+        for (int k = 0; k < 64; ++k) coef[kZigzag[k]] = blk[kZigzag[k]] * c.q[k];
         idct_islow(coef, c.plane.data() + ((size_t)by * 8) * (c.bw * 8) + (size_t)bx * 8, c.bw * 8);
       }
   }
@@ -586,8 +624,7 @@ int jpeg_reconstruct(JpegFile* J, unsigned char* out, size_t cap, int* ow_, int*
     const int rc = upsample(comps[i], hmax, vmax, W, H, &f[i]);
     if (rc) return rc;
   }
-  const bool rgb = adobe_transform == 0 || (adobe_transform < 0 && comps[0].id == 'R' && comps[1].id == 'G' && comps[2].id == 'B');
-  if (rgb) {
+  if (jpeg_is_rgb(*J)) {
     for (size_t i = 0; i < (size_t)W * H; ++i) { out[i * 3] = f[2][i]; out[i * 3 + 1] = f[1][i]; out[i * 3 + 2] = f[0][i]; }
     return RTP_OK;
   }
@@ -624,10 +661,9 @@ void fill_geom(const JpegFile& J, rtp::JpegGeom* g) {
   for (int c = 0; c < g->ncomp; ++c) {
     const JComp& jc = J.comps[c];
     g->h[c] = jc.h; g->v[c] = jc.v; g->bw[c] = jc.bw; g->bh[c] = jc.bh; g->dw[c] = jc.dw; g->dh[c] = jc.dh;
-    for (int k = 0; k < 64; ++k) g->qn[c][kZigzag[k]] = J.qt[jc.tq][k];
+    for (int k = 0; k < 64; ++k) g->qn[c][kZigzag[k]] = jc.q[k];
   }
-  g->rgb = g->ncomp == 3 && (J.adobe_transform == 0 ||
-                             (J.adobe_transform < 0 && J.comps[0].id == 'R' && J.comps[1].id == 'G' && J.comps[2].id == 'B'));
+  g->rgb = jpeg_is_rgb(J);
 }
 
 void copy_huff(const Huff& h, JdHuff* o) {
@@ -649,7 +685,7 @@ bool plan_scan(const unsigned char* d, size_t n, size_t pos, JpegFile& J, JComp*
   int nblk = 0;
   for (int i = 0; i < ns; ++i) {
     nblk += sc[i]->h * sc[i]->v;
-    if (!J.qset[sc[i]->tq] || J.hmax % sc[i]->h || J.vmax % sc[i]->v) return false;
+    if (!sc[i]->qlatched || J.hmax % sc[i]->h || J.vmax % sc[i]->v) return false;
   }
   if (nblk > JD_MAX_MCU_BLOCKS) return false;
   const long mcus = (long)J.mcux * J.mcuy;
@@ -1631,9 +1667,8 @@ int jpeg_plan(const unsigned char* bytes, size_t n, int sub_bits, uint32_t* stag
   int rc = jpeg_coefficients(bytes, n, &J, false, force_host ? nullptr : &rq);
   if (rc) return rc;
   out->path = rq.taken ? RTP_JPEG_ENTROPY_DEVICE : RTP_JPEG_ENTROPY_HOST;
-  for (auto& c : J.comps) {
-    if (!J.qset[c.tq]) return cfail(RTP_EIO, "JPEG: missing quantisation table");
-  }
+  rc = latch_remaining(&J);
+  if (rc) return rc;
   if (J.comps.size() == 3)
     for (auto& c : J.comps)
       if (J.hmax % c.h || J.vmax % c.v) return cfail(RTP_EINVAL, "JPEG: fractional sampling ratios are not supported");
@@ -1658,8 +1693,8 @@ int jpeg_reconstruct_host(const JpegGeom& g, const short* coef, unsigned char* o
     const size_t nc = (size_t)jc.bw * jc.bh * 64;
     jc.coef.assign(coef + off, coef + off + nc);
     off += nc;
-    for (int k = 0; k < 64; ++k) J.qt[c][k] = g.qn[c][kZigzag[k]];
-    J.qset[c] = true;
+    for (int k = 0; k < 64; ++k) jc.q[k] = g.qn[c][kZigzag[k]];
+    jc.qlatched = true;
   }
   int w = 0, h = 0;
   return jpeg_reconstruct(&J, out_bgr, capacity, &w, &h);

@@ -1,5 +1,5 @@
 """Files and ctypes helpers shared by test_jpeg_decode_cpu.py and test_jpeg_decode.py: the baseline / progressive fixtures of
-tests/golden/codecs, a grid of files written by rtp_encode_jpeg, and the internal entries of the GPU JPEG decoder's host side."""
+tests/golden/codecs, the layout fixtures of tests/golden/codecs/layouts, a grid of files written by rtp_encode_jpeg, and the internal entries of the GPU JPEG decoder's host side."""
 import ctypes as C
 import functools
 import glob
@@ -14,10 +14,49 @@ SIZES = [(1, 1), (7, 5), (17, 17), (33, 31), (65, 9), (301, 173)]
 KINDS = ["noise", "checker", "flat"]
 QUALITIES = [25, 75, 100]
 DEVICE, HOST = 0, 1   # RTP_JPEG_ENTROPY_*
+# tests/golden/codecs/layouts (tools/make_codec_fixtures.py --layouts; pixels = libjpeg's): where the planner sends the entropy decoding.
+# DEVICE: one interleaved scan of at most 10 blocks per MCU with nothing irregular.  Y / Cb / Cr (h, v) in the comments.
+LAYOUTS = {
+    "l440_37x29": DEVICE, "l440_2x9": DEVICE, "l440_1x5": DEVICE,   # (1,2)(1,1)(1,1): h1v2 fancy up-sampling
+    "l411_37x9": DEVICE,                                            # (4,1)
+    "l42_40x20": DEVICE, "l24_21x40": DEVICE,                       # (4,2), (2,4): 10 blocks per MCU
+    "l14_9x40": DEVICE, "l31_37x29": DEVICE,                        # (1,4), (3,1)
+    "lmixed_33x17": DEVICE, "lmixed_3x9": DEVICE,                   # (2,2)(2,1)(1,2): 8 blocks
+    "llumaup_37x29": DEVICE,                                        # (1,1)(2,2)(2,2): 9 blocks, luma up-sampled
+    "lgray_h2v2_37x29": DEVICE,                                     # one component declared (2,2)
+    "l420_3scans": HOST, "l440_3scans_dri5": HOST,                  # one scan per component
+    "l420_dri1_40x24": DEVICE, "l42_dri1_40x20": DEVICE,            # a restart marker behind every MCU
+    "l420_dri2_fill": HOST,                                         # FF FF in front of every RSTn
+    "lsof1_tables3": DEVICE, "lsof0_tables3": DEVICE,               # chroma quantiser and Huffman tables under id 3
+    "lq16_300_260": DEVICE, "lq8_255": DEVICE,                      # 16-bit DQT; 8-bit tables of 255
+    "l3scans_requant": HOST,                                        # table 1 redefined between the Cb scan and the Cr scan
+    "lq_twice": DEVICE,                                             # table 1 defined twice in front of the only scan
+    "ladobe0_rgb": DEVICE, "ladobe1_420": DEVICE, "ladobe2_ycc": DEVICE, "lids_rgb": DEVICE, "lids_012_ycc": DEVICE,   # no JFIF
+    "ljfif_adobe0_ycc": DEVICE, "ljfif_ids_rgb_ycc": DEVICE,        # JFIF wins over the Adobe transform and the ids
+    "lkeep_rgb_q85": DEVICE,                                        # Pillow's own keep_rgb file
+}
 
 
 def fixture(name):
     return open(os.path.join(GOLD, name + ".jpg"), "rb").read()
+
+
+def layout(name):
+    """(file bytes, libjpeg's pixels as BGR) of a layout fixture"""
+    base = os.path.join(GOLD, "layouts", name)
+    return open(base + ".jpg", "rb").read(), np.load(base + ".npy")
+
+
+def layout_files():
+    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "layouts", "*.jpg")))
+
+
+def frame_components(data):
+    """[(id, h, v, tq)] of the frame header"""
+    i = 2
+    while data[i + 1] not in (0xC0, 0xC1, 0xC2):
+        i += 2 + ((data[i + 2] << 8) | data[i + 3])
+    return [(data[i + 10 + 3 * c], data[i + 11 + 3 * c] >> 4, data[i + 11 + 3 * c] & 15, data[i + 12 + 3 * c]) for c in range(data[i + 9])]
 
 
 def progressive_names():

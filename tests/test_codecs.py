@@ -2,7 +2,17 @@
 
 JPEG is pinned bit-for-bit against Pillow's (libjpeg-turbo) decode of the same files — the library
 cv::imread runs — through the fixtures made by tools/make_codec_fixtures.py; PNG is lossless and
-pinned against the source arrays.  Y4M colour conversion is PARITY UNPINNED (stated in codecs.cpp)."""
+pinned against the source arrays.
+
+What the JPEG fixtures pin: baseline and progressive files as Pillow writes them (4:4:4, 4:2:2, 4:2:0, grey; standard and
+optimised tables; restart intervals), and in tests/golden/codecs/layouts the layouts Pillow does not write: 4:4:0, 4:1:1, (4,2),
+(2,4), (1,4), (3,1), mixed chroma ratios, up-sampled luma and a grey file declared (2,2) (h1v2 fancy up-sampling, integral
+replication x3 and x4, MCUs of up to 10 blocks); one scan per component; restart intervals of 1 and fill bytes in front of RSTn;
+SOF1 and tables under id 3; 16-bit and 255-valued quantisers; a quantiser redefined between two scans (each component keeps the
+table of its first scan) or twice in front of one; and the colour model in libjpeg's order (JFIF seen -> YCbCr, else the Adobe
+transform, else the component ids).
+What stays UNPINNED: files whose IDCT output leaves +-380 around the level shift (libjpeg's range-limit table wraps there, and its
+SIMD and C IDCTs disagree with each other), and Y4M colour conversion (stated in codecs.cpp)."""
 import glob
 import os
 
@@ -27,6 +37,41 @@ def test_jpeg_decode_bit_exact_vs_libjpeg(name):
     assert np.array_equal(got, want), f"max diff {np.abs(got.astype(int) - want.astype(int)).max()}, {int((got != want).sum())} values"
     # and through the file loader the CLI uses
     assert np.array_equal(r.load_image(os.path.join(GOLD, name + ".jpg")), want)
+
+
+LAYOUTS = os.path.join(GOLD, "layouts")
+LAYOUT_NAMES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(LAYOUTS, "*.jpg")))
+
+
+def test_layout_fixtures_are_all_there():
+    import _jpegcases as jc
+    assert LAYOUT_NAMES == sorted(jc.LAYOUTS) and len(LAYOUT_NAMES) == 31
+    for name in LAYOUT_NAMES:
+        assert os.path.exists(os.path.join(LAYOUTS, name + ".npy")), name
+
+
+@pytest.mark.parametrize("name", LAYOUT_NAMES)
+def test_jpeg_layouts_bit_exact_vs_libjpeg(name):
+    """sampling factors, scan structures, quantisers and colour markers Pillow does not write itself (tools/make_codec_fixtures.py
+    --layouts): the pixels are libjpeg's"""
+    import caffe_rtpose_amd as r
+    want = np.load(os.path.join(LAYOUTS, name + ".npy"))
+    assert want.shape[0] <= 40 and want.shape[1] <= 48
+    data = open(os.path.join(LAYOUTS, name + ".jpg"), "rb").read()
+    got = r.decode_image(data)
+    assert got.shape == want.shape
+    diff = np.abs(got.astype(int) - want.astype(int))
+    assert np.array_equal(got, want), f"max diff {diff.max()}, {int(diff.any(-1).sum())} of {diff.shape[0] * diff.shape[1]} pixels"
+    assert np.array_equal(r.load_image(os.path.join(LAYOUTS, name + ".jpg")), want)
+
+
+@pytest.mark.parametrize("name", LAYOUT_NAMES)
+def test_layout_fixture_pixels_are_still_pillows(name):
+    """fixture drift: the committed pixels are what the installed Pillow (libjpeg-turbo) decodes from the committed file"""
+    Image = pytest.importorskip("PIL.Image")
+    want = np.load(os.path.join(LAYOUTS, name + ".npy"))
+    got = np.asarray(Image.open(os.path.join(LAYOUTS, name + ".jpg")).convert("RGB"))[:, :, ::-1]
+    assert np.array_equal(got, want)
 
 
 @pytest.mark.parametrize("name", _cases("png"))

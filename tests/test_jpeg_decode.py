@@ -2,7 +2,9 @@
 rtp_decode_image on the host: the pixels must be identical, for every fixture (baseline files through the device's Huffman decoder,
 progressive ones through the host's), a grid of generated files at the production subsequence size and at one that spreads small
 files over several workgroups, every destination layout, the reconstruction kernels alone on full-range coefficients, and
-submitted frames (joints, frame_scale, rendered frames).  Where the Huffman decoding ran is asserted every time."""
+submitted frames (joints, frame_scale, rendered frames).  Where the Huffman decoding ran is asserted every time.
+The layout fixtures (tests/golden/codecs/layouts) are compared with libjpeg's committed pixels instead: the device side has no other
+test of MCU shapes beyond 1, 3, 4 and 6 blocks, of the up-sampling ratios beyond 2, or of the colour model handed over by the host."""
 import ctypes as C
 import os
 import subprocess
@@ -92,6 +94,24 @@ def test_every_fixture_equals_the_host_decoder(engine, decoded):
     assert path == jc.HOST and np.array_equal(out.cpu().numpy(), decoded(data))
 
 
+@pytest.mark.parametrize("name", sorted(jc.LAYOUTS))
+def test_layout_fixtures_equal_libjpeg(engine, name):
+    """tests/golden/codecs/layouts against the committed libjpeg pixels (not the host decoder): MCUs of up to 10 blocks in every block
+    map, restart interval 1, tables under id 3, h1v2 / x3 / x4 / luma up-sampling, latched quantisers, the colour model.  The DEVICE
+    ones again with subsequences so small that their boundaries fall inside these MCUs and restart segments."""
+    data, want = jc.layout(name)
+    assert want.shape[0] <= 40 and want.shape[1] <= 48
+    out, path = engine.decode_jpeg_device(data)
+    assert path == jc.LAYOUTS[name], (name, path)
+    got = out.cpu().numpy()
+    assert np.array_equal(got, want), (name, int((got != want).any(-1).sum()))
+    if jc.LAYOUTS[name] == jc.DEVICE:
+        for s, g in ((32, 4), (64, 64)):
+            out, path, rounds = _decode(engine, data, sub_bits=s, group=g)
+            got = out.cpu().numpy()
+            assert path == jc.DEVICE and np.array_equal(got, want), (name, s, g, rounds, int((got != want).any(-1).sum()))
+
+
 def test_generated_grid_at_the_production_subsequence_size(engine, decoded):
     for name, data in jc.grid():
         out, path = engine.decode_jpeg_device(data)
@@ -171,13 +191,15 @@ def test_destination_layouts(engine, decoded):
     torch = _torch()
     data = dict(jc.grid())["noise_33x31_q75"]
     want = decoded(data)
-    for layout in ("bgr", "rgb", "bgra", "chw", "crop", "crop_odd"):
-        t, order = tdf._to_device(np.zeros_like(want), layout, fill=77)
-        out, path, _ = _decode(engine, data, out=t, order=order)
-        assert path == jc.DEVICE
-        assert np.array_equal(tdf._to_host_bgr(t, layout), want), layout
-        if layout == "bgra":
-            assert (t[..., 3] == 77).all(), "the 4th channel was written"
+    # and a 4:4:0 file and an RGB-model one (no colour conversion: the channel order is the kernel's own) against libjpeg's pixels
+    for data_, want_ in ((data, want), jc.layout("l440_37x29"), jc.layout("ladobe0_rgb")):
+        for layout in ("bgr", "rgb", "bgra", "chw", "crop", "crop_odd"):
+            t, order = tdf._to_device(np.zeros_like(want_), layout, fill=77)
+            out, path, _ = _decode(engine, data_, out=t, order=order)
+            assert path == jc.DEVICE
+            assert np.array_equal(tdf._to_host_bgr(t, layout), want_), layout
+            if layout == "bgra":
+                assert (t[..., 3] == 77).all(), "the 4th channel was written"
     # a window of a larger allocation: nothing outside the window changes
     big = torch.full((31 + 10, 33 + 23, 3), 5, dtype=torch.uint8, device="cuda")
     win = big[4:4 + 31, 9:9 + 33]
@@ -253,6 +275,22 @@ def test_submitted_jpeg_frames_equal_bgr_frames(decoded):
         assert sum(a[1] for a in want) > 0, "the test frames produced no people: nothing was drawn"
     finally:
         e.close()
+
+
+def test_submitted_layout_files_equal_frames_of_libjpegs_pixels(engine):
+    """a 4:4:0 file and an Adobe transform-0 (RGB) one through rtp_submit_frame_jpeg against rtp_submit_frame of the committed pixels"""
+    e = engine
+    assert e.in_flight() == 0
+    for i, name in enumerate(("l440_37x29", "ladobe0_rgb")):
+        data, pixels = jc.layout(name)
+        fs_want = e.submit_frame(pixels, tag=20 + i)
+        want = _collect(e)
+        fs_got = e.submit_frame_jpeg(data, tag=20 + i)
+        got = _collect(e)
+        assert fs_got == fs_want, (name, "frame_scale")
+        assert got[0] == want[0] == 20 + i, (name, "tag")
+        assert got[1] == want[1] and np.array_equal(got[2], want[2]), (name, "joints")
+        assert np.array_equal(got[3], want[3]), (name, "rendered frame", int((got[3] != want[3]).any(-1).sum()))
 
 
 def _corrupt(data):

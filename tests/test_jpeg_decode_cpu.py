@@ -1,6 +1,7 @@
 """The host side of the GPU JPEG decoder, without a GPU: the planner (which files get their Huffman decoding on the device), and the
 serial emulation of the device's self-synchronising decoder (the same per-symbol step, subsequences, rounds and final pass, compiled
-for the host) against the coefficients of codecs.cpp's own entropy decoder.  Equality is exact."""
+for the host) against the coefficients of codecs.cpp's own entropy decoder.  Equality is exact.  Files: Pillow's baseline fixtures, the
+generated 4:2:0 grid, and the layout fixtures (_jpegcases.LAYOUTS: MCUs of 1 to 10 blocks, restart interval 1, tables under id 3)."""
 import ctypes as C
 import os
 import random
@@ -62,6 +63,104 @@ def test_emulation_equals_host_entropy_decoder_on_generated_files(size):
     assert len(cases) == len(jc.KINDS) * len(jc.QUALITIES)
     for n, d in cases:
         _check_file(n, d)
+
+
+DEVICE_LAYOUTS = sorted(n for n, p in jc.LAYOUTS.items() if p == jc.DEVICE)
+HOST_LAYOUTS = sorted(n for n, p in jc.LAYOUTS.items() if p == jc.HOST)
+
+
+def test_layout_table_names_every_file():
+    assert jc.layout_files() == sorted(jc.LAYOUTS)
+    assert len(HOST_LAYOUTS) == 4 and len(DEVICE_LAYOUTS) == 27
+
+
+@pytest.mark.parametrize("name", DEVICE_LAYOUTS)
+def test_emulation_equals_host_entropy_decoder_on_device_layouts(name):
+    """MCUs of 1 to 10 blocks in every block map the fixtures have, restart interval 1, tables under id 3: planned for the device"""
+    _check_file(name, jc.layout(name)[0])
+
+
+@pytest.mark.parametrize("name", HOST_LAYOUTS)
+def test_host_layouts_take_the_host_entropy_path(name):
+    """one scan per component, fill bytes in front of RSTn, a quantiser redefined between scans"""
+    data = jc.layout(name)[0]
+    hrc, hmsg = jc.host_decode(data)
+    rc, info = jc.plan(data)
+    assert rc == hrc == 0, (name, hmsg, jc.codec_error())
+    assert info[0] == jc.HOST and info[5] == 0, (name, info)
+    rc, want = jc.host_coefficients(data)
+    rc2, got, info2, rounds = jc.emulate(data, 32, 4, info[7])
+    assert rc == 0 and rc2 == hrc and info2[0] == jc.HOST and rounds == [0, 0], (name, info2, rounds)
+    assert np.array_equal(got, want), name
+
+
+def _mcu_blocks(data):
+    comps = jc.frame_components(data)
+    return sum(h * v for _, h, v, _ in comps) if len(comps) > 1 else 1
+
+
+def test_layouts_reach_the_mcu_block_limit():
+    """the device layouts hold MCUs of 8, 9 and 10 (= JD_MAX_MCU_BLOCKS) blocks, and info[7] counts whole MCUs of them"""
+    seen = {}
+    for name in DEVICE_LAYOUTS:
+        data = jc.layout(name)[0]
+        comps = jc.frame_components(data)
+        rc, info = jc.plan(data)
+        assert rc == 0 and info[0] == jc.DEVICE
+        hmax, vmax = (max(c[1] for c in comps), max(c[2] for c in comps)) if len(comps) > 1 else (1, 1)
+        mcus = -(-info[1] // (8 * hmax)) * -(-info[2] // (8 * vmax))
+        assert info[7] == mcus * _mcu_blocks(data), (name, info)
+        seen.setdefault(_mcu_blocks(data), []).append(name)
+    assert set(seen) >= {1, 3, 4, 5, 6, 8, 9, 10} and max(seen) == 10, seen
+    assert len(seen[10]) >= 3 and any("dri1" in n for n in seen[10]), seen[10]
+    rc, info = jc.plan(jc.layout("l42_dri1_40x20")[0])
+    assert info[4] == 4, info   # every MCU its own restart segment
+
+
+def _bits_to_scan(bits):
+    bits += "1" * (-len(bits) % 8)
+    out = bytearray()
+    for i in range(0, len(bits), 8):
+        out.append(int(bits[i:i + 8], 2))
+        if out[-1] == 0xFF:
+            out.append(0)
+    return bytes(out)
+
+
+def test_more_than_ten_blocks_per_mcu_fall_back_to_the_host_path():
+    """every component 2x2: 12 blocks per MCU.  libjpeg refuses the file (no reference pixels); the host decoder accepts it, so the
+    planner must hand it to the host without an error.  Written here: one DC table {0: '0', 3: '10'}, one AC table {EOB: '0', 0/1: '10'}."""
+    W, H = 20, 17   # 2 x 2 MCUs of 16 x 16
+    seg = lambda m, p: bytes([0xFF, m]) + (len(p) + 2).to_bytes(2, "big") + bytes(p)
+    head = b"\xff\xd8" + seg(0xDB, [0] + [3] * 64)
+    head += seg(0xC0, [8, 0, H, 0, W, 3, 1, 0x22, 0, 2, 0x22, 0, 3, 0x22, 0])
+    head += seg(0xC4, [0x00, 1, 1] + [0] * 14 + [0, 3]) + seg(0xC4, [0x10, 1, 1] + [0] * 14 + [0x00, 0x01])
+    head += seg(0xDA, [3, 1, 0x00, 2, 0x00, 3, 0x00, 0, 63, 0])
+    rng = np.random.default_rng(12)
+    bits, want, pred = "", np.zeros((3, 4, 4, 64), np.int16), [0, 0, 0]   # want: component, block row, block column
+    for my in range(2):
+        for mx in range(2):
+            for c in range(3):
+                for by in range(2):
+                    for bx in range(2):
+                        diff = int(rng.choice([0, 0, 4, 7, -4, -6]))
+                        bits += "0" if diff == 0 else "10" + format(diff if diff > 0 else diff + 7, "03b")
+                        pred[c] += diff
+                        want[c, 2 * my + by, 2 * mx + bx, 0] = pred[c]
+                        ac = int(rng.choice([0, 1, -1]))
+                        want[c, 2 * my + by, 2 * mx + bx, 1] = ac
+                        bits += "0" if ac == 0 else "10" + ("1" if ac > 0 else "0") + "0"
+    data = head + _bits_to_scan(bits) + b"\xff\xd9"
+    hrc, hmsg = jc.host_decode(data)
+    assert hrc == 0, hmsg
+    rc, info = jc.plan(data)
+    assert rc == 0 and info[0] == jc.HOST and info[5] == 0 and info[7] == 48, info
+    rc, host = jc.host_coefficients(data)
+    assert rc == 0 and np.array_equal(host, want.reshape(-1))
+    for s, g in SETTINGS:
+        rc, got, info2, rounds = jc.emulate(data, s, g, info[7])
+        assert rc == 0 and info2[0] == jc.HOST and rounds == [0, 0], (s, g, info2, rounds)
+        assert np.array_equal(got, host), (s, g)
 
 
 def test_restart_fixture_has_several_anchored_segments():
