@@ -58,6 +58,31 @@ e_op — what the operands of the launch differ from the reference's (pass label
                        |d| <= 2^-11|v|: |lo - d| <= 2^-11|d| + 2^-25, |l8 - d| <= 2^-4|d| + 2^-22, and the export's fp32 sum a_hi + lo rounds once
                        (2^-24|a|): e_op + (2^-15 + 2^-22 + 2^-24)(1 + 2^-10), e_abs + (2^-22 + 2^-25) * sum|W|
 
+Beyond the e4m3 ranges (saturating=True; `2q` launches only).  The assertion |a| < 112 is replaced by four per-element terms, each computed from
+the launch's actual operands and each exactly 0 where the condition it is named for does not occur, so that every case inside the ranges keeps
+its bound bit for bit.  In the decomposition of the `2q` line above:
+  activation saturation   e4m3(4x) ends at 448, the clamp in front of the conversion holds larger values there: Qa(a_hi) = +-112 for |a_hi| >= 112 and
+                       a_hi - Qa(a_hi) = +-(|a_hi| - 112) instead of at most 2^-4|a_hi|.  The dropped part of the a_hi*W_lo correction is therefore
+                       relu(|a_hi| - 112) @ |W - f16(W)|  (the true W_lo, no bound on it).  a_hi is not exported, a = a_hi + l8 (or + lo) is:
+                       |l8| <= half a step of a_hi, so f16(a) = a_hi unless a lies exactly midway between two fp16 values; then a_hi is f16(a) or its
+                       mirror image 2a - f16(a), and the larger magnitude of the two is taken (_abs_hi).  The other terms of the 2q line only get
+                       smaller (|Qa(a_hi)| <= 112 < |a_hi|).
+  a lo + q input          the export returns a_hi + lo, the kernel reads l8 = e4m3(clamp(d * 2^12)) / 2^12, d = v - a_hi: beyond |d| = 448 / 4096 (from
+                       |v| = 256 on, where half a step of fp16 is 1/8) |l8 - d| = |d| - 448/4096 instead of 2^-4|d|.  x = |a - f16(a)| is |lo| up to the
+                       rounding of the export's fp32 sum (2^-24|a|), and |lo - d| <= 2^-11|d| + 2^-25: |d| <= (x + 2^-24|a| + 2^-25)(1 + 2^-10) =: d+.
+                       Added: relu(d+ - 448/4096) @ |W|.  The slack inside d+ (2^-10 x + 2^-24|a| + 2^-25) acts only where x is within 2^-9 of
+                       448/4096, i.e. from |a| = 256 on: 0 below.
+  fp16-subnormal W_hi     the 2q line takes |W_lo| <= 2^-11|W|; below the fp16 normal range (|W| < 2^-14) W_lo = W - f16(W) is up to 2^-25 whatever |W| is.
+                       With E = relu(|W - f16(W)| - 2^-11|W|) (0 for every normal weight: the spacing of fp16 is a power of two times 2^-10) the three
+                       terms that hold W_lo gain (2^-4 + (1 + 2^-4)*2^-4 + 2^-11)(1 + 2^-10) |a| @ E.  (A He weight set holds a few weights below 2^-14: on it
+                       this term moves a launch's bound by 2 parts in 10^6; the other three are exactly 0 there.)
+  W_lo8 saturation        e4m3(W_lo * 2^(t+11)) ends at 448.  |W_lo| <= 2^-11 max|W| <= 448 * 2^-(t+11) holds while some W_hi of the launch is normal and t is
+                       not clamped; with every weight below 2^-14, or t clamped at 40 (max|W| < 448 * 2^-41: W_hi = 0, W_lo = W), it does not.  Added:
+                       min((1 + 2^-4)|a_hi|, 112) @ relu(|W - f16(W)| - 448 * 2^-(t+11)).  (W_hi8 = e4m3(W_hi * 2^t) cannot saturate: t is chosen for it;
+                       t clamped at -20 needs max|W| > 2^28, which this project does not support.)
+The output side needs nothing new: out_rounding bounds a q block above |v| = 224 by the hi part alone.  All of this holds below the fp16 overflow:
+a value beyond 65504 is stored as infinity, and what the engine computes from there on is outside every bound here.
+
 `+pool` launches: the kernel takes the maximum of the four fp32 sums, then bias / ReLU / rounding (monotone); |max x~ - max x| <= max |x~ - x|,
 so the accumulation part of the tolerance is the largest of the four.  Stand-alone pooling steps move values: they must be EQUAL.
 `pw2` launches: the middle blob never leaves LDS; h = relu(b1 + x*w1) is recomputed with its own bound t1 (u = 2^-11, or 2^-22 where the
@@ -427,8 +452,9 @@ def _nhwc_padded(a, pad):
     return np.pad(a, ((0, 0), (pad, pad), (pad, pad), (0, 0)))
 
 
-def check_plan(summary, graph, weights, blob, fp32=False, n_interior=256, seed=0, only=None, max_samples=None, images_per_launch=None):
-    """Check every launch of a plan (or those whose layers intersect `only`).
+def check_plan(summary, graph, weights, blob, fp32=False, n_interior=256, seed=0, only=None, max_samples=None, images_per_launch=None, saturating=False):
+    """Check every launch of a plan (or those whose layers intersect `only`).  saturating: bound `2q` launches beyond the e4m3 ranges instead of asserting
+    |a| < 112 (module docstring); True / False, or a function of the Launch.
 
     weights: name -> (w [cout][cin][k][k] float32, b); blob(name) -> [N][C][H][W] float32 as rtp_get_blob returns it (the input blob under the
     graph's input name, the final maps under graph.lowres).  Returns [Report]."""
@@ -478,7 +504,7 @@ def check_plan(summary, graph, weights, blob, fp32=False, n_interior=256, seed=0
             if L.kind == "pw2":
                 _check_pw2(L, rep, graph, weights, blob, parts, name, L.layers2[bi], a, ys, xs, cls)
             else:
-                _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls)
+                _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls, saturating=saturating(L) if callable(saturating) else saturating)
     return reports
 
 
@@ -495,20 +521,65 @@ def _q_abs(label, w_launch, sum_a, sum_w, in_part=""):
     """absolute terms of the 2q bound (e4m3 subnormals in the scaled domain), t as the engine derives it from the launch's weights"""
     if "q" not in label:
         return 0.0
-    mx = max(float(np.abs(w).max()) for w in w_launch)
-    t = int(np.floor(np.log2(448.0 / mx))) if mx > 0 else 0
-    t = max(-20, min(t, 40))
+    t = _wq_t(w_launch)
     e = (2 + 2.0 ** -4) * 2.0 ** (-21 - t) * sum_a + 2.0 ** -23 * sum_w
     return e + (2.0 ** -22 + 2.0 ** -25) * sum_w if "lo" in in_part else e
 
 
-def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls):
+def _abs_hi(a64):
+    """|a_hi| of an exported a = a_hi + l8 (or + lo): |f16(a)|, or the larger of f16(a) and its mirror image where a is exactly midway between two fp16 values"""
+    h = f16(a64)
+    m = 2.0 * a64 - h
+    tie = (m != h) & (f16(m) == m)
+    return np.where(tie, np.maximum(np.abs(h), np.abs(m)), np.abs(h))
+
+
+def _wq_t(w_launch):
+    """the fp8 weight exponent of a 2q launch, as engine.cpp compute_wq_exp derives it from the launch's weights"""
+    mx = max(float(np.abs(w).max()) for w in w_launch)
+    t = int(np.floor(np.log2(448.0 / mx))) if mx > 0 else 0
+    return max(-20, min(t, 40))
+
+
+class _Saturation:
+    """the per-element terms of a 2q launch beyond the e4m3 ranges (module docstring): padded NHWC operands and weight matrices, applied patch by patch"""
+    SUBNORMAL_W = True      # (a test switches the fp16-subnormal W_hi term off to show that the other three are exactly 0 inside the ranges)
+
+    def __init__(self, a64, w64, w_launch, in_part, pad):
+        ah = _abs_hi(a64)
+        self.k = w64.shape[2]
+        self.sat_a = _nhwc_padded(np.maximum(ah - 112.0, 0.0), pad)
+        self.qa = _nhwc_padded(np.minimum((1 + 2.0 ** -4) * ah, 112.0), pad)
+        self.abs_a = _nhwc_padded(np.abs(a64), pad)
+        wlo = np.abs(_wmat(w64) - _wmat(f16(w64)))
+        self.wlo, self.wabs = wlo, np.abs(_wmat(w64))
+        self.sub_w = np.maximum(wlo - 2.0 ** -11 * self.wabs, 0.0)
+        self.sat_w = np.maximum(wlo - 448.0 * 2.0 ** -(_wq_t(w_launch) + 11), 0.0)
+        self.sat_l = None
+        if "lo" in in_part:
+            x = np.abs(a64 - f16(a64))
+            dp = (x + 2.0 ** -24 * np.abs(a64) + 2.0 ** -25) * (1 + 2.0 ** -10)
+            self.sat_l = _nhwc_padded(np.maximum(dp - 448.0 / 4096.0, 0.0), pad)
+        self.c_sub = (2.0 ** -4 + (1 + 2.0 ** -4) * 2.0 ** -4 + 2.0 ** -11) * (1 + 2.0 ** -10)
+
+    def tol(self, n, ys, xs):
+        t = _patches(self.sat_a, n, ys, xs, self.k) @ self.wlo
+        if self.SUBNORMAL_W and self.sub_w.any():
+            t = t + self.c_sub * (_patches(self.abs_a, n, ys, xs, self.k) @ self.sub_w)
+        if self.sat_w.any():
+            t = t + _patches(self.qa, n, ys, xs, self.k) @ self.sat_w
+        if self.sat_l is not None:
+            t = t + _patches(self.sat_l, n, ys, xs, self.k) @ self.wabs
+        return t
+
+
+def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls, saturating=False):
     g = graph.convs[name]
     w, b = weights[name]
     k, pad = g["k"], g["k"] // 2
     label = L.passes
     a64, w64 = _operands(label, fp32, a, w)
-    if "q" in label:
+    if "q" in label and not saturating:
         assert np.abs(a64).max() < 112.0, f"{name}: |activation| >= 112 saturates e4m3(a_hi * 4): the 2q bound does not cover it"
     ap = _nhwc_padded(a64, pad)
     wm = _wmat(w64)
@@ -521,6 +592,7 @@ def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls)
     e_abs_a = 2.0 ** -25 if ("w" in label and not fp32) else 0.0            # subnormal W_lo: half an fp16 subnormal step per term
     flush = 2.0 ** -126 * wm.shape[0] if fp32 else 0.0
     w_launch = [weights[n][0] for n in L.layers]
+    sat = _Saturation(a64, w64, w_launch, parts.get(g["bottom"], ""), pad) if ("q" in label and saturating) else None
     dests = graph.dests(name)
     N = a.shape[0]
     if L.pool:   # the un-pooled blob is never written: the destination is the pooled blob
@@ -539,6 +611,8 @@ def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls)
                         pa = np.abs(p)
                         S = pa @ wabs + np.abs(b64)
                         t = e_rel * S + e_abs_a * pa.sum(axis=1, keepdims=True) + _q_abs(label, w_launch, pa.sum(axis=1, keepdims=True), sum_w, in_part) + flush
+                        if sat is not None:
+                            t = t + sat.tol(n, 2 * yy + dy, 2 * xx + dx)
                         pre = v if pre is None else np.maximum(pre, v)
                         acc_tol = t if acc_tol is None else np.maximum(acc_tol, t)
             else:
@@ -547,6 +621,8 @@ def _check_conv(L, rep, graph, weights, blob, parts, fp32, name, a, ys, xs, cls)
                 pa = np.abs(p)
                 S = pa @ wabs + np.abs(b64)
                 acc_tol = e_rel * S + e_abs_a * pa.sum(axis=1, keepdims=True) + _q_abs(label, w_launch, pa.sum(axis=1, keepdims=True), sum_w, in_part) + flush
+                if sat is not None:
+                    acc_tol = acc_tol + sat.tol(n, yy, xx)
             r = np.maximum(pre, 0.0) if g["relu"] else pre
             imgs = np.full(len(yy), n)
             for d, off in dests:
@@ -646,7 +722,9 @@ def _split16(v32):
 class Emulation:
     """Runs the launches of an fp16 / F16X3 / mixed plan (pass labels 1, 2w, 2a, 3aw, 2q) the way the kernels do, launch by launch, each on the previous
     launches' stored outputs.  pre[layer] keeps the fp32 value of every convolution before ReLU / pooling / rounding so that a test can plant a
-    defect there and store the result again (restore).  hi / lo / q8 hold a blob's fp16 value, its fp16 rounding error and that error as the
+    defect there and store the result again (restore).  The conversions (e4m3, r16), the exponents the fp8 weights are packed and descaled with (wq_pack,
+    WLO_EXP) and the ordering of the stand-alone q pooling (pool_value) are methods, so that a subclass can plant a defect in any of them
+    (tests/test_conv_ranges_cpu.py).  hi / lo / q8 hold a blob's fp16 value, its fp16 rounding error and that error as the
     stored e4m3(lo * 2^12) / 2^12 — each kept where a tensor the blob is stored to carries that block."""
 
     def __init__(self, summary, graph, weights, frame, stop_after=None):
@@ -659,6 +737,30 @@ class Emulation:
             self.run(L)
             if stop_after in L.layers + L.layers2:   # (the network has 52 M weights: a test that needs the first stages only stops there)
                 break
+
+    WLO_EXP = 11        # W_lo8 = e4m3(W_lo * 2^(t + 11)), descaled by the E8M0 scale 127 - t - WLO_EXP (conv_ring.hip sb_odd)
+
+    def e4m3(self, x32):
+        return _e4m3(x32)
+
+    def r16(self, v32):
+        return _round16(v32)
+
+    def split16(self, v32):
+        hi = self.r16(v32)
+        return hi, self.r16(np.asarray(v32, np.float32) - hi)
+
+    def mfma_in(self, x16):
+        """an fp16 operand as the MFMA reads it: subnormals included"""
+        return x16
+
+    def wq_pack(self, name):
+        """the exponent layer `name`'s fp8 weights are packed with: the launch's (the kernel descales with wq_exp[name])"""
+        return self.wq_exp[name]
+
+    def pool_value(self, hi, part):
+        """what the stand-alone pooling step orders by: the whole value (maxpool_q_kernel: hi, ties broken by the q byte)"""
+        return hi + part
 
     def blob(self, name):
         """what rtp_get_blob returns: hi + lo in fp32, concat blobs assembled from their inputs, the final maps in fp32"""
@@ -685,18 +787,18 @@ class Emulation:
     def gemm(self, name, label, a_hi, a_lo, skip=()):
         """fp32 value of one convolution: the passes a_hi*W_hi [+ a_lo*W_hi] [+ a_hi*W_lo] + bias.  skip: passes left out (planted defects)"""
         w, b = self.weights[name]
-        w_hi, w_lo = _split16(np.asarray(w, np.float32))
+        w_hi, w_lo = self.split16(np.asarray(w, np.float32))
         pad = w.shape[2] // 2
-        v = self.conv32(a_hi, w_hi, pad)
+        v = self.conv32(self.mfma_in(a_hi), self.mfma_in(w_hi), pad)
         if "q" in label:   # a_lo is the stored e4m3(lo * 2^12) / 2^12 here; the fp8 products are exact, the scales powers of two
-            t = self.wq_exp[name]
-            v = v + self.conv32(a_lo, _e4m3(w_hi * np.float32(2.0 ** t)) * np.float32(2.0 ** -t), pad)
-            v = v + self.conv32(_e4m3(a_hi * np.float32(4)) * np.float32(0.25), _e4m3((np.asarray(w, np.float32) - w_hi) * np.float32(2.0 ** (t + 11))) * np.float32(2.0 ** -(t + 11)), pad)
+            t, tp = self.wq_exp[name], self.wq_pack(name)
+            v = v + self.conv32(a_lo, self.e4m3(w_hi * np.float32(2.0 ** tp)) * np.float32(2.0 ** -t), pad)
+            v = v + self.conv32(self.e4m3(a_hi * np.float32(4)) * np.float32(0.25), self.e4m3((np.asarray(w, np.float32) - w_hi) * np.float32(2.0 ** (tp + 11))) * np.float32(2.0 ** -(t + self.WLO_EXP)), pad)
             return v + np.asarray(b, np.float32)[None, :, None, None]
         if "a" in label[1:] and "a" not in skip:
-            v = v + self.conv32(a_lo, w_hi, pad)
+            v = v + self.conv32(self.mfma_in(a_lo), self.mfma_in(w_hi), pad)
         if "w" in label and "w" not in skip:
-            v = v + self.conv32(a_hi, w_lo, pad)
+            v = v + self.conv32(self.mfma_in(a_hi), self.mfma_in(w_lo), pad)
         return v + np.asarray(b, np.float32)[None, :, None, None]
 
     def operand(self, name):
@@ -723,7 +825,7 @@ class Emulation:
         g = self.graph.convs[name]
         if g["relu"]:
             v = np.maximum(v, np.float32(0))
-        hi, lo = _split16(v.astype(np.float32))
+        hi, lo = self.split16(v.astype(np.float32))
         dest = dest or name
         self.hi[dest] = hi
         wants = "+".join([self.parts.get(dest, "")] + [self.parts.get(c, "") for c, bots in self.graph.concats.items() if dest in bots])
@@ -732,7 +834,7 @@ class Emulation:
         else:
             self.lo.pop(dest, None)
         if "q" in wants:
-            self.q8[dest] = _e4m3((v.astype(np.float32) - hi) * np.float32(4096)) * np.float32(1.0 / 4096)
+            self.q8[dest] = self.e4m3((v.astype(np.float32) - hi) * np.float32(4096)) * np.float32(1.0 / 4096)
         else:
             self.q8.pop(dest, None)
         if dest == self.graph.lowres or dest in self.graph.concats.get(self.graph.lowres, ()):
@@ -754,7 +856,7 @@ class Emulation:
             q8 = self.operand_q(L.pool_in)
             in_part, out_part = self.parts.get(L.pool_in, ""), self.parts.get(L.pool_out, "")
             N, C, H, W = hi.shape
-            val = (hi + (lo if "lo" in in_part else q8)).reshape(N, C, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4)
+            val = self.pool_value(hi, lo if "lo" in in_part else q8).reshape(N, C, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4)
             sel = val.argmax(axis=-1)[..., None]
             take = lambda t: np.take_along_axis(t.reshape(N, C, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4), sel, -1)[..., 0]
             self.hi[L.pool_out] = take(hi)
@@ -765,9 +867,8 @@ class Emulation:
             return
         lab1 = L.passes.split("/")[0]
         if "q" in lab1:
-            mx = max(float(np.abs(self.weights[n][0]).max()) for n in L.layers)
             for n in L.layers:
-                self.wq_exp[n] = max(-20, min(int(np.floor(np.log2(448.0 / mx))), 40))
+                self.wq_exp[n] = _wq_t([self.weights[m][0] for m in L.layers])
         for bi, name in enumerate(L.layers):
             a_hi, a_lo = self.operand(self.graph.convs[name]["bottom"])
             if "q" in lab1:
@@ -780,7 +881,7 @@ class Emulation:
             lab2 = L.passes.split("/")[1]
             if self.graph.convs[name]["relu"]:
                 v = np.maximum(v, np.float32(0))
-            h_hi, h_lo = _split16(v)
+            h_hi, h_lo = self.split16(v)
             name2 = L.layers2[bi]
             v2 = self.gemm(name2, lab2, h_hi, h_lo)
             self.pre[name2] = v2
