@@ -182,6 +182,25 @@ class rtp_overlay_config(C.Structure):
     ]
 
 
+class rtp_redact_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("effect", C.c_int),
+        ("shape", C.c_int),
+        ("parts", C.POINTER(C.c_int)),
+        ("num_parts", C.c_int),
+        ("min_score", C.c_float),
+        ("min_parts", C.c_int),
+        ("scale_q8", C.c_int),
+        ("aspect_q8", C.c_int),
+        ("pad", C.c_int),
+        ("min_radius", C.c_int),
+        ("cell", C.c_int),
+        ("radius", C.c_int),
+        ("colour", C.c_uint),
+    ]
+
+
 class rtp_trail_slot(C.Structure):
     _fields_ = [
         ("owner", C.c_int),
@@ -352,6 +371,13 @@ SIGNATURES = {
     "rtp_overlay_set_state": (C.c_int, [vp, C.POINTER(rtp_trail_state)]),
     "rtp_peek_overlay_items": (C.c_int, [vp, C.POINTER(C.c_uint64), ip, ip, C.c_int]),
     "rtp_overlay_from_joints": (C.c_int, [vp, fp, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int, ip, ip, ip, C.c_int]),
+    "rtp_redact_config_default": (C.c_int, [C.POINTER(rtp_redact_config)]),
+    "rtp_redact_regions": (C.c_int, [fp, C.c_int, C.c_int, C.POINTER(rtp_redact_config), ip]),
+    "rtp_redact_apply": (C.c_int, [ip, C.c_int, C.POINTER(rtp_redact_config), C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_long]),
+    "rtp_set_redaction": (C.c_int, [vp, C.POINTER(rtp_redact_config)]),
+    "rtp_redaction_info": (C.c_int, [vp, C.POINTER(rtp_redact_config), ip]),
+    "rtp_peek_redactions": (C.c_int, [vp, C.POINTER(C.c_uint64), ip, ip, C.c_int]),
+    "rtp_redact_from_joints": (C.c_int, [vp, fp, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int, ip, ip, C.c_int]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

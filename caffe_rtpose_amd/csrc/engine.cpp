@@ -646,6 +646,7 @@ int frame_outputs_ensure(rtp_engine* e, Ctx& cx, int nframes) {
   if (e->track_on && (rc = track_ensure(e, cx, nframes))) return rc;
   if (e->smooth_on && (rc = smooth_ensure(e, cx, nframes))) return rc;
   if (e->overlay_on && (rc = overlay_ensure(e, cx, nframes))) return rc;
+  if (e->redact_on && (rc = redact_ensure(e, cx, nframes))) return rc;
   return RTP_OK;
 }
 
@@ -664,6 +665,10 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
   // the rendered image, so the stage's EXPORT part (YUV, JPEG or the copy to the host) moves behind it while the DRAW part (the pose overlay
   // or a --part_to_show view) stays where it is.  With the mode off the launches are, one for one and in order, what they were.
   const bool overlay = e->overlay_on && e->track_on && sl.busy;
+  // Redaction mode (engine_redact.cpp): its regions come from the people the frame is rendered with, and its apply kernel works in place on
+  // the rendered image BEHIND the pose overlay and IN FRONT OF overlay mode's drawing; the EXPORT part moves behind both.  Like the tracker it
+  // runs on frames in flight only: the synchronous taps carry no redaction.
+  const bool redact = e->redact_on && sl.busy;
   auto render_draw = [&](const float* poses) -> int {
     if (e->cfg.render > 1 && !materialized && (rc = run_resize(e, cx, j))) return rc;
     return render_launch(e, sl, sl.disp_cur, e->cfg.render - 1, 0, poses);
@@ -680,7 +685,7 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
     return RTP_OK;
   };
   const bool render = e->cfg.render && sl.has_disp;
-  if (render && !late_render && ((rc = render_draw(nullptr)) || (!overlay && (rc = render_export())))) return rc;
+  if (render && !late_render && ((rc = render_draw(nullptr)) || (!overlay && !redact && (rc = render_export())))) return rc;
   if (e->maps_on && (rc = maps_launch(e, cx, j))) return rc;   // the frame's maps -> its pinned buffer (engine_maps.cpp)
   if (e->crops_on && !late_crops && (rc = crops_launch(e, cx, j))) return rc;   // the frame's boxes and crops -> their pinned buffers (engine_crops.cpp)
   // the frame's people against the engine's track table (engine_track.cpp).  Only a frame in flight (rtp_submit*) advances the tracker:
@@ -692,8 +697,9 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
   // the frame's draw list and the trail table, from the people the frame is rendered with, and the chain's event
   if (overlay && (rc = overlay_update_launch(e, cx, j, late_render ? sl.smooth.joints_dev : sl.joints))) return rc;
   if (render && late_render && (rc = render_draw(sl.smooth.joints_dev))) return rc;
+  if (redact && (rc = redact_launch(e, cx, j, late_render ? sl.smooth.joints_dev : sl.joints, render))) return rc;
   if (render && overlay && (rc = overlay_draw_launch(e, cx, j))) return rc;
-  if (render && (late_render || overlay) && (rc = render_export())) return rc;
+  if (render && (late_render || overlay || redact) && (rc = render_export())) return rc;
   if (late_crops && (rc = crops_launch(e, cx, j, sl.smooth.joints_dev))) return rc;
   return RTP_OK;
 }
@@ -1135,6 +1141,7 @@ void free_ctx(Ctx& cx) {
     sl.track.free();
     sl.smooth.free();
     sl.overlay.free();
+    sl.redact.free();
     jd_free(&sl.jd);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
     for (int i = 0; i < 5; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);

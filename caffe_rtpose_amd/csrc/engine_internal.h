@@ -1,4 +1,4 @@
-// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_smooth.cpp, engine_overlay.cpp, engine_calib.cpp) share: the frame slot, the batch context and
+// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_smooth.cpp, engine_overlay.cpp, engine_redact.cpp, engine_calib.cpp) share: the frame slot, the batch context and
 // rtp_engine itself, the error / lock macros, and the declarations of every helper one of those files defines and another one calls.
 // Internal: only the engine's own files include it (it opens namespace rtp for them); nothing here is part of the library's ABI.
 #pragma once
@@ -43,6 +43,8 @@ extern "C" const char* rtp_internal_track_check(const rtp_track_config* c);
 extern "C" const char* rtp_internal_smooth_check(const rtp_smooth_config* c);
 extern "C" const char* rtp_internal_overlay_check(const rtp_overlay_config* c);
 extern "C" const char* rtp_internal_trail_check(const rtp_trail_state* st);
+extern "C" const char* rtp_internal_redact_check(const rtp_redact_config* c, int model_parts);
+extern "C" int rtp_internal_redact_list(const rtp_redact_config* c, int model_parts, int list[RTP_MAX_NUM_PARTS]);
 extern "C" int rtp_internal_yuv_fields(const rtp_yuv_view* v, char* msg, size_t msg_len, long hi[3]);
 extern "C" int rtp_internal_jpeg_geom(int W, int H, int ncomp, const int* hv, const unsigned short* qn, int rgb, rtp::JpegGeom* g);
 
@@ -151,6 +153,14 @@ struct OverlayOut {
   void free();   // (engine_overlay.cpp)
 };
 
+// rtp_set_redaction: the frame's region records and, behind their room, their number — [RTP_MAX_PEOPLE][RTP_REDACT_REGION_INTS] ints
+// and one more — with their pinned copy, and (RTP_REDACT_BLUR only) the scratch image of the display size the blur's first launch writes
+struct RedactOut {
+  int *dev = nullptr, *host = nullptr;
+  unsigned char* scratch = nullptr;
+  void free();   // (engine_redact.cpp)
+};
+
 // One frame's post-processing state (a batch context carries batch_frames of them)
 struct Slot {
   hipStream_t stream = nullptr;  // resize -> nms -> connect -> D2H of this frame (slot 0 shares the context's stream)
@@ -199,6 +209,7 @@ struct Slot {
   TrackOut track;
   SmoothOut smooth;
   OverlayOut overlay;
+  RedactOut redact;
   uint64_t tag = 0;
   bool busy = false;
 };
@@ -312,6 +323,11 @@ struct rtp_engine {
   bool overlay_on = false;
   rtp_overlay_config overlay_cfg = {};
   TrailTable* overlay_dev = nullptr;
+  // rtp_set_redaction (engine_redact.cpp): redaction mode on (only while cfg.render), its configuration (parts = nullptr inside; the
+  // list is redact_list).  No table: its kernels read and write what the frame's slot owns
+  bool redact_on = false;
+  rtp_redact_config redact_cfg = {};
+  std::vector<int> redact_list;
   int track_variant = RTP_TRACK_DEFAULT;   // kernels.h RTP_TRACK_*: the assignment's form (rtp_internal_track_variant; tools/bench_track.py times all)
   // rtp_encode_jpeg_device: the engine's own encoder, sized for the last frame size it was asked for
   JpegBufs jenc;
@@ -466,6 +482,11 @@ int overlay_ensure(rtp_engine* e, Ctx& cx, int nframes);
 int overlay_update_launch(rtp_engine* e, Ctx& cx, int sj, const float* poses);   // behind track_launch / smooth_launch(.., true) on the same stream: the chain's event
 int overlay_draw_launch(rtp_engine* e, Ctx& cx, int sj);   // the frame's list into its rendered image, in place
 void overlay_free(rtp_engine* e);
+
+// engine_redact.cpp
+int redact_ensure(rtp_engine* e, Ctx& cx, int nframes);
+// frame sj's records from the joints `poses` -> pinned memory and, with_image, the regions redacted in its rendered image, in place
+int redact_launch(rtp_engine* e, Ctx& cx, int sj, const float* poses, bool with_image);
 
 }  // namespace eng
 }  // namespace rtp

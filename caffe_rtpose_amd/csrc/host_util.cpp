@@ -1,7 +1,7 @@
 // host_util.cpp — the host-only pieces of the path behind the C-ABI: model descriptor tables,
 // default thresholds, process_and_pad_image, the JSON body, the narrow formats of maps mode and the boxes and pixels of
-// crops mode (rtp_crop_people), tracking mode (rtp_track_update), smoothing mode (rtp_smooth_update) and overlay mode
-// (rtp_overlay_update, rtp_overlay_draw).  No GPU needed.
+// crops mode (rtp_crop_people), tracking mode (rtp_track_update), smoothing mode (rtp_smooth_update), overlay mode
+// (rtp_overlay_update, rtp_overlay_draw) and redaction mode (rtp_redact_regions, rtp_redact_apply).  No GPU needed.
 #include <algorithm>
 #include <vector>
 #include <charconv>
@@ -791,6 +791,183 @@ int rtp_overlay_draw(const int* items, int num_items, unsigned char* image_bgr, 
         for (int ch = 0; ch < 3; ++ch) p[ch] = (unsigned char)((p[ch] * (256 - a) + col[ch] * a + 128) >> 8);
       }
   }
+  return RTP_OK;
+}
+
+}  // extern "C"
+
+// ---- redaction mode: the one definition of its regions and its pixels (redact.hip computes the same integers and bytes on the device)
+
+// What is wrong with the configuration for a model of model_parts parts, or nullptr.  The engine's switch reports the same text.
+extern "C" const char* rtp_internal_redact_check(const rtp_redact_config* c, int model_parts) {
+  if (!c) return "NULL rtp_redact_config";
+  if (c->struct_size != sizeof(rtp_redact_config)) return "rtp_redact_config.struct_size is not this library's sizeof(rtp_redact_config)";
+  if (model_parts < 1 || model_parts > RTP_MAX_NUM_PARTS) return "num_parts outside 1 .. RTP_MAX_NUM_PARTS";
+  if (c->effect != RTP_REDACT_MOSAIC && c->effect != RTP_REDACT_BLUR && c->effect != RTP_REDACT_FILL) return "effect is none of RTP_REDACT_MOSAIC, RTP_REDACT_BLUR and RTP_REDACT_FILL";
+  if (c->shape != RTP_REDACT_ELLIPSE && c->shape != RTP_REDACT_RECT) return "shape is neither RTP_REDACT_ELLIPSE nor RTP_REDACT_RECT";
+  if (!(c->min_score >= 0.f) || std::isinf(c->min_score)) return "min_score must be a finite number >= 0";
+  if (c->min_parts < 1) return "min_parts must be >= 1";
+  if (c->scale_q8 < 64 || c->scale_q8 > 4096) return "scale_q8 must be 64 .. 4096";
+  if (c->aspect_q8 < 64 || c->aspect_q8 > 1024) return "aspect_q8 must be 64 .. 1024";
+  if (c->pad < 0 || c->pad > 256) return "pad must be 0 .. 256";
+  if (c->min_radius < 0 || c->min_radius > 256) return "min_radius must be 0 .. 256";
+  if (c->cell != 2 && c->cell != 4 && c->cell != 8 && c->cell != 16 && c->cell != 32) return "cell must be 2, 4, 8, 16 or 32";
+  if (c->radius < 1 || c->radius > 16) return "radius must be 1 .. 16";
+  if (c->parts) {
+    if (c->num_parts < 1 || c->num_parts > RTP_MAX_NUM_PARTS) return "the part list's num_parts outside 1 .. RTP_MAX_NUM_PARTS";
+    bool seen[RTP_MAX_NUM_PARTS] = {};
+    for (int i = 0; i < c->num_parts; ++i) {
+      if (c->parts[i] < 0 || c->parts[i] >= model_parts) return "a listed part is outside the model's parts";
+      if (seen[c->parts[i]]) return "a part is listed twice";
+      seen[c->parts[i]] = true;
+    }
+  }
+  return nullptr;
+}
+
+// The list the configuration names for a model of model_parts parts (checked): its own, or the model's head parts; 0 = NULL parts and
+// neither 18 nor 15 parts
+extern "C" int rtp_internal_redact_list(const rtp_redact_config* c, int model_parts, int list[RTP_MAX_NUM_PARTS]) {
+  if (c->parts) {
+    memcpy(list, c->parts, (size_t)c->num_parts * sizeof(int));
+    return c->num_parts;
+  }
+  int head[8];
+  const int n = model_parts == 18 ? rtp_crops_head_parts(RTP_MODEL_COCO_18, head) : model_parts == 15 ? rtp_crops_head_parts(RTP_MODEL_MPI_15, head) : 0;
+  if (n > 0) memcpy(list, head, (size_t)n * sizeof(int));
+  return n > 0 ? n : 0;
+}
+
+extern "C" {
+
+int rtp_redact_config_default(rtp_redact_config* cfg) {
+  if (!cfg) return RTP_EINVAL;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->struct_size = (unsigned)sizeof *cfg;
+  cfg->effect = RTP_REDACT_MOSAIC;
+  cfg->shape = RTP_REDACT_ELLIPSE;
+  cfg->parts = nullptr;
+  cfg->num_parts = 0;
+  cfg->min_score = 0.f;
+  cfg->min_parts = 1;
+  cfg->scale_q8 = 384;
+  cfg->aspect_q8 = 320;
+  cfg->pad = 2;
+  cfg->min_radius = 4;
+  cfg->cell = 8;
+  cfg->radius = 8;
+  cfg->colour = 0;
+  return RTP_OK;
+}
+
+int rtp_redact_regions(const float* joints, int num_people, int num_parts, const rtp_redact_config* cfg, int* regions) {
+  if (rtp_internal_redact_check(cfg, num_parts) || !regions) return RTP_EINVAL;
+  int list[RTP_MAX_NUM_PARTS];
+  const int nlist = rtp_internal_redact_list(cfg, num_parts, list);
+  if (nlist < 1) return RTP_EINVAL;
+  const int n = num_people < 0 ? 0 : num_people > RTP_MAX_PEOPLE ? RTP_MAX_PEOPLE : num_people;
+  if (n > 0 && !joints) return RTP_EINVAL;
+  for (int k = 0; k < n; ++k) {
+    const float* j = joints + (size_t)k * num_parts * 3;
+    int* rec = regions + (size_t)k * RTP_REDACT_REGION_INTS;
+    float fx0 = 0.f, fx1 = 0.f, fy0 = 0.f, fy1 = 0.f;
+    int c = 0;
+    for (int i = 0; i < nlist; ++i) {
+      const float x = j[3 * list[i]], y = j[3 * list[i] + 1], s = j[3 * list[i] + 2];
+      if (!(s > cfg->min_score) || !std::isfinite(x) || !std::isfinite(y)) continue;
+      if (c++ == 0) { fx0 = fx1 = x; fy0 = fy1 = y; continue; }
+      if (x < fx0) fx0 = x;
+      if (x > fx1) fx1 = x;
+      if (y < fy0) fy0 = y;
+      if (y > fy1) fy1 = y;
+    }
+    if (c < cfg->min_parts) {
+      const int none[RTP_REDACT_REGION_INTS] = {0, 0, 0, 0, c, 0};
+      memcpy(rec, none, sizeof none);
+      continue;
+    }
+    const int x0 = overlay_round(fx0), x1 = overlay_round(fx1), y0 = overlay_round(fy0), y1 = overlay_round(fy1);
+    const int s = std::max(x1 - x0, y1 - y0) + 1;   // 1 .. 65535: s * scale_q8 < 2^28
+    const int rx = clampi(((s * cfg->scale_q8) >> 9) + cfg->pad, cfg->min_radius, RTP_REDACT_MAX_RADIUS);
+    const int ry = std::min((rx * cfg->aspect_q8) >> 8, RTP_REDACT_MAX_RADIUS);
+    const int rec_k[RTP_REDACT_REGION_INTS] = {(x0 + x1) >> 1, (y0 + y1) >> 1, rx, ry, c, 1};   // (>> of a negative sum: floor)
+    memcpy(rec, rec_k, sizeof rec_k);
+  }
+  return n;
+}
+
+int rtp_redact_apply(const int* regions, int num_regions, const rtp_redact_config* cfg, unsigned char* image_bgr, int w, int h, long stride) {
+  if (rtp_internal_redact_check(cfg, RTP_MAX_NUM_PARTS) || !image_bgr || num_regions < 0 || num_regions > RTP_MAX_PEOPLE || (num_regions > 0 && !regions) || w < 1 || h < 1 ||
+      w > 32768 || h > 32768 || stride < 3L * w)
+    return RTP_EINVAL;
+  // the valid regions, clamped, and the box [bx0, bx1] x [by0, by1] of the image that holds every covered pixel
+  struct Reg { int cx, cy, rx, ry; };
+  std::vector<Reg> regs;
+  int bx0 = w, bx1 = -1, by0 = h, by1 = -1;
+  for (int i = 0; i < num_regions; ++i) {
+    const int* r = regions + (size_t)i * RTP_REDACT_REGION_INTS;
+    if (!r[5]) continue;
+    const Reg g = {clampi(r[0], -65535, 65535), clampi(r[1], -65535, 65535), clampi(r[2], 0, RTP_REDACT_MAX_RADIUS), clampi(r[3], 0, RTP_REDACT_MAX_RADIUS)};
+    if (g.cx + g.rx < 0 || g.cx - g.rx >= w || g.cy + g.ry < 0 || g.cy - g.ry >= h) continue;
+    regs.push_back(g);
+    bx0 = std::min(bx0, std::max(g.cx - g.rx, 0)); bx1 = std::max(bx1, std::min(g.cx + g.rx, w - 1));
+    by0 = std::min(by0, std::max(g.cy - g.ry, 0)); by1 = std::max(by1, std::min(g.cy + g.ry, h - 1));
+  }
+  if (regs.empty()) return RTP_OK;
+  const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+  std::vector<unsigned char> covered((size_t)bw * bh, 0);
+  const bool ellipse = cfg->shape == RTP_REDACT_ELLIPSE;
+  for (const Reg& g : regs) {
+    const long long rx = g.rx, ry = g.ry, lim = rx * ry * rx * ry;
+    for (int py = std::max(g.cy - g.ry, 0); py <= std::min(g.cy + g.ry, h - 1); ++py)
+      for (int px = std::max(g.cx - g.rx, 0); px <= std::min(g.cx + g.rx, w - 1); ++px) {
+        const long long dx = (long long)(px - g.cx) * ry, dy = (long long)(py - g.cy) * rx;
+        if (!ellipse || dx * dx + dy * dy <= lim) covered[(size_t)(py - by0) * bw + (px - bx0)] = 1;
+      }
+  }
+  if (cfg->effect == RTP_REDACT_FILL) {
+    const unsigned char col[3] = {(unsigned char)(cfg->colour & 255), (unsigned char)((cfg->colour >> 8) & 255), (unsigned char)((cfg->colour >> 16) & 255)};
+    for (int py = by0; py <= by1; ++py)
+      for (int px = bx0; px <= bx1; ++px)
+        if (covered[(size_t)(py - by0) * bw + (px - bx0)]) memcpy(image_bgr + (size_t)py * stride + (size_t)px * 3, col, 3);
+    return RTP_OK;
+  }
+  // The image as it was, as a summed-area table over the box grown by what a covered pixel's value reads (the blur's radius, or out
+  // to its cell's borders): S[y][x][c] = the sum over rows < y and columns < x, in uint32 arithmetic modulo 2^32 — a window's
+  // sum, at most 33 * 33 * 255 (blur) or 32 * 32 * 255 (mosaic), comes out of the four corners exactly whatever has wrapped.
+  const bool mosaic = cfg->effect == RTP_REDACT_MOSAIC;
+  const int cell = cfg->cell, rad = cfg->radius;
+  const int sx0 = mosaic ? bx0 / cell * cell : std::max(bx0 - rad, 0), sy0 = mosaic ? by0 / cell * cell : std::max(by0 - rad, 0);
+  const int sx1 = mosaic ? std::min((bx1 / cell + 1) * cell, w) : std::min(bx1 + rad + 1, w);   // exclusive
+  const int sy1 = mosaic ? std::min((by1 / cell + 1) * cell, h) : std::min(by1 + rad + 1, h);
+  const int sw = sx1 - sx0, sh = sy1 - sy0;
+  std::vector<unsigned> S((size_t)(sw + 1) * (sh + 1) * 3, 0u);
+  for (int y = 0; y < sh; ++y) {
+    const unsigned char* row = image_bgr + (size_t)(sy0 + y) * stride + (size_t)sx0 * 3;
+    unsigned run[3] = {0u, 0u, 0u};
+    for (int x = 0; x < sw; ++x)
+      for (int c = 0; c < 3; ++c) {
+        run[c] += row[3 * x + c];
+        S[((size_t)(y + 1) * (sw + 1) + x + 1) * 3 + c] = S[((size_t)y * (sw + 1) + x + 1) * 3 + c] + run[c];
+      }
+  }
+  for (int py = by0; py <= by1; ++py)
+    for (int px = bx0; px <= bx1; ++px) {
+      if (!covered[(size_t)(py - by0) * bw + (px - bx0)]) continue;
+      int x0, x1, y0, y1;   // the window inside the image, x1 and y1 exclusive
+      if (mosaic) {
+        x0 = px / cell * cell; x1 = std::min(x0 + cell, w); y0 = py / cell * cell; y1 = std::min(y0 + cell, h);
+      } else {
+        x0 = std::max(px - rad, 0); x1 = std::min(px + rad + 1, w); y0 = std::max(py - rad, 0); y1 = std::min(py + rad + 1, h);
+      }
+      const unsigned cnt = (unsigned)(x1 - x0) * (unsigned)(y1 - y0);
+      unsigned char* p = image_bgr + (size_t)py * stride + (size_t)px * 3;
+      for (int c = 0; c < 3; ++c) {
+        auto at = [&](int y, int x) { return S[((size_t)(y - sy0) * (sw + 1) + (x - sx0)) * 3 + c]; };
+        const unsigned sum = at(y1, x1) - at(y0, x1) - at(y1, x0) + at(y0, x0);
+        p[c] = (unsigned char)((sum + (cnt >> 1)) / cnt);
+      }
+    }
   return RTP_OK;
 }
 

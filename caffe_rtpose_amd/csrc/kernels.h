@@ -518,6 +518,45 @@ struct OverlayDrawParams {
 };
 hipError_t launch_overlay_draw(const OverlayDrawParams& p, hipStream_t stream);
 
+// Redaction mode (redact.hip, rtp_set_redaction): two kernels.  Integers and bytes are rtp_redact_regions' and rtp_redact_apply's
+// (include/rtpose_mi355x.h spells out both).
+// redact_regions: ONE workgroup per launch, one thread per person.  The frame's people, read in device memory, give one record
+// {cx, cy, rx, ry, count, valid} each; behind the RTP_TRACK_MAX_PEOPLE records' room the launch writes n.  No table: no ordering
+// against other frames.
+#define RTP_RDC_REGION_INTS 6      // RTP_REDACT_REGION_INTS
+#define RTP_RDC_MAX_RADIUS 4096    // RTP_REDACT_MAX_RADIUS
+#define RTP_RDC_TILE 32            // both sides: a tile holds whole mosaic cells for every allowed cell
+#define RTP_RDC_MAX_BLUR 16        // the largest blur radius: the halo of a tile
+enum { RTP_RDC_MOSAIC = 0, RTP_RDC_BLUR = 1, RTP_RDC_FILL = 2 };   // RTP_REDACT_*
+struct RedactRegionsParams {
+  const float* joints;       // [max_people][num_parts][3]
+  const int* num_people;
+  int* regions;              // [RTP_TRACK_MAX_PEOPLE][RTP_RDC_REGION_INTS]   (the first n are written)
+  int* num_regions;          // n = clamp(*num_people, 0, RTP_TRACK_MAX_PEOPLE)
+  int num_parts, nlist, min_parts;
+  float min_score;
+  int scale_q8, aspect_q8, pad, min_radius;
+  unsigned char list[RTP_TRACK_MAX_PARTS];
+};
+hipError_t launch_redact_regions(const RedactRegionsParams& p, hipStream_t stream);
+// redact_apply: one workgroup of 256 threads per tile of RTP_RDC_TILE x RTP_RDC_TILE pixels, four pixels of one row per thread.  The
+// workgroup culls the valid regions against its tile into LDS; a tile that no region touches reads nothing else and stores nothing.
+// Every covered pixel's value is computed from `src` and stored to `dst` at the same position.  FILL and MOSAIC run with
+// dst == src (a mosaic cell is read by exactly one workgroup, before a barrier in front of its first store).  BLUR reads a halo that
+// neighbouring workgroups write, so it takes two launches: pass 0 with dst = a scratch image, pass 1 (copy = 1) copies the covered
+// pixels from the scratch image back.  launch_redact_apply enqueues what the effect needs.
+struct RedactApplyParams {
+  const int* regions;
+  const int* num_regions;    // clamped to 0 .. RTP_TRACK_MAX_PEOPLE
+  unsigned char* image;      // BGR, redacted in place
+  unsigned char* scratch;    // BLUR only: h rows of `stride` bytes, never the image
+  int w, h;
+  long stride;
+  int effect, ellipse, cell, radius;
+  unsigned colour;
+};
+hipError_t launch_redact_apply(const RedactApplyParams& p, hipStream_t stream);
+
 struct NmsParams {
   const float* src;  // resized map [src_planes][H][W]
   float* peaks;      // [num_parts][max_peaks+1][3]  (in/out)

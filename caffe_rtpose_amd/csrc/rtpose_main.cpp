@@ -61,6 +61,8 @@ int rtp_set_smoothing(rtp_engine* e, const rtp_smooth_config* cfg) __attribute__
 int rtp_peek_smoothed(rtp_engine* e, uint64_t* tag, float* joints_s_host, float* vel_host, unsigned char* flags_host, int* num_people, int capacity) __attribute__((weak));
 // (nor overlay mode: --draw_tracks then runs rtp_overlay_update and rtp_overlay_draw in the re-orderer, as with --host_draw)
 int rtp_set_track_overlay(rtp_engine* e, const rtp_overlay_config* cfg) __attribute__((weak));
+// (nor redaction mode: --redact then runs rtp_redact_regions and rtp_redact_apply in the re-orderer, as with --host_redact)
+int rtp_set_redaction(rtp_engine* e, const rtp_redact_config* cfg) __attribute__((weak));
 double rtp_display_fit_scale(int ow, int oh, int disp_w, int disp_h);
 int rtp_preprocess_frame(const unsigned char* bgr, int w, int h, int disp_w, int disp_h, int net_w, int net_h, int num_scales,
                          double start_scale, double scale_gap, float* net_input, unsigned char* display_bgr, float* frame_scale);
@@ -120,6 +122,14 @@ struct Flags {
   bool draw_tracks = false, host_draw = false;
   std::string draw_what = "box,label,trail";
   int trail_len = 16, label_scale = 1, draw_alpha = 192;
+  // --redact (needs --write_frames or --write_video): every person's head (or the region around --redact_parts) mosaicked, blurred or
+  // filled in the rendered frames.  One real GPU worker: the engine's redaction mode (on the GPU, behind the pose overlay and in front of
+  // --draw_tracks' drawing, before the frame is encoded or converted there).  Otherwise, or with --host_redact: the re-orderer applies
+  // rtp_redact_regions + rtp_redact_apply to the raw rendered frame, before any rtp_overlay_draw.
+  bool redact = false, host_redact = false;
+  std::string redact_effect = "mosaic", redact_shape = "ellipse", redact_parts = "head";
+  int redact_cell = 8, redact_radius = 8, redact_pad = 2;
+  double redact_scale = 1.5, redact_aspect = 1.25;
   std::string caffemodel = "model/coco/pose_iter_440000.caffemodel", caffeproto = "model/coco/pose_deploy_linevec.prototxt";
   std::string resolution = "1280x720", net_resolution = "656x368", camera_resolution = "1280x720";
   double start_scale = 1, scale_gap = 0.3;
@@ -147,16 +157,19 @@ struct Flags {
 int parse_flags(int argc, char** argv, Flags& F) {
   std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video}, {"write_video", &F.write_video}, {"write_heatmaps", &F.write_heatmaps}, {"heatmap_channels", &F.heatmap_channels},
       {"write_crops", &F.write_crops}, {"crop_size", &F.crop_size}, {"crop_parts", &F.crop_parts}, {"draw_what", &F.draw_what},
+      {"redact_effect", &F.redact_effect}, {"redact_shape", &F.redact_shape}, {"redact_parts", &F.redact_parts},
       {"image_dir", &F.image_dir}, {"caffemodel", &F.caffemodel}, {"caffeproto", &F.caffeproto}, {"resolution", &F.resolution},
       {"net_resolution", &F.net_resolution}, {"camera_resolution", &F.camera_resolution}, {"precision", &F.precision}, {"model", &F.model}, {"devices", &F.devices}};
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
       {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}, {"max_crops", &F.max_crops},
       {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}, {"smooth_max_hold", &F.smooth_max_hold},
-      {"trail_len", &F.trail_len}, {"label_scale", &F.label_scale}, {"draw_alpha", &F.draw_alpha}};
+      {"trail_len", &F.trail_len}, {"label_scale", &F.label_scale}, {"draw_alpha", &F.draw_alpha},
+      {"redact_cell", &F.redact_cell}, {"redact_radius", &F.redact_radius}, {"redact_pad", &F.redact_pad}};
   std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}, {"track_max_cost", &F.track_max_cost},
-      {"smooth_min_cutoff", &F.smooth_min_cutoff}, {"smooth_beta", &F.smooth_beta}, {"smooth_d_cutoff", &F.smooth_d_cutoff}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track}, {"smooth", &F.smooth}, {"draw_tracks", &F.draw_tracks}, {"host_draw", &F.host_draw},
+      {"smooth_min_cutoff", &F.smooth_min_cutoff}, {"smooth_beta", &F.smooth_beta}, {"smooth_d_cutoff", &F.smooth_d_cutoff},
+      {"redact_scale", &F.redact_scale}, {"redact_aspect", &F.redact_aspect}};
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track}, {"smooth", &F.smooth}, {"draw_tracks", &F.draw_tracks}, {"host_draw", &F.host_draw}, {"redact", &F.redact}, {"host_redact", &F.host_redact},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -241,6 +254,16 @@ void usage() {
          "  the ids exist only in the re-orderer, which then draws on the raw rendered frame with the same definition (rtp_overlay_update +\n"
          "  rtp_overlay_draw: the same pixels), and the host encoders write the files, as with --host_jpeg / --host_video.  --host_draw asks\n"
          "  for that path with one GPU worker too: it is there to compare the two paths (the tests do), nothing is gained by it otherwise.  (--host_preprocess renders no frames at all.)  Without --draw_tracks every file is what it was.\n"
+         "  --redact [--redact_effect mosaic|blur|fill (mosaic)] [--redact_shape ellipse|rect (ellipse)] [--redact_parts head|all|p0,p1,.. (head)]\n"
+         "  [--redact_cell N (8: 2, 4, 8, 16 or 32)] [--redact_radius N (8: 1 .. 16)] [--redact_scale F (1.5)] [--redact_aspect F (1.25)] [--redact_pad N (2)]\n"
+         "  [--host_redact] (needs --write_frames or --write_video) anonymises the rendered frames: around the listed parts of every person (the\n"
+         "  head's by default) an ellipse or rectangle of half-width F x half the parts' span + N pixels, F times as tall as wide, is replaced\n"
+         "  by a mosaic of N x N cells, a box blur of radius N or black (F is converted once: (int)lrintf(F * 256)).  With ONE real GPU worker\n"
+         "  it runs on the GPU (redaction mode of the engine) behind the pose overlay and in front of --draw_tracks' drawing, so boxes and ids stay\n"
+         "  sharp, and the GPU's JPEG encoder / YUV conversion stay in use: only the anonymised, encoded frame crosses PCIe.  With --num_gpu N > 1,\n"
+         "  --dry_engine or --host_redact the re-orderer applies the same definition (rtp_redact_regions + rtp_redact_apply: the same bytes) to\n"
+         "  the raw rendered frame, before any rtp_overlay_draw, and the host encoders write the files.  --write_crops and --write_heatmaps\n"
+         "  are NOT redacted.  Without --redact every file is what it was.\n"
          "  --video FILE.y4m hands the file's Y, U, V planes to the engine (rtp_submit_frame_yuv: 1.5 bytes per pixel cross PCIe for 4:2:0,\n"
          "  the colour conversion runs on the GPU); --host_yuv converts to BGR on the producer thread instead (the same output).\n"
          "  --video FILE.mjpeg hands every frame's FILE bytes to the engine (rtp_submit_frame_jpeg: the producer only reads the file and its\n"
@@ -298,6 +321,9 @@ bool smooth_on_gpu();
 rtp_smooth_config smooth_config();
 bool overlay_on_gpu();
 rtp_overlay_config overlay_config();
+bool redact_on_gpu();
+bool host_pixels();
+rtp_redact_config redact_config(int num_parts, std::vector<int>* parts);
 
 struct EncodeJob { std::string path; std::vector<unsigned char> bgr; bool jpeg = false; };  // jpeg: bgr already holds the file
 
@@ -561,8 +587,8 @@ void worker(int widx, int device, int* status) {
   }
   // --write_frames: the files are encoded on the GPU (quality 98, rtpose.cpp:1367-1381) unless --host_jpeg; --dry_engine has no GPU
   // --write_video x.mjpeg takes the same files (main() refuses the combinations in which one output wants the GPU's and the other the host's)
-  // --draw_tracks in the re-orderer: it needs the raw frames, and the host encoders write the files
-  const bool host_draw = F.draw_tracks && !overlay_on_gpu();
+  // --draw_tracks or --redact in the re-orderer: it needs the raw frames, and the host encoders write the files
+  const bool host_draw = host_pixels();
   const bool gpu_jpeg = !dry && !host_draw && ((!F.write_frames.empty() && !F.host_jpeg) || (G.video_kind == RTP_VIDEO_MJPEG && !F.host_video));
   // --write_video x.y4m: the renderer's YUV mode unless --host_video
   const bool gpu_yuv = !dry && !host_draw && G.video_kind == RTP_VIDEO_Y4M && !F.host_video;
@@ -580,7 +606,7 @@ void worker(int widx, int device, int* status) {
   if (!F.write_video.empty() && widx == 0)
     fprintf(stderr, "--write_video: frames %s\n", gpu_yuv ? "converted to YUV 4:2:0 on the GPU (rtp_collect_rendered_yuv)"
                                                   : gpu_jpeg ? "encoded on the GPU (rtp_collect_rendered_jpeg)"
-                                                             : "converted / encoded on the host (--host_video, or --draw_tracks in the re-orderer)");
+                                                             : "converted / encoded on the host (--host_video, or --draw_tracks / --redact in the re-orderer)");
   std::vector<unsigned char> jpeg_buf(gpu_jpeg ? rtp_jpeg_max_bytes(DISP_W, DISP_H) : 0);
   if (gpu_jpeg) {
     const char* err = !rtp_set_render_jpeg || !rtp_collect_rendered_jpeg ? "this binary was linked without the engine's GPU JPEG encoder"
@@ -711,6 +737,20 @@ void worker(int widx, int device, int* status) {
       return;
     }
   }
+  // --redact likewise: the engine's redaction mode, applied to the rendered frame in front of the overlay mode's drawing
+  if (redact_on_gpu()) {
+    std::vector<int> parts;
+    const rtp_redact_config rc = redact_config(num_parts, &parts);
+    if (rtp_set_redaction(e, &rc) != RTP_OK) {
+      fprintf(stderr, "GPU %d: --redact: %s\n", device, rtp_last_error(e));
+      *status = 1;
+      G.quit_threads = true;
+      rtp_engine_destroy(e);
+      return;
+    }
+  }
+  if (F.redact && widx == 0)
+    fprintf(stderr, "--redact: %s\n", redact_on_gpu() ? "redaction on the GPU (rtp_set_redaction)" : "redaction in the re-orderer (rtp_redact_regions + rtp_redact_apply)");
   // --dry_engine: what the engine costs the HOST per frame (the staging copy of rtp_submit_frame, the joints copy of
   // rtp_collect) and when a frame completes (RATE frames/s, at least two frame times after its submit)
   std::vector<unsigned char> dry_staging;
@@ -926,7 +966,8 @@ rtp_smooth_config smooth_config() {
 }
 
 // --draw_tracks: on the GPU where the tracker is, unless --host_draw; otherwise in the re-orderer, behind its rtp_track_update
-bool overlay_on_gpu() { return F.draw_tracks && !F.host_draw && track_on_gpu() && rtp_set_track_overlay; }
+// (and not while --redact runs in the re-orderer: the drawing goes on top of the redaction, so it has to follow it there)
+bool overlay_on_gpu() { return F.draw_tracks && !F.host_draw && track_on_gpu() && rtp_set_track_overlay && !(F.redact && !redact_on_gpu()); }
 rtp_overlay_config overlay_config() {
   rtp_overlay_config oc;
   rtp_overlay_config_default(&oc);
@@ -941,6 +982,37 @@ rtp_overlay_config overlay_config() {
   oc.label_scale = F.label_scale;
   oc.alpha = F.draw_alpha;
   return oc;
+}
+
+// --redact: on the GPU with one real GPU worker, unless --host_redact; otherwise in the re-orderer, in front of its rtp_overlay_draw
+bool redact_on_gpu() { return F.redact && !F.host_redact && F.dry_engine <= 0 && !F.host_preprocess && F.num_gpu == 1 && rtp_set_redaction; }
+// the re-orderer changes pixels: the workers hand it raw frames
+bool host_pixels() { return (F.draw_tracks && !overlay_on_gpu()) || (F.redact && !redact_on_gpu()); }
+// parts: the storage of the list the configuration points to.  Names that are none of the flag's become -1 (refused by main()).
+rtp_redact_config redact_config(int num_parts, std::vector<int>* parts) {
+  rtp_redact_config rc;
+  rtp_redact_config_default(&rc);
+  rc.effect = F.redact_effect == "mosaic" ? RTP_REDACT_MOSAIC : F.redact_effect == "blur" ? RTP_REDACT_BLUR : F.redact_effect == "fill" ? RTP_REDACT_FILL : -1;
+  rc.shape = F.redact_shape == "ellipse" ? RTP_REDACT_ELLIPSE : F.redact_shape == "rect" ? RTP_REDACT_RECT : -1;
+  parts->clear();
+  if (F.redact_parts == "all") {
+    for (int p = 0; p < num_parts; ++p) parts->push_back(p);
+  } else if (F.redact_parts != "head") {
+    for (const char* q = F.redact_parts.c_str(); *q;) {
+      char* end = nullptr;
+      parts->push_back((int)strtol(q, &end, 10));
+      if (end == q) { parts->back() = -1; break; }
+      q = *end == ',' ? end + 1 : end;
+    }
+    if (parts->empty()) parts->push_back(-1);
+  }
+  if (!parts->empty()) { rc.parts = parts->data(); rc.num_parts = (int)parts->size(); }
+  rc.scale_q8 = (int)lrintf((float)F.redact_scale * 256);
+  rc.aspect_q8 = (int)lrintf((float)F.redact_aspect * 256);
+  rc.pad = F.redact_pad;
+  rc.cell = F.redact_cell;
+  rc.radius = F.redact_radius;
+  return rc;
 }
 
 // ---- re-orderer (buffer_and_order, rtpose.cpp:1214-1273) ---------------------------------------------
@@ -965,6 +1037,9 @@ void reorderer(std::atomic<bool>* workers_done) {
   const bool host_draw = F.draw_tracks && !overlay_on_gpu();
   const rtp_overlay_config oc = overlay_config();
   std::unique_ptr<rtp_trail_state> ostate;
+  // --redact on the host: on the raw rendered frame, from the joints the frame was rendered from, in front of the drawing above
+  const bool host_redact = F.redact && !redact_on_gpu();
+  std::vector<int> redact_parts, redact_regions(host_redact ? (size_t)RTP_MAX_PEOPLE * RTP_REDACT_REGION_INTS : 0);
   std::vector<int> draw_items(host_draw ? (size_t)RTP_OVERLAY_MAX_ITEMS * RTP_OVERLAY_ITEM_INTS : 0);
   auto emit = [&](Frame f) {
     if (host_track) {
@@ -979,6 +1054,12 @@ void reorderer(std::atomic<bool>* workers_done) {
       f.joints_s.assign(std::max(f.joints.size(), (size_t)1), 0.f);
       if (rtp_smooth_update(sstate.get(), &sc, f.joints.data(), f.numPeople, f.track_recs.data(), f.joints_s.data(), nullptr, nullptr) < 0) f.joints_s = f.joints;
       f.joints_s.resize(f.joints.size());
+    }
+    if (host_redact && !f.rendered_jpeg && !f.rendered_yuv && f.rendered.size() == (size_t)DISP_W * DISP_H * 3) {
+      const rtp_redact_config rc = redact_config(G.num_parts.load(), &redact_parts);
+      const float* poses = smooth_on_gpu() && f.joints_s.size() == f.joints.size() ? f.joints_s.data() : f.joints.data();
+      const int n = rtp_redact_regions(poses, f.numPeople, G.num_parts.load(), &rc, redact_regions.data());
+      if (n >= 0) rtp_redact_apply(redact_regions.data(), n, &rc, f.rendered.data(), DISP_W, DISP_H, 3L * DISP_W);
     }
     if (host_draw && f.track_recs.size() == (size_t)f.numPeople * RTP_TRACK_REC_INTS) {
       if (!ostate) { ostate.reset(new rtp_trail_state); rtp_trail_state_init(ostate.get(), G.num_parts.load()); }
@@ -1261,6 +1342,22 @@ int main(int argc, char** argv) {
     usage();
     return 1;
   }
+  if ((F.redact || F.host_redact) && (!F.redact || (F.write_frames.empty() && F.write_video.empty()))) {
+    fprintf(stderr, "--redact needs --write_frames or --write_video (it anonymises the rendered frames); --host_redact needs --redact\n");
+    usage();
+    return 1;
+  }
+  if (F.redact) {
+    std::vector<int> parts;
+    int none[RTP_REDACT_REGION_INTS];
+    const int model_parts = F.model == "mpi" ? 15 : 18;
+    const rtp_redact_config rc = redact_config(model_parts, &parts);
+    if (!std::isfinite(F.redact_scale) || !std::isfinite(F.redact_aspect) || rtp_redact_regions(nullptr, 0, model_parts, &rc, none) < 0) {
+      fprintf(stderr, "--redact: --redact_effect mosaic|blur|fill, --redact_shape ellipse|rect, --redact_parts head|all|p0,p1,.. (each part once), --redact_cell 2|4|8|16|32, "
+                      "--redact_radius 1 .. 16, --redact_scale 0.25 .. 16, --redact_aspect 0.25 .. 4, --redact_pad 0 .. 256\n");
+      return 1;
+    }
+  }
   if (F.draw_tracks) {
     const rtp_overlay_config oc = overlay_config();
     if (oc.what == 0 || (oc.what & 8u) || oc.trail_len < 0 || oc.trail_len > RTP_TRAIL_MAX || oc.label_scale < 1 || oc.label_scale > 8 || oc.alpha < 0 || oc.alpha > 256) {
@@ -1317,7 +1414,7 @@ int main(int argc, char** argv) {
                       "write an .mjpeg video next to the frames, or run twice\n", F.write_video.c_str());
       return 1;
     }
-    if (G.video_kind == RTP_VIDEO_MJPEG && !F.write_frames.empty() && !(F.dry_engine > 0) && F.host_jpeg != F.host_video && !(F.draw_tracks && !overlay_on_gpu())) {
+    if (G.video_kind == RTP_VIDEO_MJPEG && !F.write_frames.empty() && !(F.dry_engine > 0) && F.host_jpeg != F.host_video && !host_pixels()) {
       fprintf(stderr, "--write_frames with --write_video x.mjpeg: both take the same files, so give --host_jpeg and --host_video together or neither\n");
       return 1;
     }

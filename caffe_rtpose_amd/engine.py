@@ -5,7 +5,7 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, rtp_smooth_config, rtp_smooth_state, rtp_overlay_config, rtp_trail_state, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, rtp_smooth_config, rtp_smooth_state, rtp_overlay_config, rtp_trail_state, rtp_redact_config, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -893,6 +893,63 @@ def overlay_draw(items, image, num_items=None):
     return image
 
 
+REDACT_MOSAIC, REDACT_BLUR, REDACT_FILL = 0, 1, 2
+REDACT_ELLIPSE, REDACT_RECT = 0, 1
+REDACT_REGION_INTS, REDACT_MAX_RADIUS = 6, 4096
+
+
+def redact_config(effect=None, shape=None, parts=None, min_score=None, min_parts=None, scale_q8=None, aspect_q8=None, pad=None, min_radius=None, cell=None, radius=None,
+                  colour=None):
+    """rtp_redact_config: rtp_redact_config_default's values (mosaic, ellipse, the model's head parts, min_score 0, min_parts 1, scale_q8 384,
+    aspect_q8 320, pad 2, min_radius 4, cell 8, radius 8, black), each replaced where an argument is given.  effect: REDACT_MOSAIC, REDACT_BLUR or
+    REDACT_FILL; shape: REDACT_ELLIPSE or REDACT_RECT; parts: a list of part indices (None = the model's head parts), kept alive by the
+    returned structure; colour: packed b | g << 8 | r << 16."""
+    cfg = rtp_redact_config()
+    lib.rtp_redact_config_default(C.byref(cfg))
+    for name, v, conv in (("effect", effect, int), ("shape", shape, int), ("min_score", min_score, float), ("min_parts", min_parts, int), ("scale_q8", scale_q8, int),
+                          ("aspect_q8", aspect_q8, int), ("pad", pad, int), ("min_radius", min_radius, int), ("cell", cell, int), ("radius", radius, int), ("colour", colour, int)):
+        if v is not None:
+            setattr(cfg, name, conv(v))
+    if parts is not None:
+        cfg._parts = (C.c_int * max(len(parts), 1))(*[int(p) for p in parts])
+        cfg.parts = C.cast(cfg._parts, C.POINTER(C.c_int))
+        cfg.num_parts = len(parts)
+    return cfg
+
+
+def redact_regions(joints, num_parts, num_people=None, cfg=None):
+    """rtp_redact_regions, the host definition of redaction mode's regions: joints [people][num_parts][3] -> records [n][6] int32
+    {cx, cy, rx, ry, count, valid}.  num_people: the frame's count where it is not the array's (above 96 or negative, as the device may
+    hold it); cfg: a redact_config() (None = the defaults)."""
+    cfg = cfg if cfg is not None else redact_config()
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, int(num_parts), 3)
+    people = j.shape[0] if num_people is None else int(num_people)
+    n = min(max(people, 0), MAX_PEOPLE)
+    if n > j.shape[0]:
+        raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+    regions = np.zeros((max(n, 1), REDACT_REGION_INTS), np.int32)
+    rc = lib.rtp_redact_regions(_f(j) if j.size else None, people, int(num_parts), C.byref(cfg), regions.ctypes.data_as(ip))
+    if rc < 0:
+        raise RtpError(rc, "rtp_redact_regions: an argument is out of range")
+    assert rc == n
+    return regions[:n].copy()
+
+
+def redact_apply(regions, image, cfg=None, num_regions=None):
+    """rtp_redact_apply, the host definition of redaction mode's pixels: every pixel of `image`, a uint8 array [h][w][3] (BGR) whose rows
+    may be strided, that a valid region covers is replaced by the effect's value computed from the image as it was, IN PLACE; returns it."""
+    cfg = cfg if cfg is not None else redact_config()
+    rg = np.ascontiguousarray(regions, np.int32).reshape(-1, REDACT_REGION_INTS)
+    m = rg.shape[0] if num_regions is None else int(num_regions)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.strides[2] != 1 or image.strides[1] != 3 or not image.flags.writeable:
+        raise ValueError("image: a writeable uint8 array [h][w][3] with dense rows")
+    rc = lib.rtp_redact_apply(rg.ctypes.data_as(ip) if rg.size else None, m, C.byref(cfg), image.ctypes.data_as(C.POINTER(C.c_ubyte)), image.shape[1], image.shape[0],
+                              image.strides[0])
+    if rc < 0:
+        raise RtpError(rc, "rtp_redact_apply: an argument is out of range")
+    return image
+
+
 def _stream_of(obj, stream):
     """(handle or None, torch default stream?) of the stream a device frame is ordered on.  stream: a torch.cuda.Stream, a raw
     hipStream_t as int, or None = torch's current stream of a tensor's device, else the interface's `stream` entry, else NULL."""
@@ -1427,6 +1484,55 @@ class Engine:
         self._chk(lib.rtp_overlay_from_joints(self.h, _f(j) if j.size else None, people, None if img is None else img.ctypes.data_as(C.POINTER(C.c_ubyte)), w, h,
                                               recs.ctypes.data_as(ip), items.ctypes.data_as(ip), C.byref(m), int(capacity)))
         return recs[:n].copy(), items[: m.value].copy(), img
+
+    # ---- redaction mode
+    def set_redaction(self, cfg=True, **kw):
+        """rtp_set_redaction (Config.render >= 1; tracking mode is not needed): every submitted frame's rendered image has a region around
+        each person's listed parts (the head's by default) mosaicked, blurred or filled before it is exported; peek_redactions in front of
+        the frame's collect gives the records.  cfg: a redact_config(), True (= redact_config(**kw)) or None / False (off).  Crops mode and
+        maps mode keep handing out un-redacted data."""
+        if cfg is None or cfg is False:
+            self._chk(lib.rtp_set_redaction(self.h, None))
+            return
+        if cfg is True:
+            cfg = redact_config(**kw)
+        self._chk(lib.rtp_set_redaction(self.h, C.byref(cfg)))
+
+    def redaction_info(self):
+        """rtp_redaction_info: the current configuration as a dict of rtp_redact_config's fields, parts = the list."""
+        cfg = rtp_redact_config()
+        parts = (C.c_int * 70)()
+        rc = lib.rtp_redaction_info(self.h, C.byref(cfg), parts)
+        if rc:
+            raise RtpError(rc, "redaction mode is off (set_redaction)")
+        d = {name: getattr(cfg, name) for name, _ in rtp_redact_config._fields_ if name not in ("struct_size", "parts", "num_parts")}
+        d["parts"] = list(parts)[: cfg.num_parts]
+        return d
+
+    def peek_redactions(self, capacity=MAX_PEOPLE):
+        """rtp_peek_redactions: (tag, records [n][6] int32) of the oldest frame in flight, which stays in flight (follow with a collect)."""
+        regions = np.zeros((max(int(capacity), 1), REDACT_REGION_INTS), np.int32)
+        tag, n = C.c_uint64(0), C.c_int(0)
+        self._chk(lib.rtp_peek_redactions(self.h, C.byref(tag), regions.ctypes.data_as(ip), C.byref(n), int(capacity)))
+        return tag.value, regions[: n.value].copy()
+
+    def redact_from_joints(self, joints, num_people=None, image=None, capacity=MAX_PEOPLE):
+        """rtp_redact_from_joints: the async path's redact_regions and redact_apply kernels on joints [people][num_parts][3] (idle engine,
+        mode on).  image: a uint8 array [h][w][3] up to the display size, or None (regions only).  Returns (records [n][6], the redacted
+        image or None)."""
+        P = self.num_parts
+        j = np.ascontiguousarray(joints, np.float32).reshape(-1, P, 3)
+        people = j.shape[0] if num_people is None else int(num_people)
+        n = min(max(people, 0), MAX_PEOPLE)
+        if n > j.shape[0]:
+            raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+        regions = np.zeros((max(int(capacity), 1), REDACT_REGION_INTS), np.int32)
+        img = None if image is None else np.ascontiguousarray(image, np.uint8).copy()
+        h, w = (0, 0) if img is None else img.shape[:2]
+        m = C.c_int(0)
+        self._chk(lib.rtp_redact_from_joints(self.h, _f(j) if j.size else None, people, None if img is None else img.ctypes.data_as(C.POINTER(C.c_ubyte)), w, h,
+                                             regions.ctypes.data_as(ip), C.byref(m), int(capacity)))
+        return regions[: m.value].copy(), img
 
     def crops_from_joints(self, display_bgr, joints, pixels=True):
         """rtp_crops_from_joints: (boxes, crops) of the current mode for the given display image and joints [people][num_parts][3]

@@ -1171,6 +1171,114 @@ int rtp_peek_overlay_items(rtp_engine* e, uint64_t* tag, int* items_host, int* n
 int rtp_overlay_from_joints(rtp_engine* e, const float* joints_host, int num_people, unsigned char* image_host_in_out, int w, int h,
                             int* recs_out, int* items_out, int* num_items, int capacity);
 
+/* ---- redaction mode: people's heads mosaicked, blurred or filled in the rendered frame (redact.hip) ------------------------ */
+
+/* The rendered frame shows the people's faces on every export path.  Redaction mode, off by default and usable while
+ * rtp_config.render >= 1 (it does NOT need tracking mode), replaces for every person of a submitted frame a region around the listed
+ * parts (the head's by default) BEFORE the image is exported: the raw host copy, rtp_collect_rendered_device, JPEG mode and YUV mode
+ * all carry it, only the encoded frame crosses PCIe and the host touches no pixel.  Each submitted frame's chain gains
+ * redact_regions, one workgroup that reads num_people and the joints in device memory and writes one record per person, and
+ * redact_apply, one workgroup per tile of the rendered image, behind the pose overlay and in front of overlay mode's drawing: boxes,
+ * ids and trails stay sharp on top of the redaction.  rtp_redact_regions and rtp_redact_apply are the one definition of both; the
+ * kernels' integers and bytes equal them exactly.
+ *
+ * CROPS MODE AND MAPS MODE KEEP HANDING OUT UN-REDACTED DATA: crops are resampled from the un-rendered display image, and the maps
+ * are the network's.  A deployment that must not leak faces must not enable them, or must treat their output as sensitive.  The
+ * synchronous taps (rtp_render) carry no redaction either.
+ *
+ * THE REGIONS.  n = clamp(num_people, 0, RTP_MAX_PEOPLE) (a negative device num_people is the connect kernels' RTP_ERANGE flag and
+ * counts as 0).  Per person k:
+ *  1. A listed part COUNTS under tracking's rule: score > min_score and x, y finite.  c = the number of listed parts that count.
+ *     Where c < min_parts the record is {0, 0, 0, 0, c, 0}.
+ *  2. Over the counting listed parts, in float32 comparisons: fx0 = min x, fx1 = max x, fy0 = min y, fy1 = max y.  Each is rounded
+ *     ONCE with overlay mode's q(v) = (int)floorf(clampf(v, -32767.0f, 32767.0f) + 0.5f): x0 = q(fx0), x1 = q(fx1), y0 = q(fy0),
+ *     y1 = q(fy1).  Everything from here on is integer arithmetic.
+ *  3. cx = floor((x0 + x1) / 2), cy = floor((y0 + y1) / 2) (floor for negative sums too); s = max(x1 - x0, y1 - y0) + 1;
+ *     rx = clamp(((s * scale_q8) >> 9) + pad, min_radius, RTP_REDACT_MAX_RADIUS);  ry = min((rx * aspect_q8) >> 8, RTP_REDACT_MAX_RADIUS).
+ * THE RECORD is RTP_REDACT_REGION_INTS int32: {cx, cy, rx, ry, c, valid (1 or 0)}.
+ *
+ * THE PIXELS.  A pixel (px, py) is COVERED by a valid region (valid != 0) when |px - cx| <= rx and |py - cy| <= ry and, for
+ * RTP_REDACT_ELLIPSE, with dx = px - cx, dy = py - cy in int64, (dx * ry)^2 + (dy * rx)^2 <= (rx * ry)^2 (a zero radius therefore
+ * covers the centre column or row).  A record's cx and cy are taken as clamp(v, -65535, 65535), its rx and ry as
+ * clamp(v, 0, RTP_REDACT_MAX_RADIUS).  A pixel covered by at least one region is replaced by a value computed from the image AS IT
+ * WAS BEFORE THE CALL, so the result depends neither on the order of the regions nor on how they overlap; every other byte, the
+ * padding between rows included, keeps its value.  The value, per channel:
+ *   RTP_REDACT_FILL    the colour (packed b | g << 8 | r << 16).
+ *   RTP_REDACT_MOSAIC  cells of cell x cell pixels aligned to the image's origin, the pixel's cell being (px / cell, py / cell):
+ *                      (sum + (cnt >> 1)) / cnt over the cnt pixels of that cell that lie inside the image, covered or not.
+ *   RTP_REDACT_BLUR    (sum + (cnt >> 1)) / cnt over the window [px - radius, px + radius] x [py - radius, py + radius] clipped to
+ *                      the image (a box filter, NOT computed in place).
+ *
+ * The defaults of rtp_redact_config_default (mosaic, ellipse, the model's head parts, min_score 0, min_parts 1, scale_q8 384,
+ * aspect_q8 320, pad 2, min_radius 4, cell 8, radius 8, black) are choices, not measurements: a head's radius is taken as 3/4 of
+ * the span of its key points, and a head as 5/4 as tall as it is wide. */
+#define RTP_REDACT_MOSAIC 0
+#define RTP_REDACT_BLUR 1
+#define RTP_REDACT_FILL 2
+#define RTP_REDACT_ELLIPSE 0
+#define RTP_REDACT_RECT 1
+#define RTP_REDACT_REGION_INTS 6
+#define RTP_REDACT_MAX_RADIUS 4096
+
+typedef struct rtp_redact_config {
+  unsigned int struct_size; /* sizeof(rtp_redact_config) */
+  int effect;               /* RTP_REDACT_MOSAIC | RTP_REDACT_BLUR | RTP_REDACT_FILL */
+  int shape;                /* RTP_REDACT_ELLIPSE | RTP_REDACT_RECT */
+  const int* parts;         /* part indices that span the region, any order, repeats refused (copied by the call); NULL = the model's
+                             * rtp_crops_head_parts (a model of 18 parts is taken as RTP_MODEL_COCO_18, of 15 as RTP_MODEL_MPI_15) */
+  int num_parts;            /* 1 .. RTP_MAX_NUM_PARTS (ignored when parts == NULL) */
+  float min_score;          /* >= 0, finite */
+  int min_parts;            /* >= 1: a person with fewer counting listed parts has no region */
+  int scale_q8;             /* 64 .. 4096 */
+  int aspect_q8;            /* 64 .. 1024 */
+  int pad;                  /* 0 .. 256 */
+  int min_radius;           /* 0 .. 256 */
+  int cell;                 /* 2, 4, 8, 16 or 32 (RTP_REDACT_MOSAIC) */
+  int radius;               /* 1 .. 16 (RTP_REDACT_BLUR) */
+  unsigned int colour;      /* packed b | g << 8 | r << 16 (RTP_REDACT_FILL); the bits above are ignored */
+} rtp_redact_config;
+
+/* Host only (no engine, no GPU): the defaults above. */
+int rtp_redact_config_default(rtp_redact_config* cfg);
+
+/* Host only: THE REGIONS above.  joints [num_people][num_parts][3] as rtp_collect returns them (num_parts = the model's parts per
+ * person; NULL is accepted where no person is read); regions receives n records.  Returns n, or RTP_EINVAL with regions untouched:
+ * a NULL cfg or regions, NULL joints with people, a wrong struct_size, a field out of its range, a repeated part or one outside
+ * [0, num_parts), num_parts outside 1 .. RTP_MAX_NUM_PARTS, NULL parts for a model of neither 18 nor 15 parts. */
+int rtp_redact_regions(const float* joints, int num_people, int num_parts, const rtp_redact_config* cfg, int* regions);
+
+/* Host only: THE PIXELS above, in place for the caller, onto image_bgr, h rows of w BGR pixels, `stride` bytes from row to row.
+ * num_regions 0 leaves the image untouched.  RTP_EINVAL with the image untouched: a NULL cfg or image, NULL regions with
+ * num_regions > 0, num_regions outside 0 .. RTP_MAX_PEOPLE, w or h < 1 or > 32768, a stride below 3 * w, a wrong struct_size, a
+ * field out of its range (a part list is checked against RTP_MAX_NUM_PARTS). */
+int rtp_redact_apply(const int* regions, int num_regions, const rtp_redact_config* cfg, unsigned char* image_bgr, int w, int h, long stride);
+
+/* Switches redaction mode on (or changes it), NULL cfg = off.  Refused, with the engine unchanged: rtp_config.render == 0, a wrong
+ * struct_size or a field out of range, a repeated part or one outside the model's (RTP_EINVAL); frames in flight (RTP_EAGAIN).  The
+ * regions come from the joints the frame is rendered with: smoothing mode's joints_s, held parts included, where it has
+ * RTP_SMOOTH_RENDER (a nose that drops out for one frame does not un-blur a face), the raw joints otherwise.  A frame submitted
+ * without a display image (rtp_submit) has records, but nothing is redacted.  The blur's scratch image (display size, one per frame
+ * slot) is allocated by this call, never per frame.  With the mode off the engine launches what it launched before the mode existed.
+ * Under the experiments build's RTP_GRAPH_POST=1 the mode behaves as crops mode does. */
+int rtp_set_redaction(rtp_engine* e, const rtp_redact_config* cfg);
+
+/* The current mode: *cfg with parts = NULL and num_parts = the list's length, the list itself into parts (room for
+ * RTP_MAX_NUM_PARTS ints); either pointer may be NULL.  RTP_EINVAL while the mode is off. */
+int rtp_redaction_info(const rtp_engine* e, rtp_redact_config* cfg, int* parts);
+
+/* The contract of rtp_peek_tracks: blocks until the OLDEST frame in flight is finished and hands out its tag, *num_regions = n and
+ * n records; capacity = the records regions_host holds.  The frame STAYS in flight.  Refused: mode off, NULL regions_host or
+ * num_regions, a negative capacity (RTP_EINVAL); nothing in flight (RTP_EAGAIN); capacity < n (RTP_ERANGE, *num_regions set,
+ * nothing else written; the frame stays peekable). */
+int rtp_peek_redactions(rtp_engine* e, uint64_t* tag, int* regions_host, int* num_regions, int capacity);
+
+/* Parity tap (idle engine, context 0, mode on): the two kernels of the async path on caller data.  joints_host
+ * [num_people][num_parts][3], of which n = clamp(num_people, 0, RTP_MAX_PEOPLE) people are read; num_people itself goes to the device
+ * as it is.  image_host_in_out: a dense w x h BGR image (1 <= w <= cfg.disp_w, 1 <= h <= cfg.disp_h) that comes back redacted, or
+ * NULL (w and h ignored: regions only).  Writes *num_regions = n and n records, capacity as in rtp_peek_redactions. */
+int rtp_redact_from_joints(rtp_engine* e, const float* joints_host, int num_people, unsigned char* image_host_in_out, int w, int h,
+                           int* regions_out, int* num_regions, int capacity);
+
 #ifdef __cplusplus
 }
 #endif
