@@ -749,6 +749,7 @@ std::string describe_plan(const Plan& p, int N, int B, int frames_in_flight, int
   o << "model " << p.model << " parts " << p.num_parts << " max_peaks " << p.max_peaks << " heat_channels " << p.heat_channels << "\n";
   for (int l = 0; l < p.nlevels; ++l)
     o << "level " << l << " H " << p.geom[l].H << " W " << p.geom[l].W << " halo " << p.geom[l].halo << "\n";
+  o << "postproc strip_rows " << p.strip_rows << " nstrips " << p.nstrips << " max_rows " << p.max_rows << "\n";   // Builder::postproc_sizes
   o << "arena_bytes " << p.arena_bytes << " weights_bytes " << p.weights_bytes << " tensors " << p.tensors.size() << "\n";
   {  // which streams a batch context gets (alloc_ctx; "hardware queues" above): one for everything when the runtime's hardware queues suffice
     const int nctx = plan_contexts(frames_in_flight, B);

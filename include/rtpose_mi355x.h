@@ -483,7 +483,10 @@ int rtp_caffemodel_layer(const char* path, int index, char* name, int name_len, 
                          long* count0, long* count1, float* head0);
 
 /* Build the execution plan for cfg without touching a device and describe it as text (tile
- * configuration per layer, L1/L2 pairing, arena sizes).  Returns bytes written or a negative code. */
+ * configuration per layer, L1/L2 pairing, arena sizes; `postproc strip_rows R nstrips S max_rows M`:
+ * the strip height of the fused ImResize+Nms kernel, which halves on wide nets, its strips per part
+ * and the rows of the connect tables).  Readers select lines by their first word.
+ * Returns bytes written or a negative code. */
 long rtp_plan_summary(const rtp_config* cfg, char* buf, size_t buflen);
 
 /* ---- frames already in GPU memory (no reference counterpart: the producer's OpenCV frames live on the host) ---------- */
