@@ -137,6 +137,30 @@ class rtp_track_state(C.Structure):
     ]
 
 
+class rtp_appearance_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("parts", C.POINTER(C.c_int)),
+        ("num_parts", C.c_int),
+        ("min_score", C.c_float),
+        ("min_parts", C.c_int),
+        ("margin", C.c_float),
+        ("weight", C.c_float),
+        ("max_dist", C.c_float),
+        ("unknown", C.c_float),
+        ("rate", C.c_int),
+    ]
+
+
+class rtp_appearance_state(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint),
+        ("reserved", C.c_int * 3),
+        ("owner", C.c_int * 128),
+        ("desc", C.c_uint16 * (128 * 128)),
+    ]
+
+
 class rtp_smooth_config(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint),
@@ -352,6 +376,20 @@ SIGNATURES = {
     "rtp_peek_tracks": (C.c_int, [vp, C.POINTER(C.c_uint64), ip, ip, C.c_int]),
     "rtp_track_from_joints": (C.c_int, [vp, fp, C.c_int, ip, ip, C.c_int]),
     "rtp_format_json_tracked": (C.c_long, [C.c_char_p, C.c_size_t, fp, C.c_int, C.c_int, C.c_float, ip]),
+    "rtp_appearance_config_default": (C.c_int, [C.POINTER(rtp_appearance_config)]),
+    "rtp_appearance_state_init": (C.c_int, [C.POINTER(rtp_appearance_state)]),
+    "rtp_appearance_torso_parts": (C.c_int, [C.c_int, ip]),
+    "rtp_appearance_describe": (C.c_int, [C.POINTER(C.c_ubyte), C.c_int, C.c_int, fp, C.c_int, C.c_int, C.POINTER(rtp_appearance_config), C.POINTER(C.c_uint16),
+                                          C.POINTER(C.c_ubyte)]),
+    "rtp_track_update_appearance": (C.c_int, [C.POINTER(rtp_track_state), C.POINTER(rtp_appearance_state), C.POINTER(rtp_track_config),
+                                              C.POINTER(rtp_appearance_config), fp, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_ubyte), ip]),
+    "rtp_set_track_appearance": (C.c_int, [vp, C.POINTER(rtp_appearance_config)]),
+    "rtp_appearance_reset": (C.c_int, [vp]),
+    "rtp_appearance_get_state": (C.c_int, [vp, C.POINTER(rtp_appearance_state)]),
+    "rtp_appearance_set_state": (C.c_int, [vp, C.POINTER(rtp_appearance_state)]),
+    "rtp_peek_appearance": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint16), C.POINTER(C.c_ubyte), ip, C.c_int]),
+    "rtp_appearance_from_joints": (C.c_int, [vp, C.POINTER(C.c_ubyte), fp, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_ubyte), ip, C.c_int]),
+    "rtp_track_from_frame": (C.c_int, [vp, C.POINTER(C.c_ubyte), fp, C.c_int, ip, C.POINTER(C.c_uint16), C.POINTER(C.c_ubyte), ip, C.c_int]),
     "rtp_smooth_config_default": (C.c_int, [C.POINTER(rtp_smooth_config)]),
     "rtp_smooth_state_init": (C.c_int, [C.POINTER(rtp_smooth_state), C.c_int]),
     "rtp_smooth_update": (C.c_int, [C.POINTER(rtp_smooth_state), C.POINTER(rtp_smooth_config), fp, C.c_int, ip, fp, fp, C.POINTER(C.c_ubyte)]),

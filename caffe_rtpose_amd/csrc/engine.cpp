@@ -644,6 +644,7 @@ int frame_outputs_ensure(rtp_engine* e, Ctx& cx, int nframes) {
   if (e->maps_on && (rc = maps_ensure(e, cx, nframes))) return rc;
   if (e->crops_on && (rc = crops_ensure(e, cx, nframes))) return rc;
   if (e->track_on && (rc = track_ensure(e, cx, nframes))) return rc;
+  if (e->appear_on && (rc = appear_ensure(e, cx, nframes))) return rc;
   if (e->smooth_on && (rc = smooth_ensure(e, cx, nframes))) return rc;
   if (e->overlay_on && (rc = overlay_ensure(e, cx, nframes))) return rc;
   if (e->redact_on && (rc = redact_ensure(e, cx, nframes))) return rc;
@@ -692,6 +693,9 @@ int frame_outputs_launch(rtp_engine* e, Ctx& cx, int j, bool materialized) {
   // the synchronous taps, calibration and the profiling passes run this chain on an idle engine, whose slots are not busy.  The kernels
   // of consecutive frames are chained in LAUNCH order, which is submit order: batches are launched in the order they were filled and
   // launch_batch_body walks a batch's slots in slot order.
+  // appearance mode (engine_appearance.cpp): the frame's descriptors from the RAW joints, in front of the wait track_launch enqueues, so that
+  // they overlap the previous frame's chain; the track kernel launched next is the appearance form (track_enqueue)
+  if (e->appear_on && e->track_on && sl.busy && (rc = appear_launch(e, cx, j, sl.has_disp && sl.disp_cur))) return rc;
   if (e->track_on && sl.busy && (rc = track_launch(e, cx, j, smooth || overlay))) return rc;
   if (smooth && (rc = smooth_launch(e, cx, j, overlay))) return rc;   // the frame's people through the filter table, and the chain's event
   // the frame's draw list and the trail table, from the people the frame is rendered with, and the chain's event
@@ -1139,6 +1143,7 @@ void free_ctx(Ctx& cx) {
     sl.maps.free();
     sl.crops.free();
     sl.track.free();
+    sl.appear.free();
     sl.smooth.free();
     sl.overlay.free();
     sl.redact.free();
@@ -1892,6 +1897,7 @@ void rtp_engine_destroy(rtp_engine* e) {
   (void)hipSetDevice(e->cfg.device_id);
   for (auto& c : e->ctx) free_ctx(c);
   track_free(e);
+  appear_free(e);
   smooth_free(e);
   overlay_free(e);
   if (e->dweights) (void)hipFree(e->dweights);

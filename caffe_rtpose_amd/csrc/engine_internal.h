@@ -1,4 +1,4 @@
-// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_smooth.cpp, engine_overlay.cpp, engine_redact.cpp, engine_calib.cpp) share: the frame slot, the batch context and
+// engine_internal.h — what the engine's translation units (engine.cpp, engine_jpeg.cpp, engine_yuv.cpp, engine_maps.cpp, engine_crops.cpp, engine_track.cpp, engine_appearance.cpp, engine_smooth.cpp, engine_overlay.cpp, engine_redact.cpp, engine_calib.cpp) share: the frame slot, the batch context and
 // rtp_engine itself, the error / lock macros, and the declarations of every helper one of those files defines and another one calls.
 // Internal: only the engine's own files include it (it opens namespace rtp for them); nothing here is part of the library's ABI.
 #pragma once
@@ -40,6 +40,8 @@ size_t rtp_internal_jpeg_setup(int W, int H, int quality, unsigned char qt[2][64
 // host_util.cpp
 extern "C" const char* rtp_internal_crops_check(const rtp_crops_config* c, int model_parts);
 extern "C" const char* rtp_internal_track_check(const rtp_track_config* c);
+extern "C" const char* rtp_internal_appearance_check(const rtp_appearance_config* c, int model_parts);
+extern "C" int rtp_internal_appearance_list(const rtp_appearance_config* c, int model_parts, int list[RTP_MAX_NUM_PARTS]);
 extern "C" const char* rtp_internal_smooth_check(const rtp_smooth_config* c);
 extern "C" const char* rtp_internal_overlay_check(const rtp_overlay_config* c);
 extern "C" const char* rtp_internal_trail_check(const rtp_trail_state* st);
@@ -138,6 +140,14 @@ struct TrackOut {
   void free();   // (engine_track.cpp)
 };
 
+// rtp_set_track_appearance: the frame's descriptors [96][128] uint16 and, behind them, its valid bytes [96], one block on the device and
+// one pinned copy of it
+struct AppearOut {
+  unsigned char *dev = nullptr, *host = nullptr;
+  bool fresh = false;   // appear_launch has described the slot's frame and its track kernel has not run yet
+  void free();   // (engine_appearance.cpp)
+};
+
 // rtp_set_smoothing: the frame's filtered joints [96][P][3], velocities [96][P][2] and flags [96][P], and their pinned copy, one block
 // in that order
 struct SmoothOut {
@@ -207,6 +217,7 @@ struct Slot {
   MapsOut maps;
   CropsOut crops;
   TrackOut track;
+  AppearOut appear;
   SmoothOut smooth;
   OverlayOut overlay;
   RedactOut redact;
@@ -312,6 +323,13 @@ struct rtp_engine {
   TrackTable* track_dev = nullptr;
   hipEvent_t track_prev = nullptr;
   hipStream_t track_prev_stream = nullptr;
+  // rtp_set_track_appearance (engine_appearance.cpp): the mode on (only while track_on), its configuration (parts = nullptr inside; the
+  // list is appear_list) and the device-resident descriptor table (rtp_appearance_state's layout), which the track kernel's appearance
+  // form reads and updates: the tracker's chain of events orders it
+  bool appear_on = false;
+  rtp_appearance_config appear_cfg = {};
+  std::vector<int> appear_list;
+  AppearTable* appear_dev = nullptr;
   // rtp_set_smoothing (engine_smooth.cpp): smoothing mode on (only while track_on), its configuration and the device-resident filter
   // table (rtp_smooth_state's layout); its kernels are ordered by the tracker's chain of events
   bool smooth_on = false;
@@ -471,6 +489,14 @@ int track_ensure(rtp_engine* e, Ctx& cx, int nframes);
 int track_launch(rtp_engine* e, Ctx& cx, int sj, bool table_kernel_follows = false);
 void track_forget_chain(rtp_engine* e);   // the slots' events are gone or complete: the next track kernel waits on nothing
 void track_free(rtp_engine* e);
+
+// engine_appearance.cpp
+int appear_ensure(rtp_engine* e, Ctx& cx, int nframes);
+// frame sj's descriptors on the frame's own stream behind the connect kernels, IN FRONT OF track_launch's wait on the previous frame's
+// table event, and their copy to pinned memory.  with_image = false: a frame without a display image (valid = 0 for everybody)
+int appear_launch(rtp_engine* e, Ctx& cx, int sj, bool with_image);
+void appear_track_params(const rtp_engine* e, const Slot& sl, TrackAppearParams* a);   // the track kernel's second argument for slot sl
+void appear_free(rtp_engine* e);
 
 // engine_smooth.cpp
 int smooth_ensure(rtp_engine* e, Ctx& cx, int nframes);

@@ -39,6 +39,12 @@ int track_enqueue(rtp_engine* e, Ctx& cx, int sj, hipStream_t stream) {
   p.num_parts = e->plan.num_parts; p.min_parts = c.min_parts; p.min_common = c.min_common; p.max_misses = c.max_misses;
   p.min_score = c.min_score; p.max_cost = c.max_cost;
   p.variant = e->track_variant;
+  if (e->appear_on) {   // the appearance form of the same kernel (engine_appearance.cpp): the frame's descriptors against the descriptor table
+    TrackAppearParams a;
+    appear_track_params(e, sl, &a);
+    HIPCHK(e, launch_track_appearance(p, a, stream));
+    return RTP_OK;
+  }
   HIPCHK(e, launch_track(p, stream));   // no residency stamp: every slot of a frame's chain is taken (StampKind)
   return RTP_OK;
 }
@@ -96,6 +102,7 @@ int track_ensure(rtp_engine* e, Ctx& cx, int nframes) {
     HIPCHK(e, hipHostMalloc((void**)&t.recs_host, kRecBytes, hipHostMallocDefault));
     HIPCHK(e, hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
   }
+  if (e->appear_on) return appear_ensure(e, cx, nframes);   // the appearance form reads the slot's descriptors
   return RTP_OK;
 }
 
@@ -104,6 +111,9 @@ int track_ensure(rtp_engine* e, Ctx& cx, int nframes) {
 int track_launch(rtp_engine* e, Ctx& cx, int sj, bool table_kernel_follows) {
   Slot& sl = cx.slot[sj];
   int rc;
+  // appearance mode: a caller that has not described the frame (the joints-only taps) gets a frame without a display image
+  if (e->appear_on && !sl.appear.fresh && (rc = appear_launch(e, cx, sj, false))) return rc;
+  sl.appear.fresh = false;
   if (e->track_prev && e->track_prev_stream != sl.stream) HIPCHK(e, hipStreamWaitEvent(sl.stream, e->track_prev, 0));
   if ((rc = track_enqueue(e, cx, sj, sl.stream))) return rc;
   if (!table_kernel_follows) {   // (otherwise the last table kernel of the frame's chain records it, behind itself: smooth_launch, overlay_update_launch)
@@ -149,6 +159,10 @@ extern "C" int rtp_internal_track_time(rtp_engine* e, const float* joints_host, 
   if ((rc = track_ensure(e, cx, 1))) return rc;
   std::vector<unsigned char> keep(sizeof(rtp_track_state));
   HIPCHK(e, hipMemcpy(keep.data(), e->track_dev, keep.size(), hipMemcpyDeviceToHost));
+  // appearance mode: the train runs the appearance form on the descriptors slot 0 holds (rtp_appearance_from_joints stages them) and
+  // the descriptor table comes back with the track table
+  std::vector<unsigned char> keep_appear(e->appear_on ? sizeof(AppearTable) : 0);
+  if (e->appear_on) HIPCHK(e, hipMemcpy(keep_appear.data(), e->appear_dev, keep_appear.size(), hipMemcpyDeviceToHost));
   // (from here on every HIP status is kept in `s` and checked once everything is released)
   hipEvent_t ev[2] = {nullptr, nullptr};
   unsigned long long* hold = nullptr;
@@ -171,6 +185,10 @@ extern "C" int rtp_internal_track_time(rtp_engine* e, const float* joints_host, 
   if (hold) (void)hipFree(hold);
   const hipError_t back = hipMemcpy(e->track_dev, keep.data(), keep.size(), hipMemcpyHostToDevice);
   if (s == hipSuccess) s = back;
+  if (e->appear_on) {
+    const hipError_t back_appear = hipMemcpy(e->appear_dev, keep_appear.data(), keep_appear.size(), hipMemcpyHostToDevice);
+    if (s == hipSuccess) s = back_appear;
+  }
   if (rc) return rc;
   HIPCHK(e, s);
   *period_us = ms * 1e3f / (float)launches;
@@ -188,6 +206,7 @@ int rtp_set_tracking(rtp_engine* e, const rtp_track_config* cfg) {
     if (bad) return fail(e, RTP_EINVAL, "%s: %s (min_score %g, min_parts %d, min_common %d, max_cost %g, max_misses %d)", fn, bad, (double)cfg->min_score, cfg->min_parts,
                          cfg->min_common, (double)cfg->max_cost, cfg->max_misses);
   }
+  if (!cfg && e->appear_on) return fail(e, RTP_EINVAL, "%s: appearance mode is on and needs the tracker: rtp_set_track_appearance(e, NULL) first", fn);
   if (!cfg && e->smooth_on) return fail(e, RTP_EINVAL, "%s: smoothing mode is on and needs the tracker: rtp_set_smoothing(e, NULL) first", fn);
   if (!cfg && e->overlay_on) return fail(e, RTP_EINVAL, "%s: overlay mode is on and needs the tracker: rtp_set_track_overlay(e, NULL) first", fn);
   if (!e->fifo.empty()) return fail(e, RTP_EAGAIN, "%s: %zu frames in flight (collect them first)", fn, e->fifo.size());

@@ -1,6 +1,7 @@
 // host_util.cpp — the host-only pieces of the path behind the C-ABI: model descriptor tables,
 // default thresholds, process_and_pad_image, the JSON body, the narrow formats of maps mode and the boxes and pixels of
-// crops mode (rtp_crop_people), tracking mode (rtp_track_update), smoothing mode (rtp_smooth_update), overlay mode
+// crops mode (rtp_crop_people), tracking mode (rtp_track_update), its appearance term (rtp_appearance_describe,
+// rtp_track_update_appearance), smoothing mode (rtp_smooth_update), overlay mode
 // (rtp_overlay_update, rtp_overlay_draw) and redaction mode (rtp_redact_regions, rtp_redact_apply).  No GPU needed.
 #include <algorithm>
 #include <vector>
@@ -425,6 +426,274 @@ int rtp_track_update(rtp_track_state* st, const rtp_track_config* cfg, const flo
     memcpy(st->joints[free_t], joints + (size_t)k * P * 3, (size_t)P * 3 * sizeof(float));
     slot_of[k] = free_t;
     born[k] = true;
+  }
+  st->frames++;   // 7.
+  for (int k = 0; k < n; ++k) {
+    int* r = recs + (size_t)k * RTP_TRACK_REC_INTS;
+    const int t = slot_of[k];
+    if (t < 0) { r[0] = 0; r[1] = -1; r[2] = 0; r[3] = 0; continue; }
+    r[0] = st->id[t]; r[1] = t; r[2] = st->hits[t];
+    r[3] = born[k] ? 0 : (int)cost_of[k];
+  }
+  return n;
+}
+
+}  // extern "C"
+
+// ---- appearance-aided tracking: the one definition of its arithmetic (appearance.hip and track.hip's appearance form compute the same
+// integers and float bits on the device) ------------------------------------------------------------------------------------------
+
+// What is wrong with the fields the cost and the table update read, or nullptr
+static const char* appearance_check_fields(const rtp_appearance_config* c) {
+  if (!c) return "NULL rtp_appearance_config";
+  if (c->struct_size != sizeof(rtp_appearance_config)) return "rtp_appearance_config.struct_size is not this library's sizeof(rtp_appearance_config)";
+  if (!(c->min_score >= 0.f) || std::isinf(c->min_score)) return "min_score must be a finite number >= 0";
+  if (c->min_parts < 1) return "min_parts must be >= 1";
+  if (!(c->margin >= 0.f && c->margin <= 16.f)) return "margin outside 0 .. 16";
+  if (!(c->weight >= 0.f) || std::isinf(c->weight)) return "weight must be a finite number >= 0";
+  if (!(c->max_dist > 0.f && c->max_dist <= 1.f)) return "max_dist outside (0, 1]";
+  if (!(c->unknown >= 0.f && c->unknown <= 1.f)) return "unknown outside 0 .. 1";
+  if (c->rate < 1 || c->rate > 256) return "rate outside 1 .. 256";
+  return nullptr;
+}
+
+// What is wrong with the configuration for a model of model_parts parts, or nullptr.  The engine's switch reports the same text.
+extern "C" const char* rtp_internal_appearance_check(const rtp_appearance_config* c, int model_parts) {
+  if (const char* bad = appearance_check_fields(c)) return bad;
+  if (model_parts < 1 || model_parts > RTP_MAX_NUM_PARTS) return "num_parts outside 1 .. RTP_MAX_NUM_PARTS";
+  if (c->parts) {
+    if (c->num_parts < 1 || c->num_parts > RTP_MAX_NUM_PARTS) return "the part list's num_parts outside 1 .. RTP_MAX_NUM_PARTS";
+    for (int i = 0; i < c->num_parts; ++i)
+      if (c->parts[i] < 0 || c->parts[i] >= model_parts) return "a listed part is outside the model's parts";
+  }
+  return nullptr;
+}
+
+// rtp_appearance_torso_parts: neck, shoulders and hips (COCO), and the chest (MPI)
+extern "C" int rtp_appearance_torso_parts(int model, int parts[8]) {
+  static const int coco[5] = {1, 2, 5, 8, 11}, mpi[6] = {1, 2, 5, 8, 11, 14};
+  const bool c = model == RTP_MODEL_COCO_18;
+  if (!parts || (!c && model != RTP_MODEL_MPI_15)) return RTP_EINVAL;
+  const int n = c ? 5 : 6;
+  memcpy(parts, c ? coco : mpi, n * sizeof(int));
+  return n;
+}
+
+// The configuration's list for a model of model_parts parts (checked): its own, the torso parts of a model of 18 or 15 parts, or all parts
+extern "C" int rtp_internal_appearance_list(const rtp_appearance_config* c, int model_parts, int list[RTP_MAX_NUM_PARTS]) {
+  if (c->parts) {
+    memcpy(list, c->parts, (size_t)c->num_parts * sizeof(int));
+    return c->num_parts;
+  }
+  if (model_parts == 18 || model_parts == 15) return rtp_appearance_torso_parts(model_parts == 18 ? RTP_MODEL_COCO_18 : RTP_MODEL_MPI_15, list);
+  for (int p = 0; p < model_parts; ++p) list[p] = p;
+  return model_parts;
+}
+
+extern "C" {
+
+int rtp_appearance_config_default(rtp_appearance_config* cfg) {
+  if (!cfg) return RTP_EINVAL;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->struct_size = (unsigned)sizeof *cfg;
+  cfg->min_score = 0.f;
+  cfg->min_parts = 3;
+  cfg->margin = 0.f;
+  cfg->weight = 0.125f;
+  cfg->max_dist = 1.f;
+  cfg->unknown = 0.25f;
+  cfg->rate = 32;
+  return RTP_OK;
+}
+
+int rtp_appearance_state_init(rtp_appearance_state* state) {
+  if (!state) return RTP_EINVAL;
+  memset(state, 0, sizeof *state);
+  state->struct_size = (unsigned)sizeof *state;
+  return RTP_OK;
+}
+
+int rtp_appearance_describe(const unsigned char* display_bgr, int w, int h, const float* joints, int num_people, int num_parts,
+                            const rtp_appearance_config* cfg, uint16_t* bins_out, unsigned char* valid_out) {
+#pragma clang fp contract(off)
+  if (rtp_internal_appearance_check(cfg, num_parts) || !bins_out || !valid_out || w < 1 || h < 1 || w > 32768 || h > 32768 || num_people < 0) return RTP_EINVAL;
+  if (num_people > 0 && (!joints || !display_bgr)) return RTP_EINVAL;
+  const int n = num_people < RTP_MAX_PEOPLE ? num_people : RTP_MAX_PEOPLE;
+  int list[RTP_MAX_NUM_PARTS];
+  const int nlist = rtp_internal_appearance_list(cfg, num_parts, list);
+  for (int k = 0; k < n; ++k) {
+    const float* jp = joints + (size_t)k * num_parts * 3;
+    uint16_t* bins = bins_out + (size_t)k * RTP_APPEARANCE_BINS;
+    memset(bins, 0, RTP_APPEARANCE_BINS * sizeof(uint16_t));
+    valid_out[k] = 0;
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    int count = 0;
+    for (int i = 0; i < nlist; ++i) {
+      const int p = list[i];
+      const float s = jp[3 * p + 2];
+      if (!(s > cfg->min_score) || !std::isfinite(jp[3 * p]) || !std::isfinite(jp[3 * p + 1])) continue;
+      const float x = jp[3 * p] + 0.0f, y = jp[3 * p + 1] + 0.0f;
+      x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+      ++count;
+    }
+    if (count < cfg->min_parts) continue;
+    const float sx = x0 + x1, sy = y0 + y1;
+    const float cx = sx * 0.5f, cy = sy * 0.5f;
+    float bw = x1 - x0, bh = y1 - y0;
+    if (!std::isfinite(bw) || !std::isfinite(bh)) continue;
+    const float gm = cfg->margin * fmaxf(bw, bh);
+    const float g = gm * 2.0f;
+    const float wg = bw + g, hg = bh + g;
+    bw = fmaxf(wg, 1.0f); bh = fmaxf(hg, 1.0f);
+    const float hw = bw * 0.5f, hh = bh * 0.5f;
+    const float left = cx - hw, top = cy - hh;
+    const float right = left + bw, bottom = top + bh;
+    const float lim = 1048576.0f;
+    if (!(fabsf(left) <= lim && fabsf(top) <= lim && fabsf(right) <= lim && fabsf(bottom) <= lim)) continue;
+    const float lq = left * 65536.0f, tq = top * 65536.0f;
+    const float stx = bw / 32.0f, sty = bh / 32.0f;
+    const float dxq = stx * 65536.0f, dyq = sty * 65536.0f;
+    const long long ox = (long long)rintf(lq), oy = (long long)rintf(tq);
+    const long long dx = (long long)rintf(dxq), dy = (long long)rintf(dyq);
+    for (int j = 0; j < RTP_APPEARANCE_GRID; ++j) {
+      long long row = (oy + j * dy + dy / 2) >> 16;
+      row = row < 0 ? 0 : row > h - 1 ? h - 1 : row;
+      for (int i = 0; i < RTP_APPEARANCE_GRID; ++i) {
+        long long col = (ox + i * dx + dx / 2) >> 16;
+        col = col < 0 ? 0 : col > w - 1 ? w - 1 : col;
+        const unsigned char* px = display_bgr + ((size_t)row * w + (size_t)col) * 3;
+        bins[(j >= 16 ? 64 : 0) + (px[2] >> 6) * 16 + (px[1] >> 6) * 4 + (px[0] >> 6)]++;
+      }
+    }
+    valid_out[k] = 1;
+  }
+  return n;
+}
+
+int rtp_track_update_appearance(rtp_track_state* st, rtp_appearance_state* ap, const rtp_track_config* cfg, const rtp_appearance_config* acfg,
+                                const float* joints, int num_people, const uint16_t* bins, const unsigned char* valid, int* recs) {
+#pragma clang fp contract(off)
+  if (!st || !ap || !recs || rtp_internal_track_check(cfg) || appearance_check_fields(acfg)) return RTP_EINVAL;
+  if (st->struct_size != sizeof(rtp_track_state) || st->num_parts < 1 || st->num_parts > RTP_MAX_NUM_PARTS) return RTP_EINVAL;
+  if (ap->struct_size != sizeof(rtp_appearance_state) || (bins && !valid)) return RTP_EINVAL;
+  const int n = num_people < 0 ? 0 : num_people > RTP_MAX_PEOPLE ? RTP_MAX_PEOPLE : num_people;
+  if (n > 0 && !joints) return RTP_EINVAL;
+  const int P = st->num_parts;
+  auto counts = [&](const float* j) { return j[2] > cfg->min_score && std::isfinite(j[0]) && std::isfinite(j[1]); };
+  auto described = [&](int k) { return bins && valid[k] != 0; };
+  // 1. trackable people
+  bool trackable[RTP_MAX_PEOPLE];
+  for (int k = 0; k < n; ++k) {
+    int c = 0;
+    for (int p = 0; p < P; ++p) c += counts(joints + ((size_t)k * P + p) * 3) ? 1 : 0;
+    trackable[k] = c >= cfg->min_parts;
+  }
+  // 2. the candidates, as keys (total bits, slot, person): the motion cost and its gate, then THE COST
+  struct Cand { uint32_t bits; int t, k; };
+  std::vector<Cand> cand;
+  for (int t = 0; t < RTP_MAX_TRACKS; ++t) {
+    if (!st->id[t]) continue;
+    const bool has = ap->owner[t] == st->id[t];
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    for (int p = 0; p < P; ++p) {
+      const float* tj = st->joints[t][p];
+      if (!counts(tj)) continue;
+      const float x = tj[0] + 0.0f, y = tj[1] + 0.0f;
+      x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+    }
+    const float w = x1 - x0, h = y1 - y0;
+    const float ww = w * w, hh = h * h;
+    const float wh = ww + hh;
+    const float d = fmaxf(wh, 1.0f);
+    for (int k = 0; k < n; ++k) {
+      if (!trackable[k]) continue;
+      float s = 0.0f;
+      int m = 0;
+      for (int p = 0; p < P; ++p) {
+        const float* pj = joints + ((size_t)k * P + p) * 3;
+        const float* tj = st->joints[t][p];
+        if (!counts(pj) || !counts(tj)) continue;
+        const float dx = pj[0] - tj[0], dy = pj[1] - tj[1];
+        const float a = dx * dx, b = dy * dy;
+        const float c = a + b;
+        s = s + c;
+        ++m;
+      }
+      if (m < cfg->min_common) continue;
+      const float q = s / (float)m;
+      const float cost = q / d;
+      if (!std::isfinite(cost) || !(cost <= cfg->max_cost)) continue;
+      float a = acfg->unknown;
+      if (has && described(k)) {
+        const uint16_t* bk = bins + (size_t)k * RTP_APPEARANCE_BINS;
+        int L = 0;
+        for (int b = 0; b < RTP_APPEARANCE_BINS; ++b) {
+          const int v = (int)ap->desc[t][b] - 16 * (int)bk[b];
+          L += v < 0 ? -v : v;
+        }
+        a = (float)L / 32768.0f;
+        if (!(a <= acfg->max_dist)) continue;
+      }
+      const float wa = acfg->weight * a;
+      const float total = cost + wa;
+      if (!std::isfinite(total)) continue;
+      const float tz = total + 0.0f;
+      Cand c;
+      memcpy(&c.bits, &tz, 4);
+      c.t = t; c.k = k;
+      cand.push_back(c);
+    }
+  }
+  // 3. greedy assignment in key order
+  std::sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.bits != b.bits ? a.bits < b.bits : a.t != b.t ? a.t < b.t : a.k < b.k; });
+  int slot_of[RTP_MAX_PEOPLE], person_of[RTP_MAX_TRACKS];
+  uint32_t cost_of[RTP_MAX_PEOPLE];
+  for (int k = 0; k < RTP_MAX_PEOPLE; ++k) { slot_of[k] = -1; cost_of[k] = 0; }
+  for (int t = 0; t < RTP_MAX_TRACKS; ++t) person_of[t] = -1;
+  for (const Cand& c : cand) {
+    if (person_of[c.t] >= 0 || slot_of[c.k] >= 0) continue;
+    person_of[c.t] = c.k; slot_of[c.k] = c.t; cost_of[c.k] = c.bits;
+  }
+  // 4. matched slots, 5. unmatched live slots
+  for (int t = 0; t < RTP_MAX_TRACKS; ++t) {
+    if (!st->id[t]) continue;
+    if (person_of[t] >= 0) {
+      memcpy(st->joints[t], joints + (size_t)person_of[t] * P * 3, (size_t)P * 3 * sizeof(float));
+      st->hits[t]++;
+      st->misses[t] = 0;
+    } else if (++st->misses[t] > cfg->max_misses) {
+      st->id[t] = st->hits[t] = st->misses[t] = 0;
+      memset(st->joints[t], 0, sizeof st->joints[t]);
+    }
+  }
+  // 6. births: the lowest free slot for each unmatched trackable person, in person order
+  bool born[RTP_MAX_PEOPLE] = {};
+  int free_t = 0;
+  for (int k = 0; k < n; ++k) {
+    if (!trackable[k] || slot_of[k] >= 0) continue;
+    while (free_t < RTP_MAX_TRACKS && st->id[free_t]) ++free_t;
+    if (free_t == RTP_MAX_TRACKS) break;
+    if (st->next_id == 0) st->next_id = 1;
+    st->id[free_t] = (int)st->next_id++;
+    if (st->next_id == 0) st->next_id = 1;
+    st->hits[free_t] = 1;
+    st->misses[free_t] = 0;
+    memcpy(st->joints[free_t], joints + (size_t)k * P * 3, (size_t)P * 3 * sizeof(float));
+    slot_of[k] = free_t;
+    born[k] = true;
+  }
+  // THE TABLE UPDATE
+  for (int k = 0; k < n; ++k) {
+    const int t = slot_of[k];
+    if (t < 0 || !described(k)) continue;
+    const uint16_t* bk = bins + (size_t)k * RTP_APPEARANCE_BINS;
+    if (ap->owner[t] == st->id[t]) {
+      for (int b = 0; b < RTP_APPEARANCE_BINS; ++b)
+        ap->desc[t][b] = (uint16_t)(((int)ap->desc[t][b] * (256 - acfg->rate) + 16 * (int)bk[b] * acfg->rate + 128) >> 8);
+    } else {
+      for (int b = 0; b < RTP_APPEARANCE_BINS; ++b) ap->desc[t][b] = (uint16_t)(16 * (int)bk[b]);
+      ap->owner[t] = st->id[t];
+    }
   }
   st->frames++;   // 7.
   for (int k = 0; k < n; ++k) {

@@ -430,6 +430,45 @@ enum { RTP_TRACK_ARGMIN_256 = 0, RTP_TRACK_ARGMIN_1024 = 1, RTP_TRACK_SORT_256 =
 #define RTP_TRACK_DEFAULT RTP_TRACK_SORT_1024
 hipError_t launch_track(const TrackParams& p, hipStream_t stream);
 
+// Appearance-aided tracking (appearance.hip, track.hip; rtp_set_track_appearance).  Integers and float bits are
+// rtp_appearance_describe's and rtp_track_update_appearance's (include/rtpose_mi355x.h spells out the arithmetic).
+// appear_describe: one workgroup of 256 threads per person slot, grid RTP_TRACK_MAX_PEOPLE; *num_people is read on the device (negative
+// = 0 people) and the workgroups of slots >= min(*num_people, 96) leave at once.  Wave 0 derives the slot's box (crops.hip's way), every
+// thread takes 4 of the 1024 samples into 128 LDS counters, and the 128 uint16 leave as 16 stores of 16 bytes, with the valid byte.
+// src == nullptr (a frame without a display image): valid = 0 and zeros for every person.  Stateless.
+#define RTP_APPEAR_BINS 128      // RTP_APPEARANCE_BINS
+#define RTP_APPEAR_GRID 32       // RTP_APPEARANCE_GRID
+struct AppearDescribeParams {
+  const unsigned char* src;  // display image, u8 BGR HWC (device), or nullptr
+  int w, h;
+  const float* joints;       // [max_people][num_parts][3]
+  const int* num_people;
+  unsigned short* bins;      // [RTP_TRACK_MAX_PEOPLE][RTP_APPEAR_BINS], 16-byte aligned
+  unsigned char* valid;      // [RTP_TRACK_MAX_PEOPLE]
+  int num_parts, nlist, min_parts;
+  float min_score, margin;
+  unsigned char list[RTP_TRACK_MAX_PARTS];
+};
+hipError_t launch_appear_describe(const AppearDescribeParams& p, hipStream_t stream);
+// The appearance form of the track kernel: the same kernel with THE COST in phase B (the 128-bin L1 distance of a pair that passed the
+// motion gate; table and descriptors are read through L2 with 16-byte loads) and THE TABLE UPDATE in phase F.  All four forms
+// (p.variant); the instantiations launch_track launches are the code they were.  AppearTable is rtp_appearance_state's layout
+// (engine_appearance.cpp asserts it).
+struct AppearTable {
+  unsigned struct_size;
+  int reserved[3];
+  int owner[RTP_TRACK_SLOTS];
+  unsigned short desc[RTP_TRACK_SLOTS][RTP_APPEAR_BINS];
+};
+struct TrackAppearParams {
+  const unsigned short* bins;   // the frame's descriptors (appear_describe's), 16-byte aligned
+  const unsigned char* valid;
+  AppearTable* table;           // 16-byte aligned
+  float weight, max_dist, unknown;
+  int rate;
+};
+hipError_t launch_track_appearance(const TrackParams& p, const TrackAppearParams& a, hipStream_t stream);
+
 // Smoothing mode (smooth.hip, rtp_set_smoothing): the frame's people, read in device memory behind the track kernel with their
 // records, go through a per-(track slot, part) One-Euro filter; the filter table is updated and joints_s, vel and flags are written.
 // Float bits and bytes are rtp_smooth_update's (include/rtpose_mi355x.h spells out the arithmetic).  ONE workgroup per launch that

@@ -56,6 +56,8 @@ int rtp_peek_crops(rtp_engine* e, uint64_t* tag, float* boxes_host, int* num_box
 // (nor tracking mode: --track then runs rtp_track_update in the re-orderer, as under --dry_engine)
 int rtp_set_tracking(rtp_engine* e, const rtp_track_config* cfg) __attribute__((weak));
 int rtp_peek_tracks(rtp_engine* e, uint64_t* tag, int* recs_host, int* num_recs, int capacity) __attribute__((weak));
+// (nor appearance mode: --track_appearance then runs rtp_appearance_describe and rtp_track_update_appearance in the re-orderer, as under --dry_engine)
+int rtp_set_track_appearance(rtp_engine* e, const rtp_appearance_config* cfg) __attribute__((weak));
 // (nor smoothing mode: --smooth then runs rtp_smooth_update in the re-orderer, as under --dry_engine)
 int rtp_set_smoothing(rtp_engine* e, const rtp_smooth_config* cfg) __attribute__((weak));
 int rtp_peek_smoothed(rtp_engine* e, uint64_t* tag, float* joints_s_host, float* vel_host, unsigned char* flags_host, int* num_people, int capacity) __attribute__((weak));
@@ -110,6 +112,13 @@ struct Flags {
   bool track = false;
   double track_max_cost = 0.0625;
   int track_max_misses = 15, track_min_parts = 3;
+  // --track_appearance (needs --track): a colour descriptor per person in the tracker's cost, so that ids survive a crossing.  One real
+  // GPU worker: the engine's appearance mode (rtp_set_track_appearance).  Otherwise the re-orderer runs rtp_appearance_describe on the
+  // frame's display image, which the producer or the worker keeps for it, and rtp_track_update_appearance where it runs rtp_track_update.
+  bool track_appearance = false;
+  double appearance_weight = 0.125, appearance_max_dist = 1.0;
+  int appearance_rate = 32;
+  std::string appearance_parts = "torso";
   // --smooth (needs --track): every tracked person's parts through the One-Euro filter, parts that drop out held for --smooth_max_hold
   // frames.  One real GPU worker: the engine's smoothing mode with both apply flags (the filter runs on the GPU behind the track kernel;
   // rendered frames and crops show the smoothed people).  Otherwise the re-orderer runs rtp_smooth_update behind rtp_track_update.
@@ -157,19 +166,19 @@ struct Flags {
 int parse_flags(int argc, char** argv, Flags& F) {
   std::map<std::string, std::string*> sflags = {{"write_frames", &F.write_frames}, {"write_json", &F.write_json}, {"video", &F.video}, {"write_video", &F.write_video}, {"write_heatmaps", &F.write_heatmaps}, {"heatmap_channels", &F.heatmap_channels},
       {"write_crops", &F.write_crops}, {"crop_size", &F.crop_size}, {"crop_parts", &F.crop_parts}, {"draw_what", &F.draw_what},
-      {"redact_effect", &F.redact_effect}, {"redact_shape", &F.redact_shape}, {"redact_parts", &F.redact_parts},
+      {"redact_effect", &F.redact_effect}, {"redact_shape", &F.redact_shape}, {"redact_parts", &F.redact_parts}, {"appearance_parts", &F.appearance_parts},
       {"image_dir", &F.image_dir}, {"caffemodel", &F.caffemodel}, {"caffeproto", &F.caffeproto}, {"resolution", &F.resolution},
       {"net_resolution", &F.net_resolution}, {"camera_resolution", &F.camera_resolution}, {"precision", &F.precision}, {"model", &F.model}, {"devices", &F.devices}};
   std::map<std::string, int*> iflags = {{"part_to_show", &F.part_to_show}, {"camera", &F.camera}, {"start_frame", &F.start_frame},
       {"start_device", &F.start_device}, {"num_gpu", &F.num_gpu}, {"num_scales", &F.num_scales}, {"frames_in_flight", &F.frames_in_flight}, {"batch_frames", &F.batch_frames},
       {"test_worker_delay_ms", &F.test_worker_delay_ms}, {"dry_people", &F.dry_people}, {"json_writers", &F.json_writers}, {"producer_threads", &F.producer_threads}, {"calibrate", &F.calibrate}, {"video_fps", &F.video_fps}, {"max_crops", &F.max_crops},
-      {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}, {"smooth_max_hold", &F.smooth_max_hold},
+      {"track_max_misses", &F.track_max_misses}, {"track_min_parts", &F.track_min_parts}, {"appearance_rate", &F.appearance_rate}, {"smooth_max_hold", &F.smooth_max_hold},
       {"trail_len", &F.trail_len}, {"label_scale", &F.label_scale}, {"draw_alpha", &F.draw_alpha},
       {"redact_cell", &F.redact_cell}, {"redact_radius", &F.redact_radius}, {"redact_pad", &F.redact_pad}};
-  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}, {"track_max_cost", &F.track_max_cost},
+  std::map<std::string, double*> dflags = {{"start_scale", &F.start_scale}, {"scale_gap", &F.scale_gap}, {"dry_engine", &F.dry_engine}, {"crop_margin", &F.crop_margin}, {"track_max_cost", &F.track_max_cost}, {"appearance_weight", &F.appearance_weight}, {"appearance_max_dist", &F.appearance_max_dist},
       {"smooth_min_cutoff", &F.smooth_min_cutoff}, {"smooth_beta", &F.smooth_beta}, {"smooth_d_cutoff", &F.smooth_d_cutoff},
       {"redact_scale", &F.redact_scale}, {"redact_aspect", &F.redact_aspect}};
-  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track}, {"smooth", &F.smooth}, {"draw_tracks", &F.draw_tracks}, {"host_draw", &F.host_draw}, {"redact", &F.redact}, {"host_redact", &F.host_redact},
+  std::map<std::string, bool*> bflags = {{"fullscreen", &F.fullscreen}, {"no_frame_drops", &F.no_frame_drops}, {"host_preprocess", &F.host_preprocess}, {"host_jpeg", &F.host_jpeg}, {"host_video", &F.host_video}, {"host_yuv", &F.host_yuv}, {"host_decode", &F.host_decode}, {"gpu_decode", &F.gpu_decode}, {"no_display", &F.no_display}, {"track", &F.track}, {"track_appearance", &F.track_appearance}, {"smooth", &F.smooth}, {"draw_tracks", &F.draw_tracks}, {"host_draw", &F.host_draw}, {"redact", &F.redact}, {"host_redact", &F.host_redact},
       {"no_text", &F.no_text}, {"logtostderr", &F.logtostderr}, {"share_weights", &F.share_weights}, {"pin_workers", &F.pin_workers}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -240,6 +249,15 @@ void usage() {
          "  --dry_engine or --host_preprocess the re-orderer, which sees the frames in order, runs the same definition on the host\n"
          "  (rtp_track_update): the ids are the same.  Frames dropped without --no_frame_drops are simply not seen by the tracker.  Without\n"
          "  --track every file is what it was.\n"
+         "  --track_appearance [--appearance_weight F (0.125)] [--appearance_max_dist F (1)] [--appearance_rate N (32, of 256)]\n"
+         "  [--appearance_parts torso|all|LIST] (needs --track) adds a look at the pixels to the association: per person two 64-bin colour\n"
+         "  histograms (upper and lower half of a 32 x 32 sample grid over the box of the listed parts, in the un-rendered display image), per\n"
+         "  track a histogram that moves N / 256 of the way to the matched person's every frame, and F times their L1 distance (0 .. 1) added\n"
+         "  to the motion cost; a pair further apart than --appearance_max_dist is no match.  Two people who swap places between two frames keep\n"
+         "  their ids.  With ONE real GPU worker it runs on the GPU (appearance mode of the engine).  With --num_gpu N > 1, --dry_engine or\n"
+         "  --host_preprocess the re-orderer runs the same definitions on the host (rtp_appearance_describe, rtp_track_update_appearance) on the\n"
+         "  frame's display image (video files and --gpu_decode then hand the workers BGR frames, as under --host_yuv / --host_decode): the same\n"
+         "  ids.  The files carry the ids as with --track alone.\n"
          "  --smooth [--smooth_min_cutoff F (1/30)] [--smooth_beta F (0.01)] [--smooth_d_cutoff F (1/30)] [--smooth_max_hold N (5)] (needs --track)\n"
          "  filters every tracked person's parts over time (One-Euro filter, cutoffs in cycles per frame, beta per pixel) and holds a part that\n"
          "  dropped out at its last filtered value for up to N frames: the --write_json bodies then hold the smoothed joints.  With ONE real GPU\n"
@@ -303,6 +321,8 @@ struct Frame {
   std::vector<unsigned char> crops;     // for a frame without a display image) (rtp_peek_crops); crop_n < 0: not a --write_crops run
   int crop_n = -1;
   std::vector<float> joints_s;          // --smooth: the frame's smoothed joints [numPeople][num_parts][3] (rtp_peek_smoothed, or the re-orderer's rtp_smooth_update)
+  std::vector<unsigned char> display;   // --track_appearance in the re-orderer: the frame's un-rendered display image (DISP_W x DISP_H BGR); display_raw:
+  bool display_raw = false;             // the BGR frame itself (img_w x img_h), which the re-orderer warps to the display image first
   std::vector<int> track_recs;          // --track: the frame's records [numPeople][RTP_TRACK_REC_INTS] (rtp_peek_tracks, or the re-orderer's rtp_track_update)
   std::vector<unsigned char> rendered;  // --write_frames: display-resolution frame with the pose overlay (or its JPEG file: rendered_jpeg)
   bool rendered_jpeg = false;
@@ -317,6 +337,8 @@ struct Frame {
 
 bool track_on_gpu();
 rtp_track_config track_config();
+bool appearance_on_host();
+rtp_appearance_config appearance_config(int num_parts, std::vector<int>* parts);
 bool smooth_on_gpu();
 rtp_smooth_config smooth_config();
 bool overlay_on_gpu();
@@ -376,9 +398,9 @@ void producer() {
   } else nframes = (int)G.image_list.size();
   // Y4M: the planes go to the engine as they are in the file, unless the frames do not reach rtp_submit_frame at all (--host_preprocess,
   // --dry_engine), --host_yuv asks for the host conversion, or this binary was linked without the entry
-  const bool yuv_planes = vid && rtp_video_chroma(vid) != 0 && !F.host_yuv && !F.host_preprocess && !(F.dry_engine > 0) && rtp_submit_frame_yuv != nullptr;
+  const bool yuv_planes = vid && rtp_video_chroma(vid) != 0 && !F.host_yuv && !F.host_preprocess && !(F.dry_engine > 0) && !appearance_on_host() && rtp_submit_frame_yuv != nullptr;   // (--track_appearance in the re-orderer describes people on the BGR frame)
   // JPEG files go to the engine as they are on disk (the same exceptions; --host_decode asks for the host decoder)
-  const bool jpeg_can = !F.host_decode && !F.host_preprocess && !(F.dry_engine > 0) && rtp_submit_frame_jpeg != nullptr;
+  const bool jpeg_can = !F.host_decode && !F.host_preprocess && !(F.dry_engine > 0) && !appearance_on_host() && rtp_submit_frame_jpeg != nullptr;
   const bool jpeg_files = jpeg_can && F.gpu_decode;                           // --image_dir: the producer pool unless asked
   const bool mjpeg_bytes = vid && rtp_video_chroma(vid) == 0 && jpeg_can;     // --video x.mjpeg: the GPU unless asked
   std::vector<unsigned char> img;
@@ -495,7 +517,9 @@ void producer() {
     fr.commit_time = wall();
     if (F.host_preprocess) {
       fr.data.resize((size_t)F.num_scales * 3 * NET_H * NET_W);
-      if (rtp_preprocess_frame(img.data(), w, h, DISP_W, DISP_H, NET_W, NET_H, F.num_scales, F.start_scale, F.scale_gap, fr.data.data(), nullptr, &fr.scale) != RTP_OK) {
+      if (appearance_on_host()) fr.display.resize((size_t)DISP_W * DISP_H * 3);   // the re-orderer describes people on it
+      if (rtp_preprocess_frame(img.data(), w, h, DISP_W, DISP_H, NET_W, NET_H, F.num_scales, F.start_scale, F.scale_gap, fr.data.data(),
+                               fr.display.empty() ? nullptr : fr.display.data(), &fr.scale) != RTP_OK) {
         fprintf(stderr, "preprocess failed for frame %d\n", fi);
         continue;
       }
@@ -641,6 +665,19 @@ void worker(int widx, int device, int* status) {
   int num_parts = F.model == "mpi" ? 15 : 18, heat_channels = F.model == "mpi" ? 44 : 57;
   if (!dry) rtp_engine_info(e, &num_parts, nullptr, &heat_channels, nullptr, nullptr);
   G.num_parts.store(num_parts);
+  if (appearance_on_host()) {   // the re-orderer's configuration against the model's parts, refused here as rtp_set_track_appearance refuses it on the GPU path
+    std::vector<int> parts;
+    const rtp_appearance_config ac = appearance_config(num_parts, &parts);
+    uint16_t no_bins[RTP_APPEARANCE_BINS];
+    unsigned char no_valid[1];
+    if (rtp_appearance_describe(nullptr, 1, 1, nullptr, 0, num_parts, &ac, no_bins, no_valid) != 0) {
+      fprintf(stderr, "GPU %d: --track_appearance: --appearance_parts lists a part outside the model's %d parts\n", device, num_parts);
+      *status = 1;
+      G.quit_threads = true;
+      if (e) rtp_engine_destroy(e);
+      return;
+    }
+  }
   // --write_heatmaps: maps mode, u8 on the net grid; concat_stage7 holds the parts, the background, then the PAF channels
   size_t heat_bytes = 0;
   if (!F.write_heatmaps.empty()) {
@@ -708,6 +745,18 @@ void worker(int widx, int device, int* status) {
     const rtp_track_config tc = track_config();
     if (rtp_set_tracking(e, &tc) != RTP_OK) {
       fprintf(stderr, "GPU %d: --track: %s\n", device, rtp_last_error(e));
+      *status = 1;
+      G.quit_threads = true;
+      rtp_engine_destroy(e);
+      return;
+    }
+  }
+  // --track_appearance likewise: the engine's appearance mode (the describe kernel and the appearance form of the track kernel)
+  if (gpu_track && F.track_appearance) {
+    std::vector<int> parts;
+    const rtp_appearance_config ac = appearance_config(num_parts, &parts);
+    if (!rtp_set_track_appearance || rtp_set_track_appearance(e, &ac) != RTP_OK) {
+      fprintf(stderr, "GPU %d: --track_appearance: %s\n", device, rtp_set_track_appearance ? rtp_last_error(e) : "this library has no appearance mode");
       *status = 1;
       G.quit_threads = true;
       rtp_engine_destroy(e);
@@ -910,6 +959,12 @@ void worker(int widx, int device, int* status) {
                           : fr.yuv            ? rtp_submit_frame_yuv(e, &yv, (uint64_t)fr.index, &fr.scale)
                           : fr.jpeg           ? rtp_submit_frame_jpeg(e, fr.image.data(), fr.image.size(), (uint64_t)fr.index, &fr.scale, nullptr, nullptr)
                                               : rtp_submit_frame(e, fr.image.data(), fr.img_w, fr.img_h, (uint64_t)fr.index, &fr.scale);
+      // --track_appearance in the re-orderer: the BGR frame travels on (a move; the producer hands BGR frames only in that case) and
+      // is warped to the display image there, off this thread
+      if (appearance_on_host() && !F.host_preprocess && !fr.jpeg && !fr.yuv && fr.image.size() == (size_t)fr.img_w * fr.img_h * 3) {
+        fr.display = std::move(fr.image);
+        fr.display_raw = true;
+      }
       fr.image.clear();
       fr.image.shrink_to_fit();
       if (src != RTP_OK && fr.jpeg && (src == RTP_EIO || src == RTP_EINVAL)) {   // a file the decoder refuses: skipped like one the producer cannot decode
@@ -950,6 +1005,31 @@ rtp_track_config track_config() {
   tc.max_misses = F.track_max_misses;
   tc.min_parts = F.track_min_parts;
   return tc;
+}
+
+// --track_appearance: on the GPU where the tracker is; otherwise in the re-orderer, with its tracker
+bool appearance_on_host() { return F.track && F.track_appearance && !track_on_gpu(); }
+// parts: the storage of the list the configuration points to.  Names that are none of the flag's become -1 (refused by main()).
+rtp_appearance_config appearance_config(int num_parts, std::vector<int>* parts) {
+  rtp_appearance_config ac;
+  rtp_appearance_config_default(&ac);
+  ac.weight = (float)F.appearance_weight;
+  ac.max_dist = (float)F.appearance_max_dist;
+  ac.rate = F.appearance_rate;
+  parts->clear();
+  if (F.appearance_parts == "all") {
+    for (int p = 0; p < num_parts; ++p) parts->push_back(p);
+  } else if (F.appearance_parts != "torso") {
+    for (const char* q = F.appearance_parts.c_str(); *q;) {
+      char* end = nullptr;
+      parts->push_back((int)strtol(q, &end, 10));
+      if (end == q) { parts->back() = -1; break; }
+      q = *end == ',' ? end + 1 : end;
+    }
+    if (parts->empty()) parts->push_back(-1);
+  }
+  if (!parts->empty()) { ac.parts = parts->data(); ac.num_parts = (int)parts->size(); }
+  return ac;
 }
 
 // --smooth: on the GPU where the tracker is; otherwise in the re-orderer, behind its rtp_track_update
@@ -1028,6 +1108,12 @@ void reorderer(std::atomic<bool>* workers_done) {
   const bool host_track = F.track && !track_on_gpu();
   const rtp_track_config tc = track_config();
   std::unique_ptr<rtp_track_state> tstate;
+  // --track_appearance on the host: the descriptors of the frame's display image, then rtp_track_update_appearance in rtp_track_update's place
+  const bool host_appear = appearance_on_host();
+  std::vector<int> appear_parts;
+  std::unique_ptr<rtp_appearance_state> astate;
+  std::vector<uint16_t> appear_bins(host_appear ? (size_t)RTP_MAX_PEOPLE * RTP_APPEARANCE_BINS : 0);
+  std::vector<unsigned char> appear_valid(host_appear ? (size_t)RTP_MAX_PEOPLE : 0), appear_disp;
   // --smooth on the host: behind the tracker, on the records the frame carries by then (the re-orderer's or the GPU's)
   const bool host_smooth = F.smooth && F.track && !smooth_on_gpu();
   const rtp_smooth_config sc = smooth_config();
@@ -1045,7 +1131,26 @@ void reorderer(std::atomic<bool>* workers_done) {
     if (host_track) {
       if (!tstate) { tstate.reset(new rtp_track_state); rtp_track_state_init(tstate.get(), G.num_parts.load()); }
       f.track_recs.assign((size_t)std::max(f.numPeople, 1) * RTP_TRACK_REC_INTS, 0);
-      if (rtp_track_update(tstate.get(), &tc, f.joints.data(), f.numPeople, f.track_recs.data()) < 0)
+      int tracked;
+      if (host_appear) {
+        const int P = G.num_parts.load();
+        if (!astate) { astate.reset(new rtp_appearance_state); rtp_appearance_state_init(astate.get()); }
+        const rtp_appearance_config ac = appearance_config(P, &appear_parts);
+        if (f.display_raw) {   // the frame warped as the engine warps it
+          double s = 1;
+          appear_disp.resize((size_t)DISP_W * DISP_H * 3);
+          if (f.display.size() == (size_t)f.img_w * f.img_h * 3 && rtp_warp_display(f.display.data(), f.img_w, f.img_h, appear_disp.data(), DISP_W, DISP_H, &s) == RTP_OK) f.display.swap(appear_disp);
+          else f.display.clear();
+        }
+        // (the workers have refused a part list that does not fit the model: the call fails for no frame)
+        const bool described = f.display.size() == (size_t)DISP_W * DISP_H * 3 &&
+                               rtp_appearance_describe(f.display.data(), DISP_W, DISP_H, f.joints.data(), f.numPeople, P, &ac, appear_bins.data(), appear_valid.data()) >= 0;
+        tracked = rtp_track_update_appearance(tstate.get(), astate.get(), &tc, &ac, f.joints.data(), f.numPeople, described ? appear_bins.data() : nullptr,
+                                              described ? appear_valid.data() : nullptr, f.track_recs.data());
+        f.display.clear();
+        f.display.shrink_to_fit();
+      } else tracked = rtp_track_update(tstate.get(), &tc, f.joints.data(), f.numPeople, f.track_recs.data());
+      if (tracked < 0)
         for (int k = 0; k < f.numPeople; ++k) f.track_recs[(size_t)k * RTP_TRACK_REC_INTS + 1] = -1;
       f.track_recs.resize((size_t)f.numPeople * RTP_TRACK_REC_INTS);
     }
@@ -1326,6 +1431,17 @@ int main(int argc, char** argv) {
   if (F.track && (!(F.track_max_cost > 0) || !std::isfinite(F.track_max_cost) || F.track_max_misses < 0 || F.track_min_parts < 1)) {
     fprintf(stderr, "--track: --track_max_cost must be a finite number > 0, --track_max_misses >= 0, --track_min_parts >= 1\n");
     return 1;
+  }
+  if (F.track_appearance) {
+    std::vector<int> parts;
+    const rtp_appearance_config ac = appearance_config(RTP_MAX_NUM_PARTS, &parts);
+    bool bad_part = false;
+    for (int p : parts) bad_part = bad_part || p < 0;
+    if (!F.track || !(F.appearance_weight >= 0) || !std::isfinite(F.appearance_weight) || !(F.appearance_max_dist > 0 && F.appearance_max_dist <= 1) || ac.rate < 1 || ac.rate > 256 || bad_part) {
+      fprintf(stderr, "--track_appearance needs --track; --appearance_weight must be a finite number >= 0, --appearance_max_dist in (0, 1], --appearance_rate 1 .. 256, "
+                      "--appearance_parts torso, all or a comma-separated list of part indices\n");
+      return 1;
+    }
   }
   if (F.smooth && !F.track) {
     fprintf(stderr, "--smooth needs --track (the filter follows tracked people)\n");

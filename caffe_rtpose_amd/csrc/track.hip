@@ -26,6 +26,11 @@
 //   D  one thread per slot: hits / misses, slots freed.   E  thread 0: births in person order, each into the lowest free slot.
 //   F  the joints of every tracked person into its slot, zeros into freed slots, the records.
 // Table and records are written with ordinary vector stores.
+//
+// The appearance form (rtp_set_track_appearance; rtp_track_update_appearance is its definition) is the same body with a third template
+// parameter: phase B adds the 128-bin L1 distance between the slot's descriptor and the person's to a pair that passed the motion gate,
+// phase F blends or replaces the descriptors of the slots that took a person.  It has instantiations of its own (a second kernel argument); the
+// four track_kernel instantiations instantiate none of it.
 #include <atomic>
 
 #include "kernels.h"
@@ -53,8 +58,51 @@ __device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
   return v;
 }
 
-template <bool SORT, int kThreads>
-__global__ __launch_bounds__(kThreads) void track_kernel(TrackParams p) {
+// THE COST's appearance term on two packed uint16: |desc - 16 * bins| of both halves
+__device__ __forceinline__ int l1_pair(unsigned d, unsigned b) {
+  const int lo = (int)(d & 0xffffu) - 16 * (int)(b & 0xffffu), hi = (int)(d >> 16) - 16 * (int)(b >> 16);
+  return (lo < 0 ? -lo : lo) + (hi < 0 ? -hi : hi);
+}
+// THE TABLE UPDATE on two packed uint16 (rate 256 replaces: (16 * bins * 256 + 128) >> 8 = 16 * bins); each half is cut to 16 bits as the host's cast does
+__device__ __forceinline__ unsigned blend_pair(unsigned d, unsigned b, int rate) {
+  const unsigned lo = ((d & 0xffffu) * (unsigned)(256 - rate) + 16u * (b & 0xffffu) * (unsigned)rate + 128u) >> 8;
+  const unsigned hi = ((d >> 16) * (unsigned)(256 - rate) + 16u * (b >> 16) * (unsigned)rate + 128u) >> 8;
+  return (lo & 0xffffu) | (hi << 16);
+}
+// The key of a pair (slot t, person k) that passed the motion gate with `cost`: the bits of total + 0.0f, or kNone where the pair is no
+// candidate.  One thread sums the 128 bins in order of integers, so nothing depends on how work is spread.  Table and descriptors come
+// through L2 as 16 + 16 loads of 16 bytes.
+__device__ __forceinline__ unsigned appear_key(const TrackAppearParams& a, int t, int k, bool has, float cost) {
+  float dist = a.unknown;
+  if (has && a.valid[k]) {
+    const uint4* d = reinterpret_cast<const uint4*>(&a.table->desc[t][0]);
+    const uint4* b = reinterpret_cast<const uint4*>(a.bins + (long)k * RTP_APPEAR_BINS);
+    int L = 0;
+#pragma unroll 4
+    for (int i = 0; i < RTP_APPEAR_BINS / 8; ++i) {
+      const uint4 dv = d[i], bv = b[i];
+      L += l1_pair(dv.x, bv.x) + l1_pair(dv.y, bv.y) + l1_pair(dv.z, bv.z) + l1_pair(dv.w, bv.w);
+    }
+    dist = (float)L / 32768.0f;
+    if (!(dist <= a.max_dist)) return kNone;
+  }
+  const float wa = a.weight * dist;
+  const float total = cost + wa;
+  if (!__builtin_isfinite(total)) return kNone;
+  return __float_as_uint(total + 0.0f);
+}
+
+struct NoAppear {};
+__device__ __forceinline__ NoAppear appear_args() { return {}; }
+__device__ __forceinline__ const TrackAppearParams& appear_args(const TrackAppearParams& a) { return a; }
+
+// A = nothing: the plain form, track_kernel<SORT, kThreads>(TrackParams).  A = TrackAppearParams: the appearance form, a second kernel
+// argument: phase A notes which slots HAVE a descriptor, phase B takes THE COST's key where the plain form takes the motion cost's, and
+// phase F gains THE TABLE UPDATE.  In the plain form none of it is instantiated.
+template <bool SORT, int kThreads, class... A>
+__global__ __launch_bounds__(kThreads) void track_kernel(TrackParams p, A... appear) {
+  constexpr bool APPEAR = sizeof...(A) != 0;
+  const auto& a = appear_args(appear...);
   constexpr int kWaves = kThreads / 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   unsigned* const s_cost = reinterpret_cast<unsigned*>(s_dyn);                                      // [kPairs]
@@ -68,6 +116,7 @@ __global__ __launch_bounds__(kThreads) void track_kernel(TrackParams p) {
   __shared__ short s_slots[kSlots], s_pers[kPeople];
   __shared__ short s_person_of[kSlots], s_slot_of[kPeople];
   __shared__ unsigned char s_free[kSlots], s_freed[kSlots], s_born[kPeople];
+  __shared__ unsigned char s_has[APPEAR ? kSlots : 1], s_upd[APPEAR ? kPeople : 1];   // slot t has a descriptor; person k's table update: 0 none, 1 blend, 2 replace
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   TrackTable* tb = p.table;
@@ -97,6 +146,7 @@ __global__ __launch_bounds__(kThreads) void track_kernel(TrackParams p) {
       const float wh = ww + hh;
       s_d[t] = fmaxf(wh, 1.0f);
     }
+    if constexpr (APPEAR) s_has[t] = flag && a.table->owner[t] == tb->id[t] ? 1 : 0;
   } else if (tid < kSlots + kPeople) {
     const int k = tid - kSlots;
     s_slot_of[k] = -1;
@@ -146,7 +196,10 @@ __global__ __launch_bounds__(kThreads) void track_kernel(TrackParams p) {
     if (m >= p.min_common) {
       const float q = s / (float)m;
       const float cost = q / s_d[t];
-      if (__builtin_isfinite(cost) && cost <= p.max_cost) key = __float_as_uint(cost + 0.0f);
+      if (__builtin_isfinite(cost) && cost <= p.max_cost) {
+        if constexpr (APPEAR) key = appear_key(a, t, k, s_has[t] != 0, cost);
+        else key = __float_as_uint(cost + 0.0f);
+      }
     }
     s_cost[idx] = key;
     if (SORT && key != kNone) s_idx[atomicAdd(&s_count, 1)] = (unsigned short)idx;   // (at most C <= 12288 entries)
@@ -288,6 +341,28 @@ __global__ __launch_bounds__(kThreads) void track_kernel(TrackParams p) {
     else r = make_int4(s_rec_id[k], t, s_rec_hits[k], s_born[k] ? 0 : (int)s_cost_of[k]);
     reinterpret_cast<int4*>(p.recs)[k] = r;
   }
+  if constexpr (APPEAR) {
+    // THE TABLE UPDATE: what happens to each person's slot is decided on the owners as they stand (s_rec_id = the slot's id now), then,
+    // behind a barrier, one thread per 8 bins blends or replaces them and the first of a replaced slot's threads writes the owner
+    if (tid < n) {
+      const int t = s_slot_of[tid];
+      s_upd[tid] = (t >= 0 && a.valid[tid]) ? (a.table->owner[t] == s_rec_id[tid] ? 1 : 2) : 0;
+    }
+    __syncthreads();
+    for (int e = tid; e < n * (RTP_APPEAR_BINS / 8); e += kThreads) {
+      const int k = e >> 4, g = e & 15;
+      const int u = s_upd[k];
+      if (!u) continue;
+      const int t = s_slot_of[k];
+      const int rate = u == 1 ? a.rate : 256;
+      uint4* dp = reinterpret_cast<uint4*>(&a.table->desc[t][0]) + g;
+      const uint4 bv = reinterpret_cast<const uint4*>(a.bins + (long)k * RTP_APPEAR_BINS)[g];
+      uint4 dv = *dp;
+      dv.x = blend_pair(dv.x, bv.x, rate); dv.y = blend_pair(dv.y, bv.y, rate); dv.z = blend_pair(dv.z, bv.z, rate); dv.w = blend_pair(dv.w, bv.w, rate);
+      *dp = dv;
+      if (g == 0 && u == 2) a.table->owner[t] = s_rec_id[k];
+    }
+  }
 }
 
 
@@ -310,7 +385,44 @@ hipError_t launch_one(const TrackParams& p, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// The appearance form: the same dynamic LDS (table and descriptors are read through L2, nothing is staged), opted into for its own kernel
+template <bool SORT, int kThreads>
+hipError_t launch_one_appear(const TrackParams& p, const TrackAppearParams& a, hipStream_t stream) {
+  const size_t lds = kPairs * sizeof(unsigned) + (SORT ? kMaxSort * sizeof(unsigned short) : 0);
+  if (lds > 60 * 1024) {
+    static std::atomic<unsigned> have{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned bit = 1u << (dev & 31);
+    if (!(have.load(std::memory_order_relaxed) & bit)) {
+      const hipError_t e = hipFuncSetAttribute((const void*)track_kernel<SORT, kThreads, TrackAppearParams>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      have.fetch_or(bit, std::memory_order_relaxed);
+    }
+  }
+  hipLaunchKernelGGL((track_kernel<SORT, kThreads, TrackAppearParams>), dim3(1), dim3(kThreads), lds, stream, p, a);
+  return hipGetLastError();
+}
+
+bool track_params_ok(const TrackParams& p) {
+  return p.joints && p.num_people && p.table && p.recs && p.num_parts >= 1 && p.num_parts <= RTP_TRACK_MAX_PARTS && p.min_parts >= 1 && p.min_common >= 1 &&
+         p.max_misses >= 0 && p.min_score >= 0.f && p.max_cost > 0.f && (unsigned long long)(uintptr_t)p.recs % 16 == 0 && p.variant >= 0 &&
+         p.variant < RTP_TRACK_VARIANTS;
+}
+
 }  // namespace
+
+hipError_t launch_track_appearance(const TrackParams& p, const TrackAppearParams& a, hipStream_t stream) {
+  if (!track_params_ok(p) || !a.bins || !a.valid || !a.table || (unsigned long long)(uintptr_t)a.bins % 16 != 0 || (unsigned long long)(uintptr_t)a.table % 16 != 0 ||
+      !(a.weight >= 0.f) || !(a.max_dist > 0.f && a.max_dist <= 1.f) || !(a.unknown >= 0.f && a.unknown <= 1.f) || a.rate < 1 || a.rate > 256)
+    return hipErrorInvalidValue;
+  switch (p.variant) {
+    case RTP_TRACK_ARGMIN_256: return launch_one_appear<false, 256>(p, a, stream);
+    case RTP_TRACK_ARGMIN_1024: return launch_one_appear<false, 1024>(p, a, stream);
+    case RTP_TRACK_SORT_256: return launch_one_appear<true, 256>(p, a, stream);
+    default: return launch_one_appear<true, 1024>(p, a, stream);
+  }
+}
 
 hipError_t launch_track(const TrackParams& p, hipStream_t stream) {
   if (!p.joints || !p.num_people || !p.table || !p.recs || p.num_parts < 1 || p.num_parts > RTP_TRACK_MAX_PARTS || p.min_parts < 1 || p.min_common < 1 ||

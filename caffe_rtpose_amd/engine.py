@@ -5,7 +5,7 @@ import sys
 
 import numpy as np
 
-from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, rtp_smooth_config, rtp_smooth_state, rtp_overlay_config, rtp_trail_state, rtp_redact_config, fp, ip
+from ._lib import lib, rtp_config, rtp_frame_view, rtp_yuv_view, rtp_maps_config, rtp_maps_view, rtp_crops_config, rtp_crops_view, rtp_track_config, rtp_track_state, rtp_appearance_config, rtp_appearance_state, rtp_smooth_config, rtp_smooth_state, rtp_overlay_config, rtp_trail_state, rtp_redact_config, fp, ip
 
 MODEL_COCO_18, MODEL_MPI_15 = 0, 1
 PREC_FP16, PREC_FP32, PREC_MIXED, PREC_F16X3 = 0, 1, 2, 3
@@ -736,6 +736,108 @@ def format_json_tracked(joints, num_parts, frame_scale, recs=None):
     return buf.raw[:n]
 
 
+APPEARANCE_BINS = 128
+
+
+def appearance_torso_parts(model):
+    """rtp_appearance_torso_parts: neck, shoulders and hips (COCO), and the chest (MPI)."""
+    parts = (C.c_int * 8)()
+    n = lib.rtp_appearance_torso_parts(int(model), parts)
+    if n < 0:
+        raise RtpError(n, "bad model")
+    return list(parts)[:n]
+
+
+def appearance_config(parts=None, min_score=None, min_parts=None, margin=None, weight=None, max_dist=None, unknown=None, rate=None):
+    """rtp_appearance_config: rtp_appearance_config_default's values (the torso parts, min_score 0, min_parts 3, margin 0, weight 0.125,
+    max_dist 1, unknown 0.25, rate 32), each replaced where an argument is given.  The part list lives as long as the result."""
+    cfg = rtp_appearance_config()
+    lib.rtp_appearance_config_default(C.byref(cfg))
+    for name, v, conv in (("min_score", min_score, float), ("min_parts", min_parts, int), ("margin", margin, float), ("weight", weight, float),
+                          ("max_dist", max_dist, float), ("unknown", unknown, float), ("rate", rate, int)):
+        if v is not None:
+            setattr(cfg, name, conv(v))
+    if parts is not None:
+        cfg._keep = (C.c_int * max(len(parts), 1))(*[int(p) for p in parts])
+        cfg.parts, cfg.num_parts = cfg._keep, len(parts)
+    return cfg
+
+
+class AppearanceState:
+    """rtp_appearance_state, the descriptor table as plain data: numpy views owner [128] and desc [128][128] (Q4) onto the structure
+    itself (writes through them change it).  == compares every byte."""
+
+    def __init__(self, c=None):
+        if c is None:
+            c = rtp_appearance_state()
+            lib.rtp_appearance_state_init(C.byref(c))
+        self.c = c
+        self.owner = np.ctypeslib.as_array(c.owner)
+        self.desc = np.ctypeslib.as_array(c.desc).reshape(MAX_TRACKS, APPEARANCE_BINS)
+
+    def copy(self):
+        c = rtp_appearance_state()
+        C.memmove(C.byref(c), C.byref(self.c), C.sizeof(c))
+        return AppearanceState(c=c)
+
+    def tobytes(self):
+        return C.string_at(C.byref(self.c), C.sizeof(self.c))
+
+    def __eq__(self, other):
+        return isinstance(other, AppearanceState) and self.tobytes() == other.tobytes()
+
+
+def _u16(a):
+    assert a.dtype == np.uint16 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
+def appearance_describe(display_bgr, joints, num_parts, cfg=None):
+    """rtp_appearance_describe, the host definition of the descriptor: (bins [n][128] uint16, valid [n] uint8) of joints
+    [people][num_parts][3] on the u8 BGR display image [h][w][3]; cfg: an appearance_config() (None = the defaults)."""
+    cfg = cfg if cfg is not None else appearance_config()
+    img = np.ascontiguousarray(display_bgr, np.uint8)
+    h, w = img.shape[:2]
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, int(num_parts), 3)
+    people = j.shape[0]
+    n = min(people, MAX_PEOPLE)
+    bins = np.zeros((max(n, 1), APPEARANCE_BINS), np.uint16)
+    valid = np.zeros(max(n, 1), np.uint8)
+    rc = lib.rtp_appearance_describe(_u8(img), w, h, _f(j) if j.size else None, people, int(num_parts), C.byref(cfg), _u16(bins), _u8(valid))
+    if rc < 0:
+        raise RtpError(rc, "rtp_appearance_describe: an argument is out of range")
+    assert rc == n
+    return bins[:n].copy(), valid[:n].copy()
+
+
+def track_update_appearance(track_state, appearance_state, joints, num_people=None, bins=None, valid=None, track_cfg=None, appearance_cfg=None):
+    """rtp_track_update_appearance, the host definition of appearance-aided tracking: advances both states (a TrackState and an
+    AppearanceState) by one frame of joints [people][num_parts][3] with their descriptors (appearance_describe's; bins None = a
+    frame without a display image) and returns the records [n][4] int32 {id, slot, hits, total cost bits}."""
+    tcfg = track_cfg if track_cfg is not None else track_config()
+    acfg = appearance_cfg if appearance_cfg is not None else appearance_config()
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, track_state.num_parts, 3)
+    people = j.shape[0] if num_people is None else int(num_people)
+    n = min(max(people, 0), MAX_PEOPLE)
+    if n > j.shape[0]:
+        raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+    b = v = None
+    if bins is not None:
+        b = np.ascontiguousarray(bins, np.uint16).reshape(-1, APPEARANCE_BINS)
+        v = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+        if b.shape[0] < n or v.shape[0] < n:
+            raise ValueError(f"{n} people, {b.shape[0]} descriptors and {v.shape[0]} valid bytes")
+        if not n:
+            b, v = np.zeros((1, APPEARANCE_BINS), np.uint16), np.zeros(1, np.uint8)
+    recs = np.zeros((max(n, 1), TRACK_REC_INTS), np.int32)
+    rc = lib.rtp_track_update_appearance(C.byref(track_state.c), C.byref(appearance_state.c), C.byref(tcfg), C.byref(acfg), _f(j) if j.size else None, people,
+                                         _u16(b) if b is not None else None, _u8(v) if v is not None else None, recs.ctypes.data_as(ip))
+    if rc < 0:
+        raise RtpError(rc, "rtp_track_update_appearance: an argument is out of range")
+    assert rc == n
+    return recs[:n].copy()
+
+
 SMOOTH_RENDER, SMOOTH_CROPS = 1, 2
 _SMOOTH_CELL = np.dtype([("owner", np.int32), ("last", np.uint32), ("pos", np.float32, 2), ("vel", np.float32, 2), ("score", np.float32)])
 
@@ -1378,6 +1480,74 @@ class Engine:
         n = C.c_int(0)
         self._chk(lib.rtp_track_from_joints(self.h, _f(j) if j.size else None, people, recs.ctypes.data_as(ip), C.byref(n), cap))
         return recs[: n.value].copy()
+
+    # ---- appearance-aided tracking
+    def set_track_appearance(self, cfg=True, **kw):
+        """rtp_set_track_appearance (tracking mode must be on): every submitted frame's people get a colour descriptor from the frame's
+        display image, the track kernel's cost gains the appearance term, and peek_appearance in front of the frame's collect gives the
+        descriptors.  cfg: an appearance_config(), True (= appearance_config(**kw)) or None / False (off: the descriptor table is
+        discarded).  Off -> on starts from an empty descriptor table; a new cfg while the mode is on keeps it."""
+        if cfg is None or cfg is False:
+            self._chk(lib.rtp_set_track_appearance(self.h, None))
+            return
+        if cfg is True:
+            cfg = appearance_config(**kw)
+        self._chk(lib.rtp_set_track_appearance(self.h, C.byref(cfg)))
+
+    def appearance_reset(self):
+        """rtp_appearance_reset: an empty descriptor table; idle engine."""
+        self._chk(lib.rtp_appearance_reset(self.h))
+
+    def appearance_state(self):
+        """rtp_appearance_get_state: the engine's descriptor table as an AppearanceState; idle engine."""
+        st = AppearanceState()
+        self._chk(lib.rtp_appearance_get_state(self.h, C.byref(st.c)))
+        return st
+
+    def set_appearance_state(self, state):
+        """rtp_appearance_set_state: the engine's descriptor table becomes a copy of `state` (an AppearanceState); idle engine."""
+        self._chk(lib.rtp_appearance_set_state(self.h, C.byref(state.c)))
+
+    def peek_appearance(self, capacity=MAX_PEOPLE):
+        """rtp_peek_appearance: (tag, bins [n][128] uint16, valid [n] uint8) of the oldest frame in flight, which stays in flight."""
+        bins = np.zeros((max(int(capacity), 1), APPEARANCE_BINS), np.uint16)
+        valid = np.zeros(max(int(capacity), 1), np.uint8)
+        tag, n = C.c_uint64(0), C.c_int(0)
+        self._chk(lib.rtp_peek_appearance(self.h, C.byref(tag), _u16(bins), _u8(valid), C.byref(n), int(capacity)))
+        return tag.value, bins[: n.value].copy(), valid[: n.value].copy()
+
+    def _appearance_tap_args(self, display_bgr, joints, num_people):
+        img = None
+        if display_bgr is not None:
+            img = np.ascontiguousarray(display_bgr, np.uint8)
+            if img.shape != (self.cfg.c.disp_h, self.cfg.c.disp_w, 3):
+                raise ValueError(f"display image {img.shape}: the engine's display is {(self.cfg.c.disp_h, self.cfg.c.disp_w, 3)}")
+        j = np.ascontiguousarray(joints, np.float32).reshape(-1, self.num_parts, 3)
+        people = j.shape[0] if num_people is None else int(num_people)
+        cap = min(max(people, 0), MAX_PEOPLE)
+        if cap > j.shape[0]:
+            raise ValueError(f"num_people {people}: the array holds {j.shape[0]} people")
+        return img, j, people, cap
+
+    def appearance_from_joints(self, display_bgr, joints, num_people=None):
+        """rtp_appearance_from_joints: the async path's describe kernel on the display image [disp_h][disp_w][3] (None: a frame without
+        one) and joints [people][num_parts][3] (idle engine); no table is touched.  Returns (bins [n][128], valid [n])."""
+        img, j, people, cap = self._appearance_tap_args(display_bgr, joints, num_people)
+        bins, valid = np.zeros((max(cap, 1), APPEARANCE_BINS), np.uint16), np.zeros(max(cap, 1), np.uint8)
+        n = C.c_int(0)
+        self._chk(lib.rtp_appearance_from_joints(self.h, _u8(img) if img is not None else None, _f(j) if j.size else None, people, _u16(bins), _u8(valid), C.byref(n), cap))
+        return bins[: n.value].copy(), valid[: n.value].copy()
+
+    def track_from_frame(self, display_bgr, joints, num_people=None):
+        """rtp_track_from_frame: the async path's describe and track kernels on the display image (None: a frame without one) and joints
+        (idle engine); both of the engine's tables advance by one frame.  Returns (records [n][4], bins [n][128], valid [n])."""
+        img, j, people, cap = self._appearance_tap_args(display_bgr, joints, num_people)
+        recs = np.zeros((max(cap, 1), TRACK_REC_INTS), np.int32)
+        bins, valid = np.zeros((max(cap, 1), APPEARANCE_BINS), np.uint16), np.zeros(max(cap, 1), np.uint8)
+        n = C.c_int(0)
+        self._chk(lib.rtp_track_from_frame(self.h, _u8(img) if img is not None else None, _f(j) if j.size else None, people, recs.ctypes.data_as(ip), _u16(bins),
+                                           _u8(valid), C.byref(n), cap))
+        return recs[: n.value].copy(), bins[: n.value].copy(), valid[: n.value].copy()
 
     # ---- smoothing mode
     def set_smoothing(self, cfg=True, **kw):

@@ -899,6 +899,152 @@ int rtp_track_from_joints(rtp_engine* e, const float* joints_host, int num_peopl
 long rtp_format_json_tracked(char* buf, size_t buflen, const float* joints, int num_people, int num_parts, float frame_scale,
                              const int* recs);
 
+/* ---- appearance-aided tracking: a colour descriptor per person in the assignment cost (appearance.hip, track.hip) --------- */
+
+/* The tracker's cost is joint displacement alone.  Two people who pass each other between two frames have the lower summed
+ * displacement with their ids swapped, and a person who reappears where somebody else stood inherits that track.  This mode, off by
+ * default and usable only while tracking mode is on, gives the tracker a look at the pixels: a colour histogram per person, taken
+ * from the frame's un-rendered display image around a list of parts, a table of one smoothed histogram per track slot, and an
+ * appearance term in the cost.  The per-frame descriptors also leave the engine with the joints (rtp_peek_appearance), for
+ * matching people across cameras or engines.  While the mode is off nothing changes, neither a launch nor a byte.  On: each frame's
+ * chain gains ONE kernel (appear_describe) on the frame's own stream behind the connect kernels, and the frame's track kernel is
+ * the appearance form of the same kernel.  rtp_appearance_describe and rtp_track_update_appearance are the one definition of the
+ * arithmetic; the kernels' integers and float bits equal them exactly.
+ *
+ * THE DESCRIPTOR of person k, from the display image (u8 HWC BGR, w x h) and the person's joints.
+ *   Which parts count: the list `parts` / `num_parts` as in rtp_crops_config; NULL = the model's torso parts
+ *   (rtp_appearance_torso_parts; a model of 18 parts is taken as RTP_MODEL_COCO_18, of 15 as RTP_MODEL_MPI_15, any other model: all
+ *   its parts).  A list entry p counts when score > min_score and x and y are finite (a NaN score never counts).  A repeated entry
+ *   counts once per repeat.  count < min_parts: the person has no descriptor (valid = 0, the bins are zeros).
+ *   The box, in float32, every operation rounded on its own (no fused multiply-add), in exactly this order — the crops box up to and
+ *   without its aspect step:
+ *     Every counting x and y is first taken as x + 0.0f (so that -0 is +0 and min / max do not depend on the order).
+ *     x0 = min x, x1 = max x, y0 = min y, y1 = max y
+ *     cx = (x0 + x1) * 0.5f            cy = (y0 + y1) * 0.5f
+ *     w = x1 - x0                      h = y1 - y0
+ *     (an infinite w or h, the overflow of two huge coordinates: no descriptor)
+ *     g = (margin * fmaxf(w, h)) * 2.0f
+ *     w = fmaxf(w + g, 1.0f)           h = fmaxf(h + g, 1.0f)
+ *     left = cx - w * 0.5f             top = cy - h * 0.5f
+ *     right = left + w                 bottom = top + h
+ *     The box is NOT clipped to the image.  Unless |left|, |top|, |right| and |bottom| are all <= 1048576.0f (2^20; an infinity or
+ *     a NaN from an overflow fails this), the person has no descriptor.
+ *   The samples, a fixed RTP_APPEARANCE_GRID x RTP_APPEARANCE_GRID (32 x 32) grid, integers only past these four conversions (Q16,
+ *   int64):
+ *     ox = (int64)rintf(left * 65536.0f)                 oy = (int64)rintf(top * 65536.0f)
+ *     dx = (int64)rintf((w / 32.0f) * 65536.0f)          dy = (int64)rintf((h / 32.0f) * 65536.0f)
+ *     Sample (i, j), i, j = 0 .. 31, reads the pixel at column clamp((ox + i * dx + dx / 2) >> 16, 0, w - 1) and row
+ *     clamp((oy + j * dy + dy / 2) >> 16, 0, h - 1) of the image (>> is the arithmetic shift: floor; dx, dy >= 0, so / 2 is a shift
+ *     too).  The border is replicated: every person with a descriptor has exactly 1024 samples.
+ *   The bins: a sample's bin is (j >= 16 ? 64 : 0) + (r >> 6) * 16 + (g >> 6) * 4 + (b >> 6).  Grid rows 0 .. 15 and 16 .. 31 keep
+ *   separate histograms, so that upper and lower clothing differ.  The descriptor is uint16 bins[RTP_APPEARANCE_BINS] and sums to 1024.
+ *
+ * THE TABLE, one entry per track slot: owner[t] and desc[t][RTP_APPEARANCE_BINS] in Q4 (counts times 16).  Slot t HAS a descriptor
+ * when owner[t] == id[t] != 0 (id: the track table's).  This is smoothing mode's owner rule: nothing is cleared when a track dies.
+ *
+ * THE COST.  Steps 1 and 2 of rtp_track_update are unchanged: the motion cost and its max_cost gate.  Then, for a pair (t, k) that
+ * passed, everything float32 and every operation rounded on its own:
+ *   slot t has a descriptor (in the tables as they stand before the update) and person k's is valid:
+ *     L = sum over the bins b of |desc[t][b] - 16 * bins_k[b]|  (an integer; 0 .. 32768 for descriptors this definition produced)
+ *     a = (float)L / 32768.0f  (exact);  a <= max_dist, or the pair is no candidate
+ *   otherwise a = unknown, and the max_dist gate is skipped.
+ *   wa = weight * a;  total = cost + wa.  The pair is a CANDIDATE when total is finite.
+ * Steps 3 to 7 run on the candidates' keys (bits of total + 0.0f as uint32, slot t, person k).  A matched person's record carries
+ * the bits of total + 0.0f where rtp_track_update's carries the cost's.
+ *
+ * THE TABLE UPDATE, after step 6, for every person k with a slot t (matched or born) and a valid descriptor, id = the slot's id now:
+ *   owner[t] == id:  desc[t][b] = (desc[t][b] * (256 - rate) + 16 * bins_k[b] * rate + 128) >> 8  for every bin (rate 256 replaces)
+ *   otherwise:       desc[t][b] = 16 * bins_k[b],  owner[t] = id
+ * A person without a valid descriptor leaves its slot's entry alone.
+ *
+ * With weight 0, max_dist 1 and unknown 0, records and track table are rtp_track_update's bit for bit, whatever the descriptors are.
+ * The defaults of rtp_appearance_config_default (the torso parts, min_score 0, min_parts 3, margin 0, weight 0.125, max_dist 1,
+ * unknown 0.25, rate 32) are choices, not measurements: at weight 0.125 a person in entirely different colours costs as much as two
+ * times tracking mode's default max_cost, and rate 32 moves a slot's histogram an eighth of the way to the frame's. */
+#define RTP_APPEARANCE_BINS 128
+#define RTP_APPEARANCE_GRID 32
+typedef struct rtp_appearance_config {
+  unsigned int struct_size; /* sizeof(rtp_appearance_config) */
+  const int* parts;         /* part indices that span the box, any order, repeats allowed (copied by the call); NULL = the torso parts */
+  int num_parts;            /* 1 .. RTP_MAX_NUM_PARTS (ignored when parts == NULL) */
+  float min_score;          /* >= 0, finite */
+  int min_parts;            /* >= 1 */
+  float margin;             /* >= 0, <= 16 */
+  float weight;             /* >= 0, finite */
+  float max_dist;           /* > 0, <= 1 */
+  float unknown;            /* >= 0, <= 1 */
+  int rate;                 /* 1 .. 256 */
+} rtp_appearance_config;
+
+typedef struct rtp_appearance_state { /* plain data; the device copy has the same layout */
+  unsigned int struct_size;           /* sizeof(rtp_appearance_state) */
+  int reserved[3];                    /* zeros (desc starts at a multiple of 16 bytes) */
+  int owner[RTP_MAX_TRACKS];          /* the id the slot's descriptor belongs to; 0 = none yet */
+  uint16_t desc[RTP_MAX_TRACKS][RTP_APPEARANCE_BINS]; /* Q4 */
+} rtp_appearance_state;
+
+/* Host only (no engine, no GPU).  rtp_appearance_config_default: the defaults above.  rtp_appearance_state_init: an empty table.
+ * rtp_appearance_torso_parts: the part indices of a torso box for rtp_appearance_config.parts: neck, shoulders and hips for
+ * RTP_MODEL_COCO_18 (5); neck, shoulders, hips and chest for RTP_MODEL_MPI_15 (6).  Returns their number, or RTP_EINVAL for another
+ * model.  The first two return RTP_OK, or RTP_EINVAL for a NULL pointer. */
+int rtp_appearance_config_default(rtp_appearance_config* cfg);
+int rtp_appearance_state_init(rtp_appearance_state* state);
+int rtp_appearance_torso_parts(int model, int parts[8]);
+
+/* Host only: THE DESCRIPTOR above.  display_bgr: u8 HWC BGR of w x h; joints [num_people][num_parts][3] as rtp_collect returns them
+ * (num_parts here = the model's parts per person).  Writes n = min(num_people, RTP_MAX_PEOPLE) descriptors into
+ * bins_out [n][RTP_APPEARANCE_BINS] and n bytes (1 or 0) into valid_out; nothing behind them.  Returns n, or RTP_EINVAL: a NULL cfg,
+ * bins_out or valid_out, wrong struct_size, w or h < 1 or > 32768, num_people < 0, num_parts outside 1 .. RTP_MAX_NUM_PARTS, a
+ * configuration field out of its range, a listed part outside [0, num_parts), NULL joints or display_bgr with people. */
+int rtp_appearance_describe(const unsigned char* display_bgr, int w, int h, const float* joints, int num_people, int num_parts,
+                            const rtp_appearance_config* cfg, uint16_t* bins_out, unsigned char* valid_out);
+
+/* Host only: rtp_track_update with THE COST and THE TABLE UPDATE above, one frame.  joints, num_people and recs as in
+ * rtp_track_update; bins [n][RTP_APPEARANCE_BINS] and valid [n] are rtp_appearance_describe's for the same people.  bins == NULL: every
+ * person counts as having no descriptor (a frame without a display image).  Returns n, or RTP_EINVAL with BOTH states untouched:
+ * whatever rtp_track_update refuses, a NULL appearance state or configuration, a wrong struct_size in either, an appearance field
+ * out of its range, bins without valid.  (The part list of appearance_cfg is not read here.) */
+int rtp_track_update_appearance(rtp_track_state* track_state, rtp_appearance_state* appearance_state, const rtp_track_config* track_cfg,
+                                const rtp_appearance_config* appearance_cfg, const float* joints, int num_people, const uint16_t* bins,
+                                const unsigned char* valid, int* recs);
+
+/* Switches the mode on (or changes it), NULL cfg = off (the descriptor table is discarded; the track table is kept either way).
+ * Usable only while tracking mode is on, and rtp_set_tracking(e, NULL) is refused while this mode is on.  Off -> on starts from an
+ * empty descriptor table; while the mode is on, a new cfg keeps it.  Refused, with the engine unchanged: wrong struct_size, a field
+ * out of range, a listed part outside the model's parts, tracking mode off (RTP_EINVAL); frames in flight (RTP_EAGAIN).  The
+ * descriptors always come from the RAW joints (the kernel runs in front of the tracker); smoothing, overlay, crops and redaction
+ * mode read the records and joints they read without it.  A frame without a display image (rtp_submit, rtp_submit_device) gets
+ * valid = 0 for everybody and is tracked with a = unknown; so are the joints-only taps (rtp_track_from_joints,
+ * rtp_smooth_from_joints, rtp_overlay_from_joints) while the mode is on. */
+int rtp_set_track_appearance(rtp_engine* e, const rtp_appearance_config* cfg);
+
+/* Idle engine only (RTP_EAGAIN with frames in flight); RTP_EINVAL while the mode is off.  reset: an empty descriptor table.
+ * get / set: the whole table, e.g. to carry it over to another engine with the track table; set also refuses (RTP_EINVAL) a wrong
+ * struct_size.  rtp_track_reset and rtp_track_set_state leave this table alone: a slot's entry counts only while its owner is the
+ * slot's id. */
+int rtp_appearance_reset(rtp_engine* e);
+int rtp_appearance_get_state(rtp_engine* e, rtp_appearance_state* state);
+int rtp_appearance_set_state(rtp_engine* e, const rtp_appearance_state* state);
+
+/* The contract of rtp_peek_tracks: blocks until the OLDEST frame in flight is finished and hands out its tag, *num = n and the
+ * frame's n descriptors into bins_host [n][RTP_APPEARANCE_BINS] and valid_host [n]; capacity = the descriptors the two buffers hold.
+ * Entry k is person k of rtp_collect, record k of rtp_peek_tracks and slot k of crops mode.  The frame STAYS in flight; peeking
+ * twice returns the same.  Refused: mode off, NULL bins_host, valid_host or num, a negative capacity (RTP_EINVAL); nothing in flight
+ * (RTP_EAGAIN); capacity < n (RTP_ERANGE, *num = n, nothing else written; the frame stays peekable). */
+int rtp_peek_appearance(rtp_engine* e, uint64_t* tag, uint16_t* bins_host, unsigned char* valid_host, int* num, int capacity);
+
+/* Parity taps (idle engine, context 0; the mode must be on): the kernels of the async path on caller data.  display_bgr_host: u8 HWC
+ * BGR of cfg.disp_w x cfg.disp_h, or NULL = a frame without a display image; joints_host [num_people][num_parts][3], of which
+ * n = clamp(num_people, 0, RTP_MAX_PEOPLE) people are read; num_people itself goes to the device as it is.  Capacity as in
+ * rtp_peek_appearance; both return RTP_OK and *num = n.
+ * rtp_appearance_from_joints: the describe kernel alone; writes n descriptors and valid bytes; no table is touched.
+ * rtp_track_from_frame: the describe kernel and the track kernel; writes n records and (bins_host and valid_host both NULL or both
+ * given) the n descriptors; it ADVANCES both tables by one frame. */
+int rtp_appearance_from_joints(rtp_engine* e, const unsigned char* display_bgr_host, const float* joints_host, int num_people,
+                               uint16_t* bins_host, unsigned char* valid_host, int* num, int capacity);
+int rtp_track_from_frame(rtp_engine* e, const unsigned char* display_bgr_host, const float* joints_host, int num_people, int* recs_host,
+                         uint16_t* bins_host, unsigned char* valid_host, int* num, int capacity);
+
 /* ---- smoothing mode: tracked people filtered over time, per joint (smooth.hip) ------------------------------------------ */
 
 /* The joints of rtp_collect are per-frame NMS peaks: on a still person they jitter by a fraction of a pixel to a few pixels, and a
